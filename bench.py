@@ -15,7 +15,16 @@ One "step" = one call of ``xrft_amd.power_spectrum`` over the rank's whole (nt, 
 resident in HBM.  Batches shard over ranks as independent time slabs (weak scaling: nt per GPU is fixed); there is
 no data-path collective.  value = GFFT/s = 1e-9 * (points transformed by all ranks) / (max-over-ranks wall time).
 
-Extra objects on the JSON line:
+A plain run does only what the headline figure needs: it generates the seeded input, warms up, times exactly --steps steps
+and prints the JSON line (value, ms_per_step = wall time of the timed region / --steps).  Everything else it can measure or
+check runs only with --full (the objects below: per-kernel events, the memory-floor self-test, the traffic profile, the CPU
+baseline and parity, the extra legs, and with N > 1 the identity of the gathered isotropic blocks on every rank).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step returned (the spectra and their coordinates) as
+DIR/<name>.npy in float32 / float64; an array of more than DUMP_SAMPLES elements is written as its values at a fixed, seeded
+sample of flat positions (sorted), so two builds run with the same arguments can be compared file for file.
+
+Extra objects on the JSON line with --full:
   roofline     : achieved = 8 B/point (4 B read + 4 B written per input point) * points per step / wall
                  time of the step (all kernels + gaps), frac = achieved / 8 TB/s.  The timed region is the plain product call,
                  nothing recorded inside it; "kernel" holds the same figure for the longest kernel alone (its launch's points / its
@@ -42,6 +51,9 @@ if REPO not in sys.path:
 
 HBM_PEAK = 8.0e12  # B/s, MI355X spec (MI355X_MICROARCH.md)
 BYTES_PER_POINT = 8.0  # f32 in (4 B) + f32 out (4 B) per input point
+# --dump-outputs: elements kept of one output array (split over the ranks): 16 MiB of float64 or complex64 values, under 64 MB per run
+DUMP_SAMPLES = 1 << 21
+DUMP_SEED = 20261016
 
 
 def _cpu_pool_init():
@@ -94,13 +106,17 @@ def parse_args(argv=None):
     ap.add_argument("--nt", type=int, default=None, help="time slabs per GPU (default: 64; c5: 450 = 3600 / 8 under weak scaling; c2: 1024 rows)")
     ap.add_argument("--ny", type=int, default=4096)
     ap.add_argument("--nx", type=int, default=4096)
-    ap.add_argument("--cpu-slabs", type=int, default=10, help="slabs timed through the CPU oracle on one thread (0 = skip)")
-    ap.add_argument("--cpu-pool", type=int, default=-1, help="worker processes for the all-cores CPU figure, one slab each "
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: per-kernel HIP "
+                    "events (`roofline`), the memory-floor self-test, the CPU baseline and parity, the c2 / c4 / c5 legs, the gathered blocks' identity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                    "as DIR/<name>.npy (float32 / float64; a fixed seeded sample of an array larger than DUMP_SAMPLES elements)")
+    ap.add_argument("--cpu-slabs", type=int, default=10, help="(--full) slabs timed through the CPU oracle on one thread (0 = skip)")
+    ap.add_argument("--cpu-pool", type=int, default=-1, help="(--full) worker processes for the all-cores CPU figure, one slab each "
                     "(-1 = as many as host cores, slabs and memory allow; 0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short c2 / c4 / c5 legs that follow the headline at N = 1 (`extra_workloads`)")
-    ap.add_argument("--extra-steps", type=int, default=10, help="timed steps of each extra leg")
-    ap.add_argument("--no-floor", action="store_true", help="skip the library's memory-floor self-test (`roofline.measured_floor`)")
+    ap.add_argument("--no-profile", action="store_true", help="(--full) do not record per-kernel HIP events")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the short c2 / c4 / c5 legs that follow the headline at N = 1 (`extra_workloads`)")
+    ap.add_argument("--extra-steps", type=int, default=10, help="(--full) timed steps of each extra leg")
+    ap.add_argument("--no-floor", action="store_true", help="(--full) skip the library's memory-floor self-test (`roofline.measured_floor`)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --nt slabs PER GPU (default); strong: --nt slabs in total, contiguous blocks per rank")
     ap.add_argument("--workload", choices=["ps", "c2", "c4", "c5"], default="ps",
@@ -319,10 +335,9 @@ class Workload:
             self.dist.barrier()
         self.env.sync(self.dev)
 
-    def measure(self, steps, warmup, profile):
-        """W warm-up steps, then EXACTLY K steps between barriers with nothing else switched on (the wall clock of the product call);
-        then, outside the timed region, K more steps with the library's per-kernel HIP events for `roofline.kernel`.
-        Returns (seconds of the timed region, {kernel: (launches, ms)} of the profiled steps, the last result, the plan)."""
+    def measure(self, steps, warmup):
+        """W warm-up steps, then EXACTLY K steps between barriers with nothing else switched on (the wall clock of the product call).
+        Returns (seconds of the timed region, the result of the last timed step, the plan)."""
         from xrft_amd import api
 
         # setup (not a step): prime torch's caching allocator so that no hipMalloc of a multi-GiB output lands in the timed
@@ -341,19 +356,34 @@ class Workload:
             res = self.step()
         self.barrier()
         dt = time.perf_counter() - t0
-        prof = {}
-        if plan is not None and profile:
-            # the first launch that carries timestamps stalls its queue once (0.5 ms): one untimed step with the events on, records dropped
-            plan.set_profiling(True)
+        return dt, res, plan
+
+    def profile(self, steps, plan):
+        """Outside the timed region: K more steps with the library's per-kernel HIP events for `roofline.kernel`.
+        Returns {kernel: (launches, ms)} of the profiled steps."""
+        if plan is None:
+            return {}
+        # the first launch that carries timestamps stalls its queue once (0.5 ms): one untimed step with the events on, records dropped
+        plan.set_profiling(True)
+        res = self.step()
+        self.barrier()
+        plan.set_profiling(True)  # (clears the records)
+        for _ in range(steps):
             res = self.step()
-            self.barrier()
-            plan.set_profiling(True)  # (clears the records)
-            for _ in range(steps):
-                res = self.step()
-            self.barrier()
-            prof = plan.read_profile()
-            plan.set_profiling(False)
-        return dt, prof, res, plan
+        self.barrier()
+        del res
+        prof = plan.read_profile()
+        plan.set_profiling(False)
+        return prof
+
+    def outputs(self, res):
+        """(file name, DataArray) of what a caller of the timed path receives from one step."""
+        if self.name in ("ps", "c5"):
+            return [("power_spectrum", res)]
+        if self.name == "c2":
+            return [("dft", res)]
+        cs, ia, ib = res
+        return [("cross_spectrum", cs), ("isotropic_power_spectrum_a", ia), ("isotropic_power_spectrum_b", ib)]
 
     def parity(self, res):
         """max |hip - oracle| / max |oracle| on the first unit of the workload (one slab / one row / one slab pair), the oracle = the CPU
@@ -407,6 +437,54 @@ def kernel_roofline(wl, prof, steps):
                           "kernel alone has to move (input or intermediate read + intermediate or result written)"
                           + (" -- of one isotropic_power_spectrum call, the plan the events are recorded on: 4 B per point" if wl.name == "c4" else "")
             }, {k: round(v[1] / steps, 3) for k, v in kern.items()}, round(kernel_ms, 3)
+
+
+def dump_outputs(wl, res, out_dir, rank, world):
+    """--dump-outputs: the arrays of one step's result and their coordinates as out_dir/<name>.npy, complex values as a trailing
+    (real, imag) axis, float64 where the result is float64 (or an integer coordinate), float32 otherwise.  An array of more than
+    DUMP_SAMPLES / world elements is written as its values at the sorted, unique flat positions drawn by
+    numpy.random.default_rng(DUMP_SEED) -- the same positions in every run of the same shape.  With N > 1 every rank writes its
+    own shard, named <name>.rank<r>.npy.  Returns what was written (rank 0's files go on the JSON line)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    cap = max(1, DUMP_SAMPLES // world)
+    tag = f".rank{rank}" if world > 1 else ""
+    arrays = []
+    for name, da in wl.outputs(res):
+        n = int(np.prod(da.shape))
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=cap)) if n > cap else None
+        v = da.data
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            if v.is_conj():
+                v = v.resolve_conj()
+            if idx is not None:
+                v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+            v = v.cpu().numpy()
+        else:
+            v = np.asarray(v)
+            if idx is not None:
+                v = v.reshape(-1)[idx]
+        arrays.append((name, v, list(da.shape), idx is not None))
+        for cname, c in da.coords.items():
+            cv = np.asarray(c.values)
+            if cv.ndim >= 1 and cv.dtype.kind in "biufc":
+                arrays.append((f"{name}.{cname}", cv, list(cv.shape), False))
+    files, total = {}, 0
+    for name, v, shape, sampled in arrays:
+        wide = v.dtype in (np.float64, np.complex128) or v.dtype.kind in "biu"
+        if np.iscomplexobj(v):
+            v = np.stack([v.real, v.imag], axis=-1)
+        v = np.ascontiguousarray(v, dtype=np.float64 if wide else np.float32)
+        fname = f"{name}{tag}.npy"
+        np.save(os.path.join(out_dir, fname), v)
+        total += v.nbytes
+        files[fname] = {"shape": shape, "dtype": str(v.dtype), "sampled": sampled}
+    return {"dir": out_dir, "files": files, "bytes": total,
+            "sample": f"arrays of more than {cap} elements: values at the sorted unique flat positions of "
+                      f"numpy.random.default_rng({DUMP_SEED}).integers(0, size, {cap})"}
 
 
 def measured_floor(wl):
@@ -535,7 +613,8 @@ def extra_leg(name, args, env, dev):
     api.clear_plan_cache()
     wl = Workload(name, args, env, dev, 0, 1, None, default_sizes=True)
     steps = max(args.extra_steps, 50) if name == "c2" else args.extra_steps  # (c2's step is one 0.18-ms kernel: the barrier + synchronize bracket of a timed region is 0.4 ms)
-    dt, prof, res, plan = wl.measure(steps, 1, True)
+    dt, res, plan = wl.measure(steps, 1)
+    prof = wl.profile(steps, plan)
     value = 1e-9 * wl.points_per_step * steps / dt
     leg = {"metric": wl.metric, "value": round(value, 3), "unit": "GFFT/s", "steps": steps, "warmup": 1,
            "ms_per_step": round(1e3 * dt / steps, 3), "dtype": wl.dtype, "bytes_per_point": wl.bpp,
@@ -587,7 +666,9 @@ def run(args, env):
     nt, nt_total, ny, nx = wl.nt, wl.nt_total, wl.ny, wl.nx
     collective = wl.collective
 
-    dt, prof, ps, plan = wl.measure(args.steps, args.warmup, not args.no_profile)
+    dt, ps, plan = wl.measure(args.steps, args.warmup)
+    dumped = dump_outputs(wl, ps, args.dump_outputs, rank, world) if args.dump_outputs else None
+    prof = wl.profile(args.steps, plan) if args.full and not args.no_profile else {}
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if dist is not None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -601,7 +682,7 @@ def run(args, env):
 
         shard_sizes = [None] * world
         dist.all_gather_object(shard_sizes, int(nt))
-        if collective is not None:
+        if collective is not None and args.full:
             _cs, ia_, ib_ = ps
             dig = hashlib.sha1(np.ascontiguousarray(np.asarray(ia_.values)).tobytes() + np.ascontiguousarray(np.asarray(ib_.values)).tobytes()).hexdigest()
             digs = [None] * world
@@ -643,12 +724,13 @@ def run(args, env):
         # ---- CPU baseline (the oracle on a bounded sample, 1 thread) + parity of the same slabs
         cpu = None
         parity = None
-        if args.cpu_slabs > 0 and world == 1 and args.workload == "ps" and env.measures:
+        if args.full and args.cpu_slabs > 0 and world == 1 and args.workload == "ps" and env.measures:
             cpu, parity = cpu_baseline(wl, ps, args)
         out = {
             "metric": wl.metric, "value": round(value, 3), "unit": "GFFT/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": wl.dtype, "data": env.data_label,
+            "full": args.full, "dump_outputs": dumped,
             "config": {"workload": wl.wl, "nt_per_gpu": nt, "nt_total": nt_total, "ny": ny, "nx": nx, "parallelism": wl.par,
                        "collective": collective, "shard_sizes": shard_sizes, "slabs_per_s": round(nt_total * args.steps / dt, 2),
                        "ranks_in_process_group": ranks_reported, "process_group_backend": env.backend if dist is not None else None},
@@ -656,8 +738,8 @@ def run(args, env):
         }
         if plan is not None:
             out["plan"] = plan.describe().strip().split("\n")
-        # ---- the other BASELINE.json configurations, in this same process (N = 1, the headline command only): short legs after the headline
-        if world == 1 and args.workload == "ps" and env.measures and not args.no_extra and (ny, nx) == (4096, 4096):
+        # ---- the other BASELINE.json configurations, in this same process (N = 1, the headline command with --full): short legs after the headline
+        if args.full and world == 1 and args.workload == "ps" and env.measures and not args.no_extra and (ny, nx) == (4096, 4096):
             import gc
 
             del ps, wl, plan

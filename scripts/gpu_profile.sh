@@ -24,11 +24,11 @@ f=$(find $O/prof_bench -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$O/prof_c2" -o bench -- python3 "$GRAFT_REPO_ROOT/bench.py" --workload c2 --steps 20 --warmup 5 --cpu-slabs 0 --no-extra > "$GRAFT_REPO_ROOT/$O/prof_c2.json" 2> "$GRAFT_REPO_ROOT/$O/prof_c2.err"; echo "rocprof c2 rc=$?")
 f=$(find $O/prof_c2 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/c2_kernel_stats.csv && head -4 "$f" | cut -c1-200
 find $O -name "*kernel_trace.csv" -size +8M -delete
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "bench rc=$?"
+timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "bench rc=$?"
 # (C2's step is one 0.18-ms kernel: 50 steps, or the barrier + synchronize bracket of the timed region -- 0.4 ms -- is a fifth of it)
-timeout 300 python3 bench.py --gpus 1 --steps 50 --warmup 5 --workload c2 --cpu-slabs 0 > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench c2 rc=$?"
+timeout 300 python3 bench.py --gpus 1 --steps 50 --warmup 5 --workload c2 --cpu-slabs 0 --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench c2 rc=$?"
 for w in c4 c5; do
-  timeout 300 python3 bench.py --gpus 1 --steps 10 --warmup 3 --workload $w --cpu-slabs 0 > $O/bench_$w.json 2> $O/bench_$w.err; echo "bench $w rc=$?"
+  timeout 300 python3 bench.py --gpus 1 --steps 10 --warmup 3 --workload $w --cpu-slabs 0 --full > $O/bench_$w.json 2> $O/bench_$w.err; echo "bench $w rc=$?"
 done
 timeout 1500 python3 scripts/bench_configs.py > $O/bench_configs.txt 2>&1; echo "configs rc=$?"
 timeout 300 python3 scripts/host_overhead.py > $O/host_overhead.txt 2>&1; echo "host rc=$?"
