@@ -81,7 +81,7 @@ int fastg_build_iso(xrfthip_plan* P, const int32_t* bm) {
     const int ny = (int)P->d.ny, nx = (int)P->d.nx, n = P->g_n, rs = P->g_rs, nb = P->nbins;
     const bool packed = P->g_packed;
     const bool cross = P->d.out_mode == XRFTHIP_OUT_CROSS;  // (bit 15 of a position: the sample is the conjugate of the stored product)
-    if ((size_t)ny * rs > (cross ? 32767u : 65535u) || nb < 1) { P->fastg = false; return XRFTHIP_OK; }  // (16-bit positions; the other paths take the plan)
+    if ((size_t)ny * rs > (cross ? 32767u : 65535u) || nb < 1) { settle_family(P, true); return XRFTHIP_OK; }  // (16-bit positions; the generic passes take the plan)
     std::vector<unsigned> start((size_t)nb + 1, 0u);
     for (size_t e = 0; e < (size_t)ny * nx; ++e) if (bm[e] >= 0 && bm[e] < nb) ++start[(size_t)bm[e] + 1];
     for (int b = 0; b < nb; ++b) start[(size_t)b + 1] += start[(size_t)b];
@@ -300,6 +300,36 @@ template <typename T> int fastgy_blue_tables(xrfthip_plan* P) {
     if (!rc) rc = P->gy_blueb.upload(bh.data(), bh.size() * sizeof(C2<T>));
     return rc;
 }
+// FastGY: one transform axis that is not the contiguous one (XRFTHIP_AXIS_Y), any smooth length: one pass in LDS with the radices as data
+// (fastg.h: fastgy_kernel) -- or, along the CONTIGUOUS axis of a 1-D plan whose length holds ONE prime 17 ... 127 (365 / 730 / 1460-sample
+// (station, time) rows), the same kernel's prime-factor / Rader form with the lanes along the samples (FORM 3, gy_rows)
+int try_fastgy(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const bool cplx_in = P->cplx_in, two = plan_two(P);  // (two REAL fields: a column of each = one packed sequence; no flipped field)
+    if (!(d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER || (two && !cplx_in)) || env_ll("XRFTHIP_FASTG", 1) == 0) return kDeclined;
+    const uint32_t conj = (cplx_in && d.out_mode == XRFTHIP_OUT_COMPLEX) ? (XRFTHIP_INVERSE | XRFTHIP_PHASE_IN) : 0u;  // (xrft.ifft: conj in, conj out, the input rotated)
+    const uint32_t half = !cplx_in ? (XRFTHIP_HALF_X | (d.out_mode != XRFTHIP_OUT_PHASE ? XRFTHIP_REALDIM_X2 : 0u)) : 0u;
+    int rc;
+    if (d.flags & XRFTHIP_AXIS_Y) {
+        const uint32_t allowed = XRFTHIP_AXIS_Y | XRFTHIP_SHIFT_Y | (d.out_mode != XRFTHIP_OUT_POWER ? XRFTHIP_ISHIFT_Y : 0u) | conj | half;
+        if ((d.flags & ~allowed) || ((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_Y)) || !fastgy_try(P)) return kDeclined;
+        P->family = P->chosen = Family::FastGY;
+        const long long m = P->gy_blue_m ? P->gy_blue_m : d.ny;  // length of the passes
+        rc = plan_twiddle(P, P->g_twy, m, m);
+        if (!rc && !P->gy_rad_p) rc = fastg_rev(P->g_ry, (int)m, P->g_revy, P->g_hrevy);
+        if (!rc && P->gy_rad_p) rc = P->dbl ? fastgy_rader_tables<double>(P) : fastgy_rader_tables<float>(P);
+        if (!rc && P->gy_blue_m) rc = P->dbl ? fastgy_blue_tables<double>(P) : fastgy_blue_tables<float>(P);
+    } else {  // (every other 1-D length has its kernels elsewhere)
+        const uint32_t allowed = XRFTHIP_SHIFT_X | (d.out_mode != XRFTHIP_OUT_POWER ? XRFTHIP_ISHIFT_X : 0u) | conj | half;
+        const bool half_ok = !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X)) && !((d.flags & XRFTHIP_REALDIM_X2) && !(d.flags & XRFTHIP_HALF_X));
+        if (!half_ok || d.ndim != 1 || (d.flags & ~allowed) || !fastgy_try(P, true)) return kDeclined;
+        P->family = P->chosen = Family::FastGY;
+        rc = plan_twiddle(P, P->g_twy, d.nx, d.nx);
+        if (!rc) rc = P->dbl ? fastgy_rader_tables<double>(P) : fastgy_rader_tables<float>(P);
+    }
+    return rc;
+}
+
 int run_fastgy(const xrfthip_plan* P, const void* in, const void* in_b, void* out, hipStream_t st) {
     const xrfthip_desc& d = P->d;
     FastGY p{};
@@ -360,6 +390,27 @@ long long fastg_threads(const xrfthip_plan* P) {
         if (res > best_res) { best = w; best_res = res; }
     }
     return best * 64;
+}
+
+// FastG: a small slab of any smooth shape, either precision, that none of the specialised kernels before it takes: one pass in LDS (fastg.h);
+// complex input (fft of complex data, every inverse transform): power / complex, no detrend, no real_dim, no radial sums.  A 1-D transform
+// along x: the same kernel on groups of rows (g_one_d)
+int try_fastg(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const bool cplx_in = P->cplx_in;
+    const bool cin_ok = !cplx_in || ((d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_COMPLEX) && !d.detrend && !(d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2 | XRFTHIP_ISO)) &&
+                                     (!(d.flags & XRFTHIP_C2R_X) || !(d.nx & 1)));
+    const uint32_t okg = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | ((cplx_in && d.out_mode == XRFTHIP_OUT_COMPLEX) ? (XRFTHIP_INVERSE | XRFTHIP_PHASE_IN | XRFTHIP_C2R_X) : 0u) |
+                         (d.out_mode == XRFTHIP_OUT_COMPLEX ? (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X)
+                          : d.out_mode == XRFTHIP_OUT_CROSS ? (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X | XRFTHIP_REALDIM_X2 | XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT)  // (no flipped field: the other paths)
+                          : (XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT | XRFTHIP_REALDIM_X2));
+    const bool one_ok = d.ndim != 1 || !(d.flags & (XRFTHIP_ISO | XRFTHIP_SHIFT_Y | XRFTHIP_ISHIFT_Y));
+    if (!(one_ok && cin_ok && (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_CROSS) && !(d.flags & ~okg) &&
+          !((d.flags & XRFTHIP_HALF_X) && (d.flags & (XRFTHIP_ISO | XRFTHIP_SHIFT_X | XRFTHIP_SHIFT_Y))) && env_ll("XRFTHIP_FASTG", 1) != 0 && fastg_try(P))) return kDeclined;
+    P->family = P->chosen = Family::FastG;
+    int rc = P->dbl ? fastg_setup_t<double>(P) : fastg_setup_t<float>(P);
+    if (!rc) rc = plan_ones(P, std::max<long long>(std::max(d.ny, d.nx), P->g_rows));
+    return rc;
 }
 
 int run_fastg(const xrfthip_plan* P, const void* in, const void* in_b, void* out, double* iso, hipStream_t st) {

@@ -51,21 +51,21 @@ int fastm_rpu(long long nx, bool two, bool dbl) { const MGeomRt r = mgeom(nx, db
 int fastm_rk2(long long ny, long long nx, bool two, bool dbl) { return std::max(1, std::min(fastm_rk(ny, nx, dbl), fastm_rpu(nx, two, dbl))); }
 // ... of a plan: the table's geometry, or what fastn_setup chose when either pass runs on the run-time-radix kernels (fastn.h)
 bool plan_two(const xrfthip_plan* P) { return P->d.out_mode == XRFTHIP_OUT_CROSS || P->d.out_mode == XRFTHIP_OUT_PHASE; }
-int plan_cw(const xrfthip_plan* P) { return P->fastn ? P->n_cw : fastm_cw(P->yny, P->ynx, P->dbl); }
-int plan_rk2(const xrfthip_plan* P) { return P->fastn ? P->n_rk : fastm_rk2(P->yny, P->ynx, plan_two(P), P->dbl); }
-int plan_nxb(const xrfthip_plan* P) { return P->fastn ? P->n_nxb : (int)(P->ynx / fastm_cw(P->yny, P->ynx, P->dbl)); }
+int plan_cw(const xrfthip_plan* P) { return P->family == Family::FastN ? P->n_cw : fastm_cw(P->yny, P->ynx, P->dbl); }
+int plan_rk2(const xrfthip_plan* P) { return P->family == Family::FastN ? P->n_rk : fastm_rk2(P->yny, P->ynx, plan_two(P), P->dbl); }
+int plan_nxb(const xrfthip_plan* P) { return P->family == Family::FastN ? P->n_nxb : (int)(P->ynx / fastm_cw(P->yny, P->ynx, P->dbl)); }
 
 // radial sums inside pass 2 when the per-bin tables fit behind the transforms' LDS (64 KB of dynamic LDS per workgroup); otherwise
 // the spectrum is stored and summed by run_radial_sums
 // a radial bin map (fastm_build_tfirst) is gathered per bin without atomics or tables; a cross spectrum with a true-phase factor keeps
 // the general path (the factor of a sample and of its Hermitian twin differ)
 bool fastm_iso_gather(const xrfthip_plan* P) {
-    return P->fastm && (P->d.flags & XRFTHIP_ISO) && P->nbins >= 1 && P->ytfirst_on && !(P->d.out_mode == XRFTHIP_OUT_CROSS && P->fph_on);
+    return fastm_pipeline(P) && (P->d.flags & XRFTHIP_ISO) && P->nbins >= 1 && P->ytfirst_on && !(P->d.out_mode == XRFTHIP_OUT_CROSS && P->fph_on);
 }
 bool fastm_iso_fused(const xrfthip_plan* P) {
-    if (!P->fastm || !(P->d.flags & XRFTHIP_ISO) || P->nbins < 1) return false;
+    if (!fastm_pipeline(P) || !(P->d.flags & XRFTHIP_ISO) || P->nbins < 1) return false;
     if (fastm_iso_gather(P)) return true;
-    if (P->fastn && P->n_r.rt) return false;  // (the run-time-radix row kernel fuses the gather of a radial map only: any other map is summed from the stored spectrum)
+    if (P->family == Family::FastN && P->n_r.rt) return false;  // (the run-time-radix row kernel fuses the gather of a radial map only: any other map is summed from the stored spectrum)
     const bool cx = P->d.out_mode == XRFTHIP_OUT_CROSS;
     const MGeomRt R = mgeom(P->ynx, P->dbl);
     return (cx ? R.lds_rows : R.lds_r1) + (size_t)P->nbins * (cx ? 20 : 12) <= 64 * 1024;
@@ -85,7 +85,7 @@ int fastm_iso_ncopy(const xrfthip_plan* P) {
 // rows per pass-2 workgroup of this plan: two fields share a workgroup's sequences (MRowsG in fastm.h)
 int fastm_gather_rpu(const xrfthip_plan* P) { return fastm_rows_rpu(P); }
 int fastm_rows_rpu(const xrfthip_plan* P) {
-    if (P->fastn) return P->n_rpu;
+    if (P->family == Family::FastN) return P->n_rpu;
     const bool two = P->d.out_mode == XRFTHIP_OUT_CROSS || P->d.out_mode == XRFTHIP_OUT_PHASE;
     const MGeomRt r = mgeom(P->ynx, P->dbl);
     return two ? r.g / 2 : r.g_r1;
@@ -401,7 +401,6 @@ bool fastn_setup(xrfthip_plan* P) {
     if (!rows_rt && pitch != d.nx) return false;
     int rk = (int)std::max<long long>(1, std::min<long long>((long long)(128 / (cw * cs)), rpu));
     if (rpu % rk != 0) return false;
-    P->fastn = true;
     P->n_c.rt = cols_rt; P->n_c.geo = gc; P->n_c.lds = cols_rt ? fastn_lds(gc, cs, true) + (rad_p ? 2 * (((size_t)d.ny + 7) & ~(size_t)7) * 2 : 0) : 0;
     P->n_rad_p = rad_p; P->n_rq = rq; P->n_rp = rp;
     P->n_dbg = (int)env_ll("XRFTHIP_FASTN_DBG", 0);
@@ -495,7 +494,7 @@ void fastm_launch_cols(const xrfthip_plan* P, const FastM& p, long long gc, hipS
     const xrfthip_desc& d = P->d;
     const MGeomRt C = mgeom_cols(P->yny, P->ynx, P->dbl);
     const bool wide = fastm_wide(P->yny, P->ynx, P->dbl);
-    const bool rt = P->fastn && P->n_c.rt;  // (the run-time-radix kernel: fastn.h)
+    const bool rt = P->family == Family::FastN && P->n_c.rt;  // (the run-time-radix kernel: fastn.h)
     xrfthip_plan::ProfRec* rec = prof_begin(P, rt ? "fastn_cols" : "fastm_cols", st);
     if (rt) fastn_launch_cols(P, p, st);
     const dim3 grid((unsigned)(8 * ((p.nunits + 7) / 8))), blk((unsigned)C.thr);
@@ -537,7 +536,7 @@ void fastm_launch_rows(const xrfthip_plan* P, const FastM& p, long long gc, hipS
     const xrfthip_desc& d = P->d;
     const MGeomRt R = mgeom(P->ynx, P->dbl);
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
-    const bool rt = P->fastn && P->n_r.rt;  // (the run-time-radix kernel: fastn.h)
+    const bool rt = P->family == Family::FastN && P->n_r.rt;  // (the run-time-radix kernel: fastn.h)
     xrfthip_plan::ProfRec* rec = prof_begin(P, rt ? "fastn_rows" : "fastm_rows", st);
     const bool fused = fastm_iso_fused(P), full = two;  // (full: pass 1's sequence count per workgroup)
     if (rt) { fastn_launch_rows(P, p, gc, fused, st); prof_end(rec, st); return; }
@@ -556,6 +555,57 @@ void fastm_launch_rows(const xrfthip_plan* P, const FastM& p, long long gc, hipS
 #undef XF_
 #undef MR_
     prof_end(rec, st);
+}
+
+// the flags the two y-first passes of fastm.h / fastn.h take (real slabs, float32 or float64)
+static bool fastm_flags_ok(const xrfthip_desc& d) {
+    const uint32_t shifts = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X, ish = XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X;
+    const uint32_t isof = XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT;  // radial sums: fused into pass 2, or a pass over the stored spectrum (run_radial_sums)
+    const uint32_t halff = XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2;     // real_dim: half output, no mirror columns
+    const uint32_t allowed = d.out_mode == XRFTHIP_OUT_POWER ? (shifts | isof | halff) : d.out_mode == XRFTHIP_OUT_CROSS ? (shifts | ish | isof | halff)
+                             : (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_PHASE) ? (shifts | ish | XRFTHIP_HALF_X) : 0u;
+    const bool half_ok = !((d.flags & halff) && (d.flags & XRFTHIP_ISO)) && !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X));
+    return half_ok && d.ndim == 2 && (d.dtype == XRFTHIP_F64 || d.dtype == XRFTHIP_F32) && !(d.flags & ~allowed);
+}
+
+// FastM: real slabs on the regular lat/lon lengths, the mixed-radix form of the y-first pipeline (fastm.h)
+int try_fastm(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    if (!(fastm_flags_ok(d) && fastm_len(d.ny, P->dbl) && fastm_len(d.nx, P->dbl) && env_ll("XRFTHIP_FASTM", 1) != 0 && env_ll("XRFTHIP_FASTN_TABLES", 1) != 0)) return kDeclined;
+    const bool two = plan_two(P);
+    const int rpu2 = fastm_rpu(d.nx, two, P->dbl);
+    if (rpu2 < 1 || rpu2 % fastm_rk2(d.ny, d.nx, two, P->dbl) != 0 || d.nx % fastm_cw(d.ny, d.nx, P->dbl) != 0) return kDeclined;
+    P->family = P->chosen = Family::FastM;
+    const int rpu = two ? fastm_rpu(d.nx, true, P->dbl) : mgeom(d.nx, P->dbl).g;  // (the largest count a row kernel of this plan may use)
+    P->yny = d.ny; P->ynx = d.nx; P->y_pitch = d.nx;
+    P->y_nrow_pad = (int)((d.ny / 2 + 1 + rpu - 1) / rpu * rpu);
+    int rc = plan_twiddle(P, P->tw_fx, d.nx, d.nx);
+    if (!rc) rc = plan_twiddle(P, P->tw_fy, d.ny, d.ny);
+    if (!rc) rc = plan_ones(P, std::max(d.ny, d.nx));
+    return rc;
+}
+
+// FastN: every other large real slab whose lengths the butterflies factor (the columns: any length, through a chirp convolution): the
+// y-first pipeline with the lengths as data (fastn.h) -- either pass may still be the table kernel of fastm.h when its length is in the table
+int try_fastn(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    if (!(fastm_flags_ok(d) && env_ll("XRFTHIP_FASTN", 1) != 0)) return kDeclined;
+    P->yny = d.ny; P->ynx = d.nx;
+    if (!fastn_setup(P)) return kDeclined;
+    P->family = P->chosen = Family::FastN;
+    const int rpu = P->n_r.rt ? P->n_rpu : (plan_two(P) ? fastm_rpu(d.nx, true, P->dbl) : mgeom(d.nx, P->dbl).g);  // (the largest count a row kernel of this plan may use)
+    P->y_nrow_pad = (int)((d.ny / 2 + 1 + rpu - 1) / rpu * rpu);
+    const long long ylen = P->n_blue_m ? P->n_blue_m : d.ny;
+    int rc = plan_twiddle(P, P->tw_fx, d.nx, d.nx);
+    if (!rc) rc = plan_twiddle(P, P->tw_fy, ylen, ylen);
+    if (!rc) rc = plan_ones(P, std::max(d.ny, d.nx));
+    if (!rc && P->n_c.rt && P->n_rad_p) rc = P->dbl ? fastn_rader_tables<double>(P) : fastn_rader_tables<float>(P);
+    else if (!rc && P->n_c.rt) rc = P->dbl ? fastn_upload_twm<double>(P->n_c.geo, P->n_c.twm, P->n_blue_m != 0) : fastn_upload_twm<float>(P->n_c.geo, P->n_c.twm, P->n_blue_m != 0);
+    if (!rc && P->n_r.rt) rc = P->dbl ? fastn_upload_twm<double>(P->n_r.geo, P->n_r.twm) : fastn_upload_twm<float>(P->n_r.geo, P->n_r.twm);
+    if (!rc && P->n_blue_m) rc = P->dbl ? fastn_blue_tables<double>(P) : fastn_blue_tables<float>(P);
+    if (!rc && P->n_c.rt) rc = P->n_c.geo_dev.upload(&P->n_c.geo, sizeof(NGeo));
+    if (!rc && P->n_r.rt) rc = P->n_r.geo_dev.upload(&P->n_r.geo, sizeof(NGeo));
+    return rc;
 }
 
 int run_fastm(const xrfthip_plan* P, const void* in, const void* in1, void* out, double* iso, char* ws, hipStream_t st) {
@@ -622,6 +672,24 @@ MGeomRt mygeom(long long n, bool dbl) {
     }
     return mgeom(n, dbl);
 }
+// FastMY: one transform axis that is not the contiguous one (XRFTHIP_AXIS_Y): pass 1 of the table kernels is the whole transform
+int try_fastmy(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const bool cplx_in = P->cplx_in, two = plan_two(P);
+    const uint32_t allowed = XRFTHIP_AXIS_Y | XRFTHIP_SHIFT_Y | (d.out_mode != XRFTHIP_OUT_POWER ? XRFTHIP_ISHIFT_Y : 0u) |
+                             ((cplx_in && d.out_mode == XRFTHIP_OUT_COMPLEX) ? (XRFTHIP_INVERSE | XRFTHIP_PHASE_IN) : 0u) |  // (xrft.ifft along the axis)
+                             (!cplx_in ? (XRFTHIP_HALF_X | (d.out_mode != XRFTHIP_OUT_PHASE ? XRFTHIP_REALDIM_X2 : 0u)) : 0u);  // (real_dim along the axis: half output)
+    if (!((d.flags & XRFTHIP_AXIS_Y) && d.ndim == 2 && (!cplx_in || !two) &&
+          (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER || two) && !(d.flags & ~allowed) && fastmy_len(d.ny, P->dbl) &&
+          !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_Y)) &&  // (the half output is unshifted: also refused by xrfthip_plan_create, kept here so the two cannot drift apart)
+          d.batch * d.nx < (1LL << 30) && env_ll("XRFTHIP_FASTM", 1) != 0)) return kDeclined;
+    if (!(cplx_in && !two) && d.nx % ((two ? 1 : 2) * mygeom(d.ny, P->dbl).g) != 0) return kDeclined;  // (complex columns: any count, the last block guarded)
+    P->family = P->chosen = Family::FastMY;
+    int rc = plan_twiddle(P, P->tw_fy, d.ny, d.ny);
+    if (!rc) rc = plan_ones(P, d.ny);
+    return rc;
+}
+
 int run_fastmy(const xrfthip_plan* P, const void* in, const void* in1, void* out, hipStream_t st) {
     const xrfthip_desc& d = P->d;
     const MGeomRt C = mygeom(d.ny, P->dbl);
@@ -667,6 +735,21 @@ MGeomRt mxgeom(long long n, bool dbl) {
     if (dbl && n == 2048) return mgeom_t<double, 2048>();
     return mygeom(n, dbl);
 }
+// FastMX: one short transform axis, the contiguous one: rows packed in pairs through the same passes
+int try_fastmx(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const bool cplx_in = P->cplx_in, two = plan_two(P);
+    const uint32_t allowed = XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | (d.out_mode != XRFTHIP_OUT_PHASE ? XRFTHIP_REALDIM_X2 : 0u) | (d.out_mode != XRFTHIP_OUT_POWER ? XRFTHIP_ISHIFT_X : 0u) |
+                             ((cplx_in && d.out_mode == XRFTHIP_OUT_COMPLEX) ? (XRFTHIP_INVERSE | XRFTHIP_PHASE_IN | XRFTHIP_C2R_X) : 0u);  // (xrft.ifft along the contiguous axis: conj in, conj out, the input rotated; irfft: two half rows per transform)
+    if (!(d.ndim == 1 && (!cplx_in || (!two && !(d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2)))) && (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER || two) &&
+          !(d.flags & ~allowed) && !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X)) && !((d.flags & XRFTHIP_REALDIM_X2) && !(d.flags & XRFTHIP_HALF_X)) &&
+          fastmx_len(d.nx, P->dbl) && d.batch < (1LL << 31) - 16 && env_ll("XRFTHIP_FASTM", 1) != 0)) return kDeclined;
+    P->family = P->chosen = Family::FastMX;
+    int rc = plan_twiddle(P, P->tw_fx, d.nx, d.nx);
+    if (!rc) rc = plan_ones(P, d.nx);
+    return rc;
+}
+
 int run_fastmx(const xrfthip_plan* P, const void* in, const void* in1, void* out, hipStream_t st) {
     const xrfthip_desc& d = P->d;
     const MGeomRt C = mxgeom(d.nx, P->dbl);

@@ -9,7 +9,7 @@ int fast_phase_tables(xrfthip_plan* P) {
         const long long n = ax == 0 ? d.ny : d.nx;
         const bool sign = d.out_mode == XRFTHIP_OUT_COMPLEX && !(d.flags & XRFTHIP_INVERSE) && (d.flags & (ax == 0 ? XRFTHIP_ISHIFT_Y : XRFTHIP_ISHIFT_X));  // (an inverse plan rotates its input)
         std::vector<cf> t((size_t)n);
-        const bool dtab = (P->fastm || P->fastmy || P->fastmx || P->fastg || P->fastgy || P->fusedi) && P->dbl;
+        const bool dtab = dbl_phase_tables(P);
         std::vector<C2<double>> td(dtab ? (size_t)n : 0);
         for (long long k = 0; k < n; ++k) {
             double re = 1.0, im = 0.0;
@@ -30,21 +30,14 @@ int fast_phase_tables(xrfthip_plan* P) {
     return XRFTHIP_OK;
 }
 
-bool phase_nontrivial(const xrfthip_plan* P) {
+// an isotropic cross spectrum with a true-phase factor that is not 1 (two fields with different lags): its radial sums would need
+// the factor per sample, which neither FastG's pass nor FastY's column pass carries (settle_family)
+bool cross_iso_phase(const xrfthip_plan* P) {
+    if (P->d.out_mode != XRFTHIP_OUT_CROSS || !(P->d.flags & XRFTHIP_ISO)) return false;
     for (int ax = 0; ax < 2; ++ax)
         for (size_t k = 0; k + 1 < P->host_phase[ax].size(); k += 2)
             if (std::fabs(P->host_phase[ax][k] - 1.0) > 1e-12 || std::fabs(P->host_phase[ax][k + 1]) > 1e-12) return true;
     return false;
-}
-
-// the specialised path is taken unless an isotropic cross spectrum carries a true-phase factor that is not 1 (two
-// fields with different lags): its radial sums would need the factor per sample inside the column pass
-bool fast_on(const xrfthip_plan* P) {
-    if (P->fastm) return true;
-    if (P->fast1d) return true;  // (a window rides on a slab-shaped table: fasty_window_spectra_1d)
-    if (!P->fast4096) return false;
-    if (P->d.out_mode == XRFTHIP_OUT_CROSS && (P->d.flags & XRFTHIP_ISO) && phase_nontrivial(P)) return false;
-    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -71,7 +64,7 @@ YGeomRt yrows_geom(long long nx, bool fs) {  // .rk = rows per workgroup; fs: th
     switch (nx) { case 4096: return yrows_geom_t<4096>(); case 2048: return yrows_geom_t<2048>(); case 1024: return yrows_geom_t<1024>();
                   case 512: return yrows_geom_t<512>(); default: return yrows_geom_t<256>(); }
 }
-long long fasty_rows_gx(const xrfthip_plan* P) { return yrows_geom(P->ynx, P->fast1d).gxy; }
+long long fasty_rows_gx(const xrfthip_plan* P) { return yrows_geom(P->ynx, P->family == Family::FastY1D).gxy; }
 int ilog2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 // Four-step 1-D with a window w[n], n = nx i1 + i2: the slab-shaped float32 window table pass 1 reads, and -- column i2 of the view has
@@ -133,7 +126,7 @@ int fasty_window_spectra(xrfthip_plan* P) {
         r0 = o0r; i0 = o0i; r1 = o1r; i1 = o1i;
     }
     const int nent = P->y_nrow_pad;
-    if ((P->fastm || P->fusedi) && P->dbl) {
+    if (dbl_phase_tables(P)) {
         std::vector<C2<double>> d0((size_t)nent), d1((size_t)nent);
         for (int k = 0; k < nent; ++k) {
             d0[(size_t)k].re = k <= nyh ? r0[(size_t)k] : 0.0; d0[(size_t)k].im = k <= nyh ? i0[(size_t)k] : 0.0;
@@ -316,8 +309,6 @@ bool fasty_iso_tables_fit(const xrfthip_plan* P, int nbins) {
     return nbins <= 65534 && (size_t)nbins * (8 * hw + 4) <= half;
 }
 
-bool fasty_on(const xrfthip_plan* P) { return P->yfirst && fast_on(P); }
-
 // Workgroups of `kernel` the whole device holds at once (a persistent launch's grid): the occupancy calculator's count per CU times the CUs,
 // asked once per kernel.
 long long resident_workgroups(const void* kernel, int threads, size_t lds) {
@@ -353,7 +344,7 @@ void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long gc, hipS
     prof_end(rec, st);
     if (d.detrend) {  // plane (2-D) or line through the whole sequence (four-step 1-D) from the per-column sums -> what pass 2 has to add back
         rec = prof ? prof_begin(P, "fasty_fit", st) : nullptr;
-        if (P->fast1d) { auto kf = &fasty_fit1d_kernel; XRFT_LAUNCH(kf, dim3((unsigned)gc), dim3(256), 3 * 256 * sizeof(double), st, (const double*)p.colfit, const_cast<float*>(p.corr), (int)P->ynx, (int)P->yny, (int)d.detrend); }
+        if (P->family == Family::FastY1D) { auto kf = &fasty_fit1d_kernel; XRFT_LAUNCH(kf, dim3((unsigned)gc), dim3(256), 3 * 256 * sizeof(double), st, (const double*)p.colfit, const_cast<float*>(p.corr), (int)P->ynx, (int)P->yny, (int)d.detrend); }
         else { auto kf = &fasty_fit_kernel; XRFT_LAUNCH(kf, dim3((unsigned)gc), dim3(256), 3 * 256 * sizeof(double), st, (const double*)p.colfit, p.win_x, const_cast<float*>(p.corr), (int)P->ynx, (int)P->yny, (int)d.detrend); }
         prof_end(rec, st);
     }
@@ -361,20 +352,20 @@ void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long gc, hipS
 
 void fasty_launch_rows(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof) {
     const xrfthip_desc& d = P->d;
-    const YGeomRt R = yrows_geom(P->ynx, P->fast1d);
+    const YGeomRt R = yrows_geom(P->ynx, P->family == Family::FastY1D);
     const bool iso_on = (d.flags & XRFTHIP_ISO) != 0;
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
     xrfthip_plan::ProfRec* rec = prof ? prof_begin(P, "fasty_rows", st) : nullptr;
     const int rpu = two ? R.gxy : R.rk;  // a cross spectrum spends both transforms of a thread on one row (field 0, field 1)
     // (four-step: rows 0 .. ny/2 - 1 in whole units, the Nyquist rows of R.gxy consecutive slabs in one extra unit each)
-    const dim3 grid((unsigned)(P->fast1d ? gc * ((P->yny / 2) / rpu) + (gc + R.gxy - 1) / R.gxy : gc * (P->y_nrow_pad / rpu))), blk((unsigned)R.thr);
+    const dim3 grid((unsigned)(P->family == Family::FastY1D ? gc * ((P->yny / 2) / rpu) + (gc + R.gxy - 1) / R.gxy : gc * (P->y_nrow_pad / rpu))), blk((unsigned)R.thr);
     const int hw = d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1;
     const size_t lds = R.lds;  // (the radial-sum tables alias the transforms' LDS)
     // nothing but the radial sums of a radial map leaves the pass: the persistent kernel of fasty_iso.h (as many workgroups as the chip holds)
     // (measured, profiles/r06_tune_iso.txt: with the pipelined gather in BOTH kernels the workgroup-per-unit kernel is level or ahead -- 19.1 against 19.5 us per 4096^2
     // slab, 4.87 against 5.26 at 2048^2, 1.21 against 1.20 at 1024^2 -- so the persistent kernel is opt-in: XRFTHIP_ISOROWS=1; =2 its profiling build)
     const bool iso_persistent = P->tune_isorows == 2 || P->tune_isorows == 1;
-    if (iso_on && p.out == nullptr && p.tfirst != nullptr && !P->fast1d && iso_persistent && P->ynx >= 1024 &&
+    if (iso_on && p.out == nullptr && p.tfirst != nullptr && P->family != Family::FastY1D && iso_persistent && P->ynx >= 1024 &&
         (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_CROSS)) {
         const long long total = gc * (P->y_nrow_pad / rpu);
         const bool tim = P->tune_isorows == 2;
@@ -409,7 +400,7 @@ void fasty_launch_rows(const xrfthip_plan* P, const FastY& p, long long gc, hipS
         else if (d.out_mode == XRFTHIP_OUT_CROSS) { if (iso_on) { auto k = &fasty_rows_kernel<NN, 2, true>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } else { auto k = &fasty_rows_kernel<NN, 2, false>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } } \
         else if (d.out_mode == XRFTHIP_OUT_PHASE) { auto k = &fasty_rows_kernel<NN, 3, false>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } \
         else { auto k = &fasty_rows_kernel<NN, 0, false>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } } while (0)
-    if (P->fast1d) {  // four-step 1-D: rows of 256 samples, transposed stores
+    if (P->family == Family::FastY1D) {  // four-step 1-D: rows of 256 samples, transposed stores
         if (P->fast1d_win) {
             if (d.out_mode == XRFTHIP_OUT_POWER) { auto k = &fasty_rows_kernel<256, 1, false, true, true>; XRFT_LAUNCH(k, grid, blk, lds, st, p); }
             else { auto k = &fasty_rows_kernel<256, 0, false, true, true>; XRFT_LAUNCH(k, grid, blk, lds, st, p); }
@@ -473,11 +464,87 @@ FastY fasty_params(const xrfthip_plan* P, const float* in, void* out, double* is
     p.nslab = (int)gc;
     p.shift_y = (d.flags & XRFTHIP_SHIFT_Y) ? (int)(P->yny / 2) : 0;
     p.shift_x = (d.flags & XRFTHIP_SHIFT_X) ? (int)(P->ynx / 2) : 0;  // (four-step 1-D: the shift by N/2 samples is k2 + nx/2)
-    if (P->fast1d) p.win_y = p.win_x = reinterpret_cast<const float*>(P->ones4096.p);  // (a window of the whole sequence: win2d)
+    if (P->family == Family::FastY1D) p.win_y = p.win_x = reinterpret_cast<const float*>(P->ones4096.p);  // (a window of the whole sequence: win2d)
     p.win2d = reinterpret_cast<const float*>(P->fast1d_win ? P->win2d.p : nullptr);
     p.scale = (float)d.scale;
     p.tune = (int)P->tune_y;
     return p;
+}
+
+// FastY: real float32 slabs whose two lengths are 256 .. 4096 powers of two, every mode (fasty_fits: also the fallback FastS builds beside itself)
+bool fasty_fits(const xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const uint32_t shifts = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X, ish = XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X, isof = XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT;
+    const uint32_t halff = XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2;  // real_dim: half output, no mirror
+    const uint32_t allowed = d.out_mode == XRFTHIP_OUT_POWER ? (shifts | isof | halff) : d.out_mode == XRFTHIP_OUT_COMPLEX ? (shifts | ish | XRFTHIP_HALF_X)
+                             : d.out_mode == XRFTHIP_OUT_CROSS ? (shifts | ish | isof | halff) : d.out_mode == XRFTHIP_OUT_PHASE ? (shifts | ish | XRFTHIP_HALF_X) : 0u;
+    return d.ndim == 2 && fasty_len(d.ny) && fasty_len(d.nx) && d.dtype == XRFTHIP_F32 &&
+           !(d.flags & ~allowed) && !((d.flags & halff) && (d.flags & XRFTHIP_ISO)) && !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X));
+}
+int fasty_tables(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    P->yny = d.ny; P->ynx = d.nx;
+    const int rpu = yrows_geom(d.nx).rk;
+    P->y_nrow_pad = (int)((d.ny / 2 + 1 + rpu - 1) / rpu * rpu);
+    int rc = plan_twiddle(P, P->tw_fx, d.nx, d.nx);
+    if (!rc) rc = plan_twiddle(P, P->tw_fy, d.ny, d.ny);
+    if (!rc) rc = plan_ones(P, std::max(d.ny, d.nx));
+    return rc;
+}
+int try_fasty(xrfthip_plan* P) {
+    if (!fasty_fits(P)) return kDeclined;
+    P->family = P->chosen = Family::FastY;
+    return fasty_tables(P);
+}
+
+// FastY1D: one long real float32 sequence per slab, N = n1 * 256 samples (2^16 .. 2^20): the two passes of the y-first pipeline are
+// the two steps of its four-step transform (fasty.h, FS)
+int try_fast1d(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const long long n1 = d.nx / 256;
+    const bool pow2 = d.nx >= 65536 && d.nx <= (1LL << 20) && (d.nx & (d.nx - 1)) == 0;
+    const uint32_t ok1 = XRFTHIP_SHIFT_X | (d.out_mode == XRFTHIP_OUT_COMPLEX ? XRFTHIP_ISHIFT_X : 0u);
+    if (!(d.ndim == 1 && pow2 && d.dtype == XRFTHIP_F32 && (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER) &&
+          !(d.flags & ~ok1) && env_ll("XRFTHIP_FAST1D", 1) != 0)) return kDeclined;
+    P->family = P->chosen = Family::FastY1D;
+    P->yny = n1; P->ynx = 256;
+    const int rpu = yrows_geom(256, true).rk;
+    P->y_nrow_pad = (int)((n1 / 2 + 1 + rpu - 1) / rpu * rpu);
+    int rc = plan_twiddle(P, P->tw_fx, 256, 256);
+    if (!rc) rc = plan_twiddle(P, P->tw_fy, n1, n1);
+    if (!rc) rc = plan_twiddle(P, P->tw_big1d, d.nx, d.nx / 2 + 1);
+    if (!rc) rc = plan_ones(P, std::max<long long>(n1, 256));
+    return rc;
+}
+
+// FastYC: complex float32 slabs of the fasty lengths (fasty_c2c.h); FastYCFourStep: ONE long complex float32 sequence per batch entry,
+// 2^16 .. 2^20 points (xrft.ifft of the spectrum of a long row, fft of complex rows: the inverse twin of BASELINE config 2): the same two
+// passes on the [n / 256][256] view, pass 2 in its four-step form (before: the generic four-step passes, 49 GFFT/s)
+int try_fastyc(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    if (d.dtype != XRFTHIP_C64 || d.detrend || (d.out_mode != XRFTHIP_OUT_COMPLEX && d.out_mode != XRFTHIP_OUT_POWER) || env_ll("XRFTHIP_FASTYC", 1) == 0) return kDeclined;
+    const bool cplx_out = d.out_mode == XRFTHIP_OUT_COMPLEX;
+    const uint32_t okc = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X | (cplx_out ? (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X | XRFTHIP_INVERSE | XRFTHIP_PHASE_IN | XRFTHIP_C2R_X) : 0u);
+    const uint32_t okf = XRFTHIP_SHIFT_X | (cplx_out ? (XRFTHIP_ISHIFT_X | XRFTHIP_INVERSE | XRFTHIP_PHASE_IN) : 0u);
+    const bool c2r = (d.flags & XRFTHIP_C2R_X) != 0;  // (irfftn: the half spectrum in, nx real samples per row out; the row transforms have nx/2 points)
+    int rc;
+    if (d.ndim == 2 && fasty_len(d.ny) && (c2r ? (d.nx % 2 == 0 && fasty_len(d.nx / 2)) : fasty_len(d.nx)) && !(d.flags & ~okc)) {
+        P->family = P->chosen = Family::FastYC;
+        const long long nxt = c2r ? d.nx / 2 : d.nx;
+        rc = plan_twiddle(P, P->tw_fx, nxt, nxt);
+        if (!rc && c2r) rc = plan_twiddle(P, P->tw_big1d, d.nx, d.nx / 32);  // W_nx^u, u < (nx/2) / 16
+        if (!rc) rc = plan_twiddle(P, P->tw_fy, d.ny, d.ny);
+        P->yny = d.ny; P->ynx = d.nx;
+    } else if (d.ndim == 1 && d.nx >= 65536 && d.nx <= 1048576 && (d.nx & (d.nx - 1)) == 0 && !(d.flags & ~okf)) {
+        P->family = P->chosen = Family::FastYCFourStep;
+        rc = plan_twiddle(P, P->tw_fx, 256, 256);
+        if (!rc) rc = plan_twiddle(P, P->tw_big1d, d.nx, d.nx / 16);  // W_N^j, j < N / 16: the four-step twiddles of a row (k1 u, k1 NT)
+        if (!rc) rc = plan_twiddle(P, P->tw_fy, d.nx / 256, d.nx / 256);
+        P->yny = d.nx / 256; P->ynx = 256;
+    } else {
+        return kDeclined;
+    }
+    return rc ? rc : plan_ones(P, 4096);
 }
 
 int run_fasty(const xrfthip_plan* P, const float* in, const float* in1, void* out, double* iso, char* ws, hipStream_t st) {
@@ -507,8 +574,8 @@ int run_fasty(const xrfthip_plan* P, const float* in, const float* in1, void* ou
 int run_fastyc(const xrfthip_plan* P, const void* in, void* out, char* ws, hipStream_t st) {
     const xrfthip_desc& d0 = P->d;
     // (the four-step form: every batch entry is ONE sequence of d.nx points, transformed as the [d.nx / 256][256] view)
-    struct { long long batch, ny, nx; uint32_t flags; int out_mode; double scale; } d{d0.batch, P->fastyc_fs ? d0.nx / 256 : d0.ny, P->fastyc_fs ? 256 : d0.nx, d0.flags, d0.out_mode, d0.scale};
-    const bool fs = P->fastyc_fs;
+    const bool fs = P->family == Family::FastYCFourStep;
+    struct { long long batch, ny, nx; uint32_t flags; int out_mode; double scale; } d{d0.batch, fs ? d0.nx / 256 : d0.ny, fs ? 256 : d0.nx, d0.flags, d0.out_mode, d0.scale};
     const bool c2r = (d.flags & XRFTHIP_C2R_X) != 0;
     const long long nxt = c2r ? d.nx / 2 : d.nx;  // points of the row transforms
     const YGeomRt C = ycols_geom(d.ny), R = yrows_geom(nxt);

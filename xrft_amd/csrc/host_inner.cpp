@@ -96,7 +96,7 @@ xrfthip_plan* create_fused_inner(const xrfthip_desc& d) {
     xrfthip_plan* P = new (std::nothrow) xrfthip_plan();
     if (!P) return nullptr;
     P->d = d;
-    P->fusedi = true;
+    P->family = P->chosen = Family::FusedInner;
     P->inner = d.inner > 1 ? d.inner : 1; P->mid = midlay ? d.mid : 1;
     P->dbl = dbl; P->cplx_in = false; P->rsize = rs; P->csize = cs;
     P->nx_out = (d.flags & XRFTHIP_HALF_X) ? d.nx / 2 + 1 : d.nx;
@@ -217,6 +217,7 @@ int create_inner_plan(xrfthip_plan** plan, const xrfthip_desc& d) {
     xrfthip_plan* P = new (std::nothrow) xrfthip_plan();
     if (!P) return XRFTHIP_ALLOC_FAILED;
     P->d = d;
+    P->family = P->chosen = Family::Composite;
     P->inner = d.inner; P->mid = d.mid;
     P->dbl = d.dtype == XRFTHIP_F64 || d.dtype == XRFTHIP_C128;
     P->cplx_in = d.dtype >= XRFTHIP_C64;

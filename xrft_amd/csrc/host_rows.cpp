@@ -27,7 +27,7 @@ int fasts_build_tfirst(xrfthip_plan* P, const int32_t* bm) {
             if (twin && (t[m] != c || t[(nx - m) % nx] != c)) { radial = false; break; }
         }
     }
-    if (!radial) { P->fasts = false; return XRFTHIP_OK; }
+    if (!radial) { settle_family(P, true); return XRFTHIP_OK; }
     std::vector<uint16_t> f((size_t)(nyh + 1) * (P->nbins + 1), (uint16_t)(H + 1));
     for (int ky = 0; ky <= nyh; ++ky) {
         const int32_t* r = bm + (size_t)ky * nx;
@@ -39,6 +39,24 @@ int fasts_build_tfirst(xrfthip_plan* P, const int32_t* bm) {
         }
     }
     return P->s_tfirst.upload(f.data(), f.size() * sizeof(uint16_t));
+}
+
+// FastS: a small float32 slab (64 | 128 | 256 points per axis) fits the registers of one workgroup: full power spectra in ONE pass.  A 256 x 256
+// plan also builds FastY's tables: an isotropic plan whose bin map turns out not to be a radial one falls back to them (fasts_build_tfirst)
+int try_fasts(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    auto small_len = [](long long n) { return n == 64 || n == 128 || n == 256; };
+    const uint32_t oks = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X | (d.out_mode == XRFTHIP_OUT_POWER ? (XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT) : (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X));
+    if (!(d.ndim == 2 && d.dtype == XRFTHIP_F32 && small_len(d.ny) && small_len(d.nx) && (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_COMPLEX) &&
+          !(d.flags & ~oks) && env_ll("XRFTHIP_FASTS", 1) != 0)) return kDeclined;
+    P->family = P->chosen = Family::FastS;
+    P->tune_sgrid = env_ll("XRFTHIP_FASTS_GRID", -1);
+    P->tune_sstagger = env_ll("XRFTHIP_FASTS_STAGGER", (3 << 8) | 2);  // (three classes 6.8 us apart: (4096, 256, 256) linear + Hann 310 -> 320 (the walk) -> 328 GFFT/s, profiles/r06_fasts_prefetch.txt)
+    int rc = plan_twiddle(P, P->tw_sy, d.ny, d.ny);
+    if (!rc) rc = plan_twiddle(P, P->tw_sx, d.nx, d.nx);
+    if (!rc) rc = plan_ones(P, 256);
+    if (!rc && fasty_fits(P)) rc = fasty_tables(P);
+    return rc;
 }
 
 int run_fasts(const xrfthip_plan* P, const void* in, void* out, double* iso, hipStream_t st) {
@@ -81,10 +99,59 @@ int run_fasts(const xrfthip_plan* P, const void* in, void* out, double* iso, hip
     return XRFTHIP_OK;
 }
 
+// FastR: one real float32 row of 4096 .. 65536 samples per workgroup, transformed in registers in ONE pass (fastr.h): 12 bytes per sample
+// through memory where the four-step form (FastY1D) moves 28.  FastRRows: complex rows of 256 .. 4096 points, two rows per thread through one
+// LDS buffer (the row pass of fasty_c2c.h on the input's own rows; XRFTHIP_CROWS=0: FastRComplex / FastMX); FastRComplex: complex rows of
+// 2048 .. 16384 points (xrft.ifft / fft of complex data along the contiguous axis), the same transform without the packing and the split
+int try_fastr(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    if (d.ndim != 1 || (d.out_mode != XRFTHIP_OUT_COMPLEX && d.out_mode != XRFTHIP_OUT_POWER)) return kDeclined;
+    const bool cplx_out = d.out_mode == XRFTHIP_OUT_COMPLEX;
+    const uint32_t okr = XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | (!cplx_out ? XRFTHIP_REALDIM_X2 : 0u) | (cplx_out ? XRFTHIP_ISHIFT_X : 0u);
+    const uint32_t okc = XRFTHIP_SHIFT_X | (cplx_out ? (XRFTHIP_ISHIFT_X | XRFTHIP_INVERSE | XRFTHIP_PHASE_IN) : 0u);
+    const bool c2r = (d.flags & XRFTHIP_C2R_X) != 0;  // (irfft along the contiguous axis: rows of nx/2 + 1 complex values in, nx real samples out)
+    int rc;
+    if (d.dtype == XRFTHIP_C64 && !d.detrend) {
+        if ((c2r ? (d.nx % 2 == 0 && fasty_len(d.nx / 2) && cplx_out) : fasty_len(d.nx)) && !(d.flags & ~(okc | (cplx_out ? XRFTHIP_C2R_X : 0u))) &&
+            env_ll("XRFTHIP_CROWS", 1) != 0) {
+            P->family = P->chosen = Family::FastRRows;
+            rc = plan_twiddle(P, P->tw_fx, c2r ? d.nx / 2 : d.nx, c2r ? d.nx / 2 : d.nx);
+            if (!rc && c2r) rc = plan_twiddle(P, P->tw_big1d, d.nx, d.nx / 32);
+            if (!rc) rc = plan_ones(P, 4096);
+        } else if ((d.nx == 16384 || d.nx == 8192 || d.nx == 4096 || d.nx == 2048) && !(d.flags & ~okc) && env_ll("XRFTHIP_FASTC", 1) != 0) {
+            P->family = P->chosen = Family::FastRComplex;
+            P->tune_rgrid = env_ll("XRFTHIP_FASTR_GRID", 0);
+            P->tune_rstagger = env_ll("XRFTHIP_FASTR_STAGGER", 0);
+            const long long thr = d.nx / 32;  // threads per row: 32 complex values each
+            rc = plan_twiddle(P, P->tw_rm, d.nx, thr);
+            if (!rc) rc = plan_twiddle(P, P->tw_rs, thr, 32);
+        } else {
+            return kDeclined;
+        }
+    } else if ((d.nx == 65536 || d.nx == 32768 || d.nx == 16384 || d.nx == 8192 || d.nx == 4096) && d.dtype == XRFTHIP_F32 && !(d.flags & ~okr) &&
+               !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X)) && env_ll("XRFTHIP_FASTR", 1) != 0) {
+        P->family = P->chosen = Family::FastR;
+        // 65536 samples: one resident workgroup per CU walks the rows (measured: 359 vs 344 GFFT/s for a workgroup per row, profiles/r04_fastr.txt);
+        // the shorter rows (several workgroups per CU): a workgroup per row
+        // 32768 / 16384 samples (one / two workgroups per CU): a resident set, too -- with the start stagger run_fastr picks (profiles/r06_rows_stagger.txt)
+        P->tune_rgrid = env_ll("XRFTHIP_FASTR_GRID", d.nx == 65536 ? kCUs : (d.nx == 32768 && d.batch >= 2 * kCUs) ? kCUs : (d.nx == 16384 && cplx_out && d.batch >= 4 * kCUs) ? 2 * kCUs : 0);
+        // two classes of workgroups 10 us apart: dft (1024, 65536) 388 -> 441 GFFT/s, power_spectrum 517 -> 586 (profiles/r06_c2_stagger.txt); -1: run_fastr's rule
+        P->tune_rstagger = env_ll("XRFTHIP_FASTR_STAGGER", d.nx == 65536 ? ((2 << 8) | 3) : -1);
+        const long long thr = d.nx / 64;  // threads per row: 32 packed complex values each
+        rc = plan_twiddle(P, P->tw_rm, d.nx / 2, thr);
+        if (!rc) rc = plan_twiddle(P, P->tw_rs, thr, 32);
+        if (!rc) rc = plan_twiddle(P, P->tw_rn, d.nx, thr);
+    } else {
+        return kDeclined;
+    }
+    return rc;
+}
+
 // one pass over 65536-sample float32 rows (fastr.h): a 1024-thread workgroup per row, or a resident set walking the rows
 int run_fastr(const xrfthip_plan* P, const void* in, void* out, hipStream_t st) {
     const xrfthip_desc& d = P->d;
-    if (P->fastr_rows) {  // complex rows of 256 .. 4096 points: the row pass of the complex two-pass pipeline on the input's own rows
+    const bool cin = P->family == Family::FastRComplex;
+    if (P->family == Family::FastRRows) {  // complex rows of 256 .. 4096 points: the row pass of the complex two-pass pipeline on the input's own rows
         const bool c2r = (d.flags & XRFTHIP_C2R_X) != 0;
         const long long nxt = c2r ? d.nx / 2 : d.nx;
         const YGeomRt R = yrows_geom(nxt);
@@ -132,7 +199,7 @@ int run_fastr(const xrfthip_plan* P, const void* in, void* out, hipStream_t st) 
     p.shift = (d.flags & XRFTHIP_SHIFT_X) ? 1 : 0;
     p.scale = (float)d.scale;
     p.stagger = (int)P->tune_rstagger;
-    if (P->fastr_cin) {  // (the flags as fastm_xonly_kernel reads them: the input rotated and conjugated for an inverse, the phase table on the input or on the output)
+    if (cin) {  // (the flags as fastm_xonly_kernel reads them: the input rotated and conjugated for an inverse, the phase table on the input or on the output)
         p.inv = (d.flags & XRFTHIP_INVERSE) ? 1 : 0;
         p.ishift = ((d.flags & XRFTHIP_INVERSE) && (d.flags & XRFTHIP_ISHIFT_X)) ? 1 : 0;
         p.ph_in = ((d.flags & XRFTHIP_PHASE_IN) && P->fph_on) ? 1 : 0;
@@ -142,10 +209,10 @@ int run_fastr(const xrfthip_plan* P, const void* in, void* out, hipStream_t st) 
     if (P->tune_rstagger < 0) {
         // rows of 32768 / 16384 samples on a resident set: three classes of workgroups 3.4 us apart for a complex result (6.8 us when the true-phase table rides
         // along: fft (2048, 32768) 275 -> 346 GFFT/s, dft 415 -> 435, fft (4096, 16384) 333 -> 356); a power spectrum gains nothing from a stagger
-        const bool cplx = d.out_mode == XRFTHIP_OUT_COMPLEX && !P->fastr_cin;
+        const bool cplx = d.out_mode == XRFTHIP_OUT_COMPLEX && !cin;
         p.stagger = d.batch < 2 * g ? 0 : (cplx && d.nx == 32768) ? ((3 << 8) | (p.ph_on ? 2 : 1)) : (cplx && d.nx == 16384) ? ((3 << 8) | 1) : 0;
     }
-    const dim3 grid((unsigned)std::min<long long>(g, 0x7fffffffLL)), blk((unsigned)(P->fastr_cin ? d.nx / 32 : d.nx / 64));
+    const dim3 grid((unsigned)std::min<long long>(g, 0x7fffffffLL)), blk((unsigned)(cin ? d.nx / 32 : d.nx / 64));
     const bool pw = d.out_mode == XRFTHIP_OUT_POWER;
     // profiling (bench.py's roofline.kernel): the start / stop timestamps ride on the kernel's own dispatch packet (hipExtLaunchKernelGGL)
     // instead of two event records around it -- barrier packets either side of a 0.18-ms kernel cost the C2 bench line 50 us per step
@@ -169,7 +236,7 @@ int run_fastr(const xrfthip_plan* P, const void* in, void* out, hipStream_t st) 
         else if (d.nx == 8192) RK_((fastc_kernel<16, 16, MM>), (R2Geom<16, 16>::LDS)); \
         else if (d.nx == 4096) RK_((fastc_kernel<16, 8, MM>), (R2Geom<16, 8>::LDS)); \
         else RK_((fastc_kernel<8, 8, MM>), (R2Geom<8, 8>::LDS)); } while (0)
-    if (P->fastr_cin) { if (pw) RC_(1); else RC_(0); }
+    if (cin) { if (pw) RC_(1); else RC_(0); }
     else if (pw) { if (p.half) RL_(1, true); else RL_(1, false); } else { if (p.half) RL_(0, true); else RL_(0, false); }
 #undef RC_
 #undef RL_

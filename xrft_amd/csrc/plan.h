@@ -2,13 +2,18 @@
 // plan.h -- what the host side of libxrft_hip.so shares between its translation units (not part of the C ABI: include/xrft_hip.h is):
 // the plan (struct xrfthip_plan), device tables, the small host helpers, and the declarations of the per-family host functions.
 //
-//   xrft_hip.cpp     the plan builder (xrfthip_plan_create: which kernels serve a descriptor), the generic tile passes (tile_fft.h), workspace
-//                    layout, xrfthip_exec's dispatch, describe / profiling, the C ABI of the plan
-//   host_fasty.cpp   the y-first float32 two-pass pipeline (fasty.h, fasty_iso.h) and its complex form (fasty_c2c.h): tables, launchers
+//   xrft_hip.cpp     the plan builder (xrfthip_plan_create: descriptor checks, then the families' try_* in order of precedence), the generic
+//                    tile passes (tile_fft.h), workspace layout, xrfthip_exec's dispatch, describe / profiling, the C ABI of the plan
+//   host_fasty.cpp   the y-first float32 two-pass pipeline (fasty.h, fasty_iso.h) and its complex form (fasty_c2c.h): try_*, tables, launchers
+//                    (FastY, FastY1D, FastYC, FastYCFourStep)
 //   host_fastm.cpp   the mixed-radix pipeline on the lat/lon lengths (fastm.h), its run-time-radix form (fastn.h), the one-axis table kernels
+//                    (FastM, FastN, FastMY, FastMX)
 //   host_fastg.cpp   the one-pass lengths-as-data kernels (fastg.h): small slabs, one axis of any smooth length, Rader / Bluestein tables
+//                    (FastG, FastGY)
 //   host_rows.cpp    the register-resident one-pass kernels: small float32 slabs (fasts.h), long rows and complex rows (fastr.h)
+//                    (FastS, FastR, FastRComplex, FastRRows)
 //   host_inner.cpp   two transform axes that are not the trailing pair (xrfthip_desc.inner / .mid): the fused passes and the composite plan
+//                    (FusedInner, Composite)
 //   ops.cpp          the stand-alone operations of the ABI (detrend, spectrum tail, gather, convert, reduce, isotropize, ...)
 //   inst_g1..7.cpp   the explicit instantiations of the fasty / fastm / fastn kernel templates (instances.h)
 //
@@ -17,7 +22,7 @@
 //     The x pass reads the user's array (detrend / window / flip / ifftshift fused into its loads) and the last pass writes the
 //     user's output (fftshift / phase / scaling / |F|^2 / cross / mirror fused into its stores); the only intermediate is the
 //     half spectrum of ONE group of slabs, re-used for every group.
-//   * the specialised families above, each with its own launcher (run_fast*).
+//   * the specialised families above, each with its own launcher (run_fast*): enum class Family, one value per plan.
 // Nothing allocates or synchronises in exec.
 #include <algorithm>
 #include <functional>
@@ -312,6 +317,29 @@ int build_twiddle(DevBuf& buf, long long N, long long count) {  // W_N^k, k < co
     return buf.upload(tw.data(), tw.size() * sizeof(C2<T>));
 }
 
+// The kernel family that serves a plan: one launcher (and one describe form) each.  xrfthip_plan_create picks it, the first of the
+// families' try_* (in order of precedence) that takes the descriptor; settle_family can hand it on once the plan's tables arrive.
+enum class Family {
+    Generic,         // the tile passes (tile_fft.h)
+    Composite,       // xrfthip_desc.inner / .mid: two one-axis plans (sub_x, sub_y)
+    FusedInner,      // ... or the two fused passes where the axes lie (fastn.h)
+    FastS,           // one pass over a small float32 slab in registers (fasts.h)
+    FastG,           // one pass over a small slab, or groups of rows (g_one_d), lengths as data (fastg.h)
+    FastGY,          // one pass along one axis that is not the contiguous one, or along rows with one Rader prime (gy_rows) (fastg.h)
+    FastMX,          // short rows, table lengths (fastm.h, fastm_xonly_kernel)
+    FastMY,          // one axis that is not the contiguous one, table lengths (fastm.h, fastm_yonly_kernel)
+    FastR,           // one pass over a long real float32 row in registers (fastr.h)
+    FastRComplex,    // ... complex rows of 2048 .. 16384 points (fastc_kernel)
+    FastRRows,       // complex rows of 256 .. 4096 points: the row pass of fasty_c2c.h on the input's own rows
+    FastYC,          // the two passes of fasty_c2c.h over complex float32 slabs
+    FastYCFourStep,  // ... over ONE long complex sequence per batch entry, the four-step form of pass 2
+    FastY,           // the two y-first passes over real float32 slabs of powers of two (fasty.h)
+    FastY1D,         // ... as the two steps of a four-step transform of one long real sequence
+    FastM,           // the two y-first passes, table lengths (fastm.h)
+    FastN,           // ... with the lengths as data (fastn.h; either pass may still be a table kernel)
+};
+constexpr int kDeclined = 1;  // a try_* that does not take the descriptor (XRFTHIP_OK: taken, its tables built; < 0: an error)
+
 }  // namespace xrfth
 using namespace xrfth;
 
@@ -333,21 +361,17 @@ struct xrfthip_plan {
     size_t off_acc = 0, off_coef = 0, off_w = 0, off_w2 = 0, off_f0 = 0, off_pt = 0, off_rowfit = 0, off_corr = 0, off_isopart = 0, off_isotmp = 0, off_rdv = 0, ws_bytes = 0;
     int iso_chunks = 1;  // workgroups per slab of the generic radial-sum pass (partial sums added in order)
     std::string desc_text;
-    // specialised path for real float32 slabs whose two lengths are 256 .. 4096 powers of two (fasty.h)
-    bool fast4096 = false;  // (the flag keeps its first name: the headline shape is where the path started)
+    Family family = Family::Generic;  // what xrfthip_exec runs
+    Family chosen = Family::Generic;  // what the plan's tables serve: `family`, unless settle_family parks a FastY plan on the generic passes
+    // FastY: real float32 slabs whose two lengths are 256 .. 4096 powers of two (fasty.h), columns -> [fit] -> rows, no untile pass
     DevBuf tw_fx, tw_fy, ones4096, fph[2];
     std::vector<double> host_phase[2];  // complex, as handed to xrfthip_plan_set_phase (empty = none)
-    // two-pass "y first" pipeline for full power spectra (fasty.h): columns -> [fit] -> rows, no untile pass
-    bool yfirst = false;
-    // ... and, as the two steps of a four-step transform, one long real sequence per slab: N = yny * ynx samples viewed as
+    // FastY1D: as the two steps of a four-step transform, one long real sequence per slab: N = yny * ynx samples viewed as
     // a [yny][ynx] slab (fasty.h, FS).  yny / ynx are d.ny / d.nx for the 2-D plans.
-    bool fast1d = false;
-    bool fastyc = false;  // ... the same two passes for COMPLEX float32 slabs (fasty_c2c.h): xrft.ifft over two axes, xrft.fft of complex data
-    // ... and its mixed-radix float64 form (fastm.h): lengths 360 / 720 / 1440
-    bool fastm = false;
-    // ... and the same pipeline with the LENGTHS AS DATA (fastn.h): either pass (or both) of a `fastm` plan may be the run-time-radix kernel -- every
+    // FastYC: the same two passes for COMPLEX float32 slabs (fasty_c2c.h): xrft.ifft over two axes, xrft.fft of complex data
+    // FastM: the mixed-radix form (fastm.h): the lat/lon lengths
+    // FastN: the same pipeline with the LENGTHS AS DATA (fastn.h): either pass (or both) may be the run-time-radix kernel -- every
     // length that is a product of the butterflies 2 ... 20 (7, 11, 13 included), and for the columns any other length through a chirp convolution
-    bool fastn = false;
     struct NSide { bool rt = false; NGeo geo{}; size_t lds = 0; DevBuf twm, geo_dev; };
     NSide n_c, n_r;                 // pass 1 (columns, length ny) and pass 2 (rows, length nx)
     int n_cw = 0, n_rk = 1, n_rpu = 0, n_nxb = 0;  // the intermediate's layout: columns per block, rows per line; rows per pass-2 workgroup; column blocks per row
@@ -357,17 +381,13 @@ struct xrfthip_plan {
     int n_rad_p = 0;                // ... or, ny = q p with ONE prime 17 ... 127 whose p - 1 the butterflies factor: the prime-factor form with Rader's algorithm along p
     std::vector<int> n_rq, n_rp;    // the radices of q and of p - 1
     DevBuf n_rgeo, n_radpin, n_radpout, n_radb;
-    // ... and xrfthip_desc.inner > 1 (two adjacent transform axes, the independent elements innermost) as the same two passes (fastn.h: fastn_cols_kernel on the
+    // FusedInner: xrfthip_desc.inner > 1 (two adjacent transform axes, the independent elements innermost) as the same two passes (fastn.h: fastn_cols_kernel on the
     // [ny][nx inner] view, fastn_fit_inner_kernel, fastn_irows_kernel).  n_c: the ny-point columns of the view; n_r: GE sequences of nx points per row workgroup
-    bool fusedi = false;
     int n_dbg = 0, fi_dbg = 0, fi_vec = 1;  // the measuring scripts' ablation switches (XRFTHIP_FASTN_DBG / _FI_DBG / _FI_VEC), read when the plan is made: xrfthip_exec reads no environment
     DevBuf winx_exp;                // the window along x expanded to the view's columns (never null: ones)
-    // ... and pass 1 alone for ONE transform axis that is not the contiguous one (XRFTHIP_AXIS_Y, fastm_yonly_kernel)
-    bool fastmy = false;
-    // ... and the same transform over short contiguous rows packed in pairs (ndim = 1, fastm_xonly_kernel)
-    bool fastmx = false;
-    // ... and ONE pass for a small real slab of any smooth shape, either precision, held in LDS with run-time radices (fastg.h)
-    bool fastg = false;
+    // FastMY: pass 1 alone for ONE transform axis that is not the contiguous one (XRFTHIP_AXIS_Y, fastm_yonly_kernel)
+    // FastMX: the same transform over short contiguous rows packed in pairs (ndim = 1, fastm_xonly_kernel)
+    // FastG: ONE pass for a small real slab of any smooth shape, either precision, held in LDS with run-time radices (fastg.h)
     std::vector<int> g_rx, g_ry;
     DevBuf g_twx, g_twy, g_twr, g_revx, g_revy, g_isopos, g_isostart;
     std::vector<unsigned> g_hrevx, g_hrevy;  // (host copies: the radial-sum lists are built from them when the bin map arrives)
@@ -375,8 +395,7 @@ struct xrfthip_plan {
     int g_rows = 0, g_lpr = 1, g_nred = 0;
     int g_rs = 0, g_n = 0;  // LDS row stride; length of the x transforms: nx / 2 (rows packed in pairs of samples) or nx (an odd nx)
     bool g_packed = true;
-    // ... and ONE pass for one transform axis that is not the contiguous one (XRFTHIP_AXIS_Y), any smooth length, real input (fastg.h: fastgy_kernel)
-    bool fastgy = false;
+    // FastGY: ONE pass for one transform axis that is not the contiguous one (XRFTHIP_AXIS_Y), any smooth length, real input (fastg.h: fastgy_kernel)
     int gy_G = 0, gy_thr = 0, gy_blue_m = 0;  // gy_blue_m: Bluestein inside the tile on blue_m rows (a prime factor of ny with no butterfly)
     int gy_rad_p = 0;                         // ... or, ny = q p with ONE such prime p <= 127 and p - 1 smooth: the prime-factor form with Rader's algorithm along p
     bool gy_rows = false;                     // ... the same form along the CONTIGUOUS axis of a 1-D plan ([batch rows][nx samples]; fastgy_kernel FORM 3): gy_n = nx
@@ -387,17 +406,15 @@ struct xrfthip_plan {
     size_t gy_lds = 0;
     DevBuf gy_bluec, gy_blueb;
     size_t g_lds = 0;
-    // ... and ONE pass for a small real float32 slab that fits the registers of a CU: 256 x 256 power spectra (fasts.h)
-    bool fasts = false;
+    // FastS: ONE pass for a small real float32 slab that fits the registers of a CU: 256 x 256 power spectra (fasts.h)
     DevBuf tw_sy, tw_sx, s_tfirst;
     long long tune_sstagger = 0;  // XRFTHIP_FASTS_STAGGER: classes << 8 | steps of 3.4 us between the classes of a resident set of slab workgroups
     long long tune_sgrid = -1;    // XRFTHIP_FASTS_GRID: workgroups of the launch (0 = one per slab, the default; else a resident set walking the slabs)
-    // ... and ONE pass for a long real float32 row that fits the registers of a CU: 65536 samples per workgroup (fastr.h)
-    bool fastr = false;
-    bool fastr_rows = false;      // ... complex rows of 256 .. 4096 points: pass 2 of the complex two-pass pipeline on the rows of the input itself (fastyc_rows_kernel, nrows > 0)
-    bool fastyc_fs = false;       // fastyc on ONE long complex sequence per batch entry (ndim = 1, 2^16 .. 2^20 points): the [n / 256][256] view, the four-step form of pass 2 (FastYC::fs)
+    // FastR: ONE pass for a long real float32 row that fits the registers of a CU: 65536 samples per workgroup (fastr.h); FastRComplex: its
+    // complex-row form, rows of 2048 .. 16384 complex64 points, forward or inverse (fastc_kernel); FastRRows: complex rows of 256 .. 4096
+    // points, pass 2 of the complex two-pass pipeline on the rows of the input itself (fastyc_rows_kernel, nrows > 0)
+    // FastYCFourStep: ONE long complex sequence per batch entry (ndim = 1, 2^16 .. 2^20 points): the [n / 256][256] view, the four-step form of pass 2 (FastYC::fs)
     DevBuf fs_phx;                // ... the x factor of a separable input phase (PHASE_IN): 256 entries (fph[0]: the factor per row of the view)
-    bool fastr_cin = false;       // ... its complex-row form: rows of 2048 .. 16384 complex64 points, forward or inverse (fastc_kernel)
     DevBuf tw_rm, tw_rs, tw_rn;   // W_M^p (p < 1024), W_1024^n (n < 32), W_N^p (p < 1024)
     long long tune_rstagger = 0;  // XRFTHIP_FASTR_STAGGER: classes << 8 | units of 3.4 us between the start of consecutive classes of workgroups (FastR::stagger)
     long long tune_rgrid = 0;     // XRFTHIP_FASTR_GRID: workgroups of the launch (0 = one per row; default: a resident set of one per CU walking the rows)
@@ -452,10 +469,10 @@ MGeomRt mygeom(long long n, bool dbl);
 SGeomRt sgeom(long long ny, long long nx);
 YGeomRt ycols_geom(long long ny);
 YGeomRt yrows_geom(long long nx, bool fs = false);
-bool fast_on(const xrfthip_plan* P);
 bool fastg_factor(long long n, std::vector<int>& out);
 bool fastg_try(xrfthip_plan* P);
 bool fastgy_try(xrfthip_plan* P, bool rows = false);
+bool cross_iso_phase(const xrfthip_plan* P);
 bool fastm_iso_fused(const xrfthip_plan* P);
 bool fastm_iso_gather(const xrfthip_plan* P);
 bool fastm_len(long long n, bool dbl);
@@ -466,8 +483,6 @@ bool fastn_factor(long long n, int maxr, std::vector<int>& out, int need_last = 
 bool fastn_pick(long long n, int g, bool blue, bool dbl, bool cols, int maxr, int thr_force, NGeo& out);
 bool fastn_setup(xrfthip_plan* P);
 bool fasty_iso_tables_fit(const xrfthip_plan* P, int nbins);
-bool fasty_on(const xrfthip_plan* P);
-bool phase_nontrivial(const xrfthip_plan* P);
 bool plan_two(const xrfthip_plan* P);
 bool rader_split(long long n, bool allow17, int& p_out, std::vector<int>& rq, std::vector<int>& rp);
 int build_unit_windows(xrfthip_plan* P, const int32_t* bm, int rpu);
@@ -526,6 +541,35 @@ void fastn_launch_rows(const xrfthip_plan* P, const FastM& m, long long gc, bool
 void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof);
 void fasty_launch_rows(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof);
 void layout_workspace(xrfthip_plan* P);
+void settle_family(xrfthip_plan* P, bool decline = false);
+int plan_twiddle(xrfthip_plan* P, DevBuf& buf, long long N, long long count);
+int plan_ones(xrfthip_plan* P, long long n);
+bool fasty_fits(const xrfthip_plan* P);
+int fasty_tables(xrfthip_plan* P);
+
+// the families' try_* (xrfthip_plan_create calls them in this order; the first that does not return kDeclined decides)
+int try_fasts(xrfthip_plan* P);
+int try_fastyc(xrfthip_plan* P);
+int try_fastr(xrfthip_plan* P);
+int try_fasty(xrfthip_plan* P);
+int try_fast1d(xrfthip_plan* P);
+int try_fastm(xrfthip_plan* P);
+int try_fastmx(xrfthip_plan* P);
+int try_fastmy(xrfthip_plan* P);
+int try_fastgy(xrfthip_plan* P);
+int try_fastg(xrfthip_plan* P);
+int try_fastn(xrfthip_plan* P);
+
+inline bool fasty_len(long long n) { return n == 256 || n == 512 || n == 1024 || n == 2048 || n == 4096; }  // the lengths of fasty.h / fasty_c2c.h
+
+// sets of families
+inline bool fastm_pipeline(const xrfthip_plan* P) { return P->family == Family::FastM || P->family == Family::FastN; }  // fastm.h / fastn.h two passes
+inline bool two_pass_y(const xrfthip_plan* P) { return fastm_pipeline(P) || P->family == Family::FastY || P->family == Family::FastY1D; }  // columns -> [fit] -> rows
+inline bool inner_layout(const xrfthip_plan* P) { return P->family == Family::FusedInner || P->family == Family::Composite; }  // (no tile passes of their own)
+inline bool dbl_phase_tables(const xrfthip_plan* P) {  // the families that read float64 phase / window-spectrum tables in a float64 plan
+    const Family f = P->family;
+    return P->dbl && (f == Family::FastM || f == Family::FastN || f == Family::FastMY || f == Family::FastMX || f == Family::FastG || f == Family::FastGY || f == Family::FusedInner);
+}
 void prof_end(xrfthip_plan::ProfRec* r, hipStream_t st);
 xrfthip_plan* create_fused_inner(const xrfthip_desc& d);
 xrfthip_plan::ProfRec* prof_begin(const xrfthip_plan* P, const std::string& label, hipStream_t st);

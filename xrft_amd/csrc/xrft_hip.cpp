@@ -517,6 +517,23 @@ int upload_real_table(xrfthip_plan* P, DevBuf& buf, const double* h, int64_t n, 
     return buf.upload(f.data(), cnt * sizeof(float));
 }
 
+// the specialised families' tables in the plan's precision: W_N^k (k < count), and a table of n ones (the windows' stand-in)
+int plan_twiddle(xrfthip_plan* P, DevBuf& buf, long long N, long long count) {
+    return P->dbl ? build_twiddle<double>(buf, N, count) : build_twiddle<float>(buf, N, count);
+}
+int plan_ones(xrfthip_plan* P, long long n) {
+    const std::vector<double> ones((size_t)n, 1.0);
+    return upload_real_table(P, P->ones4096, ones.data(), n, 0);
+}
+
+// Where a plan's tables hand it on (finalize_plan, xrfthip_plan_set_binmap).  decline: the chosen family cannot serve the plan, for good --
+// FastS passes it to the FastY tables built beside it (256 x 256, try_fasts) or to the generic passes, every other family to the generic
+// passes.  Then the one rule that is decided again whenever a table changes: a FastY isotropic cross spectrum with a true-phase factor that
+// is not 1 runs the generic passes, and FastY again once the factor is 1.
+void settle_family(xrfthip_plan* P, bool decline) {
+    if (decline) P->chosen = (P->chosen == Family::FastS && P->tw_fy.p) ? Family::FastY : Family::Generic;
+    P->family = (P->chosen == Family::FastY && cross_iso_phase(P)) ? Family::Generic : P->chosen;
+}
 
 // workgroups per slab of radial_binsum_det_kernel: chunks of <= 2^17 elements (its int64 sums hold 2^17 values), at most 128
 int iso_chunk_count(long long total) {
@@ -558,23 +575,29 @@ int run_radial_sums(int32_t dtype, const void* spec, const int32_t* d_binmap, lo
 
 void layout_workspace(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
-    if (P->fastr || P->fasts || P->fastg || P->fastgy) { P->G = (int)std::max<long long>(1, std::min<long long>(d.batch, 1 << 30)); P->ws_bytes = 0; return; }  // one pass, registers + LDS: no intermediate
-    if (P->fastyc) {  // the tiled intermediate of one group of slabs
-        long long G = d.slabs_per_group > 0 ? d.slabs_per_group : (P->tune_fast_group > 0 ? P->tune_fast_group : std::max<long long>(1, (32LL * 4096 * 4096) / (d.ny * d.nx)));
-        G = std::max<long long>(1, std::min<long long>(G, std::max<long long>(d.batch, 1)));
-        P->G = (int)G;
-        P->off_w = 0;
-        size_t w2_cols = (size_t)d.nx;  // complex columns of the intermediate per row
-        if (d.flags & XRFTHIP_C2R_X) { const size_t cw = 2 * (size_t)ycols_geom(d.ny).gxy; w2_cols = (size_t)d.nx / 2 + cw; }  // (+ the block of the Nyquist column)
-        P->ws_bytes = (((size_t)G * (size_t)d.ny * w2_cols * sizeof(cf)) + 255) & ~(size_t)255;
-        return;
+    bool fast = false;  // the two y-first passes: their intermediate, per-column sums and corrections (else the generic passes' layout)
+    switch (P->family) {
+        case Family::FastR: case Family::FastRComplex: case Family::FastRRows: case Family::FastS: case Family::FastG: case Family::FastGY:
+            P->G = (int)std::max<long long>(1, std::min<long long>(d.batch, 1 << 30)); P->ws_bytes = 0;  // one pass, registers + LDS: no intermediate
+            return;
+        case Family::FastYC: case Family::FastYCFourStep: {  // the tiled intermediate of one group of slabs
+            long long G = d.slabs_per_group > 0 ? d.slabs_per_group : (P->tune_fast_group > 0 ? P->tune_fast_group : std::max<long long>(1, (32LL * 4096 * 4096) / (d.ny * d.nx)));
+            G = std::max<long long>(1, std::min<long long>(G, std::max<long long>(d.batch, 1)));
+            P->G = (int)G;
+            P->off_w = 0;
+            size_t w2_cols = (size_t)d.nx;  // complex columns of the intermediate per row
+            if (d.flags & XRFTHIP_C2R_X) { const size_t cw = 2 * (size_t)ycols_geom(d.ny).gxy; w2_cols = (size_t)d.nx / 2 + cw; }  // (+ the block of the Nyquist column)
+            P->ws_bytes = (((size_t)G * (size_t)d.ny * w2_cols * sizeof(cf)) + 255) & ~(size_t)255;
+            return;
+        }
+        case Family::FastY: case Family::FastY1D: case Family::FastM: case Family::FastN: fast = true; break;
+        case Family::Generic: case Family::FastMX: case Family::FastMY: break;
+        case Family::Composite: case Family::FusedInner: break;  // (never here: they lay out their own workspace)
     }
-    const bool fast = fast_on(P);
     long long G = d.slabs_per_group > 0 ? d.slabs_per_group : P->tune_group;
     size_t slab_w = (size_t)d.ny * std::max(P->width, P->w_cols) * P->csize;
-    const bool yf = fast && P->yfirst;
     if (fast) {
-        slab_w = (size_t)P->y_nrow_pad * (size_t)(P->y_pitch > 0 ? P->y_pitch : P->ynx) * (P->fastm ? P->csize : sizeof(cf));
+        slab_w = (size_t)P->y_nrow_pad * (size_t)(P->y_pitch > 0 ? P->y_pitch : P->ynx) * (fastm_pipeline(P) ? P->csize : sizeof(cf));
         if (G <= 0) G = P->tune_fast_group > 0 ? P->tune_fast_group : std::max<long long>(1, (64LL * 4096 * 4096) / (d.ny * d.nx));  // y-first, 4096^2: 16: 62.7, 32: 61.4 us per slab; 32 -> 64: 301-303 -> 306-307 GFFT/s (tails, launch gaps and the plane-fit bubble amortise)
     }
     if (G <= 0) {
@@ -591,29 +614,29 @@ void layout_workspace(xrfthip_plan* P) {
     P->mom_chunks = (int)std::max<long long>(1, std::min<long long>(d.ny, (2048 + G - 1) / G));
     P->off_acc = off; off = al(off + (size_t)G * P->mom_chunks * 6 * sizeof(double) * nf);  // per-chunk partial sums of ONE group of slabs
     P->off_coef = off; off = al(off + ncoef * 6 * sizeof(double) * nf);
-    bool need_w = d.ndim == 2 || yf, need_w2 = false;
+    bool need_w = d.ndim == 2 || fast, need_w2 = false;
     for (const Pass& p : P->passes) { if (p.out_kind == B_W2) need_w2 = true; if (p.out_kind == B_W) need_w = true; }
-    P->off_w = off; if (need_w) off = al(off + (size_t)G * slab_w * (yf ? nf : 1));  // (y first: field 1's intermediate follows field 0's)
+    P->off_w = off; if (need_w) off = al(off + (size_t)G * slab_w * (fast ? nf : 1));  // (y first: field 1's intermediate follows field 0's)
     P->off_w2 = off; if (need_w2) off = al(off + (size_t)G * d.ny * d.nx * P->csize);
     P->off_f0 = off; if (nf == 2 && !fast) off = al(off + (size_t)G * slab_w);
-    const size_t nfit = (size_t)(yf ? 2 * P->ynx : d.ny);  // per-column sums + subtracted lines
-    P->off_rowfit = off; if (fast) off = al(off + (size_t)G * nfit * 2 * sizeof(double) * (yf ? nf : 1));
-    P->off_corr = off; if (fast) off = al(off + (size_t)G * nfit * 2 * sizeof(float) * (yf ? nf : 1));  // (16 bytes per column: fasty uses 8, fastm's float64 pairs all 16)
+    const size_t nfit = (size_t)(fast ? 2 * P->ynx : d.ny);  // per-column sums + subtracted lines
+    P->off_rowfit = off; if (fast) off = al(off + (size_t)G * nfit * 2 * sizeof(double) * nf);
+    P->off_corr = off; if (fast) off = al(off + (size_t)G * nfit * 2 * sizeof(float) * nf);  // (16 bytes per column: fasty uses 8, fastm's float64 pairs all 16)
     P->off_isopart = off;
-    if (yf && !P->fastm && (d.flags & XRFTHIP_ISO)) {  // per-workgroup partial radial sums of one group of slabs (reduced in order)
+    if (fast && !fastm_pipeline(P) && (d.flags & XRFTHIP_ISO)) {  // per-workgroup partial radial sums of one group of slabs (reduced in order)
         const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
         const long long gx = fasty_rows_gx(P);  // YRows<NX>::GX
         const size_t upr = (size_t)P->y_nrow_pad / (two ? gx : 2 * gx);
         off = al(off + (size_t)G * upr * P->nbins * (two ? 2 : 1) * sizeof(double));
     }
     P->off_rdv = off;
-    if (yf && !P->fastm && ((P->tune_y >> 21) & 1)) off = al(off + (size_t)G * (size_t)std::max<long long>(P->ynx / 8, 1) * sizeof(unsigned));  // (tuning: rendezvous counters of pass 1)
+    if (fast && !fastm_pipeline(P) && ((P->tune_y >> 21) & 1)) off = al(off + (size_t)G * (size_t)std::max<long long>(P->ynx / 8, 1) * sizeof(unsigned));  // (tuning: rendezvous counters of pass 1)
     P->off_isotmp = off;
     if (fastm_iso_fused(P)) {  // fastm with the radial sums inside pass 2: one partial table per row workgroup
         const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
         P->off_isopart = off;
         off = al(off + (size_t)G * (P->y_nrow_pad / fastm_rows_rpu(P)) * P->nbins * (two ? 2 : 1) * sizeof(double));
-    } else if ((!fast || P->fastm) && (d.flags & XRFTHIP_ISO)) {  // generic and fastm kernels: the spectrum is stored (into the caller's array, or here), then summed
+    } else if ((!fast || fastm_pipeline(P)) && (d.flags & XRFTHIP_ISO)) {  // generic and fastm kernels: the spectrum is stored (into the caller's array, or here), then summed
         const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
         const size_t out_esz = two ? P->csize : P->rsize;
         const long long total = d.ny * P->nx_out;
@@ -682,16 +705,20 @@ static int run_moments(const xrfthip_plan* P, const void* in, long long g0, long
 // set: window spectra and phase tables of the specialised paths (device allocations + blocking copies) and the workspace
 // layout.  xrfthip_exec itself takes the plan as const: no allocation, no copy, no synchronisation, no getenv.
 int finalize_plan(xrfthip_plan* P) {
-    if (P->fusedi) return fusedi_tables(P);  // (its workspace layout does not depend on the tables)
-    // the radial sums of a cross spectrum with a true-phase factor that is not 1 (two fields with different lags) need the factor per sample: the other paths
-    if (P->fastg && P->d.out_mode == XRFTHIP_OUT_CROSS && (P->d.flags & XRFTHIP_ISO) && phase_nontrivial(P)) P->fastg = false;
-    if (P->fastg || P->fastgy) {
-        if (P->d.out_mode != XRFTHIP_OUT_POWER) { const int rc = fast_phase_tables(P); if (rc) return rc; }
-    } else if (P->fasts) {
-        if (P->d.out_mode != XRFTHIP_OUT_POWER) { const int rc = fast_phase_tables(P); if (rc) return rc; }
-    } else if (P->fastr || P->fastyc) {
-        if (P->d.out_mode != XRFTHIP_OUT_POWER) { const int rc = fast_phase_tables(P); if (rc) return rc; }
-        if (P->fastyc_fs) {
+    const bool phase = P->d.out_mode != XRFTHIP_OUT_POWER;  // (the complex modes: the combined phase tables, fast_phase_tables)
+    int rc = XRFTHIP_OK;
+    switch (P->chosen) {
+        case Family::FusedInner: return fusedi_tables(P);  // (its workspace layout does not depend on the tables)
+        case Family::Generic: case Family::Composite: break;
+        case Family::FastG:
+            if (cross_iso_phase(P)) { settle_family(P, true); break; }
+            [[fallthrough]];
+        case Family::FastGY: case Family::FastS: case Family::FastR: case Family::FastRComplex: case Family::FastRRows: case Family::FastYC: case Family::FastMX: case Family::FastMY:
+            if (phase) rc = fast_phase_tables(P);
+            break;
+        case Family::FastYCFourStep: {
+            if (phase) rc = fast_phase_tables(P);
+            if (rc) break;
             // a window has no separable form over the view; an input phase (PHASE_IN: the lag's factor on the source samples) must be one -- exp(i theta n) is:
             // row factor ph[256 i1], column factor ph[i2] / ph[0]; checked, else the generic passes take the plan
             bool ok = P->host_win_x.empty() && !P->win[1].p;
@@ -716,34 +743,25 @@ int finalize_plan(xrfthip_plan* P) {
                     ok = worst < 1e-9 && m0 > 0.0;
                 }
                 if (ok) {
-                    int rc = P->fph[0].upload(py.data(), py.size() * sizeof(cf));
+                    rc = P->fph[0].upload(py.data(), py.size() * sizeof(cf));
                     if (!rc) rc = P->fs_phx.upload(px.data(), px.size() * sizeof(cf));
-                    if (rc) return rc;
                 }
             }
-            if (!ok) P->fastyc = P->fastyc_fs = false;  // (the generic four-step passes)
+            if (!rc && !ok) settle_family(P, true);  // (the generic four-step passes)
+            break;
         }
-    } else if (P->fastmx) {
-        if (P->d.out_mode != XRFTHIP_OUT_POWER) { const int rc = fast_phase_tables(P); if (rc) return rc; }
-    } else if (P->fastmy) {
-        if (P->d.out_mode != XRFTHIP_OUT_POWER) { const int rc = fast_phase_tables(P); if (rc) return rc; }
-    } else if (P->fastm) {
-        int rc = fasty_window_spectra(P);
-        if (!rc && P->d.out_mode != XRFTHIP_OUT_POWER) rc = fast_phase_tables(P);
-        if (rc) return rc;
-    } else if (P->fast1d) {
-        P->fast1d_win = !P->host_win_x.empty();
-        int rc = P->fast1d_win ? fasty_window_spectra_1d(P) : fasty_window_spectra(P);
-        if (!rc && P->d.out_mode != XRFTHIP_OUT_POWER) rc = fast_phase_tables(P);
-        if (rc) return rc;
-    } else if (P->fast4096) {
-        int rc = XRFTHIP_OK;
-        if (P->yfirst) {
+        case Family::FastM: case Family::FastN: case Family::FastY:
             rc = fasty_window_spectra(P);
-            if (!rc && P->d.out_mode != XRFTHIP_OUT_POWER) rc = fast_phase_tables(P);
-        }
-        if (rc) return rc;
+            if (!rc && phase) rc = fast_phase_tables(P);
+            break;
+        case Family::FastY1D:
+            P->fast1d_win = !P->host_win_x.empty();  // (a window rides on a slab-shaped table)
+            rc = P->fast1d_win ? fasty_window_spectra_1d(P) : fasty_window_spectra(P);
+            if (!rc && phase) rc = fast_phase_tables(P);
+            break;
     }
+    if (rc) return rc;
+    settle_family(P);
     layout_workspace(P);
     return XRFTHIP_OK;
 }
@@ -896,297 +914,22 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
         if (c.T == 0 || n_try >= env_ll("XRFTHIP_X_FOURSTEP_MIN", 1LL << 40)) P->width = d.nx;
     }
     P->mirror = !cplx_in && !(d.flags & (XRFTHIP_HALF_X | XRFTHIP_AXIS_Y)) && P->width == d.nx / 2 + 1 && d.nx > 1;
-    auto fast_len = [](long long n) { return n == 256 || n == 512 || n == 1024 || n == 2048 || n == 4096; };
-    {
-        const uint32_t shifts = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X, ish = XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X, isof = XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT;
-        const uint32_t halff = XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2;  // real_dim: half output, no mirror
-        const uint32_t allowed = d.out_mode == XRFTHIP_OUT_POWER ? (shifts | isof | halff) : d.out_mode == XRFTHIP_OUT_COMPLEX ? (shifts | ish | XRFTHIP_HALF_X)
-                                 : d.out_mode == XRFTHIP_OUT_CROSS ? (shifts | ish | isof | halff) : d.out_mode == XRFTHIP_OUT_PHASE ? (shifts | ish | XRFTHIP_HALF_X) : 0u;
-        P->fast4096 = d.ndim == 2 && fast_len(d.ny) && fast_len(d.nx) && d.dtype == XRFTHIP_F32 &&
-                      !(d.flags & ~allowed) && !((d.flags & halff) && (d.flags & XRFTHIP_ISO)) && !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X)) &&
-                      !env_ll("XRFTHIP_NO_FAST", 0);
+    // the families in order of precedence: the first whose try_* does not decline serves the plan (its tables built); none: the generic passes
+    static int (*const kTry[])(xrfthip_plan*) = {try_fasts, try_fastyc, try_fastr, try_fasty, try_fast1d, try_fastm, try_fastmx, try_fastmy, try_fastgy, try_fastg, try_fastn};
+    int rc = kDeclined;
+    if (!env_ll("XRFTHIP_NO_FAST", 0))
+        for (auto try_family : kTry)
+            if ((rc = try_family(P)) != kDeclined) break;
+    if (rc == kDeclined) rc = XRFTHIP_OK;
+    const bool one_axis = P->family == Family::FastGY || P->family == Family::FastMY;
+    if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_PHASE_IN) && !one_axis) rc = XRFTHIP_BAD_ARG;  // (the generic column tiles have no input phase)
+    if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_HALF_X) && !one_axis) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (... and no half output: the caller transposes)
+    if (!rc) {
+        set_kernel_attrs_once();
+        // nbins must be known before tiles are sized (the LDS histogram shares the tile's allocation): ISO plans are
+        // (re)built in xrfthip_plan_set_binmap.  Build now for everything else.
+        if (!(d.flags & XRFTHIP_ISO)) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
     }
-    {   // complex float32 slabs of these lengths: the two-pass pipeline's complex form (fasty_c2c.h)
-        const uint32_t okc = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X | (d.out_mode == XRFTHIP_OUT_COMPLEX ? (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X | XRFTHIP_INVERSE | XRFTHIP_PHASE_IN | XRFTHIP_C2R_X) : 0u);
-        const bool c2r = (d.flags & XRFTHIP_C2R_X) != 0;  // (irfftn: the half spectrum in, nx real samples per row out; the row transforms have nx/2 points)
-        P->fastyc = d.ndim == 2 && d.dtype == XRFTHIP_C64 && fast_len(d.ny) && (c2r ? (d.nx % 2 == 0 && fast_len(d.nx / 2)) : fast_len(d.nx)) && !d.detrend &&
-                    (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER) && !(d.flags & ~okc) && !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTYC", 1) != 0;
-        if (P->fastyc) {
-            std::vector<float> ones((size_t)4096, 1.0f);
-            int rcc = build_twiddle<float>(P->tw_fx, c2r ? d.nx / 2 : d.nx, c2r ? d.nx / 2 : d.nx);
-            if (!rcc && c2r) rcc = build_twiddle<float>(P->tw_big1d, d.nx, d.nx / 32);  // W_nx^u, u < (nx/2) / 16
-            if (!rcc) rcc = build_twiddle<float>(P->tw_fy, d.ny, d.ny);
-            if (!rcc) rcc = P->ones4096.upload(ones.data(), ones.size() * sizeof(float));
-            if (rcc) { delete P; return rcc; }
-            P->yny = d.ny; P->ynx = d.nx;
-        }
-    }
-    {   // ONE long complex float32 sequence per batch entry, 2^16 .. 2^20 points (xrft.ifft of the spectrum of a long row, fft of complex rows: the inverse twin of
-        // BASELINE config 2): the same two passes on the [n / 256][256] view, pass 2 in its four-step form (before: the generic four-step passes, 49 GFFT/s)
-        const uint32_t okf = XRFTHIP_SHIFT_X | (d.out_mode == XRFTHIP_OUT_COMPLEX ? (XRFTHIP_ISHIFT_X | XRFTHIP_INVERSE | XRFTHIP_PHASE_IN) : 0u);
-        const bool fs = d.ndim == 1 && d.dtype == XRFTHIP_C64 && d.nx >= 65536 && d.nx <= 1048576 && (d.nx & (d.nx - 1)) == 0 && !d.detrend &&
-                        (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER) && !(d.flags & ~okf) && !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTYC", 1) != 0;
-        if (fs) {
-            P->fastyc = P->fastyc_fs = true;
-            std::vector<float> ones((size_t)4096, 1.0f);
-            int rcc = build_twiddle<float>(P->tw_fx, 256, 256);
-            if (!rcc) rcc = build_twiddle<float>(P->tw_big1d, d.nx, d.nx / 16);  // W_N^j, j < N / 16: the four-step twiddles of a row (k1 u, k1 NT)
-            if (!rcc) rcc = build_twiddle<float>(P->tw_fy, d.nx / 256, d.nx / 256);
-            if (!rcc) rcc = P->ones4096.upload(ones.data(), ones.size() * sizeof(float));
-            if (rcc) { delete P; return rcc; }
-            P->yny = d.nx / 256; P->ynx = 256;
-        }
-    }
-    // a small float32 slab (64 | 128 | 256 points per axis) fits the registers of one workgroup: full power spectra in ONE pass (fasts.h)
-    {
-        auto small_len = [](long long n) { return n == 64 || n == 128 || n == 256; };
-        const uint32_t oks = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X | (d.out_mode == XRFTHIP_OUT_POWER ? (XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT) : (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X));
-        P->fasts = d.ndim == 2 && d.dtype == XRFTHIP_F32 && small_len(d.ny) && small_len(d.nx) && (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_COMPLEX) &&
-                   !(d.flags & ~oks) && !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTS", 1) != 0;
-    }
-    if (P->fasts) {  // (takes precedence over the two-pass pipeline wherever the plan is looked at; an isotropic plan whose bin map turns out
-                     // not to be a radial one falls back to it: xrfthip_plan_set_binmap)
-        P->tune_sgrid = env_ll("XRFTHIP_FASTS_GRID", -1);
-        P->tune_sstagger = env_ll("XRFTHIP_FASTS_STAGGER", (3 << 8) | 2);  // (three classes 6.8 us apart: (4096, 256, 256) linear + Hann 310 -> 320 (the walk) -> 328 GFFT/s, profiles/r06_fasts_prefetch.txt)
-        std::vector<float> ones((size_t)256, 1.0f);
-        int rcs = build_twiddle<float>(P->tw_sy, d.ny, d.ny);
-        if (!rcs) rcs = build_twiddle<float>(P->tw_sx, d.nx, d.nx);
-        if (!rcs) rcs = P->ones4096.upload(ones.data(), ones.size() * sizeof(float));
-        if (rcs) { delete P; return rcs; }
-    }
-    if (P->fast4096) {
-        // every mode of these slabs takes the two-pass y-first pipeline (fasty.h)
-        P->yfirst = true;
-        if (P->yfirst) {
-            P->yny = d.ny; P->ynx = d.nx;
-            const int rpu = yrows_geom(d.nx).rk;
-            P->y_nrow_pad = (int)((d.ny / 2 + 1 + rpu - 1) / rpu * rpu);
-        }
-        int rc4 = build_twiddle<float>(P->tw_fx, d.nx, d.nx);
-        if (!rc4) rc4 = build_twiddle<float>(P->tw_fy, d.ny, d.ny);
-        std::vector<float> ones((size_t)std::max(d.ny, d.nx), 1.0f);
-        if (!rc4) rc4 = P->ones4096.upload(ones.data(), ones.size() * sizeof(float));
-        if (rc4) { delete P; return rc4; }
-    }
-    {   // one real float32 row of 65536 samples per workgroup, transformed in registers in ONE pass (fastr.h): 12 bytes per sample through
-        // memory where the four-step form below moves 28
-        const uint32_t okr = XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | (d.out_mode == XRFTHIP_OUT_POWER ? XRFTHIP_REALDIM_X2 : 0u) | (d.out_mode == XRFTHIP_OUT_COMPLEX ? XRFTHIP_ISHIFT_X : 0u);
-        P->fastr = d.ndim == 1 && (d.nx == 65536 || d.nx == 32768 || d.nx == 16384 || d.nx == 8192 || d.nx == 4096) && d.dtype == XRFTHIP_F32 && (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER) &&
-                   !(d.flags & ~okr) && !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X)) && !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTR", 1) != 0;
-        // ... and complex rows of 2048 .. 16384 points (xrft.ifft / fft of complex data along the contiguous axis): the same transform without the packing and the split
-        const uint32_t okc = XRFTHIP_SHIFT_X | (d.out_mode == XRFTHIP_OUT_COMPLEX ? (XRFTHIP_ISHIFT_X | XRFTHIP_INVERSE | XRFTHIP_PHASE_IN) : 0u);
-        P->fastr_cin = !P->fastr && d.ndim == 1 && d.dtype == XRFTHIP_C64 && (d.nx == 16384 || d.nx == 8192 || d.nx == 4096 || d.nx == 2048) && !d.detrend &&
-                       (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER) && !(d.flags & ~okc) && !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTC", 1) != 0;
-        // rows of 256 .. 4096 points: two rows per thread through one LDS buffer (the row pass of fasty_c2c.h on the input's own rows; XRFTHIP_CROWS=0: fastc_kernel / fastm_xonly_kernel)
-        const bool c2r1 = (d.flags & XRFTHIP_C2R_X) != 0;  // (irfft along the contiguous axis: rows of nx/2 + 1 complex values in, nx real samples out)
-        P->fastr_rows = !P->fastr && d.ndim == 1 && d.dtype == XRFTHIP_C64 && (c2r1 ? (d.nx % 2 == 0 && fast_len(d.nx / 2) && d.out_mode == XRFTHIP_OUT_COMPLEX) : fast_len(d.nx)) && !d.detrend &&
-                        (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER) && !(d.flags & ~(okc | (d.out_mode == XRFTHIP_OUT_COMPLEX ? XRFTHIP_C2R_X : 0u))) &&
-                        !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_CROWS", 1) != 0;
-        if (P->fastr_rows) {
-            P->fastr = true;
-            P->fastr_cin = false;
-            std::vector<float> ones((size_t)4096, 1.0f);
-            int rcr = build_twiddle<float>(P->tw_fx, c2r1 ? d.nx / 2 : d.nx, c2r1 ? d.nx / 2 : d.nx);
-            if (!rcr && c2r1) rcr = build_twiddle<float>(P->tw_big1d, d.nx, d.nx / 32);
-            if (!rcr) rcr = P->ones4096.upload(ones.data(), ones.size() * sizeof(float));
-            if (rcr) { delete P; return rcr; }
-        } else
-        if (P->fastr_cin) {
-            P->fastr = true;
-            P->tune_rgrid = env_ll("XRFTHIP_FASTR_GRID", 0);
-            P->tune_rstagger = env_ll("XRFTHIP_FASTR_STAGGER", 0);
-            const long long thr = d.nx / 32;  // threads per row: 32 complex values each
-            int rcr = build_twiddle<float>(P->tw_rm, d.nx, thr);
-            if (!rcr) rcr = build_twiddle<float>(P->tw_rs, thr, 32);
-            if (rcr) { delete P; return rcr; }
-        } else
-        if (P->fastr) {
-            // 65536 samples: one resident workgroup per CU walks the rows (measured: 359 vs 344 GFFT/s for a workgroup per row, profiles/r04_fastr.txt);
-            // the shorter rows (several workgroups per CU): a workgroup per row
-            // 32768 / 16384 samples (one / two workgroups per CU): a resident set, too -- with the start stagger run_fastr picks (profiles/r06_rows_stagger.txt)
-            P->tune_rgrid = env_ll("XRFTHIP_FASTR_GRID", d.nx == 65536 ? kCUs : (d.nx == 32768 && d.batch >= 2 * kCUs) ? kCUs : (d.nx == 16384 && d.out_mode == XRFTHIP_OUT_COMPLEX && d.batch >= 4 * kCUs) ? 2 * kCUs : 0);
-            // two classes of workgroups 10 us apart: dft (1024, 65536) 388 -> 441 GFFT/s, power_spectrum 517 -> 586 (profiles/r06_c2_stagger.txt); -1: run_fastr's rule
-            P->tune_rstagger = env_ll("XRFTHIP_FASTR_STAGGER", d.nx == 65536 ? ((2 << 8) | 3) : -1);
-            const long long thr = d.nx / 64;  // threads per row: 32 packed complex values each
-            int rcr = build_twiddle<float>(P->tw_rm, d.nx / 2, thr);
-            if (!rcr) rcr = build_twiddle<float>(P->tw_rs, thr, 32);
-            if (!rcr) rcr = build_twiddle<float>(P->tw_rn, d.nx, thr);
-            if (rcr) { delete P; return rcr; }
-        }
-    }
-    {   // one long real float32 sequence per slab, N = n1 * 256 samples (2^16 .. 2^20): the two passes of the y-first pipeline are
-        // the two steps of its four-step transform (fasty.h, FS)
-        const long long n1 = d.nx / 256;
-        const bool pow2 = d.nx >= 65536 && d.nx <= (1LL << 20) && (d.nx & (d.nx - 1)) == 0;
-        const uint32_t ok1 = XRFTHIP_SHIFT_X | (d.out_mode == XRFTHIP_OUT_COMPLEX ? XRFTHIP_ISHIFT_X : 0u);
-        P->fast1d = !P->fastr && d.ndim == 1 && pow2 && d.dtype == XRFTHIP_F32 && (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER) &&
-                    !(d.flags & ~ok1) && !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FAST1D", 1) != 0;
-        if (P->fast1d) {
-            P->yfirst = true;
-            P->yny = n1; P->ynx = 256;
-            const int rpu = yrows_geom(256, true).rk;
-            P->y_nrow_pad = (int)((n1 / 2 + 1 + rpu - 1) / rpu * rpu);
-            int rc1 = build_twiddle<float>(P->tw_fx, 256, 256);
-            if (!rc1) rc1 = build_twiddle<float>(P->tw_fy, n1, n1);
-            if (!rc1) rc1 = build_twiddle<float>(P->tw_big1d, d.nx, d.nx / 2 + 1);
-            std::vector<float> ones((size_t)std::max<long long>(n1, 256), 1.0f);
-            if (!rc1) rc1 = P->ones4096.upload(ones.data(), ones.size() * sizeof(float));
-            if (rc1) { delete P; return rc1; }
-        }
-    }
-    {   // real float64 slabs on the regular lat/lon lengths: the mixed-radix form of the y-first pipeline (fastm.h)
-        const uint32_t shifts = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X, ish = XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X;
-        const uint32_t isof = XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT;  // radial sums: fused into pass 2, or a pass over the stored spectrum (run_radial_sums)
-        const uint32_t halff = XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2;     // real_dim: half output, no mirror columns
-        const uint32_t allowed = d.out_mode == XRFTHIP_OUT_POWER ? (shifts | isof | halff) : d.out_mode == XRFTHIP_OUT_CROSS ? (shifts | ish | isof | halff)
-                                 : (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_PHASE) ? (shifts | ish | XRFTHIP_HALF_X) : 0u;
-        const bool half_ok = !((d.flags & halff) && (d.flags & XRFTHIP_ISO)) && !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X));
-        P->fastm = half_ok && d.ndim == 2 && (d.dtype == XRFTHIP_F64 || d.dtype == XRFTHIP_F32) && !P->fast4096 && fastm_len(d.ny, P->dbl) && fastm_len(d.nx, P->dbl) && !(d.flags & ~allowed) &&
-                   !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTM", 1) != 0 && env_ll("XRFTHIP_FASTN_TABLES", 1) != 0;
-        if (P->fastm) {
-            const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
-            const int rpu = fastm_rpu(d.nx, two, P->dbl);
-            if (rpu < 1 || rpu % fastm_rk2(d.ny, d.nx, two, P->dbl) != 0 || d.nx % fastm_cw(d.ny, d.nx, P->dbl) != 0) P->fastm = false;
-        }
-        if (P->fastm) {
-            const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
-            const int rpu = two ? fastm_rpu(d.nx, true, P->dbl) : mgeom(d.nx, P->dbl).g;  // (the largest count a row kernel of this plan may use)
-            P->yfirst = true;
-            P->yny = d.ny; P->ynx = d.nx; P->y_pitch = d.nx;
-            P->y_nrow_pad = (int)((d.ny / 2 + 1 + rpu - 1) / rpu * rpu);
-            int rcm = P->dbl ? build_twiddle<double>(P->tw_fx, d.nx, d.nx) : build_twiddle<float>(P->tw_fx, d.nx, d.nx);
-            if (!rcm) rcm = P->dbl ? build_twiddle<double>(P->tw_fy, d.ny, d.ny) : build_twiddle<float>(P->tw_fy, d.ny, d.ny);
-            std::vector<double> ones((size_t)std::max(d.ny, d.nx), 1.0);
-            std::vector<float> onesf((size_t)std::max(d.ny, d.nx), 1.0f);
-            if (!rcm) rcm = P->dbl ? P->ones4096.upload(ones.data(), ones.size() * sizeof(double)) : P->ones4096.upload(onesf.data(), onesf.size() * sizeof(float));
-            if (rcm) { delete P; return rcm; }
-        }
-    }
-    {   // one transform axis that is not the contiguous one, real input: pass 1 of the same kernels is the whole transform
-        const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
-        const uint32_t allowed = XRFTHIP_AXIS_Y | XRFTHIP_SHIFT_Y | (d.out_mode != XRFTHIP_OUT_POWER ? XRFTHIP_ISHIFT_Y : 0u) |
-                                 ((cplx_in && d.out_mode == XRFTHIP_OUT_COMPLEX) ? (XRFTHIP_INVERSE | XRFTHIP_PHASE_IN) : 0u) |  // (xrft.ifft along the axis)
-                                 (!cplx_in ? (XRFTHIP_HALF_X | (d.out_mode != XRFTHIP_OUT_PHASE ? XRFTHIP_REALDIM_X2 : 0u)) : 0u);  // (real_dim along the axis: half output)
-        P->fastmy = (d.flags & XRFTHIP_AXIS_Y) && d.ndim == 2 && (!cplx_in || !two) &&
-                    (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER || two) && !(d.flags & ~allowed) && fastmy_len(d.ny, P->dbl) &&
-                    !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_Y)) &&  // (the half output is unshifted: also refused by xrfthip_plan_create, kept here so the two cannot drift apart)
-                    d.batch * d.nx < (1LL << 30) && !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTM", 1) != 0;
-        if (P->fastmy && !(cplx_in && !two) && d.nx % ((two ? 1 : 2) * mygeom(d.ny, P->dbl).g) != 0) P->fastmy = false;  // (complex columns: any count, the last block guarded)
-        if (P->fastmy) {
-            int rcm = P->dbl ? build_twiddle<double>(P->tw_fy, d.ny, d.ny) : build_twiddle<float>(P->tw_fy, d.ny, d.ny);
-            std::vector<double> ones((size_t)d.ny, 1.0);
-            std::vector<float> onesf((size_t)d.ny, 1.0f);
-            if (!rcm) rcm = P->dbl ? P->ones4096.upload(ones.data(), ones.size() * sizeof(double)) : P->ones4096.upload(onesf.data(), onesf.size() * sizeof(float));
-            if (rcm) { delete P; return rcm; }
-        }
-    }
-    {   // ... on any other smooth length: one pass in LDS with the radices as data (fastg.h: fastgy_kernel)
-        const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;  // (two REAL fields: a column of each = one packed sequence; no flipped field)
-        const uint32_t allowed = XRFTHIP_AXIS_Y | XRFTHIP_SHIFT_Y | (d.out_mode != XRFTHIP_OUT_POWER ? XRFTHIP_ISHIFT_Y : 0u) |
-                                 ((cplx_in && d.out_mode == XRFTHIP_OUT_COMPLEX) ? (XRFTHIP_INVERSE | XRFTHIP_PHASE_IN) : 0u) |  // (xrft.ifft along the axis: conj in, conj out, the input rotated)
-                                 (!cplx_in ? (XRFTHIP_HALF_X | (d.out_mode != XRFTHIP_OUT_PHASE ? XRFTHIP_REALDIM_X2 : 0u)) : 0u);
-        P->fastgy = !P->fastmy && (d.flags & XRFTHIP_AXIS_Y) && (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER || (two && !cplx_in)) && !(d.flags & ~allowed) &&
-                    !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_Y)) &&
-                    !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTG", 1) != 0 && fastgy_try(P);
-        if (P->fastgy) {
-            const long long m = P->gy_blue_m ? P->gy_blue_m : d.ny;  // length of the passes
-            int rcg = P->dbl ? build_twiddle<double>(P->g_twy, m, m) : build_twiddle<float>(P->g_twy, m, m);
-            if (!rcg && !P->gy_rad_p) rcg = fastg_rev(P->g_ry, (int)m, P->g_revy, P->g_hrevy);
-            if (!rcg && P->gy_rad_p) rcg = P->dbl ? fastgy_rader_tables<double>(P) : fastgy_rader_tables<float>(P);
-            if (!rcg && P->gy_blue_m) rcg = P->dbl ? fastgy_blue_tables<double>(P) : fastgy_blue_tables<float>(P);
-            if (rcg) { delete P; return rcg; }
-        }
-    }
-    {   // ... and along the CONTIGUOUS axis of a 1-D plan when the length holds ONE prime 17 ... 127 (365 / 730 / 1460-sample (station, time) rows): the same kernel's
-        // prime-factor / Rader form with the lanes along the samples (fastg.h, FORM 3); every other 1-D length has its kernels below
-        const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
-        const uint32_t allowed = XRFTHIP_SHIFT_X | (d.out_mode != XRFTHIP_OUT_POWER ? XRFTHIP_ISHIFT_X : 0u) |
-                                 ((cplx_in && d.out_mode == XRFTHIP_OUT_COMPLEX) ? (XRFTHIP_INVERSE | XRFTHIP_PHASE_IN) : 0u) |
-                                 (!cplx_in ? (XRFTHIP_HALF_X | (d.out_mode != XRFTHIP_OUT_PHASE ? XRFTHIP_REALDIM_X2 : 0u)) : 0u);
-        const bool half_ok = !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X)) && !((d.flags & XRFTHIP_REALDIM_X2) && !(d.flags & XRFTHIP_HALF_X));
-        if (half_ok && !P->fastgy && d.ndim == 1 && (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER || (two && !cplx_in)) && !(d.flags & ~allowed) &&
-            !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTG", 1) != 0 && fastgy_try(P, true)) {
-            P->fastgy = true;
-            int rcg = P->dbl ? build_twiddle<double>(P->g_twy, d.nx, d.nx) : build_twiddle<float>(P->g_twy, d.nx, d.nx);
-            if (!rcg) rcg = P->dbl ? fastgy_rader_tables<double>(P) : fastgy_rader_tables<float>(P);
-            if (rcg) { delete P; return rcg; }
-        }
-    }
-    {   // one short transform axis, the contiguous one, real input: rows packed in pairs through the same three passes
-        const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
-        const uint32_t allowed = XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | (d.out_mode != XRFTHIP_OUT_PHASE ? XRFTHIP_REALDIM_X2 : 0u) | (d.out_mode != XRFTHIP_OUT_POWER ? XRFTHIP_ISHIFT_X : 0u) |
-                                 ((cplx_in && d.out_mode == XRFTHIP_OUT_COMPLEX) ? (XRFTHIP_INVERSE | XRFTHIP_PHASE_IN | XRFTHIP_C2R_X) : 0u);  // (xrft.ifft along the contiguous axis: conj in, conj out, the input rotated; irfft: two half rows per transform)
-        P->fastmx = !P->fastr && d.ndim == 1 && (!cplx_in || (!two && !(d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2)))) && (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_POWER || two) &&
-                    !(d.flags & ~allowed) && !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X)) && !((d.flags & XRFTHIP_REALDIM_X2) && !(d.flags & XRFTHIP_HALF_X)) &&
-                    fastmx_len(d.nx, P->dbl) && d.batch < (1LL << 31) - 16 && !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTM", 1) != 0;
-        if (P->fastmx) {
-            int rcm = P->dbl ? build_twiddle<double>(P->tw_fx, d.nx, d.nx) : build_twiddle<float>(P->tw_fx, d.nx, d.nx);
-            std::vector<double> ones((size_t)d.nx, 1.0);
-            std::vector<float> onesf((size_t)d.nx, 1.0f);
-            if (!rcm) rcm = P->dbl ? P->ones4096.upload(ones.data(), ones.size() * sizeof(double)) : P->ones4096.upload(onesf.data(), onesf.size() * sizeof(float));
-            if (rcm) { delete P; return rcm; }
-        }
-    }
-    {   // a small slab of any smooth shape, either precision, that none of the specialised kernels above takes: one pass in LDS (fastg.h)
-        // complex input (fft of complex data, every inverse transform): power / complex, no detrend, no real_dim, no radial sums
-        const bool cin_ok = !cplx_in || ((d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_COMPLEX) && !d.detrend && !(d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2 | XRFTHIP_ISO)) &&
-                                         (!(d.flags & XRFTHIP_C2R_X) || !(d.nx & 1)));
-        const uint32_t okg = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | ((cplx_in && d.out_mode == XRFTHIP_OUT_COMPLEX) ? (XRFTHIP_INVERSE | XRFTHIP_PHASE_IN | XRFTHIP_C2R_X) : 0u) |
-                             (d.out_mode == XRFTHIP_OUT_COMPLEX ? (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X)
-                              : d.out_mode == XRFTHIP_OUT_CROSS ? (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X | XRFTHIP_REALDIM_X2 | XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT)  // (no flipped field: the other paths)
-                              : (XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT | XRFTHIP_REALDIM_X2));
-        // (a 1-D transform along x that neither the register kernels nor the table lengths take: the same kernel on groups of rows)
-        const bool one_ok = d.ndim != 1 || (!P->fastr && !P->fastmx && !P->fast1d && !(d.flags & (XRFTHIP_ISO | XRFTHIP_SHIFT_Y | XRFTHIP_ISHIFT_Y)));
-        P->fastg = one_ok && cin_ok && !P->fasts && !P->fast4096 && !P->fastm && (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_CROSS) && !(d.flags & ~okg) &&
-                   !((d.flags & XRFTHIP_HALF_X) && (d.flags & (XRFTHIP_ISO | XRFTHIP_SHIFT_X | XRFTHIP_SHIFT_Y))) &&
-                   !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTG", 1) != 0 && fastg_try(P);
-        if (P->fastg) {
-            int rcg = P->dbl ? fastg_setup_t<double>(P) : fastg_setup_t<float>(P);
-            std::vector<double> ones((size_t)std::max<long long>(std::max(d.ny, d.nx), P->g_rows), 1.0);
-            std::vector<float> onesf(ones.size(), 1.0f);
-            if (!rcg) rcg = P->dbl ? P->ones4096.upload(ones.data(), ones.size() * sizeof(double)) : P->ones4096.upload(onesf.data(), onesf.size() * sizeof(float));
-            if (rcg) { delete P; return rcg; }
-        }
-    }
-    {   // every other large real slab whose lengths the butterflies factor (the columns: any length, through a chirp convolution): the y-first pipeline with the
-        // lengths as data (fastn.h) -- either pass may still be the table kernel of fastm.h when its length is in the table
-        const uint32_t shifts = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X, ish = XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X;
-        const uint32_t isof = XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT, halff = XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2;
-        const uint32_t allowed = d.out_mode == XRFTHIP_OUT_POWER ? (shifts | isof | halff) : d.out_mode == XRFTHIP_OUT_CROSS ? (shifts | ish | isof | halff)
-                                 : (d.out_mode == XRFTHIP_OUT_COMPLEX || d.out_mode == XRFTHIP_OUT_PHASE) ? (shifts | ish | XRFTHIP_HALF_X) : 0u;
-        const bool half_ok = !((d.flags & halff) && (d.flags & XRFTHIP_ISO)) && !((d.flags & XRFTHIP_HALF_X) && (d.flags & XRFTHIP_SHIFT_X));
-        const bool cand = half_ok && d.ndim == 2 && (d.dtype == XRFTHIP_F64 || d.dtype == XRFTHIP_F32) && !P->fast4096 && !P->fastm && !P->fastg && !P->fasts && !(d.flags & ~allowed) &&
-                          !env_ll("XRFTHIP_NO_FAST", 0) && env_ll("XRFTHIP_FASTN", 1) != 0;
-        if (cand) {
-            P->yny = d.ny; P->ynx = d.nx;
-            if (fastn_setup(P)) {
-                P->fastm = true; P->yfirst = true;
-                const bool two = plan_two(P);
-                const int rpu = P->n_r.rt ? P->n_rpu : (two ? fastm_rpu(d.nx, true, P->dbl) : mgeom(d.nx, P->dbl).g);  // (the largest count a row kernel of this plan may use)
-                P->y_nrow_pad = (int)((d.ny / 2 + 1 + rpu - 1) / rpu * rpu);
-                const long long ylen = P->n_blue_m ? P->n_blue_m : d.ny;
-                int rcn = P->dbl ? build_twiddle<double>(P->tw_fx, d.nx, d.nx) : build_twiddle<float>(P->tw_fx, d.nx, d.nx);
-                if (!rcn) rcn = P->dbl ? build_twiddle<double>(P->tw_fy, ylen, ylen) : build_twiddle<float>(P->tw_fy, ylen, ylen);
-                std::vector<double> ones((size_t)std::max(d.ny, d.nx), 1.0);
-                std::vector<float> onesf((size_t)std::max(d.ny, d.nx), 1.0f);
-                if (!rcn) rcn = P->dbl ? P->ones4096.upload(ones.data(), ones.size() * sizeof(double)) : P->ones4096.upload(onesf.data(), onesf.size() * sizeof(float));
-                if (!rcn && P->n_c.rt && P->n_rad_p) rcn = P->dbl ? fastn_rader_tables<double>(P) : fastn_rader_tables<float>(P);
-                else if (!rcn && P->n_c.rt) rcn = P->dbl ? fastn_upload_twm<double>(P->n_c.geo, P->n_c.twm, P->n_blue_m != 0) : fastn_upload_twm<float>(P->n_c.geo, P->n_c.twm, P->n_blue_m != 0);
-                if (!rcn && P->n_r.rt) rcn = P->dbl ? fastn_upload_twm<double>(P->n_r.geo, P->n_r.twm) : fastn_upload_twm<float>(P->n_r.geo, P->n_r.twm);
-                if (!rcn && P->n_blue_m) rcn = P->dbl ? fastn_blue_tables<double>(P) : fastn_blue_tables<float>(P);
-                if (!rcn && P->n_c.rt) rcn = P->n_c.geo_dev.upload(&P->n_c.geo, sizeof(NGeo));
-                if (!rcn && P->n_r.rt) rcn = P->n_r.geo_dev.upload(&P->n_r.geo, sizeof(NGeo));
-                if (rcn) { delete P; return rcn; }
-            }
-        }
-    }
-    if ((d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_PHASE_IN) && !P->fastgy && !P->fastmy) { delete P; return XRFTHIP_BAD_ARG; }  // (the generic column tiles have no input phase)
-    if ((d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_HALF_X) && !P->fastgy && !P->fastmy) { delete P; return XRFTHIP_UNSUPPORTED_LENGTH; }  // (... and no half output: the caller transposes)
-    set_kernel_attrs_once();
-    // nbins must be known before tiles are sized (the LDS histogram shares the tile's allocation): ISO plans are
-    // (re)built in xrfthip_plan_set_binmap.  Build now for everything else.
-    int rc = XRFTHIP_OK;
-    if (!(d.flags & XRFTHIP_ISO)) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
     if (!rc) rc = finalize_plan(P);
     if (rc) { delete P; return rc; }
     *plan = P;
@@ -1227,26 +970,26 @@ int xrfthip_plan_set_binmap(xrfthip_plan* plan, const int32_t* h_binmap, int64_t
     int rc = plan->binmap.upload(h_binmap, (size_t)ny * nx_out * sizeof(int32_t));
     if (rc) return rc;
     plan->nbins = nbins;
-    if (plan->fasts) {  // a radial map within the workgroup's reach: the sums are taken from the staged rows (fasts.h); else the other paths
-        const int rcs = fasts_build_tfirst(plan, h_binmap);
-        if (rcs) return rcs;
+    switch (plan->chosen) {
+        case Family::FastS:  // a radial map within the workgroup's reach: the sums are taken from the staged rows (fasts.h); else FastY's tables or the generic passes
+            rc = fasts_build_tfirst(plan, h_binmap);
+            if (rc || plan->chosen != Family::FastY) break;
+            [[fallthrough]];
+        case Family::FastY:
+            rc = fasty_build_tcodes(plan, h_binmap);
+            if (!rc && !plan->ytfirst_on && !fasty_iso_tables_fit(plan, nbins)) settle_family(plan, true);  // (any map: the atomic tables alias half of the transforms' LDS)
+            break;
+        case Family::FastG:  // any map: per-bin position lists (fastg.h)
+            rc = fastg_build_iso(plan, h_binmap);
+            break;
+        case Family::FastM: case Family::FastN:  // a radial map: the fused radial sums are gathered per bin (fastm_rows_kernel)
+            rc = fastm_build_tfirst(plan, h_binmap);
+            break;
+        case Family::Generic: case Family::Composite: case Family::FusedInner: case Family::FastGY: case Family::FastMX: case Family::FastMY:
+        case Family::FastR: case Family::FastRComplex: case Family::FastRRows: case Family::FastYC: case Family::FastYCFourStep: case Family::FastY1D:
+            break;
     }
-    if (plan->fastg) {  // any map: per-bin position lists (fastg.h)
-        const int rcs = fastg_build_iso(plan, h_binmap);
-        if (rcs) return rcs;
-    }
-    if (plan->fast4096 && !plan->fasts) {
-        int rcf = XRFTHIP_OK;
-        if (plan->yfirst) {
-            rcf = fasty_build_tcodes(plan, h_binmap);
-            if (!rcf && !plan->ytfirst_on && !fasty_iso_tables_fit(plan, nbins)) plan->fast4096 = false;  // (any map: the atomic tables alias half of the transforms' LDS)
-        }
-        if (rcf) return rcf;
-    }
-    if (plan->fastm) {  // a radial map: the fused radial sums are gathered per bin (fastm_rows_kernel)
-        const int rcf = fastm_build_tfirst(plan, h_binmap);
-        if (rcf) return rcf;
-    }
+    if (rc) return rc;
     plan->passes.clear();
     plan->passes_f0.clear();
     int rcb = plan->dbl ? build_plan_t<double>(*plan) : build_plan_t<float>(*plan);
@@ -1333,11 +1076,15 @@ int xrfthip_plan_profile_read(xrfthip_plan* plan, char* buf, size_t buflen) {
 
 int xrfthip_plan_uses_bluestein(const xrfthip_plan* plan) {
     if (!plan) return 0;
-    if (plan->sub_x) return xrfthip_plan_uses_bluestein(plan->sub_x) || xrfthip_plan_uses_bluestein(plan->sub_y);
-    if (plan->fastgy) return plan->gy_blue_m > 0;
-    if (plan->fastn) return plan->n_blue_m > 0;
-    if (plan->fusedi) return 0;
-    if (plan->fastyc || plan->fastg || plan->fasts || plan->fastr || plan->fastmx || plan->fastmy || plan->fastm || plan->fast1d || plan->fast4096) return 0;  // (the generic passes of such a plan never run)
+    switch (plan->family) {
+        case Family::Composite: return xrfthip_plan_uses_bluestein(plan->sub_x) || xrfthip_plan_uses_bluestein(plan->sub_y);
+        case Family::FastGY: return plan->gy_blue_m > 0;
+        case Family::FastN: return plan->n_blue_m > 0;
+        case Family::Generic: break;
+        case Family::FusedInner: case Family::FastS: case Family::FastG: case Family::FastMX: case Family::FastMY: case Family::FastR: case Family::FastRComplex:
+        case Family::FastRRows: case Family::FastYC: case Family::FastYCFourStep: case Family::FastY: case Family::FastY1D: case Family::FastM:
+            return 0;  // (the generic passes of such a plan never run)
+    }
     for (const Pass& ps : plan->passes) if (ps.g.blue_n > 0) return 1;
     for (const Pass& ps : plan->passes_f0) if (ps.g.blue_n > 0) return 1;
     return 0;
@@ -1348,17 +1095,20 @@ int xrfthip_plan_kernel_info(const xrfthip_plan* plan, int32_t* kind, int32_t* p
     const xrfthip_plan* P = plan;
     const bool two = P->d.out_mode == XRFTHIP_OUT_CROSS || P->d.out_mode == XRFTHIP_OUT_PHASE;
     int k = XRFTHIP_K_GENERIC, n = 0;
-    if (P->sub_x) k = XRFTHIP_K_COMPOSITE;
-    else if (P->fusedi) { k = XRFTHIP_K_FASTN; n = P->n_cw; }
-    else if (P->fastg) { k = P->g_one_d ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG; n = P->g_one_d ? P->g_rows : 1; }
-    else if (P->fasts) { k = XRFTHIP_K_FASTS; n = 1; }
-    else if (P->fastyc) { k = XRFTHIP_K_FASTY; n = 0; }
-    else if (P->fastr) { k = XRFTHIP_K_FASTR; n = 1; }
-    else if (P->fastmx) { k = XRFTHIP_K_FASTM_X; const MGeomRt C = mxgeom(P->d.nx, P->dbl); n = (two || (P->cplx_in && !(P->d.flags & XRFTHIP_C2R_X))) ? C.g : 2 * C.g; }
-    else if (P->fastgy) { k = P->gy_rows ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG_Y; n = ((P->cplx_in || two) ? 1 : 2) * P->gy_G; }
-    else if (P->fastmy) { k = XRFTHIP_K_FASTM_Y; const MGeomRt C = mygeom(P->d.ny, P->dbl); n = ((P->cplx_in || two) ? 1 : 2) * C.g; }
-    else if (P->fastm) { k = P->fastn ? XRFTHIP_K_FASTN : XRFTHIP_K_FASTM; n = plan_cw(P); }
-    else if (fasty_on(P)) { k = XRFTHIP_K_FASTY; n = 0; }
+    switch (P->family) {
+        case Family::Generic: break;
+        case Family::Composite: k = XRFTHIP_K_COMPOSITE; break;
+        case Family::FusedInner: k = XRFTHIP_K_FASTN; n = P->n_cw; break;
+        case Family::FastG: k = P->g_one_d ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG; n = P->g_one_d ? P->g_rows : 1; break;
+        case Family::FastS: k = XRFTHIP_K_FASTS; n = 1; break;
+        case Family::FastYC: case Family::FastYCFourStep: case Family::FastY: case Family::FastY1D: k = XRFTHIP_K_FASTY; break;
+        case Family::FastR: case Family::FastRComplex: case Family::FastRRows: k = XRFTHIP_K_FASTR; n = 1; break;
+        case Family::FastMX: { k = XRFTHIP_K_FASTM_X; const MGeomRt C = mxgeom(P->d.nx, P->dbl); n = (two || (P->cplx_in && !(P->d.flags & XRFTHIP_C2R_X))) ? C.g : 2 * C.g; break; }
+        case Family::FastGY: k = P->gy_rows ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG_Y; n = ((P->cplx_in || two) ? 1 : 2) * P->gy_G; break;
+        case Family::FastMY: { k = XRFTHIP_K_FASTM_Y; const MGeomRt C = mygeom(P->d.ny, P->dbl); n = ((P->cplx_in || two) ? 1 : 2) * C.g; break; }
+        case Family::FastM: k = XRFTHIP_K_FASTM; n = plan_cw(P); break;
+        case Family::FastN: k = XRFTHIP_K_FASTN; n = plan_cw(P); break;
+    }
     *kind = k; *per_workgroup = n;
     return XRFTHIP_OK;
 }
@@ -1372,7 +1122,12 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
     if (!plan || !buf || !buflen) return XRFTHIP_BAD_ARG;
     std::string s;
     const xrfthip_desc& d = plan->d;
-    if (plan->fusedi) {
+    if (!inner_layout(plan))  // (FusedInner / Composite: a header of their own)
+        appendf(s, "xrfthip plan: ndim=%d batch=%lld ny=%lld nx=%lld dtype=%d mode=%d detrend=%d flags=0x%x width=%lld nx_out=%lld mirror=%d group=%d ws=%zuB\n",
+                d.ndim, (long long)d.batch, (long long)d.ny, (long long)d.nx, d.dtype, d.out_mode, d.detrend, d.flags,
+                plan->width, plan->nx_out, (int)plan->mirror, plan->G, plan->ws_bytes);
+    switch (plan->family) {
+    case Family::FusedInner: {
         auto rads = [](const NGeo& g) { std::string t; for (int i = 0; i < g.np; ++i) t += (i ? "x" : "") + std::to_string(g.r[i]); return t; };
         const NGeo &gc = plan->n_c.geo, &gr = plan->n_r.geo;
         appendf(s, "xrfthip plan: [batch %lld][ny %lld][mid %lld][nx %lld][inner %lld] dtype=%d mode=%d detrend=%d flags=0x%x ws=%zuB\n"
@@ -1381,12 +1136,9 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
                    "back in the spectral domain, (ky, kx, e) and its Hermitian twin stored as runs of %d elements\n",
                 (long long)d.batch, (long long)d.ny, (long long)plan->mid, (long long)d.nx, (long long)plan->inner, d.dtype, d.out_mode, d.detrend, d.flags, plan->ws_bytes,
                 gc.thr, gc.g, gc.n, plan->n_rad_p ? ("Rader, prime " + std::to_string(plan->n_rad_p)).c_str() : rads(gc).c_str(), plan->n_c.lds, plan->y_nrow_pad, plan->n_rk, plan->n_nxb, plan->n_rk, plan->n_cw, gr.thr, gr.g, gr.n, rads(gr).c_str(), plan->n_r.lds, gr.g);
-        const size_t n = std::min(buflen - 1, s.size());
-        memcpy(buf, s.data(), n);
-        buf[n] = 0;
-        return (int)n;
+        break;
     }
-    if (plan->sub_x) {
+    case Family::Composite:
         appendf(s, "xrfthip plan: [batch %lld][ny %lld][mid %lld][nx %lld][inner %lld] dtype=%d mode=%d detrend=%d flags=0x%x ws=%zuB\n  [inner layout] no transposed copy: %sx where it lies, then y\n",
                 (long long)d.batch, (long long)d.ny, (long long)plan->mid, (long long)d.nx, (long long)plan->inner, d.dtype, d.out_mode, d.detrend, d.flags, plan->ws_bytes,
                 d.detrend ? "detrend pass (plane per (batch, inner) element), " : "");
@@ -1396,15 +1148,9 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
             s += "  ";
             for (const char* c = tmp.data(); *c; ++c) { s += *c; if (*c == '\n' && c[1]) s += "  "; }
         }
-        const size_t n = std::min(buflen - 1, s.size());
-        memcpy(buf, s.data(), n);
-        buf[n] = 0;
-        return (int)n;
-    }
-    appendf(s, "xrfthip plan: ndim=%d batch=%lld ny=%lld nx=%lld dtype=%d mode=%d detrend=%d flags=0x%x width=%lld nx_out=%lld mirror=%d group=%d ws=%zuB\n",
-            d.ndim, (long long)d.batch, (long long)d.ny, (long long)d.nx, d.dtype, d.out_mode, d.detrend, d.flags,
-            plan->width, plan->nx_out, (int)plan->mirror, plan->G, plan->ws_bytes);
-    if (plan->fastg) {
+        break;
+    case Family::Generic: break;
+    case Family::FastG: {
         std::string rxs, rys;
         for (int r : plan->g_rx) rxs += (rxs.empty() ? "" : "x") + std::to_string(r);
         for (int r : plan->g_ry) rys += (rys.empty() ? "" : "x") + std::to_string(r);
@@ -1430,19 +1176,25 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         if (plan->d.flags & XRFTHIP_ISO)
             appendf(s, "  [fastg radial sums] in the same pass: per bin the LDS positions of its samples (any bin map), a bin per wave, float64, a fixed shuffle tree -- no atomics%s\n",
                     (plan->d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? "; the spectrum is not stored" : "");
-    } else if (plan->fasts) {
+        break;
+    }
+    case Family::FastS: {
         const SGeomRt G = sgeom(plan->d.ny, plan->d.nx);
         appendf(s, "  [fasts] one pass, one %d-thread workgroup per %lld x %lld slab (%d fit a CU): the packed columns' transform, their split and the rows' "
                    "transform in registers (32 complex per thread, r32x%lld / r32x%lld, three LDS exchanges in halves), exact plane detrend in the workgroup, |F|^2 "
                    "rows staged in LDS and written whole with the fftshift and the Hermitian mirror, lds=%zuB; 8 algorithmic bytes per sample through memory\n",
                 G.thr, (long long)plan->d.ny, (long long)plan->d.nx, G.per_cu, (long long)plan->d.ny / 32, (long long)plan->d.nx / 32, G.lds);
-    } else if (plan->fastyc && plan->fastyc_fs) {
+        break;
+    }
+    case Family::FastYCFourStep: {
         const YGeomRt C = ycols_geom(plan->d.nx / 256), R = yrows_geom(256);
         appendf(s, "  [fasty complex rows, four-step] two passes over the [%lld][256] view of every %lld-point sequence: cols: %d thr, FFT%lld along the view's rows index (input rotation / lag phase / "
                    "conjugation on load) -> W2 in whole lines -> rows: %d thr, %d rows/unit x W_N^(i2 k1), FFT256, stored transposed (X[k1 + %lld k2]: runs of %d samples)%s; 32 bytes per point through memory\n",
                 (long long)plan->d.nx / 256, (long long)plan->d.nx, C.thr, (long long)plan->d.nx / 256, R.thr, R.rk, (long long)plan->d.nx / 256, R.rk / 2,
                 (plan->d.flags & XRFTHIP_INVERSE) ? "; inverse: conjugate in / out" : "");
-    } else if (plan->fastyc) {
+        break;
+    }
+    case Family::FastYC: {
         const YGeomRt C = ycols_geom(plan->d.ny), R = yrows_geom(plan->d.nx);
         if (plan->d.flags & XRFTHIP_C2R_X) {
             const YGeomRt R2 = yrows_geom(plan->d.nx / 2);
@@ -1454,7 +1206,9 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
                    "(FFT%lld), whole rows out (scale, %sfftshift); 32 B per point through memory\n",
                 C.thr, C.gxy, (long long)plan->d.ny, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse: conjugate in / out" : "forward", 2 * C.gxy, (long long)plan->d.ny,
                 std::max(1, 16 / (2 * C.gxy)), 2 * C.gxy, std::max(1, 16 / (2 * C.gxy)), 2 * C.gxy, R.thr, R.rk, (long long)plan->d.nx, plan->fph_on ? "phase, " : "");
-    } else if (plan->fastr && plan->fastr_rows) {
+        break;
+    }
+    case Family::FastRRows: {
         const bool c2r = (plan->d.flags & XRFTHIP_C2R_X) != 0;
         const YGeomRt R = yrows_geom(c2r ? plan->d.nx / 2 : plan->d.nx);
         if (c2r) appendf(s, "  [fasty complex rows] one pass: %d thr, %d rows/unit of the row-major half spectrum back to %lld real samples each (FFT%lld on the packed row; two rows per "
@@ -1462,12 +1216,16 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         else
         appendf(s, "  [fasty complex rows] one pass: %d thr, %d rows/unit of the row-major input (FFT%lld, %s; two rows per thread through one LDS buffer), whole rows out; "
                    "16 algorithmic bytes per point through memory\n", R.thr, R.rk, (long long)plan->d.nx, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse" : "forward");
-    } else if (plan->fastr && plan->fastr_cin) {
+        break;
+    }
+    case Family::FastRComplex: {
         appendf(s, "  [fastr complex rows] one pass, one %lld-thread workgroup per %lld-point complex row: the %s transform in registers (32 per thread, two LDS "
                    "exchanges), natural order through the LDS, lds=%zuB; 16 algorithmic bytes per point through memory\n",
                 (long long)plan->d.nx / 32, (long long)plan->d.nx, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse" : "forward",
                 plan->d.nx == 16384 ? R2Geom<32, 16>::LDS : plan->d.nx == 8192 ? R2Geom<16, 16>::LDS : plan->d.nx == 4096 ? R2Geom<16, 8>::LDS : R2Geom<8, 8>::LDS);
-    } else if (plan->fastr) {
+        break;
+    }
+    case Family::FastR: {
         const long long nxr = plan->d.nx;
         appendf(s, "  [fastr] one pass, one %lld-thread workgroup per %lld-sample row (grid %lld): the packed %lld-point complex transform in registers (32 per thread, "
                    "r32x%dx%d, LDS exchanges%s), real split through the LDS, lds=%zuB; per-row detrend + window + full (or half) spectrum; "
@@ -1475,11 +1233,15 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
                 nxr / 64, nxr, plan->tune_rgrid > 0 ? std::min<long long>(plan->tune_rgrid, plan->d.batch) : (long long)plan->d.batch, nxr / 2,
                 nxr >= 32768 ? 32 : nxr == 4096 ? 8 : 16, nxr == 65536 ? 32 : nxr <= 8192 ? 8 : 16, nxr == 65536 ? " in halves" : "",
                 nxr == 65536 ? kFastRLds : nxr == 32768 ? R2Geom<32, 16>::LDS : nxr == 16384 ? R2Geom<16, 16>::LDS : nxr == 8192 ? R2Geom<16, 8>::LDS : R2Geom<8, 8>::LDS);
-    } else if (plan->fastmx) {
+        break;
+    }
+    case Family::FastMX: {
         const MGeomRt C = mxgeom(plan->d.nx, plan->dbl);
         appendf(s, "  [fastm x-only] %d thr, %d row pairs per workgroup (FFT%lld r%dx%dx%d in LDS), lds=%zuB: per-row detrend + window + transform + full (or half) spectrum in one pass\n",
                 C.thr, C.g, (long long)plan->d.nx, C.r0, C.r1, C.r2, C.lds_cols);
-    } else if (plan->fastgy) {
+        break;
+    }
+    case Family::FastGY: {
         std::string rys;
         for (int r : plan->g_ry) rys += (rys.empty() ? "" : "x") + std::to_string(r);
         const bool onecol = plan->cplx_in || plan->d.out_mode == XRFTHIP_OUT_CROSS || plan->d.out_mode == XRFTHIP_OUT_PHASE;
@@ -1502,11 +1264,15 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         if (plan->gy_blue_m)
             appendf(s, "  [fastg y-only Bluestein] %lld points as a circular convolution of %d inside the tile (chirp products, forward and inverse passes)%s\n",
                     (long long)plan->d.ny, plan->gy_blue_m, plan->gy_tw_lds ? "" : "; twiddles from memory");
-    } else if (plan->fastmy) {
+        break;
+    }
+    case Family::FastMY: {
         const MGeomRt C = mygeom(plan->d.ny, plan->dbl);
         appendf(s, "  [fastm y-only] %d thr, %d packed column pairs (FFT%lld r%dx%dx%d in LDS), lds=%zuB: per-column detrend + window + transform + both halves of the spectrum in one pass, in place in memory order\n",
                 C.thr, C.g, (long long)plan->d.ny, C.r0, C.r1, C.r2, C.lds_cols);
-    } else if (plan->fastm && plan->fastn) {
+        break;
+    }
+    case Family::FastN: {
         auto rads = [](const NGeo& g) { std::string t; for (int i = 0; i < g.np; ++i) t += (i ? "x" : "") + std::to_string(g.r[i]); return t; };
         std::string cs_, rs_;
         if (plan->n_c.rt) {
@@ -1539,7 +1305,9 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
             appendf(s, "  [fastn radial sums] %s\n", fastm_iso_gather(plan) ? "fused into the row pass: radial map, per-bin gather from the spectra in LDS, no atomics"
                                                    : fastm_iso_fused(plan) ? "fused into the row pass: int64 fixed-point tables behind the transforms' LDS"
                                                                            : "a pass over the stored spectrum");
-    } else if (plan->fastm) {
+        break;
+    }
+    case Family::FastM: {
         const MGeomRt C = mgeom_cols(plan->yny, plan->ynx, plan->dbl), R = mgeom(plan->ynx, plan->dbl);
         appendf(s, "  [fastm] cols: %d thr, %d packed column pairs (FFT%lld r%dx%dx%d in LDS), lds=%zuB -> W2[slab][%d/%d][nx/%d][%d][%d] complex -> fit -> rows: %d thr, %d rows/unit (FFT%lld r%dx%dx%d), lds=%zuB, trend added back in the spectral domain, fftshift + mirror rows\n",
                 C.thr, C.g, (long long)plan->yny, C.r0, C.r1, C.r2, C.lds_cols, plan->y_nrow_pad, fastm_rk2(plan->yny, plan->ynx, plan->d.out_mode >= XRFTHIP_OUT_CROSS, plan->dbl), fastm_cw(plan->yny, plan->ynx, plan->dbl), fastm_rk2(plan->yny, plan->ynx, plan->d.out_mode >= XRFTHIP_OUT_CROSS, plan->dbl), fastm_cw(plan->yny, plan->ynx, plan->dbl),
@@ -1548,9 +1316,12 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
             appendf(s, "  [fastm radial sums] %s\n", fastm_iso_gather(plan) ? "fused into the row pass: radial map, per-bin gather from the spectra in LDS, no atomics"
                                                    : fastm_iso_fused(plan) ? "fused into the row pass: int64 fixed-point tables behind the transforms' LDS"
                                                                            : "a pass over the stored spectrum (the tables do not fit beside the transforms)");
-    } else if (fasty_on(plan)) {
-        const YGeomRt C = ycols_geom(plan->yny), R = yrows_geom(plan->ynx, plan->fast1d);
-        if (plan->fast1d) appendf(s, "  [fasty four-step] %lld samples = [%lld][%lld]: columns = step 1 (half spectrum k1 <= %lld), rows x W_N^(i2 k1) = step 2, transposed stores + Hermitian mirror\n",
+        break;
+    }
+    case Family::FastY: case Family::FastY1D: {
+        const bool fs = plan->family == Family::FastY1D;
+        const YGeomRt C = ycols_geom(plan->yny), R = yrows_geom(plan->ynx, fs);
+        if (fs) appendf(s, "  [fasty four-step] %lld samples = [%lld][%lld]: columns = step 1 (half spectrum k1 <= %lld), rows x W_N^(i2 k1) = step 2, transposed stores + Hermitian mirror\n",
                                   (long long)plan->d.nx, (long long)plan->yny, (long long)plan->ynx, (long long)plan->yny / 2);
         appendf(s, "  [fasty] cols: %d thr, %d x 2 packed column pairs (FFT%lld r16x16x%lld, column-local detrend fused), %d columns/unit, lds=%zuB -> W2[slab][%d/%d][nx/%d][2][%d][%d] -> rows: %d thr, %d rows/unit (FFT%lld r16x16x%lld), lds=%zuB, |F|^2 + fftshift + mirror rows\n",
                 C.thr, C.gxy, (long long)plan->d.ny, (long long)plan->d.ny / 256, C.cw, C.lds, plan->y_nrow_pad, C.rk, C.cw, C.rk, 2 * C.gxy,
@@ -1558,9 +1329,13 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         if ((plan->d.flags & XRFTHIP_ISO) && plan->ytcodes.p)
             appendf(s, "  [fasty radial sums] fused into the row pass (runs of equal bins from the staged rows, int64 fixed-point tables), bin codes: %s\n",
                     plan->ytfirst_on ? "radial map: per-bin gather, no atomics" : plan->ytcodes_compact ? "compact (radial map: first bin + step mask per 16 samples)" : "full (4 bytes per sample)");
+        break;
     }
-    describe_passes(s, plan->passes_f0, "f0");
-    describe_passes(s, plan->passes, "main");
+    }
+    if (!inner_layout(plan)) {
+        describe_passes(s, plan->passes_f0, "f0");
+        describe_passes(s, plan->passes, "main");
+    }
     const size_t n = std::min(buflen - 1, s.size());
     memcpy(buf, s.data(), n);
     buf[n] = 0;
@@ -1577,16 +1352,9 @@ int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1,
     if (cross && !d_in1) return XRFTHIP_BAD_ARG;
     if (!d_out && !(d.flags & XRFTHIP_NO_SPECTRUM_OUT)) return XRFTHIP_BAD_ARG;
     if (iso && (!d_iso || !P->binmap.p)) return d_iso ? XRFTHIP_MISSING_TABLE : XRFTHIP_BAD_ARG;
-    if (P->fusedi) {
-        if (ws_bytes < P->ws_bytes || !d_workspace) return XRFTHIP_WORKSPACE_TOO_SMALL;
-        return d.batch == 0 ? XRFTHIP_OK : run_fused_inner(P, d_in0, d_in1, d_out, (char*)d_workspace, (hipStream_t)stream);
-    }
-    if (P->sub_x) {
-        if (ws_bytes < P->ws_bytes || !d_workspace) return XRFTHIP_WORKSPACE_TOO_SMALL;
-        return d.batch == 0 ? XRFTHIP_OK : run_inner_plan(P, d_in0, d_out, (char*)d_workspace, (hipStream_t)stream);
-    }
-    if (P->passes.empty()) return XRFTHIP_MISSING_TABLE;
-    if (ws_bytes < P->ws_bytes || (!d_workspace && P->ws_bytes)) return XRFTHIP_WORKSPACE_TOO_SMALL;
+    const bool inner = inner_layout(P);  // (always a workspace)
+    if (!inner && P->passes.empty()) return XRFTHIP_MISSING_TABLE;
+    if (ws_bytes < P->ws_bytes || (!d_workspace && (inner || P->ws_bytes))) return XRFTHIP_WORKSPACE_TOO_SMALL;
     if (d.batch == 0) return XRFTHIP_OK;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)d_workspace;
@@ -1594,17 +1362,20 @@ int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1,
     const bool det = d.detrend != XRFTHIP_DETREND_NONE;
     double* acc = (double*)(ws + P->off_acc);
     double* coef = (double*)(ws + P->off_coef);
-    if (iso) HIP_TRY(hipMemsetAsync(d_iso, 0, (size_t)d.batch * P->nbins * (cross ? 16 : 8), st));
-    if (P->fastg) return run_fastg(P, d_in0, d_in1, out, (double*)d_iso, st);
-    if (P->fasts) return run_fasts(P, d_in0, out, (double*)d_iso, st);
-    if (P->fastyc) return run_fastyc(P, d_in0, out, ws, st);
-    if (P->fastr) return run_fastr(P, d_in0, out, st);
-    if (P->fastmx) return run_fastmx(P, d_in0, d_in1, out, st);
-    if (P->fastgy) return run_fastgy(P, d_in0, d_in1, out, st);
-    if (P->fastmy) return run_fastmy(P, d_in0, d_in1, out, st);
-    if (P->fastm) return run_fastm(P, d_in0, d_in1, out, (double*)d_iso, ws, st);
-    if (fasty_on(P)) {
-        return run_fasty(P, (const float*)d_in0, (const float*)d_in1, out, (double*)d_iso, ws, st);
+    if (iso && !inner) HIP_TRY(hipMemsetAsync(d_iso, 0, (size_t)d.batch * P->nbins * (cross ? 16 : 8), st));
+    switch (P->family) {
+        case Family::FusedInner: return run_fused_inner(P, d_in0, d_in1, d_out, ws, st);
+        case Family::Composite: return run_inner_plan(P, d_in0, d_out, ws, st);
+        case Family::FastG: return run_fastg(P, d_in0, d_in1, out, (double*)d_iso, st);
+        case Family::FastS: return run_fasts(P, d_in0, out, (double*)d_iso, st);
+        case Family::FastYC: case Family::FastYCFourStep: return run_fastyc(P, d_in0, out, ws, st);
+        case Family::FastR: case Family::FastRComplex: case Family::FastRRows: return run_fastr(P, d_in0, out, st);
+        case Family::FastMX: return run_fastmx(P, d_in0, d_in1, out, st);
+        case Family::FastGY: return run_fastgy(P, d_in0, d_in1, out, st);
+        case Family::FastMY: return run_fastmy(P, d_in0, d_in1, out, st);
+        case Family::FastM: case Family::FastN: return run_fastm(P, d_in0, d_in1, out, (double*)d_iso, ws, st);
+        case Family::FastY: case Family::FastY1D: return run_fasty(P, (const float*)d_in0, (const float*)d_in1, out, (double*)d_iso, ws, st);
+        case Family::Generic: break;
     }
     for (long long g0 = 0; g0 < d.batch; g0 += P->G) {
         const long long gc = std::min<long long>(P->G, d.batch - g0);
