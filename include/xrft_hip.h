@@ -107,7 +107,8 @@ typedef enum xrfthip_detrend_kind {
 #define XRFTHIP_FLIP0_Y 0x4000u
 #define XRFTHIP_FLIP0_X 0x8000u
 /* inner / mid layouts only (ABI 0.1.6): real_dim along the FIRST of the two transform axes -- ky = 0..ny/2 is stored, output [batch][ny/2 + 1][mid][nx][inner], unshifted;
- * with REALDIM_X2 and POWER|CROSS 0 < ky < ny/2 counts twice.  Real input, no SHIFT_*, not together with HALF_X. */
+ * with REALDIM_X2 and POWER|CROSS 0 < ky < ny/2 counts twice.  Real input, no SHIFT_*, not together with HALF_X.  ny may be odd: ky = 0..(ny-1)/2 is stored
+ * (numpy.fft.rfft's (ny-1)/2 + 1 rows, no Nyquist row), and every ky > 0 counts twice; XRFTHIP_UNSUPPORTED_LENGTH where only the composite of one-axis plans exists. */
 #define XRFTHIP_HALF_Y 0x10000u
 
 typedef struct xrfthip_desc {

@@ -184,3 +184,19 @@ def test_label_memo_is_keyed_by_tokens_not_by_object_identity():
     k1 = api._akey(view)
     base[3] = 99.0
     assert api._akey(view) != k1
+
+
+def test_swap_xy_is_an_involution_that_maps_every_x_bit_to_its_y_bit():
+    from xrft_amd import _lib as L
+
+    pairs = [(L.SHIFT_X, L.SHIFT_Y), (L.ISHIFT_X, L.ISHIFT_Y), (L.FLIP_X, L.FLIP_Y), (L.HALF_X, L.HALF_Y), (L.FLIP0_X, L.FLIP0_Y)]
+    other = L.REALDIM_X2 | L.ISO | L.INVERSE | L.PHASE_IN
+    for fx, fy in pairs:
+        assert api._swap_xy(fx) == fy and api._swap_xy(fy) == fx
+        assert api._swap_xy(fx | other) == fy | other
+    every = 0
+    for fx, fy in pairs:
+        every |= fx | fy
+    for flags in range(0, 1 << 17, 37):
+        assert api._swap_xy(api._swap_xy(flags)) == flags
+    assert api._swap_xy(every | other) == every | other

@@ -12,7 +12,9 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "emu"))
 import build_emu  # noqa: E402
 
-from xrft_amd import _lib, api, engine  # noqa: E402
+from xrft_amd import _lib, api  # noqa: E402
+
+from accuracy import ROWS, family, make, radial_map  # noqa: E402,F401  (the routing table lives beside the accuracy bounds: the ladder executes every row)
 
 L = _lib
 F32, F64, C64 = torch.float32, torch.float64, torch.complex64
@@ -25,19 +27,6 @@ def emulated_library():
     yield
     api._plan_cache.clear()
     _lib._state.update(dll=None, path=None, device="cuda")
-
-
-def make(ndim=2, batch=2, ny=1, nx=1, dtype=F32, out_mode=L.OUT_POWER, detrend=L.DETREND_NONE, flags=0, **kw):
-    if ndim == 1:
-        ny = 1
-    return engine.SpectralPlan(ndim=ndim, batch=batch, ny=ny, nx=nx, dtype=dtype, out_mode=out_mode, detrend=detrend, flags=flags, scale=1.0, **kw)
-
-
-def radial_map(ny, nx):
-    ky = np.minimum(np.arange(ny), ny - np.arange(ny))[:, None]
-    kx = np.minimum(np.arange(nx), nx - np.arange(nx))[None, :]
-    nb = min(ny, nx) // 2 + 1
-    return np.minimum(np.floor(np.hypot(ky, kx)).astype(np.int32), nb - 1), nb
 
 
 def scattered_map(ny, nx, nb):
@@ -54,53 +43,9 @@ def set_binmap(p, bm, nb):
     _lib.check(p._dll.xrfthip_plan_set_binmap(p._h, bm.ctypes.data_as(C.c_void_p), bm.shape[0], bm.shape[1], nb))
 
 
-def family(p):
-    """(kernel kind, the first family tag describe prints)"""
-    line = p.describe().splitlines()[1]
-    return p.kernel_info()[0], line[line.index("[") + 1:line.index("]")]
-
-
 RAD256, NB256 = radial_map(256, 256)
 RAD64, NB64 = radial_map(64, 64)
 RAD1K, NB1K = radial_map(1024, 1024)
-
-# (id, make() arguments, environment, expected kind, expected tag)
-ROWS = [
-    ("fasty", dict(ny=4096, nx=4096), {}, L.K_FASTY, "fasty"),
-    ("fasty-cross", dict(ny=1024, nx=1024, out_mode=L.OUT_CROSS), {}, L.K_FASTY, "fasty"),
-    ("fasts-over-fasty", dict(ny=256, nx=256), {}, L.K_FASTS, "fasts"),
-    ("fasts", dict(ny=64, nx=128, detrend=L.DETREND_LINEAR), {}, L.K_FASTS, "fasts"),
-    ("fasts-off-fastg", dict(ny=128, nx=128), {"XRFTHIP_FASTS": "0"}, L.K_FASTG, "fastg"),
-    ("fasts-off-fasty", dict(ny=256, nx=256), {"XRFTHIP_FASTS": "0"}, L.K_FASTY, "fasty"),
-    ("fastm", dict(ny=720, nx=1440, dtype=F64), {}, L.K_FASTM, "fastm"),
-    ("fastm-f32", dict(ny=360, nx=720, detrend=L.DETREND_LINEAR), {}, L.K_FASTM, "fastm"),
-    ("fastn", dict(ny=3000, nx=3000, dtype=F64), {}, L.K_FASTN, "fastn"),
-    ("fastn-tables-off", dict(ny=720, nx=1440, dtype=F64), {"XRFTHIP_FASTN_TABLES": "0"}, L.K_FASTN, "fastn"),
-    ("fastg", dict(ny=50, nx=50, dtype=F64), {}, L.K_FASTG, "fastg"),
-    ("fastg-complex", dict(ny=96, nx=128, dtype=C64, out_mode=L.OUT_COMPLEX), {}, L.K_FASTG, "fastg"),
-    ("fastg-off", dict(ny=50, nx=50, dtype=F64), {"XRFTHIP_FASTG": "0"}, L.K_FASTN, "fastn"),
-    ("fastyc", dict(ny=1024, nx=1024, dtype=C64, out_mode=L.OUT_COMPLEX), {}, L.K_FASTY, "fasty complex"),
-    ("fastyc-off", dict(ny=1024, nx=1024, dtype=C64, out_mode=L.OUT_COMPLEX), {"XRFTHIP_FASTYC": "0"}, L.K_GENERIC, "main"),
-    ("fastyc-four-step", dict(ndim=1, nx=1 << 20, dtype=C64, out_mode=L.OUT_COMPLEX), {}, L.K_FASTY, "fasty complex rows, four-step"),
-    ("fastr", dict(ndim=1, nx=65536), {}, L.K_FASTR, "fastr"),
-    ("fastr-off-fast1d", dict(ndim=1, nx=65536), {"XRFTHIP_FASTR": "0"}, L.K_FASTY, "fasty four-step"),
-    ("fast1d", dict(ndim=1, nx=1 << 20, detrend=L.DETREND_LINEAR), {}, L.K_FASTY, "fasty four-step"),
-    ("fastr-complex", dict(ndim=1, nx=16384, dtype=C64, out_mode=L.OUT_COMPLEX), {}, L.K_FASTR, "fastr complex rows"),
-    ("fastr-rows-over-complex", dict(ndim=1, nx=2048, dtype=C64, out_mode=L.OUT_COMPLEX), {}, L.K_FASTR, "fasty complex rows"),
-    ("crows-off", dict(ndim=1, nx=2048, dtype=C64, out_mode=L.OUT_COMPLEX), {"XRFTHIP_CROWS": "0"}, L.K_FASTR, "fastr complex rows"),
-    ("fastmx", dict(ndim=1, nx=1000, dtype=F64), {}, L.K_FASTM_X, "fastm x-only"),
-    ("fastmx-off", dict(ndim=1, nx=1000, dtype=F64), {"XRFTHIP_FASTM": "0"}, L.K_FASTG_ROWS, "fastg rows"),
-    ("fastg-rows", dict(ndim=1, nx=50, dtype=F64), {}, L.K_FASTG_ROWS, "fastg rows"),
-    ("fastgy-rows", dict(ndim=1, nx=365, dtype=F64), {}, L.K_FASTG_ROWS, "fastg rows Rader"),
-    ("fastmy", dict(ny=100, nx=200, dtype=F64, flags=L.AXIS_Y), {}, L.K_FASTM_Y, "fastm y-only"),
-    ("fastgy", dict(ny=103, nx=206, dtype=F64, flags=L.AXIS_Y), {}, L.K_FASTG_Y, "fastg y-only"),
-    ("fastmy-off", dict(ny=100, nx=200, dtype=F64, flags=L.AXIS_Y), {"XRFTHIP_FASTM": "0"}, L.K_FASTG_Y, "fastg y-only"),
-    ("fusedi", dict(ny=128, nx=256, inner=4), {}, L.K_FASTN, "inner layout"),
-    ("composite", dict(ny=128, nx=256, dtype=C64, out_mode=L.OUT_COMPLEX, mid=4), {}, L.K_COMPOSITE, "inner layout"),
-    ("no-fast", dict(ny=4096, nx=4096), {"XRFTHIP_NO_FAST": "1"}, L.K_GENERIC, "main"),
-    ("no-fast-rows", dict(ndim=1, nx=65536), {"XRFTHIP_NO_FAST": "1"}, L.K_GENERIC, "main"),
-    ("generic-prime", dict(ndim=1, nx=1031, dtype=F64), {}, L.K_GENERIC, "main"),
-]
 
 
 @pytest.mark.parametrize("kw,env,kind,tag", [r[1:] for r in ROWS], ids=[r[0] for r in ROWS])

@@ -558,8 +558,11 @@ def _execute_axis_y(c, da, mode, scale, k, da2=None, c2=None, extra_flags=0):
 
 def _swap_xy(flags):
     """The per-axis flag bits with the roles of x and y exchanged."""
-    out = flags & ~(_lib.SHIFT_X | _lib.SHIFT_Y | _lib.ISHIFT_X | _lib.ISHIFT_Y | _lib.FLIP_X | _lib.FLIP_Y | _lib.HALF_X | _lib.HALF_Y)
-    for fx, fy in ((_lib.SHIFT_X, _lib.SHIFT_Y), (_lib.ISHIFT_X, _lib.ISHIFT_Y), (_lib.FLIP_X, _lib.FLIP_Y), (_lib.HALF_X, _lib.HALF_Y)):
+    pairs = ((_lib.SHIFT_X, _lib.SHIFT_Y), (_lib.ISHIFT_X, _lib.ISHIFT_Y), (_lib.FLIP_X, _lib.FLIP_Y), (_lib.HALF_X, _lib.HALF_Y), (_lib.FLIP0_X, _lib.FLIP0_Y))
+    out = flags
+    for fx, fy in pairs:
+        out &= ~(fx | fy)
+    for fx, fy in pairs:
         if flags & fx:
             out |= fy
         if flags & fy:
