@@ -132,7 +132,12 @@ typedef struct xrfthip_desc {
      * ISHIFT_* / FLIP_*; windows, phases and `scale` as usual.  ABI 0.1.6: real input of a smooth shape (the two fused passes) also takes out_mode CROSS
      * (d_in1 = the second field, same layout) and XRFTHIP_HALF_X / REALDIM_X2 (real_dim along the SECOND transform axis: output [batch][ny][mid][nx/2 + 1][inner],
      * unshifted) or XRFTHIP_HALF_Y (along the FIRST: [batch][ny/2 + 1][mid][nx][inner]); XRFTHIP_UNSUPPORTED_LENGTH where only the composite of one-axis plans exists (the caller transposes).  0 or 1 = the trailing-axes layout.  A descriptor with the
-     * struct_size of the version without this field is accepted (inner = 1). */
+     * struct_size of the version without this field is accepted (inner = 1).
+     * The fused passes also take XRFTHIP_ISO (+ XRFTHIP_NO_SPECTRUM_OUT) with out_mode POWER | CROSS, under `inner` and under `mid`: every (batch, mid | inner) element is a
+     * spectrum of its own with radial sums of its own, d_iso = float64 | complex128 [batch][ne][nbins], ne = inner or mid -- the order of the array's other dims, then the bins
+     * (xrft/xrft.py:1076-1095) -- every entry written; a true-phase factor (xrfthip_plan_set_phase) is carried per sample.  Not with HALF_X / HALF_Y / REALDIM_X2; where the fused
+     * passes decline the descriptor (mid > 1 AND inner > 1, a length outside 16 .. 8192 or with a prime factor they have no butterfly for, a flipped axis):
+     * XRFTHIP_UNSUPPORTED_LENGTH, the caller transposes.  No symbol and no version number tells this capability apart: the status of xrfthip_plan_create does. */
     int64_t inner;
     /* ... and `mid` independent elements BETWEEN the two transform axes (ABI 0.1.3): with inner > 1 or mid > 1 the arrays are
      * [batch][ny][mid][nx][inner] -- batch = the product of the extents in front of the first transform axis, mid of those between the two, inner of those
@@ -159,7 +164,11 @@ int xrfthip_plan_set_window(xrfthip_plan* plan, int axis, const double* h_window
  * the INPUT and is indexed by source position; a C2R_X plan then takes nx/2 + 1 entries on axis 1.  NULL clears. */
 int xrfthip_plan_set_phase(xrfthip_plan* plan, int axis, const double* h_phase, int64_t n);
 /* h_binmap: [ny][nx_out] int32 bin codes indexed by UNSHIFTED frequency indices (nx_out = nx, or nx/2+1 with
- * HALF_X); negative = not binned.  The host computes it with the reference's float64 pd.cut expression. */
+ * HALF_X); negative = not binned.  The host computes it with the reference's float64 pd.cut expression.
+ * An ISO plan of the inner / mid layouts: [ny][nx] in the plan's own axis order (the first axis in memory = y), and the map must be RADIAL -- every sample binned; along a
+ * row the bin depends on |kx| only and never decreases with it (each bin of a row is one contiguous range of |kx|); the Hermitian twin (-ky, -kx) of a sample lies in
+ * the sample's bin.  pd.cut of sqrt(ky^2 + kx^2) always is, for any spacings.  Any other map: XRFTHIP_BAD_ARG (there is no second path to the sums where the axes lie).
+ * The plan's workspace grows by its partial sums, (ny/2 + 1) * ne * nbins * 8 bytes (x2 CROSS) per slab of a group: ask xrfthip_workspace_bytes after this call. */
 int xrfthip_plan_set_binmap(xrfthip_plan* plan, const int32_t* h_binmap, int64_t ny, int64_t nx_out, int32_t nbins);
 
 /* Per-pass timing with HIP events recorded on the exec stream around every kernel launch (bench.py's roofline
@@ -201,7 +210,7 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen);
  * d_in1 : second field for CROSS, else NULL
  * d_out : COMPLEX/CROSS: complex [batch][ny][nx_out]; POWER: real [batch][ny][nx_out]; may be NULL with
  *         XRFTHIP_NO_SPECTRUM_OUT
- * d_iso : with XRFTHIP_ISO: float64 [batch][nbins] (POWER) or complex128 [batch][nbins] (CROSS), else NULL
+ * d_iso : with XRFTHIP_ISO: float64 [batch][nbins] (POWER) or complex128 [batch][nbins] (CROSS), else NULL; inner / mid layouts: [batch][ne][nbins], ne = inner | mid
  * d_workspace / ws_bytes : >= xrfthip_workspace_bytes(plan), 256-byte aligned
  */
 int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1, void* d_out, void* d_iso,

@@ -109,6 +109,13 @@ for shape, dt in (((64, 1280, 2560), torch.float32), ((16, 2160, 4320), torch.fl
 x = cube((1024, 1024, 64), torch.float32); da = xrft.DataArray(x, ("y", "x", "t"), {"y": np.arange(1024.), "x": np.arange(1024.)})
 add("PS over (y, x) of a (1024,1024,64) f32 (y, x, t) array, linear+hann", x.numel(), 8, timeit(lambda: xrft.power_spectrum(da, dim=["y", "x"], detrend="linear", window="hann")))
 add("   fft (complex) of the same, no detrend", x.numel(), 12, timeit(lambda: xrft.fft(da, dim=["y", "x"])))
+# round 7: the isotropic forms of the same layout -- per-element radial sums from the row pass, no transposed copy
+add("   isotropic PS over (y, x) of the same (y, x, t) array, linear+hann", x.numel(), 4, timeit(lambda: xrft.isotropic_power_spectrum(da, dim=["y", "x"], detrend="linear", window="hann")))
+db = xrft.DataArray(torch.roll(x, 3, dims=1) * 0.5, ("y", "x", "t"), {"y": np.arange(1024.), "x": np.arange(1024.)})
+add("   isotropic cross spectrum over (y, x) of two such arrays", x.numel(), 8, timeit(lambda: xrft.isotropic_cross_spectrum(da, db, dim=["y", "x"], detrend="linear", window="hann")))
+del x, da, db
+x = cube((1440, 73, 144), torch.float64); da = xrft.DataArray(x, ("t", "y", "x"), {"t": np.arange(1440.), "x": np.arange(144.) * 2.5})
+add("   isotropic PS over (t, x) of a (1440,73,144) f64 (t, y, x) array, linear+hann", x.numel(), 8, timeit(lambda: xrft.isotropic_power_spectrum(da, dim=["t", "x"], detrend="linear", window="hann")))
 del x, da
 # a length with one awkward prime: the ERA5 grid (721 = 7 x 103 latitudes) -- the prime-factor form with Rader's algorithm in the column tile (round 5)
 x = cube((64, 721, 1440), torch.float32); da = xrft.DataArray(x, ("t", "lat", "lon"), {"lat": np.arange(721) * .25, "lon": np.arange(1440) * .25})

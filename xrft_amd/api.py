@@ -570,11 +570,13 @@ def _swap_xy(flags):
     return out
 
 
-def _execute_inner(c, da, mode, scale, extra_flags=0, da2=None, c2=None):
+def _execute_inner(c, da, mode, scale, extra_flags=0, da2=None, c2=None, iso=None):
     """Two transform axes that are not the trailing pair, wherever they lie -- dim = ["y", "x"] of a (y, x, time) array, dim = ["t", "x"] of a (t, y, x) array:
     the engine's layout [batch][n0][mid][n1][inner] (xrfthip_desc.inner, .mid: the products of the extents in front of, between and behind the two axes)
     transforms them where they lie, as the reference does (xrft.py:395-409) -- no transposed copy of the input or of the result.  Returns the result in
-    the input's dim order, or None when the call is not of this kind (the caller then takes the transposing path)."""
+    the input's dim order, or None when the call is not of this kind (the caller then takes the transposing path).
+    ``iso`` (bin map on the (ydim, xdim) grid, nbins, key; ``extra_flags`` then carry ISO | NO_SPECTRUM_OUT): returns the radial sums instead, one row of nbins per
+    element in the input's order of the other dims -- the reference's ``other dims + [freq_r]`` (xrft.py:1076-1095)."""
     if len(c.dim) != 2 or mode not in (_lib.OUT_COMPLEX, _lib.OUT_POWER, _lib.OUT_CROSS):
         return None
     p, q = da.get_axis_num(c.ydim), da.get_axis_num(c.xdim)
@@ -605,13 +607,23 @@ def _execute_inner(c, da, mode, scale, extra_flags=0, da2=None, c2=None):
         flags, win, ph = _swap_xy(flags), {"y": win["x"], "x": win["y"]}, {"y": ph["x"], "x": ph["y"]}
     kw = dict(ndim=2, batch=batch, ny=shape[first], nx=shape[second], inner=inner, mid=mid, dtype=t.dtype, out_mode=mode, detrend=c.detrend, flags=flags,
               scale=float(scale), window_y=win["y"], window_x=win["x"], phase_y=ph["y"], phase_x=ph["x"])
+    bkey = None
+    if iso is not None:
+        if flags & (_lib.HALF_X | _lib.HALF_Y):
+            return None  # (real_dim: the radial sums of a half spectrum are not taken where the axes lie)
+        bm, bkey = iso["binmap"], iso.get("binmap_key")
+        if p > q:  # (the map is laid out (ydim, xdim): the plan's first axis is xdim)
+            bm, bkey = np.ascontiguousarray(bm.T), (bkey, "T")
+        kw.update(binmap=bm, nbins=iso["nbins"])
     try:
-        plan = _get_plan(**kw)
+        plan = _get_plan(binmap_key=bkey, **kw)
     except _lib.XrftHipError as e:
         if e.status == _lib.UNSUPPORTED_LENGTH:  # a length the one-axis plans do not take: the transposing path
             return None
         raise
-    out, _ = plan.execute(t, t2)
+    out, iso_out = plan.execute(t, t2)
+    if iso is not None:
+        return iso_out
     shape[first], shape[second] = plan.ny_out, plan.nx_out  # (real_dim: n / 2 + 1 samples along that axis -- the second of the pair in memory, or the first: XRFTHIP_HALF_Y)
     return out.reshape(shape)
 
@@ -626,6 +638,12 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
         out = _execute_inner(c, da, mode, scale, extra_flags, da2, c2)
         if out is not None:
             return out, None, None
+    if iso is not None and (extra_flags & ~_lib.REALDIM_X2) == (_lib.ISO | _lib.NO_SPECTRUM_OUT) and (da2 is None or mode == _lib.OUT_CROSS):
+        # isotropic spectra on non-trailing axes: the radial sums of every element from the fused passes where the axes lie -- no transposed copy
+        iso_out = _execute_inner(c, da, mode, scale, extra_flags, da2, c2, iso)
+        if iso_out is not None:
+            tdims = (c.ydim, c.xdim)
+            return None, iso_out, [d for d in da.dims if d not in tdims]
     if extra_flags == 0 and iso is None and da2 is not None and mode == _lib.OUT_PHASE:
         # the cross phase of two fields on non-trailing axes: the fused cross spectrum where the axes lie, then its angle (xrft.py:871-874) -- no transposed copy
         out = _execute_inner(c, da, _lib.OUT_CROSS, scale, 0, da2, c2)

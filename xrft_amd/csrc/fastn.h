@@ -18,6 +18,7 @@
 // Either pass of a plan may instead be the table kernel of fastm.h when its length is in the table: the intermediate's layout (FastM::l_cw, l_rk)
 // is the contract between them.
 #pragma once
+#include <limits>
 #include "fastm.h"
 #include "fastg.h"  // (the column passes of the Rader form)
 
@@ -212,7 +213,13 @@ template <typename T> __device__ __forceinline__ C2<T> n_load_pair(const NColsCt
     return mk<T>(*reinterpret_cast<const T*>(c.src + (rowoff + c.coff)), *reinterpret_cast<const T*>(c.src + (rowoff + c.coff1)));
 }
 
-template <typename T, int R, bool BLUE>
+// GUARD (fastn_cols_kernel): the two columns of a packed pair belong to DIFFERENT spectra (elements e, e + 1 of an inner layout), and a NaN / inf in one would fill the
+// other's transform too.  A sample that is not finite enters the transform as 0; the column's raw sum (c.s[0], c.s[1]: not finite then) marks the column, whose half
+// spectrum is stored as NaN after the split -- what the transform of that column alone gives.
+template <typename T> __device__ __forceinline__ bool n_finite(T v) { return fabs(v) <= std::numeric_limits<T>::max(); }
+template <typename T> __device__ __forceinline__ C2<T> n_guarded(C2<T> z) { return mk<T>(n_finite<T>(z.re) ? z.re : (T)0, n_finite<T>(z.im) ? z.im : (T)0); }
+
+template <typename T, int R, bool BLUE, bool GUARD = false>
 __device__ __forceinline__ void n_first_cols(NColsCtx<T>& c, NGeoRef g, C2<T>* seq, int j, const C2<T>* __restrict__ tw) {
     typedef C2<T> CT;
     const int M0 = g.m[0];
@@ -228,7 +235,7 @@ __device__ __forceinline__ void n_first_cols(NColsCtx<T>& c, NGeoRef g, C2<T>* s
             wyv[q] = c.wy[row];
         }
     }
-    if (c.det) {
+    if (c.det || GUARD) {
 #pragma unroll
         for (int q = 0; q < R; ++q) {
             const double ri = (double)(j + q * M0) - c.ibar;  // (Bluestein: the rows beyond ny hold zeros)
@@ -244,6 +251,7 @@ __device__ __forceinline__ void n_first_cols(NColsCtx<T>& c, NGeoRef g, C2<T>* s
             a[q] = mk<T>((T)((float)a[q].re - fmaf(c.Sl[0], fi, c.Tl[0])), (T)((float)a[q].im - fmaf(c.Sl[1], fi, c.Tl[1])));
         }
         a[q] = mk<T>(a[q].re * (wyv[q] * c.wx.re), a[q].im * (wyv[q] * c.wx.im));
+        if (GUARD) a[q] = n_guarded<T>(a[q]);
         if (BLUE) { if (row < c.ny) a[q] = cmulc(a[q], c.blue_c[row]); }
     }
     dft_r<T, R>(a);
@@ -255,8 +263,9 @@ __device__ __forceinline__ void n_first_cols(NColsCtx<T>& c, NGeoRef g, C2<T>* s
 }
 
 // FORM 0: the radix passes; 1: Bluestein's chirp convolution; 2: the prime-factor form with Rader's algorithm along the prime (fastg.h)
-template <typename T, int FORM, int CAP>
+template <typename T, int FORM, int CAP, bool GUARD = false>
 __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 3)) fastn_cols_kernel(FastN P) {
+    static_assert(!GUARD || FORM != 1, "the guarded columns serve the inner layouts: radix passes or the Rader form");
     constexpr bool BLUE = FORM == 1, RADER = FORM == 2;
     typedef C2<T> CT;
     NGeoRef g = *P.g;
@@ -353,7 +362,7 @@ __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
             for (int u = 0; u < U; ++u) {
                 const int i = i0 + u * RQ;
                 if (i < ny) {
-                    if (c.det) {
+                    if (c.det || GUARD) {
                         const double ri = (double)i - c.ibar;
                         c.s[0] += (double)v[u].re; c.s[1] += (double)v[u].im;
                         c.s[2] = fma(ri, (double)v[u].re, c.s[2]); c.s[3] = fma(ri, (double)v[u].im, c.s[3]);
@@ -364,6 +373,7 @@ __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
                         z = mk<T>((T)((float)z.re - fmaf(c.Sl[0], fi, c.Tl[0])), (T)((float)z.im - fmaf(c.Sl[1], fi, c.Tl[1])));
                     }
                     z = mk<T>(z.re * (wv[u] * c.wx.re), z.im * (wv[u] * c.wx.im));
+                    if (GUARD) z = n_guarded<T>(z);
                     if (BLUE) seq[n_pad(i, g.inv_pdq)] = cmulc(z, cc_[u]);
                     else lds[(int)pin[i] * G + gi] = z;
                 }
@@ -381,12 +391,12 @@ __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
         const CT* __restrict__ tw = reinterpret_cast<const CT*>(p.tw_y);
         const int M0 = g.m[0];
         for (int j = r0; j < M0 && !(P.dbg & 4); j += RQ) {
-#define NF_(RR) n_first_cols<T, RR, false>(c, g, seq, j, tw)
+#define NF_(RR) n_first_cols<T, RR, false, GUARD>(c, g, seq, j, tw)
             XRFT_N_SWITCH(g.r[0], NF_)
 #undef NF_
         }
     }
-    if (c.det) {
+    if (c.det || GUARD) {
 #pragma unroll
         for (int m = G; m < 64; m <<= 1)
 #pragma unroll
@@ -445,12 +455,13 @@ __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
 #undef NB_
         n_fft_tail<T, CAP>(lds, g, tid, nthr, twl);
     }
-    if (c.det && tid < 4 * G) {  // (sum d, sum (i - ibar) d) per column, the waves' partial sums in wave order
+    if ((c.det || GUARD) && tid < 4 * G) {  // (sum d, sum (i - ibar) d) per column, the waves' partial sums in wave order
         const int cc = tid >> g.lg, gg = tid & (G - 1);  // cc: 0, 1 = sum d of columns 2gg, 2gg+1; 2, 3 = the first moments
         double acc = 0.0;
         for (int w = 0; w < (nthr >> 6); ++w) acc += part[(w * G + gg) * 4 + cc];
+        if (GUARD && cc < 2) part[gg * 4 + cc] = acc;  // (this thread's own entry of wave 0: the column's mark for the split below)
         const int col = xb * CW + 2 * gg + (cc & 1);
-        if (col < nx) {
+        if (c.det && col < nx) {
             double* cfp = p.colfit + ((size_t)slab * nx + col) * 4;
             cfp[cc >> 1] = acc;
             if (!c.pre) cfp[2 + (cc >> 1)] = 0.0;
@@ -458,6 +469,7 @@ __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
     }
     // split the packed spectra: Ra[k] = (Z[k] + conj Z[N-k]) / 2, Rb[k] = (Z[k] - conj Z[N-k]) / (2i); lanes (ky, column): CW consecutive lanes write the
     // CW columns of a row, RK rows complete a line of the intermediate
+    if (GUARD) __syncthreads();
     const int rk = 1 << p.l_rk, lcw = g.lg + 1;
     char* __restrict__ w2s = reinterpret_cast<char*>(reinterpret_cast<CT*>(p.w2) + (size_t)slab * p.nrow_pad * P.pitch);
     const int nst = (P.dbg & 2) ? 0 : CW * (nyh + 1);
@@ -473,7 +485,8 @@ __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
         } else {
             zc.im = -zc.im;
         }
-        const CT o = (col & 1) ? cscale(mul_mi(zk - zc), (T)0.5) : cscale(zk + zc, (T)0.5);
+        CT o = (col & 1) ? cscale(mul_mi(zk - zc), (T)0.5) : cscale(zk + zc, (T)0.5);
+        if (GUARD && !n_finite<double>(part[(col >> 1) * 4 + (col & 1)])) o = mk<T>(std::numeric_limits<T>::quiet_NaN(), std::numeric_limits<T>::quiet_NaN());
         const unsigned off = ((((unsigned)(k >> p.l_rk) * (unsigned)nxb + (unsigned)xb) << p.l_rk) + (unsigned)(k & (rk - 1))) * (unsigned)CW + (unsigned)col;
         mr_store_ct_nt<T>(w2s + (size_t)off * sizeof(CT), o);
     }
@@ -701,6 +714,12 @@ struct FastNI {
     const void* w2b;
     const void* corrb;
     double scale;
+    // ISO (power and cross spectra): the radial sums of every element e, gathered from the row in LDS.  A RADIAL bin map (fusedi_build_iso): along row ky the bin depends
+    // on |kx| only and never decreases with it, and the Hermitian twin (-ky, -kx) of a sample shares its bin
+    const unsigned short* tfirst;  // [ky <= ny/2][nbins + 1]: the smallest |kx| <= nx/2 of row ky whose bin is >= b (nx/2 + 1 if none)
+    const unsigned* twin;          // [ky <= ny/2]: first bin | (last bin + 1) << 16 the row reaches; the others are neither gathered, written nor reduced
+    double* iso_part;              // [slab][e][ky <= ny/2][nbins (x2 cross)]: the row's sums per element, added over ky in order by iso_reduce_kernel
+    int nbins;
 };
 
 template <typename T, int R>
@@ -743,8 +762,13 @@ __device__ __forceinline__ void n_first_irows(const FastNI& p, NGeoRef g, C2<T>*
 }
 
 // MODE 0: complex spectrum, 1: power spectrum, 2: cross spectrum of two fields (complex)
-template <typename T, int MODE, int CAP>
+// ISO: the radial sums of every element, too (isotropic_power_spectrum / isotropic_cross_spectrum on non-trailing axes, xrft.py:1076-1095): every element e is a
+// spectrum of its own with its own sums.  Task = (element, bin the row reaches): ONE thread adds the bin's samples |kx| = s .. e - 1 of the row in LDS, kx = |kx| then
+// kx = nx - |kx|, in float64 and in that order, and writes the sum to the (slab, e, ky) row of the partial table -- no atomics, no shuffles, nothing shared between
+// threads; lanes run along the bins (adjacent bins hold adjacent kx: neighbouring LDS words, 512-byte runs of the table per wave).
+template <typename T, int MODE, int CAP, bool ISO = false>
 __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 3)) fastn_irows_kernel(FastNI p) {
+    static_assert(!ISO || MODE == 1 || MODE == 2, "radial sums exist for power and cross spectra");
     typedef C2<T> CT;
     NGeoRef g = *p.g;
     XRFT_DYN_SMEM(smem_raw);
@@ -773,8 +797,50 @@ __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
     // WO: samples of a result row -- every kx, or kx = 0 .. nx/2 as it lies (real_dim; the twin row (-ky) then takes its samples from kx = nx - fx of the same sequences)
     const int WO = p.half ? NX / 2 + 1 : NX;
     const float ipn = g.inv_pnq, inv_nx = 1.0f / (float)WO;
-    if ((p.dbg & 2) && lds[tid].re != (T)1.2345) return;
     const bool interior_y = ky != 0 && 2 * ky != p.ny, twin = interior_y && !p.half_y;
+    if (ISO) {
+        constexpr int HW = MODE == 2 ? 2 : 1;
+        const unsigned bw = p.twin[ky];
+        const int blo = (int)(bw & 0xffffu), nbr = (int)(bw >> 16) - blo;  // (>= 1: every sample of the row is binned)
+        const int H = NX / 2, HM = (NX - 1) / 2;  // |kx| = 0 .. H; kx = nx - |kx| exists for |kx| = 1 .. HM
+        const unsigned short* __restrict__ fr = p.tfirst + (size_t)ky * (p.nbins + 1);
+        const float inv_nbr = 1.0f / (float)nbr;
+        const int fb1 = (GE >> LX) * g.str, tasks = nbr << lgo, fyt = p.ny - ky;
+        const bool phs = MODE == 2 && p.ph_on;
+        const CT* __restrict__ phx = reinterpret_cast<const CT*>(p.ph_x);
+        CT py = mk<T>((T)1, (T)0), pyt = py;
+        if (phs) { py = reinterpret_cast<const CT*>(p.ph_y)[ky]; pyt = reinterpret_cast<const CT*>(p.ph_y)[interior_y ? fyt : ky]; }
+        for (int idx = tid; idx < tasks; idx += nthr) {
+            const int ge = fdiv(idx, inv_nbr), bn = blo + (idx - ge * nbr), e = e0 + ge;
+            if (e >= p.inner) continue;  // (a ragged last block)
+            const int s = fr[bn], en = fr[bn + 1];  // the bin holds |kx| = s .. en - 1 of this row
+            const CT* seq = lds + ge * g.str;
+            double rr = 0.0, ri = 0.0;
+            auto take = [&](int kx) {
+                const int ps_ = n_pad(kx, ipn);
+                const CT va = seq[ps_];
+                if (MODE == 1) { rr += (double)((va.re * va.re + va.im * va.im) * sc); return; }
+                const CT v = cscale(cmulc(va, seq[fb1 + ps_]), sc);  // F0 conj(F1)
+                if (!phs) { rr += (double)v.re; ri += (double)v.im; return; }
+                // a true-phase factor: the sample and its Hermitian twin (-ky, -kx) carry the factors of their OWN frequencies (they differ at the Nyquist
+                // frequency of an even axis, and whenever the table is not conjugate-symmetric), so both are added as they would be stored
+                const CT a = cmul(v, cmul(py, phx[kx]));
+                rr += (double)a.re; ri += (double)a.im;
+                if (interior_y) {
+                    const CT b = cmul(cconj(v), cmul(pyt, phx[kx == 0 ? 0 : NX - kx]));
+                    rr += (double)b.re; ri += (double)b.im;
+                }
+            };
+            for (int m = s; m < min(en, H + 1); ++m) take(m);
+            for (int m = max(s, 1); m < min(en, HM + 1); ++m) take(NX - m);
+            if (interior_y && !phs) { rr *= 2.0; ri = 0.0; }  // + the twin row (-ky): V + conj V
+            double* dst = p.iso_part + ((((size_t)slab * p.inner + e) * (nyh + 1) + ky) * p.nbins + bn) * HW;
+            dst[0] = rr;
+            if (MODE == 2) dst[1] = ri;
+        }
+        if (p.out == nullptr) return;  // (XRFTHIP_NO_SPECTRUM_OUT)
+    }
+    if ((p.dbg & 2) && lds[tid].re != (T)1.2345) return;
     const int tot = (WO << lgo) * (twin ? 2 : 1);
     const int NYO = p.half_y ? nyh + 1 : p.ny;  // rows of a slab of the result
     const bool dbl_y = p.half_y && p.realdim2 && interior_y;  // (the kept half of the real FIRST axis counts twice)

@@ -433,7 +433,11 @@ void fastn_launch_cols(const xrfthip_plan* P, const FastM& m, hipStream_t st) {
     const size_t lds = P->n_c.lds;
     int maxrad = 0;
     for (int i = 0; i < hg.np; ++i) maxrad = std::max(maxrad, hg.r[i]);
-#define NC_(TT, CC) do { if (P->n_blue_m) { auto k = &fastn_cols_kernel<TT, 1, 16>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } /* (a chirp convolution's radices stop at 16) */ \
+    // (radial sums of an inner layout: a packed column pair holds two spectra -- a sample that is not finite must stay in its own, fastn.h GUARD)
+    const bool guard = P->family == Family::FusedInner && (P->d.flags & XRFTHIP_ISO);
+#define NC_(TT, CC) do { if (guard && P->n_rad_p) { auto k = &fastn_cols_kernel<TT, 2, 16, true>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } \
+                         else if (guard) { auto k = &fastn_cols_kernel<TT, 0, CC, true>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } \
+                         else if (P->n_blue_m) { auto k = &fastn_cols_kernel<TT, 1, 16>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } /* (a chirp convolution's radices stop at 16) */ \
                          else if (P->n_rad_p) { auto k = &fastn_cols_kernel<TT, 2, 16>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } \
                          else { auto k = &fastn_cols_kernel<TT, 0, CC>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } } while (0)
     if (P->dbl) NC_(double, 16); else if (maxrad > 16) NC_(float, 20); else NC_(float, 16);

@@ -29,8 +29,10 @@ xrfthip_plan* create_fused_inner(const xrfthip_desc& d) {
     if (d.out_mode != XRFTHIP_OUT_COMPLEX && d.out_mode != XRFTHIP_OUT_POWER && !crossm) return nullptr;
     // (real_dim along the second axis -- HALF_X, the power spectrum's REALDIM_X2: rows of nx/2 + 1 samples out of pass 2, unshifted along x)
     const uint32_t ok = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | XRFTHIP_HALF_Y | (d.out_mode != XRFTHIP_OUT_POWER ? (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X) : 0u) |
-                        (d.out_mode != XRFTHIP_OUT_COMPLEX ? XRFTHIP_REALDIM_X2 : 0u);
+                        (d.out_mode != XRFTHIP_OUT_COMPLEX ? (XRFTHIP_REALDIM_X2 | XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT) : 0u);
     if (d.flags & ~ok) return nullptr;  // (a flipped axis: the composite of one-axis plans)
+    // (the radial sums of every element, gathered in pass 2 -- round 7; not of a half spectrum: the trailing families refuse that pair too)
+    if ((d.flags & XRFTHIP_ISO) && (d.flags & (XRFTHIP_HALF_X | XRFTHIP_HALF_Y | XRFTHIP_REALDIM_X2))) return nullptr;
     if ((d.flags & XRFTHIP_HALF_X) && ((d.flags & XRFTHIP_SHIFT_X) || (d.nx & 1))) return nullptr;
     if ((d.flags & XRFTHIP_REALDIM_X2) && !(d.flags & (XRFTHIP_HALF_X | XRFTHIP_HALF_Y))) return nullptr;
     const bool dbl = d.dtype == XRFTHIP_F64;
@@ -120,27 +122,88 @@ xrfthip_plan* create_fused_inner(const xrfthip_desc& d) {
     if (!rc) rc = P->n_r.geo_dev.upload(&P->n_r.geo, sizeof(NGeo));
     if (!rc) rc = fusedi_tables(P);
     if (rc) { delete P; return nullptr; }
-    // workspace: the intermediate of one group of slabs, the column sums, the plane corrections
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t slab_w = (size_t)P->y_nrow_pad * (size_t)P->y_pitch * cs;
-    long long Gs = d.slabs_per_group > 0 ? d.slabs_per_group : (long long)std::max<size_t>(1, ((size_t)512 << 20) / std::max<size_t>(slab_w * (crossm ? 2 : 1), 1));
-    Gs = std::max<long long>(1, std::min<long long>(Gs, std::max<long long>(d.batch, 1)));
-    P->G = (int)Gs;
-    size_t off = 0;
-    const size_t nf = crossm ? 2 : 1;  // fields: field 1's intermediate, sums and corrections lie behind field 0's
-    P->off_w = off; off = al(off + nf * (size_t)Gs * slab_w);
-    P->off_rowfit = off; off = al(off + nf * (size_t)Gs * ncol * 4 * sizeof(double));
-    P->off_corr = off; off = al(off + nf * (size_t)Gs * ncol * cs);
-    P->ws_bytes = off;
+    fusedi_layout(P);
     return P;
 }
 
-int run_fused_inner(const xrfthip_plan* P, const void* in, const void* in1, void* out, char* ws, hipStream_t st) {
+// workspace: the intermediate of one group of slabs, the column sums, the plane corrections -- and, with radial sums, their per-(slab, element, row ky) partial table
+// (known once the bin map has arrived: xrfthip_plan_set_binmap lays the workspace out again)
+void fusedi_layout(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const bool crossm = d.out_mode == XRFTHIP_OUT_CROSS;
+    const long long ne = std::max<long long>(d.inner, std::max<long long>(d.mid, 1)), ncol = d.nx * ne;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t nf = crossm ? 2 : 1;  // fields: field 1's intermediate, sums and corrections lie behind field 0's
+    const size_t slab_w = (size_t)P->y_nrow_pad * (size_t)P->y_pitch * P->csize;
+    const size_t slab_iso = (d.flags & XRFTHIP_ISO) ? (size_t)(d.ny / 2 + 1) * (size_t)ne * (size_t)P->nbins * nf * sizeof(double) : 0;
+    long long Gs = d.slabs_per_group > 0 ? d.slabs_per_group : (long long)std::max<size_t>(1, ((size_t)512 << 20) / std::max<size_t>(slab_w * nf + slab_iso, 1));
+    Gs = std::max<long long>(1, std::min<long long>(Gs, std::max<long long>(d.batch, 1)));
+    P->G = (int)Gs;
+    size_t off = 0;
+    P->off_w = off; off = al(off + nf * (size_t)Gs * slab_w);
+    P->off_rowfit = off; off = al(off + nf * (size_t)Gs * ncol * 4 * sizeof(double));
+    P->off_corr = off; off = al(off + nf * (size_t)Gs * ncol * P->csize);
+    P->off_isopart = off; off = al(off + (size_t)Gs * slab_iso);
+    P->ws_bytes = off;
+}
+
+// The bin map of an ISO plan, [ny][nx] in the plan's own axis order: the gather of fastn_irows_kernel<.., ISO> needs a RADIAL map -- every sample of rows ky = 0 .. ny/2
+// binned, along a row the bin depends on |kx| only and never decreases with it, the Hermitian twin (-ky, -kx) of a sample in the sample's bin (pd.cut of
+// sqrt(ky^2 + kx^2) is, for any spacings: xrft.py:975-981).  Builds first[ky][b] = the smallest |kx| <= nx/2 of row ky whose bin is >= b (nx/2 + 1 if none), b = 0 .. nbins,
+// the bins each row reaches and the rows that reach each bin.  Any other map: XRFTHIP_BAD_ARG (there is no other path to the sums where the axes lie).
+int fusedi_build_iso(xrfthip_plan* P, const int32_t* bm) {
+    const int ny = (int)P->d.ny, nx = (int)P->d.nx, nyh = ny / 2, H = nx / 2, HM = (nx - 1) / 2, nb = P->nbins;
+    if (nb >= 65535 || H + 1 >= 65535) return XRFTHIP_BAD_ARG;
+    for (int ky = 0; ky <= nyh; ++ky) {
+        const int32_t* r = bm + (size_t)ky * nx;
+        const bool twin = ky != 0 && 2 * ky != ny;
+        const int32_t* t = bm + (size_t)(twin ? ny - ky : ky) * nx;
+        for (int m = 0; m <= H; ++m) {
+            const int32_t c = r[m];
+            if (c < 0 || c >= nb || (m > 0 && c < r[m - 1]) || (m >= 1 && m <= HM && r[nx - m] != c)) return XRFTHIP_BAD_ARG;
+            if (twin && (t[m] != c || t[(nx - m) % nx] != c)) return XRFTHIP_BAD_ARG;
+        }
+    }
+    std::vector<uint16_t> f((size_t)(nyh + 1) * (nb + 1), (uint16_t)(H + 1));
+    std::vector<uint32_t> w((size_t)nyh + 1);
+    for (int ky = 0; ky <= nyh; ++ky) {
+        const int32_t* r = bm + (size_t)ky * nx;
+        uint16_t* dst = f.data() + (size_t)ky * (nb + 1);
+        int m = 0;
+        for (int b = 0; b <= nb; ++b) {
+            while (m <= H && r[m] < b) ++m;
+            dst[b] = (uint16_t)m;
+        }
+        w[(size_t)ky] = (uint32_t)r[0] | (uint32_t)(r[H] + 1) << 16;
+    }
+    // the rows that reach a bin: a contiguous range when the rows' windows move monotonically with ky (a radial map's do; otherwise every row keeps all bins)
+    bool mono = true;
+    for (int ky = 1; ky <= nyh && mono; ++ky) mono = (w[(size_t)ky] & 0xffffu) >= (w[(size_t)ky - 1] & 0xffffu) && (w[(size_t)ky] >> 16) >= (w[(size_t)ky - 1] >> 16);
+    if (!mono) std::fill(w.begin(), w.end(), (uint32_t)nb << 16);
+    std::vector<uint32_t> tu((size_t)nb, 0u);
+    for (int b = 0; b < nb; ++b) {
+        int ulo = nyh + 1, uhi = 0;
+        for (int ky = 0; ky <= nyh; ++ky)
+            if ((int)(w[(size_t)ky] & 0xffffu) <= b && b < (int)(w[(size_t)ky] >> 16)) { ulo = std::min(ulo, ky); uhi = std::max(uhi, ky + 1); }
+        if (ulo > uhi) ulo = uhi = 0;  // (a bin no sample falls in: its sum is 0)
+        tu[(size_t)b] = (uint32_t)ulo | (uint32_t)uhi << 16;
+    }
+    int rc = P->ytfirst.upload(f.data(), f.size() * sizeof(uint16_t));
+    if (!rc) rc = P->ytwin.upload(w.data(), w.size() * sizeof(uint32_t));
+    if (!rc) rc = P->ytunits.upload(tu.data(), tu.size() * sizeof(uint32_t));
+    P->ytfirst_on = !rc;
+    if (!rc) fusedi_layout(P);
+    return rc;
+}
+
+int run_fused_inner(const xrfthip_plan* P, const void* in, const void* in1, void* out, double* iso, char* ws, hipStream_t st) {
     const xrfthip_desc& d = P->d;
     const bool midlay = d.mid >= 2, crossm = d.out_mode == XRFTHIP_OUT_CROSS;
     const long long ne = midlay ? d.mid : d.inner, ncol = d.nx * ne;
     const int sx = midlay ? 1 : (int)d.inner, se = midlay ? (int)d.nx : 1;
     const size_t out_esz = d.out_mode == XRFTHIP_OUT_POWER ? P->rsize : P->csize;
+    const bool isom = (d.flags & XRFTHIP_ISO) != 0;
+    if (isom && !P->ytfirst_on) return XRFTHIP_MISSING_TABLE;
     for (long long g0 = 0; g0 < d.batch; g0 += P->G) {
         const long long gc = std::min<long long>(P->G, d.batch - g0);
         const size_t slab_w = (size_t)P->y_nrow_pad * (size_t)P->y_pitch * P->csize;
@@ -176,7 +239,7 @@ int run_fused_inner(const xrfthip_plan* P, const void* in, const void* in1, void
         r.ph_y = P->fph[0].p; r.ph_x = P->fph[1].p; r.ph_on = (d.out_mode != XRFTHIP_OUT_POWER && P->fph_on) ? 1 : 0;
         r.half = (d.flags & XRFTHIP_HALF_X) ? 1 : 0; r.realdim2 = (d.flags & XRFTHIP_REALDIM_X2) ? 1 : 0;
         r.half_y = (d.flags & XRFTHIP_HALF_Y) ? 1 : 0;  // (real_dim along the first axis: rows ky = 0 .. ny/2, no twin rows)
-        r.out = (char*)out + (size_t)g0 * (size_t)(r.half_y ? d.ny / 2 + 1 : d.ny) * (size_t)P->nx_out * ne * out_esz;
+        r.out = out == nullptr ? nullptr : (char*)out + (size_t)g0 * (size_t)(r.half_y ? d.ny / 2 + 1 : d.ny) * (size_t)P->nx_out * ne * out_esz;
         const int geo = crossm ? P->n_r.geo.g / 2 : P->n_r.geo.g;  // elements a row workgroup writes
         r.ny = (int)d.ny; r.nx = (int)d.nx; r.inner = (int)ne; r.sx = sx; r.se = se; r.midlay = midlay ? 1 : 0; r.nrow_pad = P->y_nrow_pad; r.pitch = (int)P->y_pitch;
         r.l_cw = m.l_cw; r.l_rk = m.l_rk; r.detrend = d.detrend;
@@ -192,17 +255,37 @@ int run_fused_inner(const xrfthip_plan* P, const void* in, const void* in1, void
         r.neb = (int)((ne + geo - 1) / geo);
         r.nunits = (int)(gc * (d.ny / 2 + 1) * r.neb);
         r.scale = d.scale;
+        if (isom) {
+            r.tfirst = reinterpret_cast<const unsigned short*>(P->ytfirst.p); r.twin = reinterpret_cast<const unsigned*>(P->ytwin.p);
+            r.iso_part = reinterpret_cast<double*>(ws + P->off_isopart); r.nbins = P->nbins;
+        }
         int maxrad = 0;
         for (int i = 0; i < hg.np; ++i) maxrad = std::max(maxrad, hg.r[i]);
         const dim3 grid((unsigned)(8 * ((r.nunits + 7) / 8))), blk((unsigned)hg.thr);
         rec = prof_begin(P, "fastn_irows", st);
-#define NI_(TT, CC) do { if (d.out_mode == XRFTHIP_OUT_POWER) { auto k = &fastn_irows_kernel<TT, 1, CC>; XRFT_LAUNCH(k, grid, blk, P->n_r.lds, st, r); } \
+#define NI_(TT, CC) do { if (isom && crossm) { auto k = &fastn_irows_kernel<TT, 2, CC, true>; XRFT_LAUNCH(k, grid, blk, P->n_r.lds, st, r); } \
+                         else if (isom) { auto k = &fastn_irows_kernel<TT, 1, CC, true>; XRFT_LAUNCH(k, grid, blk, P->n_r.lds, st, r); } \
+                         else if (d.out_mode == XRFTHIP_OUT_POWER) { auto k = &fastn_irows_kernel<TT, 1, CC>; XRFT_LAUNCH(k, grid, blk, P->n_r.lds, st, r); } \
                          else if (crossm) { auto k = &fastn_irows_kernel<TT, 2, CC>; XRFT_LAUNCH(k, grid, blk, P->n_r.lds, st, r); } \
                          else { auto k = &fastn_irows_kernel<TT, 0, CC>; XRFT_LAUNCH(k, grid, blk, P->n_r.lds, st, r); } } while (0)
         if (P->dbl) NI_(double, 16); else if (maxrad > 16) NI_(float, 20); else NI_(float, 16);
 #undef NI_
         prof_end(rec, st);
         HIP_TRY(hipGetLastError());
+        if (isom) {
+            // iso[slab][e][bin] = the sums of the rows ky = 0 .. ny/2 that reach the bin, in row order: (slab, e) is the reduce kernel's slab
+            const int hw = crossm ? 2 : 1, nb = P->nbins * hw, upr = (int)(d.ny / 2 + 1);
+            rec = prof_begin(P, "fastn_irows_iso_reduce", st);
+            auto kr = &iso_reduce_kernel;
+            const long long nse = gc * ne;
+            for (long long s0 = 0; s0 < nse; s0 += 32768) {  // (grid.y < 65536)
+                const long long sn = std::min<long long>(32768, nse - s0);
+                XRFT_LAUNCH(kr, dim3((unsigned)((nb + 63) / 64), (unsigned)sn), dim3(256), 4 * 64 * sizeof(double), st, (const double*)r.iso_part + (size_t)s0 * upr * nb,
+                            iso + ((size_t)g0 * ne + (size_t)s0) * nb, upr, nb, reinterpret_cast<const unsigned*>(P->ytunits.p), hw);
+            }
+            prof_end(rec, st);
+            HIP_TRY(hipGetLastError());
+        }
     }
     return XRFTHIP_OK;
 }
@@ -210,7 +293,7 @@ int run_fused_inner(const xrfthip_plan* P, const void* in, const void* in1, void
 // composite plan for xrfthip_desc.inner > 1 (see xrfthip_plan::inner)
 int create_inner_plan(xrfthip_plan** plan, const xrfthip_desc& d) {
     if (xrfthip_plan* F = create_fused_inner(d)) { *plan = F; return XRFTHIP_OK; }
-    if ((d.flags & (XRFTHIP_HALF_X | XRFTHIP_HALF_Y | XRFTHIP_REALDIM_X2)) || d.out_mode == XRFTHIP_OUT_CROSS) return XRFTHIP_UNSUPPORTED_LENGTH;  // (real_dim, two fields: the fused passes only; the caller transposes)
+    if ((d.flags & (XRFTHIP_HALF_X | XRFTHIP_HALF_Y | XRFTHIP_REALDIM_X2 | XRFTHIP_ISO)) || d.out_mode == XRFTHIP_OUT_CROSS) return XRFTHIP_UNSUPPORTED_LENGTH;  // (real_dim, two fields, radial sums: the fused passes only; the caller transposes)
     const uint32_t ok = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X | XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X | XRFTHIP_FLIP_Y | XRFTHIP_FLIP_X;
     if (d.ndim != 2 || (d.flags & ~ok) || (d.out_mode != XRFTHIP_OUT_COMPLEX && d.out_mode != XRFTHIP_OUT_POWER)) return XRFTHIP_BAD_ARG;
     if (d.inner > (1LL << 30) || d.mid > (1LL << 30) || d.nx * d.inner > (1LL << 30) || d.mid * d.nx * d.inner > (1LL << 30) || d.batch * d.mid > (1LL << 40)) return XRFTHIP_BAD_ARG;

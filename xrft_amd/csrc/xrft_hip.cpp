@@ -970,6 +970,7 @@ int xrfthip_plan_set_binmap(xrfthip_plan* plan, const int32_t* h_binmap, int64_t
     int rc = plan->binmap.upload(h_binmap, (size_t)ny * nx_out * sizeof(int32_t));
     if (rc) return rc;
     plan->nbins = nbins;
+    if (plan->family == Family::FusedInner) return fusedi_build_iso(plan, h_binmap);  // (a radial map, or XRFTHIP_BAD_ARG; no tile passes to rebuild)
     switch (plan->chosen) {
         case Family::FastS:  // a radial map within the workgroup's reach: the sums are taken from the staged rows (fasts.h); else FastY's tables or the generic passes
             rc = fasts_build_tfirst(plan, h_binmap);
@@ -1136,6 +1137,11 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
                    "back in the spectral domain, (ky, kx, e) and its Hermitian twin stored as runs of %d elements\n",
                 (long long)d.batch, (long long)d.ny, (long long)plan->mid, (long long)d.nx, (long long)plan->inner, d.dtype, d.out_mode, d.detrend, d.flags, plan->ws_bytes,
                 gc.thr, gc.g, gc.n, plan->n_rad_p ? ("Rader, prime " + std::to_string(plan->n_rad_p)).c_str() : rads(gc).c_str(), plan->n_c.lds, plan->y_nrow_pad, plan->n_rk, plan->n_nxb, plan->n_rk, plan->n_cw, gr.thr, gr.g, gr.n, rads(gr).c_str(), plan->n_r.lds, gr.g);
+        if (d.flags & XRFTHIP_ISO)
+            appendf(s, "  [inner layout] [fastn fused iso] the row pass gathers, per element and bin the row reaches, the bin's samples from LDS in float64 (one thread, a fixed order, no atomics) "
+                       "-> partial[slab][element][ky][%d bins] (%zuB per slab) -> added over ky in order: per-element radial sums%s\n",
+                    plan->nbins, (size_t)(d.ny / 2 + 1) * (size_t)std::max<long long>(plan->inner, plan->mid) * (size_t)plan->nbins * (d.out_mode == XRFTHIP_OUT_CROSS ? 16 : 8),
+                    (d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? "; the spectrum is not stored" : "");
         break;
     }
     case Family::Composite:
@@ -1364,7 +1370,7 @@ int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1,
     double* coef = (double*)(ws + P->off_coef);
     if (iso && !inner) HIP_TRY(hipMemsetAsync(d_iso, 0, (size_t)d.batch * P->nbins * (cross ? 16 : 8), st));
     switch (P->family) {
-        case Family::FusedInner: return run_fused_inner(P, d_in0, d_in1, d_out, ws, st);
+        case Family::FusedInner: return run_fused_inner(P, d_in0, d_in1, out, (double*)d_iso, ws, st);
         case Family::Composite: return run_inner_plan(P, d_in0, d_out, ws, st);
         case Family::FastG: return run_fastg(P, d_in0, d_in1, out, (double*)d_iso, st);
         case Family::FastS: return run_fasts(P, d_in0, out, (double*)d_iso, st);

@@ -135,11 +135,12 @@ class SpectralPlan:
             if out.dtype != self.out_dtype() or not out.is_contiguous() or out.numel() != need or out.device != dev:
                 raise ValueError(f"out does not match the plan (dtype {self.out_dtype()}, contiguous, {need} elements on {dev})")
         iso_dtype = torch.complex128 if self.out_mode == _lib.OUT_CROSS else torch.float64
+        nspec = self.batch * self.inner * self.mid  # (an inner / mid layout: every element is a spectrum with radial sums of its own)
         if self.flags & _lib.ISO and iso is None:
-            iso = torch.empty((self.batch, self.nbins), device=dev, dtype=iso_dtype)
+            iso = torch.empty((nspec, self.nbins), device=dev, dtype=iso_dtype)
         elif self.flags & _lib.ISO:
-            if iso.dtype != iso_dtype or not iso.is_contiguous() or iso.numel() != self.batch * self.nbins or iso.device != dev:
-                raise ValueError(f"iso does not match the plan (dtype {iso_dtype}, contiguous, {self.batch * self.nbins} elements on {dev})")
+            if iso.dtype != iso_dtype or not iso.is_contiguous() or iso.numel() != nspec * self.nbins or iso.device != dev:
+                raise ValueError(f"iso does not match the plan (dtype {iso_dtype}, contiguous, {nspec * self.nbins} elements on {dev})")
         if self.batch == 0:  # nothing to transform: empty outputs, no device call
             return (out if want_out else None), iso
         stream = _stream_handle(in0)
