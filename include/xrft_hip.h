@@ -146,6 +146,25 @@ typedef struct xrfthip_desc {
      * where it lies, a detrend (one plane over (ny, nx) per (batch, mid, inner) element) first as a pass of its own; no transposed copy.  0 or 1 = none.
      * Descriptors with the struct_size of the versions without `mid` / without `inner` are accepted. */
     int64_t mid;
+    /* Input strides: a box cut out of a larger field (da.isel(y=slice(..), x=slice(..)), the reference transforms any view numpy hands it, xrft/xrft.py:439-444) is
+     * read where it lies, with no contiguous copy.  Both describe d_in0, and d_in1 of a CROSS / PHASE plan (one set of strides for the two fields); the x stride is
+     * always 1; d_out, d_iso and the workspace stay dense.  xrfthip_exec never writes its input, so a batch stride SMALLER than a slab (overlapping windows of one
+     * buffer) is legal.
+     *   in_stride_y     elements of `dtype` between consecutive rows y of one slab; 0 = nx (nx/2 + 1 of a C2R_X plan)
+     *   in_stride_batch elements between consecutive slabs; 0 = ny * nx
+     * XRFTHIP_BAD_ARG: a negative stride; 0 < in_stride_y < the row length; a non-zero stride together with inner > 1, mid > 1 or XRFTHIP_AXIS_Y (those layouts stay
+     * dense).  XRFTHIP_UNSUPPORTED_LENGTH means "the caller copies": ny * in_stride_y above 2^31 - 1 elements or 2^32 - 1 bytes (the index math inside a slab is 32-bit),
+     * a stride that is not a multiple of 16 bytes (every vector load of the kernels stays one aligned instruction: there is no scalar path), or a kernel family that
+     * does not read strided input.  The family is chosen as for the dense descriptor of the same shape and NEVER changed because of the strides: a strided plan runs
+     * the same kernels, slabs_per_group and arithmetic as the dense plan, and its result is bit-identical to that plan's on a contiguous copy.  The families that read
+     * strided input, real float32 / float64 data in every mode they serve: FastY, FastM, FastN (xrfthip_kernel_kind FASTY / FASTM / FASTN on 2-D plans), FastS, FastG
+     * (slabs and row groups, real input) and FastR (real rows: in_stride_batch only).  A table set later that moves the plan to a family outside this list (the
+     * generic passes) answers XRFTHIP_UNSUPPORTED_LENGTH from that xrfthip_plan_set_* call.  Strides equal to the dense ones are the dense plan.
+     * A strided plan needs d_in0 (and d_in1) 16-byte aligned: xrfthip_exec checks and answers XRFTHIP_BAD_ARG.  The kernels touch no byte outside the rows of the view.
+     * Descriptors with the struct_size of the three earlier versions are accepted (strides 0).  As with `inner` / `mid`, no symbol and no version number tells this
+     * capability apart: the status of xrfthip_plan_create does (an older library answers XRFTHIP_BAD_ARG to the larger struct_size). */
+    int64_t in_stride_y;
+    int64_t in_stride_batch;
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;
@@ -206,8 +225,9 @@ size_t xrfthip_workspace_bytes(const xrfthip_plan* plan);
 int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen);
 
 /*
- * d_in0 : [batch][ny][nx] input (dtype)
- * d_in1 : second field for CROSS, else NULL
+ * d_in0 : [batch][ny][nx] input (dtype); with xrfthip_desc.in_stride_y / in_stride_batch: element (b, y, x) at d_in0[b * in_stride_batch + y * in_stride_y + x],
+ *         and the pointer 16-byte aligned (XRFTHIP_BAD_ARG otherwise)
+ * d_in1 : second field for CROSS, else NULL; the same strides and alignment as d_in0
  * d_out : COMPLEX/CROSS: complex [batch][ny][nx_out]; POWER: real [batch][ny][nx_out]; may be NULL with
  *         XRFTHIP_NO_SPECTRUM_OUT
  * d_iso : with XRFTHIP_ISO: float64 [batch][nbins] (POWER) or complex128 [batch][nbins] (CROSS), else NULL; inner / mid layouts: [batch][ne][nbins], ne = inner | mid

@@ -194,6 +194,13 @@ z = torch.randn((16, 4096, 4096), dtype=torch.complex64, device=dev); dz = xrft.
 add("fft 2-D of complex data (16,4096,4096) complex64", z.numel(), 16, timeit(lambda: xrft.fft(dz, dim=["y", "x"])))
 add("   power_spectrum of the same", z.numel(), 12, timeit(lambda: xrft.power_spectrum(dz, dim=["y", "x"])))
 del z, dz
+# round 8: a box of a larger field, transformed where it lies (xrfthip_desc.in_stride_y / in_stride_batch: no contiguous copy of the box)
+for parent, ys, xs, dt in (((16, 4096, 4096), slice(1024, 3072), slice(1024, 3072), torch.float32), ((32, 1440, 720), slice(360, 1080), slice(180, 540), torch.float64),
+                           ((4096, 256, 256), slice(64, 192), slice(64, 192), torch.float32)):
+    x = cube(parent, dt); da = xrft.DataArray(x, ("t", "y", "x"), {"y": np.arange(float(parent[1])), "x": np.arange(float(parent[2]))}).isel(y=ys, x=xs)
+    tag, bpp = ("f32" if dt == torch.float32 else "f64"), (8 if dt == torch.float32 else 16)
+    add(f"PS of the {tuple(da.data.shape)} box of {parent} {tag} linear+hann, read in place", da.data.numel(), bpp, timeit(lambda: xrft.power_spectrum(da, dim=["y", "x"], detrend="linear", window="hann")))
+    del x, da
 print(f"{'workload':58s} {'GFFT/s':>8s} {'ms':>9s} {'B/pt':>5s} {'frac of 8 TB/s':>15s}  path")
 for name, g, t, bpp, frac, path in rows:
     print(f"{name:58s} {g:8.2f} {t*1e3:9.3f} {bpp:5.0f} {frac:15.3f}  {path}")

@@ -54,6 +54,8 @@ class Desc(C.Structure):
         ("flags", C.c_uint32), ("scale", C.c_double), ("slabs_per_group", C.c_int32), ("reserved", C.c_int32),
         ("inner", C.c_int64),  # > 1: arrays are [batch][ny][nx][inner], two adjacent transform axes with the independent elements innermost
         ("mid", C.c_int64),    # > 1: ... and `mid` independent elements between the two transform axes: [batch][ny][mid][nx][inner]
+        ("in_stride_y", C.c_int64),      # elements between the rows of one slab of the input (0 = nx): a box of a larger field read where it lies
+        ("in_stride_batch", C.c_int64),  # elements between its slabs (0 = ny * nx); trailing-axes layout only, strides in multiples of 16 bytes
     ]
 
 

@@ -254,10 +254,14 @@ def _akey(a):
     return d
 
 
-def _get_plan(binmap_key=None, **kw):
+def _plan_key(binmap_key, kw):
     # the bin map can be 16M entries: it is identified by the key of the (cached) host computation, not by its bytes
-    key = (engine.bluestein_in_float64(),) + tuple((k, (binmap_key if k == "binmap" else _akey(v)) if isinstance(v, np.ndarray) else v)
-                                                   for k, v in sorted(kw.items()))
+    return (engine.bluestein_in_float64(),) + tuple((k, (binmap_key if k == "binmap" else _akey(v)) if isinstance(v, np.ndarray) else v)
+                                                    for k, v in sorted(kw.items()))
+
+
+def _get_plan(binmap_key=None, **kw):
+    key = _plan_key(binmap_key, kw)  # (includes the input strides of a plan that reads a view where it lies)
     with _plan_lock:
         p = _plan_cache.get(key)
         if p is None:
@@ -278,6 +282,7 @@ def clear_plan_cache():
     """Drop every cached plan (device tables) and the shared scratch buffers."""
     with _plan_lock:
         _plan_cache.clear()
+        _STRIDED_REFUSED.clear()
         _BLUE_TABLES.clear()
         _TWO_STAGE.clear()
     engine.clear_workspaces()
@@ -476,13 +481,43 @@ def _flags_tables_uncached(c, other_lag, other_reversed):
 
 def _arrange(c, da):
     """Device tensor with the transform axes last: shape (*other, [ny,] nx); returns (tensor, other_dims)."""
+    t, other, _ = _arrange_view(c, da, view_ok=False)
+    return t, other
+
+
+_STRIDED_REFUSED = OrderedDict()  # plan keys the library answered UNSUPPORTED_LENGTH to with input strides: those calls copy, without asking again
+
+
+def _view_strides(t, ndim):
+    """(in_stride_y, in_stride_batch) if the library can read the view ``t`` (*other, [ny,] nx) where it lies -- xrfthip_desc.in_stride_y / in_stride_batch: unit
+    stride along x, the leading dims collapsing to one batch stride, both strides and the first element on 16-byte boundaries, the rows of one slab within 32-bit
+    offsets -- else None (the view is copied, as every view was before the descriptor had strides)."""
+    if t.is_contiguous() or t.numel() == 0:
+        return None
+    sy, sb = engine.strides_of(t, ndim)
+    if sy is None:
+        return None
+    esz = t.element_size()
+    ny = t.shape[-2] if ndim == 2 else 1
+    if (sy * esz) % 16 or (sb * esz) % 16 or t.data_ptr() % 16 or ny * sy > (1 << 31) - 1 or ny * sy * esz > (1 << 32) - 1:
+        return None
+    return (sy if ndim == 2 else 0), sb
+
+
+def _arrange_view(c, da, view_ok=True):
+    """_arrange that leaves a box cut out of a larger array (``da.isel(y=slice(..), x=slice(..))``) where it lies when the transform dims are already the last
+    ones, in order, and the library can address the view (_view_strides): returns (tensor, other_dims, strides or None).  Everything else is made contiguous."""
     t = _to_device(da.data)
     tdims = ([c.ydim] if c.ydim is not None else []) + [c.xdim]
     other = [d for d in da.dims if d not in tdims]
     order = other + tdims
     if tuple(order) != tuple(da.dims):
         t = t.permute([da.get_axis_num(d) for d in order])
-    return t.contiguous(), other
+    elif view_ok:
+        st = _view_strides(t, len(tdims))
+        if st is not None:
+            return t, other, st
+    return t.contiguous(), other, None
 
 
 def _label_output(c, da, out_t, other, extra_cattrs=None, drop_transform=False):
@@ -649,7 +684,7 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
         out = _execute_inner(c, da, _lib.OUT_CROSS, scale, 0, da2, c2)
         if out is not None:
             return engine.angle(out), None, None
-    t, other = _arrange(c, da)
+    t, other, strides = _arrange_view(c, da)  # (a qualifying view of a larger array stays where it lies: no contiguous copy)
     ndim = len(c.dim)
     nx = da.sizes[c.xdim]
     ny = da.sizes[c.ydim] if c.ydim is not None else 1
@@ -660,9 +695,11 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
     flags |= extra_flags
     t2 = None
     if da2 is not None:
-        t2, other2 = _arrange(c2, da2)
+        t2, other2, strides2 = _arrange_view(c2, da2)
         if t2.shape != t.shape or other2 != other:
             raise ValueError("The two datasets have different dimensions")
+        if strides2 != strides or t2.dtype != t.dtype:  # one set of strides serves both fields: anything else is copied
+            t, t2, strides = t.contiguous(), t2.contiguous(), None
         if t2.dtype != t.dtype:
             dt = torch.promote_types(t.dtype, t2.dtype)
             t, t2 = t.to(dt), t2.to(dt)
@@ -672,6 +709,25 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
     if iso is not None:
         kw.update(binmap=iso["binmap"], nbins=iso["nbins"])
         bkey = iso.get("binmap_key")
+    if strides is not None:
+        # the plan that reads the view: the family of the dense plan of this shape, or UNSUPPORTED_LENGTH (then: the copy and the dense plan, exactly as before)
+        skw = dict(kw, in_stride_y=strides[0], in_stride_batch=strides[1])
+        skey = _plan_key(bkey, skw)
+        with _plan_lock:
+            refused = skey in _STRIDED_REFUSED
+        if not refused:
+            try:
+                out, iso_out = _get_plan(binmap_key=bkey, **skw).execute(t, t2)
+                return out, iso_out, other
+            except _lib.XrftHipError as e:
+                if e.status != _lib.UNSUPPORTED_LENGTH:
+                    raise
+                with _plan_lock:
+                    _STRIDED_REFUSED[skey] = True
+                    while len(_STRIDED_REFUSED) > 64:
+                        _STRIDED_REFUSED.popitem(last=False)
+        t = t.contiguous()
+        t2 = None if t2 is None else t2.contiguous()
     try:
         plan = _get_plan(binmap_key=bkey, **kw)
     except _lib.XrftHipError as e:

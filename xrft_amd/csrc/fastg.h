@@ -76,6 +76,10 @@ struct FastG {
     const unsigned* iso_start;
     double* iso;
     int nbins;
+    // real input read where it lies (xrfthip_desc.in_stride_batch / in_stride_y): elements of T between the slabs of `in` / `in_b` (one_d: between the groups of ny rows)
+    // and between its rows; fastg_kernel<.., STR> reads them, the dense kernels never do
+    long long in_slab;
+    int in_pitch;
 };
 
 // one radix pass over the COLUMNS of the tile: sequences of length len, element stride rs, ncols of them; lanes run along the columns
@@ -243,8 +247,11 @@ __device__ __forceinline__ void fastg_cols_pass(C2<T>* tile, int ncols, int len,
 
 // MODE 1: power spectrum (real T out), 0: complex spectrum, 2: cross spectrum of two fields (two tiles in LDS, complex out)
 // CIN: the complex-input forms (cin, inverse, c2r) -- kernels of their own: their branches cost the real-input forms registers
-template <typename T, int MODE, bool CIN>
-__global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 3)) fastg_kernel(FastG p) {  // (float64: three waves per SIMD = 168 registers)
+// STR (real input only): the rows of the input are p.in_pitch elements apart, its slabs (one_d: its groups of ny rows) p.in_slab -- xrfthip_desc.in_stride_y /
+// in_stride_batch, multiples of 16 bytes; a template parameter, so that the dense kernels keep their code
+template <typename T, int MODE, bool CIN, bool STR = false>
+__global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 3)) fastg_kernel(FastG p) {
+    static_assert(!(STR && CIN), "the complex-input forms read dense input");  // (float64: three waves per SIMD = 168 registers)
     typedef C2<T> CT;
     XRFT_DYN_SMEM(smem_raw);
     CT* tile0 = reinterpret_cast<CT*>(smem_raw);
@@ -283,7 +290,7 @@ __global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
         CT* tile = tile0 + f * (ny * rs);
         const CT* __restrict__ src = (CIN && p.c2r) ? reinterpret_cast<const CT*>(p.in) + (size_t)slab * ny * (n + 1)  // (half spectra)
                                    : (CIN && p.cin) ? reinterpret_cast<const CT*>(p.in) + (size_t)slab * ny * nx  // (complex samples)
-                                           : reinterpret_cast<const CT*>(reinterpret_cast<const T*>(f ? p.in_b : p.in) + (size_t)slab * ny * nx);
+                                           : reinterpret_cast<const CT*>(reinterpret_cast<const T*>(f ? p.in_b : p.in) + (STR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * ny * nx));
         // ---- load; the plane's sums on the way (float64 per thread, then the threads in a fixed order)
         double s0 = 0.0, si = 0.0, sj = 0.0;
         const bool plane = p.detrend && !p.one_d;  // (the slab's plane; a 1-D transform fits a line per row below)
@@ -326,9 +333,10 @@ __global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
                 if (km != k && km != n) row[km] = mk<T>(tm.re + tk.re + p2.im, tm.im - tk.im - p2.re);
             }
         } else if (packed) {
+            const int p2 = STR ? p.in_pitch >> 1 : 0;  // (STR: pairs of samples per row of the input; a strided pitch is a multiple of 16 bytes)
             for (int e = tid; e < npk; e += nthr) {
                 const int i = fdiv(e, inv_n), m = e - i * n;
-                const CT z = src[e];
+                const CT z = src[STR ? i * p2 + m : e];
                 tile[i * rs + m] = z;
                 if (plane) {
                     const double u = (double)z.re + (double)z.im;
@@ -354,7 +362,7 @@ __global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
             const T* __restrict__ srcr = reinterpret_cast<const T*>(src);
             for (int e = tid; e < npk; e += nthr) {
                 const int i = fdiv(e, inv_n), m = e - i * n;
-                const T v = srcr[e];
+                const T v = srcr[STR ? i * p.in_pitch + m : e];
                 tile[i * rs + m] = mk<T>(v, (T)0);
                 if (plane) {
                     s0 += (double)v;

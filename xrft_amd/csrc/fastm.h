@@ -176,6 +176,10 @@ struct FastM {
     int detrend, nslab, nunits;
     int shift_y, shift_x;
     double scale;
+    // pass 1 on a box of a larger field, read where it lies (xrfthip_desc.in_stride_batch / in_stride_y): elements of T between the slabs of `in` and between its rows.
+    // fastm_cols_kernel<.., INSTR> and fastn_cols_kernel<.., STR> read them; nothing else does.
+    long long in_slab;
+    int in_pitch;
 };
 
 // profiling builds (scripts/build_ablate_m.sh, -DXRFT_MDBG=bits; 0 in the product): 1 = the intermediate is written with plain
@@ -282,7 +286,9 @@ template <typename T, int N> __device__ __forceinline__ void mr_fill_tw1(C2<T>* 
 // GOV = 4 (float32, 1800 / 2000 / 2160 rows: XRFT_M_WIDE32): four sequences = 8 real columns = 32-byte row segments where the default
 // geometry (at most 640 threads) takes two -- 16-byte segments load at half the rate: (64, 2000, 2000) float32 12.5 us per slab for 6 us of
 // bytes.  Taken when the row length divides into 8-column blocks; the intermediate's layout follows (FastM::l_cw, l_rk).
-template <typename T, int NY, bool DET, int GOV = 0>
+// INSTR: the input's rows are p.in_pitch elements apart, its slabs p.in_slab (multiples of 16 bytes, the base 16-byte aligned: every column-pair load stays aligned and
+// inside its row); a template parameter, so that the dense kernels keep their code.
+template <typename T, int NY, bool DET, int GOV = 0, bool INSTR = false>
 __global__ void __launch_bounds__((MGeom<T, NY, GOV>::THR), (MGeom<T, NY, GOV>::WPS)) fastm_cols_kernel(FastM p) {
     typedef MGeom<T, NY, GOV> M;
     typedef C2<T> CT;
@@ -306,8 +312,8 @@ __global__ void __launch_bounds__((MGeom<T, NY, GOV>::THR), (MGeom<T, NY, GOV>::
     const bool on = r0 < M::B0;
     const int j = on ? r0 : 0;
     const CT w0 = reinterpret_cast<const CT*>(p.tw_y)[j];
-    const char* __restrict__ src = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.in) + (size_t)slab * NY * p.nx + (size_t)xb * CW);
-    const unsigned rowb = (unsigned)p.nx * (unsigned)sizeof(T), off0 = (unsigned)j * rowb + (unsigned)g * (unsigned)sizeof(CT), rstep = (unsigned)M0 * rowb;
+    const char* __restrict__ src = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.in) + (INSTR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * NY * p.nx) + (size_t)xb * CW);
+    const unsigned rowb = (INSTR ? (unsigned)p.in_pitch : (unsigned)p.nx) * (unsigned)sizeof(T), off0 = (unsigned)j * rowb + (unsigned)g * (unsigned)sizeof(CT), rstep = (unsigned)M0 * rowb;
     const T* __restrict__ wy = reinterpret_cast<const T*>(p.win_y);
     const CT wx = *reinterpret_cast<const CT*>(reinterpret_cast<const T*>(p.win_x) + xb * CW + 2 * g);
     CT a[R0];

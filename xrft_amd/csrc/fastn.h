@@ -263,8 +263,11 @@ __device__ __forceinline__ void n_first_cols(NColsCtx<T>& c, NGeoRef g, C2<T>* s
 }
 
 // FORM 0: the radix passes; 1: Bluestein's chirp convolution; 2: the prime-factor form with Rader's algorithm along the prime (fastg.h)
-template <typename T, int FORM, int CAP, bool GUARD = false>
+// STR: the input's rows are p.in_pitch elements apart, its slabs p.in_slab (xrfthip_desc.in_stride_y / in_stride_batch; multiples of 16 bytes, the base 16-byte
+// aligned); a template parameter, so that the dense kernels keep their code.
+template <typename T, int FORM, int CAP, bool GUARD = false, bool STR = false>
 __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 3)) fastn_cols_kernel(FastN P) {
+    static_assert(!(STR && GUARD), "the inner layouts are dense");
     static_assert(!GUARD || FORM != 1, "the guarded columns serve the inner layouts: radix passes or the Rader form");
     constexpr bool BLUE = FORM == 1, RADER = FORM == 2;
     typedef C2<T> CT;
@@ -285,8 +288,8 @@ __global__ void __launch_bounds__(fastn_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
     unsigned short* pout = pin + ((ny + 7) & ~7);
     const int col0 = xb * CW + 2 * gi;  // this thread's column pair
     NColsCtx<T> c;
-    c.src = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.in) + (size_t)slab * ny * nx + (size_t)xb * CW);
-    c.rowb = (unsigned)nx * (unsigned)sizeof(T);
+    c.src = reinterpret_cast<const char*>(reinterpret_cast<const T*>(p.in) + (STR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * ny * nx) + (size_t)xb * CW);
+    c.rowb = (STR ? (unsigned)p.in_pitch : (unsigned)nx) * (unsigned)sizeof(T);
     c.coff = (unsigned)gi * (unsigned)sizeof(CT);
     c.pair_ok = P.pair_ok != 0;  // (uniform)
     c.has0 = col0 < nx; c.has1 = col0 + 1 < nx;

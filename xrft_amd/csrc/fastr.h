@@ -47,6 +47,7 @@ struct FastR {
     int ishift;        // ... its input is rotated by n/2 on load (an fftshifted spectrum: xrft.py:612-617)
     int ph_in;         // ... `ph` multiplies the INPUT samples (by source index) instead of the output (the true-phase factor of xrft.ifft, xrft.py:596-606)
     int stagger;       // fastr_kernel: start delay of workgroup class c = (block / 8) % classes, c x (stagger & 0xff) x 3.4 us; classes = stagger >> 8 (0: none)
+    long long in_row;  // fastr_kernel / fastr2_kernel<.., STR>: elements between the rows of `in` (xrfthip_desc.in_stride_batch: rows of a larger array read where they lie)
 };
 
 constexpr int kFastRThreads = 1024;
@@ -190,7 +191,8 @@ __device__ __forceinline__ void fastr_stagger(int stagger) {
 #endif
 }
 
-template <int MODE, bool HALF>
+// (STR: the rows of the input are p.in_row elements apart -- rows of a larger array, xrfthip_desc.in_stride_batch; a template parameter: the dense kernels keep their code)
+template <int MODE, bool HALF, bool STR = false>
 __global__ void __launch_bounds__(kFastRThreads) fastr_kernel(FastR p) {
     constexpr int N = 65536, M = N / 2, T = kFastRThreads;
     constexpr int A1 = 545, B1 = 17;  // exchange 1: element (k1, n1, n2') at k1 A1 + n1 B1 + n2' (8-byte elements)
@@ -209,7 +211,7 @@ __global__ void __launch_bounds__(kFastRThreads) fastr_kernel(FastR p) {
         int tid = threadIdx.x;
         XRFT_OPAQUE(tid);
         const int lo = tid & 31, hi = tid >> 5;
-        const cf* __restrict__ src = reinterpret_cast<const cf*>(p.in + (size_t)row * N) + tid;
+        const cf* __restrict__ src = reinterpret_cast<const cf*>(p.in + (STR ? (size_t)row * (size_t)p.in_row : (size_t)row * N)) + tid;
         cf a[32];
 #pragma unroll
         for (int j = 0; j < 32; ++j) a[j] = src[j * T];  // z[n], n = tid + 1024 j: samples 2n, 2n + 1
@@ -353,7 +355,7 @@ template <int R2, int R3> struct R2Geom {
     static constexpr int WPS = 4;  // (113-123 registers, none spilled: four waves per SIMD)
 };
 
-template <int R2, int R3, int MODE, bool HALF>
+template <int R2, int R3, int MODE, bool HALF, bool STR = false>
 __global__ void __launch_bounds__((R2Geom<R2, R3>::T), (R2Geom<R2, R3>::WPS)) fastr2_kernel(FastR p) {
     typedef R2Geom<R2, R3> G;
     constexpr int T = G::T, M = G::M, N = G::N, K2 = G::K2, K3 = G::K3, S1 = G::S1, S2 = G::S2;
@@ -374,7 +376,7 @@ __global__ void __launch_bounds__((R2Geom<R2, R3>::T), (R2Geom<R2, R3>::WPS)) fa
     for (long long row = blockIdx.x; row < p.nrows; row += gridDim.x) {
         int tid = threadIdx.x;
         XRFT_OPAQUE(tid);
-        const cf* __restrict__ src = reinterpret_cast<const cf*>(p.in + (size_t)row * N) + tid;
+        const cf* __restrict__ src = reinterpret_cast<const cf*>(p.in + (STR ? (size_t)row * (size_t)p.in_row : (size_t)row * N)) + tid;
         cf a[32];
 #pragma unroll
         for (int j = 0; j < 32; ++j) a[j] = src[j * T];  // z[n], n = tid + T j: samples 2n, 2n + 1

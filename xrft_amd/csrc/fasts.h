@@ -47,6 +47,10 @@ struct FastS {
     const cf* ph_x;
     int ph_on;
     int stagger;  // a resident set walking the slabs: start delay of workgroup class c = (block / 8) % classes (fastr.h fastr_stagger; XRFTHIP_FASTS_STAGGER)
+    // fasts_power_kernel<.., STR>: a box of a larger field read where it lies (xrfthip_desc.in_stride_batch / in_stride_y): elements between the slabs of `in` and
+    // between its rows; the dense kernels never read the two
+    long long in_slab;
+    int in_pitch;
 };
 
 constexpr size_t fasts_max(size_t a, size_t b) { return a > b ? a : b; }
@@ -133,7 +137,9 @@ template <int R> __device__ __forceinline__ void fasts_split(cf* b, int c) {
 
 // ISO: 0 the power spectrum; 1 the spectrum and its radial sums; 2 the radial sums only (XRFTHIP_NO_SPECTRUM_OUT).  MODE 1: power spectrum;
 // 0: the complex spectrum (xrft.fft / dft; ISO = 0)
-template <int RY, int RX, int ISO = 0, int MODE = 1>
+// STR: the rows of the input are p.in_pitch elements apart, its slabs p.in_slab (multiples of 4, the base 16-byte aligned: the 8-byte loads stay aligned and inside
+// their rows); a template parameter, so that the dense kernels keep their code
+template <int RY, int RX, int ISO = 0, int MODE = 1, bool STR = false>
 __global__ void __launch_bounds__((SGeom<RY, RX>::T), (SGeom<RY, RX>::WPS)) fasts_power_kernel(FastS p) {
     static_assert(MODE == 1 || ISO == 0, "radial sums are of power spectra");
     typedef SGeom<RY, RX> G;
@@ -208,10 +214,16 @@ __global__ void __launch_bounds__((SGeom<RY, RX>::T), (SGeom<RY, RX>::WPS)) fast
         const int jp = tid % NXP, i0 = tid / NXP;  // packed column, first row
         cf a[32], b[32];
         if (have) {  // rows i0 + RY q, columns 2 jp, 2 jp + 1 (a uniform base + 32-bit offsets: no address pairs in registers)
-            const char* __restrict__ base = reinterpret_cast<const char*>(p.in + (size_t)slab * NY * NX);
+            const char* __restrict__ base = reinterpret_cast<const char*>(p.in + (STR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * NY * NX));
+            if (STR) {  // row i0 + RY q of the view, columns 2 jp, 2 jp + 1
+                const unsigned rowb = (unsigned)p.in_pitch * 4u, off = (unsigned)i0 * rowb + (unsigned)jp * 8u, step = (unsigned)RY * rowb;
+#pragma unroll
+                for (int q = 0; q < 32; ++q) a[q] = *reinterpret_cast<const cf*>(base + (off + step * (unsigned)q));
+            } else {
             const unsigned off = (unsigned)tid * 8u;
 #pragma unroll
             for (int q = 0; q < 32; ++q) a[q] = *reinterpret_cast<const cf*>(base + (off + (unsigned)(q * T) * 8u));
+            }
         }
         if (PRE && staged) emit(prev);
         if (!have) break;

@@ -138,6 +138,8 @@ struct FastY {
     int tune;                // see kYTuneDefault
     long long* tim;          // fasty_isorows_kernel<.., TIM>: [workgroup][8] shader-clock sums of its phases (profiling build only; null otherwise)
     unsigned* rdv;           // tune bit 21: one arrival counter per (slab, group of the column blocks that share the input's 128-byte lines), zeroed per launch
+    long long in_slab;       // fasty_cols_kernel<.., STR>: elements between the slabs of `in` and between its rows (xrfthip_desc.in_stride_batch / in_stride_y):
+    int in_pitch;            // a box of a larger field read where it lies; the dense kernels never read the two
 };
 
 // phase-ablation bits for profiling builds (scripts/gpu_ablate_yf.sh compiles variants with -DXRFT_YDBG=bits); 0 in the product
@@ -247,8 +249,11 @@ template <int N> __device__ __forceinline__ int held_k(int u, int bb, int k3) {
 // ------------------------------------------------------------------------------------------------
 // W2D (four-step 1-D with a window): the window of a long sequence is not separable over its [ny][nx] view, so it comes from a
 // table laid out like the slab, read at the samples' own offsets (w[nx i1 + i2]; shared by every slab: L2-resident).
-template <int NY, bool DET, bool W2D = false>
+// STR: the input's rows are in_pitch elements apart and its slabs in_slab (a multiple of 4 each, the base 16-byte aligned: every float4 load stays aligned and inside
+// its row); a template parameter, so that the dense kernels keep their code.
+template <int NY, bool DET, bool W2D = false, bool STR = false>
 __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : YCols<NY>::THR / 128)) fasty_cols_kernel(FastY p) {
+    static_assert(!(STR && W2D), "the four-step form reads one dense sequence per slab");
     typedef P2<NY> G;
     typedef YCols<NY> Y;
     constexpr int NT = G::NT, GY = Y::GY, THR = Y::THR, GSTR = YLds<NY, GY>::GSTR;
@@ -297,8 +302,9 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
     }
     const int x0 = xb * Y::CW + 4 * g;
     // uniform 64-bit base + one 32-bit per-lane byte offset (a slab is < 4 GB): scalar-base loads, no 64-bit address per row
-    const char* __restrict__ src = reinterpret_cast<const char*>(p.in + (size_t)slab * NY * p.nx + (size_t)xb * Y::CW);
-    const unsigned off0 = ((unsigned)u * (unsigned)p.nx + 4u * (unsigned)g) * 4u, rstep = (unsigned)NT * (unsigned)p.nx * 4u;
+    const unsigned pitch = STR ? (unsigned)p.in_pitch : (unsigned)p.nx;  // elements between the input's rows
+    const char* __restrict__ src = reinterpret_cast<const char*>(p.in + (STR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * NY * p.nx) + (size_t)xb * Y::CW);
+    const unsigned off0 = ((unsigned)u * pitch + 4u * (unsigned)g) * 4u, rstep = (unsigned)NT * pitch * 4u;
     F4 wx = {1.f, 1.f, 1.f, 1.f};
     if (!W2D) wx = *reinterpret_cast<const F4*>(p.win_x + x0);
     const char* __restrict__ wsrc = reinterpret_cast<const char*>(p.win2d + (size_t)xb * Y::CW);
@@ -323,7 +329,7 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
     float T[4] = {0.f, 0.f, 0.f, 0.f}, S[4] = {0.f, 0.f, 0.f, 0.f}, S2[4] = {0.f, 0.f, 0.f, 0.f};
     F4 rt[KREF], rb[KREF];
     if (DET) {
-        const unsigned offg = 16u * (unsigned)g, rowb = (unsigned)p.nx * 4u;
+        const unsigned offg = 16u * (unsigned)g, rowb = pitch * 4u;
 #pragma unroll
         for (int k = 0; k < KREF; ++k) {
             rt[k] = *reinterpret_cast<const F4*>(src + (offg + rowb * (unsigned)(ITOP - 1 + k)));

@@ -426,6 +426,9 @@ int run_fastg(const xrfthip_plan* P, const void* in, const void* in_b, void* out
     p.ph_in = ((d.flags & XRFTHIP_PHASE_IN) && P->fph_on) ? 1 : 0;
     p.c2r = (d.flags & XRFTHIP_C2R_X) ? 1 : 0;
     if (P->g_one_d) p.nslabs = (d.batch + P->g_rows - 1) / P->g_rows;
+    // the input's own strides: a slab's rows in_pitch apart; one_d: the "slab" is a group of g_rows rows of the 1-D plan, in_stride_batch apart
+    p.in_pitch = (int)(P->g_one_d ? in_slab(P) : in_pitch(P));
+    p.in_slab = P->g_one_d ? (long long)P->g_rows * in_slab(P) : in_slab(P);
     p.nrx = (int)P->g_rx.size(); p.nry = (int)P->g_ry.size();
     for (int i = 0; i < p.nrx; ++i) p.rx[i] = P->g_rx[(size_t)i];
     for (int i = 0; i < p.nry; ++i) p.ry[i] = P->g_ry[(size_t)i];
@@ -457,6 +460,7 @@ int run_fastg(const xrfthip_plan* P, const void* in, const void* in_b, void* out
     const dim3 grid((unsigned)std::min<long long>(p.nslabs, 0x7fffffffLL)), blk((unsigned)thr);
     xrfthip_plan::ProfRec* rec = prof_begin(P, P->g_one_d ? "fastg_rows" : "fastg_slab", st);
 #define GL_(TT, MM) do { if (P->cplx_in) { auto k = &fastg_kernel<TT, (MM == 2 ? 1 : MM), true>; XRFT_LAUNCH(k, grid, blk, P->g_lds, st, p); } \
+                         else if (in_strided(P)) { auto k = &fastg_kernel<TT, MM, false, true>; XRFT_LAUNCH(k, grid, blk, P->g_lds, st, p); } /* (a box of a larger field, read where it lies) */ \
                          else { auto k = &fastg_kernel<TT, MM, false>; XRFT_LAUNCH(k, grid, blk, P->g_lds, st, p); } } while (0)
     const bool real_out = d.out_mode == XRFTHIP_OUT_POWER || (d.flags & XRFTHIP_C2R_X);  // (MODE 1: |F|^2, or the real samples of an irfftn)
     if (P->dbl) { if (cross) GL_(double, 2); else if (!real_out) GL_(double, 0); else GL_(double, 1); }
@@ -483,6 +487,8 @@ void set_attrs_fastg() {
 #define SETF(K) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, m)
     SETF((fastg_kernel<float, 0, false>)); SETF((fastg_kernel<float, 1, false>)); SETF((fastg_kernel<double, 0, false>)); SETF((fastg_kernel<double, 1, false>));
     SETF((fastg_kernel<float, 2, false>)); SETF((fastg_kernel<double, 2, false>));
+    SETF((fastg_kernel<float, 0, false, true>)); SETF((fastg_kernel<float, 1, false, true>)); SETF((fastg_kernel<float, 2, false, true>));  // (strided input)
+    SETF((fastg_kernel<double, 0, false, true>)); SETF((fastg_kernel<double, 1, false, true>)); SETF((fastg_kernel<double, 2, false, true>));
     SETF((fastg_kernel<float, 0, true>)); SETF((fastg_kernel<float, 1, true>)); SETF((fastg_kernel<double, 0, true>)); SETF((fastg_kernel<double, 1, true>));
     SETF((fastgy_kernel<float, 0, 0>)); SETF((fastgy_kernel<float, 1, 0>)); SETF((fastgy_kernel<double, 0, 0>)); SETF((fastgy_kernel<double, 1, 0>));
     SETF((fastgy_kernel<float, 0, 1>)); SETF((fastgy_kernel<float, 1, 1>)); SETF((fastgy_kernel<double, 0, 1>)); SETF((fastgy_kernel<double, 1, 1>));

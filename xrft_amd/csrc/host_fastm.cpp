@@ -435,6 +435,12 @@ void fastn_launch_cols(const xrfthip_plan* P, const FastM& m, hipStream_t st) {
     for (int i = 0; i < hg.np; ++i) maxrad = std::max(maxrad, hg.r[i]);
     // (radial sums of an inner layout: a packed column pair holds two spectra -- a sample that is not finite must stay in its own, fastn.h GUARD)
     const bool guard = P->family == Family::FusedInner && (P->d.flags & XRFTHIP_ISO);
+    const bool str = in_strided(P) && P->family == Family::FastN;  // (a box of a larger field, read where it lies; the inner layouts are dense)
+#define NCS_(TT, CC) do { if (P->n_blue_m) { auto k = &fastn_cols_kernel<TT, 1, 16, false, true>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } \
+                          else if (P->n_rad_p) { auto k = &fastn_cols_kernel<TT, 2, 16, false, true>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } \
+                          else { auto k = &fastn_cols_kernel<TT, 0, CC, false, true>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } } while (0)
+    if (str) { if (P->dbl) NCS_(double, 16); else if (maxrad > 16) NCS_(float, 20); else NCS_(float, 16); return; }
+#undef NCS_
 #define NC_(TT, CC) do { if (guard && P->n_rad_p) { auto k = &fastn_cols_kernel<TT, 2, 16, true>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } \
                          else if (guard) { auto k = &fastn_cols_kernel<TT, 0, CC, true>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } \
                          else if (P->n_blue_m) { auto k = &fastn_cols_kernel<TT, 1, 16>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } /* (a chirp convolution's radices stop at 16) */ \
@@ -465,7 +471,8 @@ FastM fastm_params(const xrfthip_plan* P, const void* in, void* out, char* ws, l
     const xrfthip_desc& d = P->d;
     const size_t slab_pts = (size_t)P->yny * P->ynx, s0 = (size_t)slot * slot_slabs;
     FastM p{};
-    p.in = (const char*)in + (size_t)g0 * slab_pts * P->rsize;
+    p.in = (const char*)in + (in_strided(P) ? (size_t)g0 * (size_t)in_slab(P) : (size_t)g0 * slab_pts) * P->rsize;
+    p.in_slab = in_slab(P); p.in_pitch = (int)in_pitch(P);
     p.w2 = ws + P->off_w + s0 * (size_t)P->y_nrow_pad * (size_t)P->y_pitch * P->csize;
     const size_t out_esz = (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_PHASE) ? P->rsize : P->csize;
     const size_t out_pts = (size_t)P->yny * ((d.flags & XRFTHIP_HALF_X) ? P->ynx / 2 + 1 : P->ynx);
@@ -507,12 +514,13 @@ void fastm_launch_cols(const xrfthip_plan* P, const FastM& p, long long gc, hipS
 #else
 #define MBIG_(k, n) ((void)0)
 #endif
-#define MC_(TT, NN) do { if (d.detrend) { auto k = &fastm_cols_kernel<TT, NN, true>; MBIG_(k, C.lds_cols); XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } \
-                         else { auto k = &fastm_cols_kernel<TT, NN, false>; MBIG_(k, C.lds_cols); XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } } while (0)
+#define MCG_(TT, NN, GG, SS) do { if (d.detrend) { auto k = &fastm_cols_kernel<TT, NN, true, GG, SS>; MBIG_(k, C.lds_cols); XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } \
+                                  else { auto k = &fastm_cols_kernel<TT, NN, false, GG, SS>; MBIG_(k, C.lds_cols); XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } } while (0)
+#define MC_(TT, NN) do { if (str) MCG_(TT, NN, 0, true); else MCG_(TT, NN, 0, false); } while (0)  /* (str: a box of a larger field, read where it lies) */
 #define XD_(NN) if (P->yny == NN) MC_(double, NN);
 #define XF_(NN) if (P->yny == NN) MC_(float, NN);
-#define MCW_(NN) if (P->yny == NN) do { if (d.detrend) { auto k = &fastm_cols_kernel<float, NN, true, 4>; MBIG_(k, C.lds_cols); XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } \
-                                            else { auto k = &fastm_cols_kernel<float, NN, false, 4>; MBIG_(k, C.lds_cols); XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } } while (0);
+#define MCW_(NN) if (P->yny == NN) do { if (str) MCG_(float, NN, 4, true); else MCG_(float, NN, 4, false); } while (0);
+    const bool str = in_strided(P);
     if (rt) {}
     else if (wide) { XRFT_M_WIDE32(MCW_) }
     else if (P->dbl) { XRFT_M_LATLON(XD_) XRFT_M_POW2(XD_) } else { XRFT_M_LATLON(XF_) XRFT_M_F32ONLY(XF_) }
@@ -520,6 +528,7 @@ void fastm_launch_cols(const xrfthip_plan* P, const FastM& p, long long gc, hipS
 #undef XD_
 #undef XF_
 #undef MC_
+#undef MCG_
     prof_end(rec, st);
     if (d.detrend) {
         rec = prof_begin(P, "fastm_fit", st);

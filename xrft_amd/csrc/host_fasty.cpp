@@ -335,12 +335,18 @@ void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long gc, hipS
                      else { auto k = &fasty_cols_kernel<NN, false>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
 #define YCW_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
                       else { auto k = &fasty_cols_kernel<NN, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
-    if (P->fast1d_win) {  // four-step 1-D with a window: the slab-shaped window table
+#define YCS_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
+                      else { auto k = &fasty_cols_kernel<NN, false, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
+    if (in_strided(P)) {  // a box of a larger field, read where it lies (FastY only: xrfthip_plan_create)
+        if (P->yny == 4096) YCS_(4096); else if (P->yny == 2048) YCS_(2048); else if (P->yny == 1024) YCS_(1024); else if (P->yny == 512) YCS_(512); else YCS_(256);
+    }
+    else if (P->fast1d_win) {  // four-step 1-D with a window: the slab-shaped window table
         if (P->yny == 4096) YCW_(4096); else if (P->yny == 2048) YCW_(2048); else if (P->yny == 1024) YCW_(1024); else if (P->yny == 512) YCW_(512); else YCW_(256);
     }
     else if (P->yny == 4096) YC_(4096); else if (P->yny == 2048) YC_(2048); else if (P->yny == 1024) YC_(1024); else if (P->yny == 512) YC_(512); else YC_(256);
 #undef YC_
 #undef YCW_
+#undef YCS_
     prof_end(rec, st);
     if (d.detrend) {  // plane (2-D) or line through the whole sequence (four-step 1-D) from the per-column sums -> what pass 2 has to add back
         rec = prof ? prof_begin(P, "fasty_fit", st) : nullptr;
@@ -431,7 +437,8 @@ FastY fasty_params(const xrfthip_plan* P, const float* in, void* out, double* is
     const YGeomRt C = ycols_geom(P->yny);
     const size_t s0 = (size_t)slot * slot_slabs;  // first slab of the slot inside the workspace arrays
     FastY p{};
-    p.in = in + (size_t)g0 * slab_pts;
+    p.in = in + (in_strided(P) ? (size_t)g0 * (size_t)in_slab(P) : (size_t)g0 * slab_pts);
+    p.in_slab = in_slab(P); p.in_pitch = (int)in_pitch(P);
     p.w2 = reinterpret_cast<cf*>(ws + P->off_w) + s0 * (size_t)P->y_nrow_pad * P->ynx;
     const size_t out_esz = (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_PHASE) ? sizeof(float) : sizeof(cf);
     const size_t out_pts = (size_t)P->yny * ((d.flags & XRFTHIP_HALF_X) ? P->ynx / 2 + 1 : P->ynx);
@@ -643,7 +650,7 @@ int run_fastyc(const xrfthip_plan* P, const void* in, void* out, char* ws, hipSt
 void set_attrs_fasty() {
     const int m = (int)kLdsMax;
 #define SETF(K) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, m)
-#define SETY(NN) SETF((fasty_cols_kernel<NN, false>)); SETF((fasty_cols_kernel<NN, true>)); SETF((fasty_cols_kernel<NN, false, true>)); SETF((fasty_cols_kernel<NN, true, true>)); SETF((fasty_rows_kernel<NN, 1, false>)); SETF((fasty_rows_kernel<NN, 1, true>)); \
+#define SETY(NN) SETF((fasty_cols_kernel<NN, false>)); SETF((fasty_cols_kernel<NN, true>)); SETF((fasty_cols_kernel<NN, false, true>)); SETF((fasty_cols_kernel<NN, true, true>)); SETF((fasty_cols_kernel<NN, false, false, true>)); SETF((fasty_cols_kernel<NN, true, false, true>)); SETF((fasty_rows_kernel<NN, 1, false>)); SETF((fasty_rows_kernel<NN, 1, true>)); \
                  SETF((fasty_rows_kernel<NN, 0, false>)); SETF((fasty_rows_kernel<NN, 2, false>)); SETF((fasty_rows_kernel<NN, 2, true>)); SETF((fasty_rows_kernel<NN, 3, false>))
     SETY(4096); SETY(2048); SETY(1024); SETY(512); SETY(256);
 #undef SETY

@@ -17,6 +17,7 @@
 #define XRFT_KI_Y_(NN) \
     XRFT_KW void fasty_cols_kernel<NN, true>(FastY); XRFT_KW void fasty_cols_kernel<NN, false>(FastY); \
     XRFT_KW void fasty_cols_kernel<NN, true, true>(FastY); XRFT_KW void fasty_cols_kernel<NN, false, true>(FastY); \
+    XRFT_KW void fasty_cols_kernel<NN, true, false, true>(FastY); XRFT_KW void fasty_cols_kernel<NN, false, false, true>(FastY);  /* (STR: strided input) */ \
     XRFT_KW void fasty_rows_kernel<NN, 1, true>(FastY); XRFT_KW void fasty_rows_kernel<NN, 1, false>(FastY); \
     XRFT_KW void fasty_rows_kernel<NN, 2, true>(FastY); XRFT_KW void fasty_rows_kernel<NN, 2, false>(FastY); \
     XRFT_KW void fasty_rows_kernel<NN, 3, false>(FastY); XRFT_KW void fasty_rows_kernel<NN, 0, false>(FastY);
@@ -40,6 +41,14 @@ XRFT_KW void fasty_rows_kernel<256, 1, false, true>(FastY); XRFT_KW void fasty_r
 #define XRFT_KI_MCD_(NN) XRFT_KW void fastm_cols_kernel<double, NN, true>(FastM); XRFT_KW void fastm_cols_kernel<double, NN, false>(FastM);
 #define XRFT_KI_MCF_(NN) XRFT_KW void fastm_cols_kernel<float, NN, true>(FastM); XRFT_KW void fastm_cols_kernel<float, NN, false>(FastM);
 #define XRFT_KI_MCW_(NN) XRFT_KW void fastm_cols_kernel<float, NN, true, 4>(FastM); XRFT_KW void fastm_cols_kernel<float, NN, false, 4>(FastM);
+XRFT_M_LATLON(XRFT_KI_MCD_) XRFT_M_POW2(XRFT_KI_MCD_) XRFT_M_LATLON(XRFT_KI_MCF_) XRFT_M_F32ONLY(XRFT_KI_MCF_) XRFT_M_WIDE32(XRFT_KI_MCW_)
+#undef XRFT_KI_MCD_
+#undef XRFT_KI_MCF_
+#undef XRFT_KI_MCW_
+/* (STR: strided input) */
+#define XRFT_KI_MCD_(NN) XRFT_KW void fastm_cols_kernel<double, NN, true, 0, true>(FastM); XRFT_KW void fastm_cols_kernel<double, NN, false, 0, true>(FastM);
+#define XRFT_KI_MCF_(NN) XRFT_KW void fastm_cols_kernel<float, NN, true, 0, true>(FastM); XRFT_KW void fastm_cols_kernel<float, NN, false, 0, true>(FastM);
+#define XRFT_KI_MCW_(NN) XRFT_KW void fastm_cols_kernel<float, NN, true, 4, true>(FastM); XRFT_KW void fastm_cols_kernel<float, NN, false, 4, true>(FastM);
 XRFT_M_LATLON(XRFT_KI_MCD_) XRFT_M_POW2(XRFT_KI_MCD_) XRFT_M_LATLON(XRFT_KI_MCF_) XRFT_M_F32ONLY(XRFT_KI_MCF_) XRFT_M_WIDE32(XRFT_KI_MCW_)
 #undef XRFT_KI_MCD_
 #undef XRFT_KI_MCF_
@@ -88,6 +97,8 @@ XRFT_KW void fastn_irows_kernel<float, 2, 16>(FastNI); XRFT_KW void fastn_irows_
 XRFT_KW void fastn_irows_kernel<float, 1, 16, true>(FastNI); XRFT_KW void fastn_irows_kernel<float, 1, 20, true>(FastNI);  /* (ISO: the per-element radial sums gathered in the row pass) */
 XRFT_KW void fastn_irows_kernel<float, 2, 16, true>(FastNI); XRFT_KW void fastn_irows_kernel<float, 2, 20, true>(FastNI);
 XRFT_KW void fastn_cols_kernel<float, 0, 16, true>(FastN); XRFT_KW void fastn_cols_kernel<float, 0, 20, true>(FastN); XRFT_KW void fastn_cols_kernel<float, 2, 16, true>(FastN);  /* (GUARD: their column pass) */
+XRFT_KW void fastn_cols_kernel<float, 0, 16, false, true>(FastN); XRFT_KW void fastn_cols_kernel<float, 0, 20, false, true>(FastN);  /* (STR: strided input) */
+XRFT_KW void fastn_cols_kernel<float, 1, 16, false, true>(FastN); XRFT_KW void fastn_cols_kernel<float, 2, 16, false, true>(FastN);
 XRFT_KW void fastn_fit_inner_kernel<float>(const double*, const float*, C2<float>*, int, int, int, int, int, int);
 #endif
 #if XRFT_KI_ON(7)
@@ -95,6 +106,7 @@ XRFT_KI_N_(double, 16) XRFT_KW void fastn_cols_kernel<double, 1, 16>(FastN); XRF
 XRFT_KW void fastn_irows_kernel<double, 0, 16>(FastNI); XRFT_KW void fastn_irows_kernel<double, 1, 16>(FastNI); XRFT_KW void fastn_irows_kernel<double, 2, 16>(FastNI);
 XRFT_KW void fastn_irows_kernel<double, 1, 16, true>(FastNI); XRFT_KW void fastn_irows_kernel<double, 2, 16, true>(FastNI);
 XRFT_KW void fastn_cols_kernel<double, 0, 16, true>(FastN); XRFT_KW void fastn_cols_kernel<double, 2, 16, true>(FastN);
+XRFT_KW void fastn_cols_kernel<double, 0, 16, false, true>(FastN); XRFT_KW void fastn_cols_kernel<double, 1, 16, false, true>(FastN); XRFT_KW void fastn_cols_kernel<double, 2, 16, false, true>(FastN);  /* (STR: strided input) */
 XRFT_KW void fastn_fit_inner_kernel<double>(const double*, const double*, C2<double>*, int, int, int, int, int, int);
 #endif
 #undef XRFT_KI_N_

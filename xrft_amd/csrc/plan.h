@@ -572,6 +572,19 @@ inline bool dbl_phase_tables(const xrfthip_plan* P) {  // the families that read
     const Family f = P->family;
     return P->dbl && (f == Family::FastM || f == Family::FastN || f == Family::FastMY || f == Family::FastMX || f == Family::FastG || f == Family::FastGY || f == Family::FusedInner);
 }
+// Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's
+// input take them: pass 1 of the two-pass families, the load of the one-pass families.  The intermediate and the output are dense.
+inline bool in_strided(const xrfthip_plan* P) { return P->d.in_stride_y != 0 || P->d.in_stride_batch != 0; }
+inline long long in_pitch(const xrfthip_plan* P) { return P->d.in_stride_y ? P->d.in_stride_y : P->d.nx; }               // elements between rows (real-input families: rows of nx)
+inline long long in_slab(const xrfthip_plan* P) { return P->d.in_stride_batch ? P->d.in_stride_batch : P->d.ny * P->d.nx; }  // elements between slabs
+inline bool family_reads_strided(const xrfthip_plan* P) {  // the families taught to address in + slab * in_stride_batch + y * in_stride_y + x (real input)
+    switch (P->family) {
+        case Family::FastY: case Family::FastM: case Family::FastN: case Family::FastS: case Family::FastR: return !P->cplx_in;
+        // (slabs and row groups; the complex-input forms are kernels of their own; a group of rows is indexed with 32 bits)
+        case Family::FastG: return !P->cplx_in && (!P->g_one_d || (long long)P->g_rows * in_slab(P) <= 0x7fffffffLL);
+        default: return false;
+    }
+}
 void prof_end(xrfthip_plan::ProfRec* r, hipStream_t st);
 xrfthip_plan* create_fused_inner(const xrfthip_desc& d);
 xrfthip_plan::ProfRec* prof_begin(const xrfthip_plan* P, const std::string& label, hipStream_t st);

@@ -762,6 +762,8 @@ int finalize_plan(xrfthip_plan* P) {
     }
     if (rc) return rc;
     settle_family(P);
+    // a strided plan runs the family the dense descriptor gets, or none: never a slower family because of the strides (the caller copies)
+    if (in_strided(P) && !family_reads_strided(P)) return XRFTHIP_UNSUPPORTED_LENGTH;
     layout_workspace(P);
     return XRFTHIP_OK;
 }
@@ -853,14 +855,23 @@ int xrfthip_last_hip_error(void) { return g_last_hip_error; }
 
 int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // (a descriptor of the version before `inner` was appended is accepted: inner = 1)
-    constexpr uint32_t kOldDescSize = (uint32_t)offsetof(xrfthip_desc, inner), kOldDescSize2 = (uint32_t)offsetof(xrfthip_desc, mid);
-    if (!plan || !desc || (desc->struct_size != sizeof(xrfthip_desc) && desc->struct_size != kOldDescSize && desc->struct_size != kOldDescSize2)) return XRFTHIP_BAD_ARG;
+    // (... and of the versions before `mid` and before the input strides: mid = 1, strides 0)
+    constexpr uint32_t kOldDescSize = (uint32_t)offsetof(xrfthip_desc, inner), kOldDescSize2 = (uint32_t)offsetof(xrfthip_desc, mid), kOldDescSize3 = (uint32_t)offsetof(xrfthip_desc, in_stride_y);
+    if (!plan || !desc || (desc->struct_size != sizeof(xrfthip_desc) && desc->struct_size != kOldDescSize && desc->struct_size != kOldDescSize2 && desc->struct_size != kOldDescSize3)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);
     dcopy.struct_size = sizeof(xrfthip_desc);
     if (dcopy.inner < 0 || dcopy.mid < 0) return XRFTHIP_BAD_ARG;
     if (dcopy.inner == 0) dcopy.inner = 1;
     if (dcopy.mid == 0) dcopy.mid = 1;
+    if (dcopy.in_stride_y < 0 || dcopy.in_stride_batch < 0) return XRFTHIP_BAD_ARG;
+    {   // strides that say what a dense array says are the dense plan (any family serves it)
+        const int64_t row = (dcopy.flags & XRFTHIP_C2R_X) ? dcopy.nx / 2 + 1 : dcopy.nx;
+        if (dcopy.in_stride_y > 0 && dcopy.in_stride_y < row) return XRFTHIP_BAD_ARG;
+        if (dcopy.in_stride_y == row) dcopy.in_stride_y = 0;
+        if (dcopy.ndim == 1) dcopy.in_stride_y = 0;  // (one row per slab: nothing to stride over)
+        if (dcopy.in_stride_y == 0 && dcopy.in_stride_batch == dcopy.ny * row) dcopy.in_stride_batch = 0;
+    }
     const xrfthip_desc& d = dcopy;
     if (d.ndim != 1 && d.ndim != 2) return XRFTHIP_BAD_ARG;
     if (d.batch < 0 || d.nx < 1 || d.ny < 1 || (d.ndim == 1 && d.ny != 1)) return XRFTHIP_BAD_ARG;
@@ -885,6 +896,15 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // AXIS_Y with HALF_X / REALDIM_X2 (ABI 0.1.4): real_dim along the ONE transformed axis -- ny / 2 + 1 rows per slab, unshifted; the one-pass kernels only (below)
     if ((d.flags & XRFTHIP_AXIS_Y) && (d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2)) &&
         (cplx_in || !(d.flags & XRFTHIP_HALF_X) || (d.flags & (XRFTHIP_SHIFT_Y | XRFTHIP_FLIP_Y | XRFTHIP_INVERSE)))) return XRFTHIP_BAD_ARG;
+
+    const bool strided = d.in_stride_y != 0 || d.in_stride_batch != 0;
+    if (strided && (d.inner > 1 || d.mid > 1 || (d.flags & XRFTHIP_AXIS_Y))) return XRFTHIP_BAD_ARG;  // (those layouts stay dense)
+    if (strided) {  // "the caller copies": the in-slab index math is 32-bit (elements, and bytes as unsigned); every vector load stays one aligned instruction
+        const int64_t esz = (d.dtype == XRFTHIP_F32 ? 4 : d.dtype == XRFTHIP_C128 ? 16 : 8);
+        const int64_t pitch = d.in_stride_y ? d.in_stride_y : d.nx;
+        if (pitch > ((1LL << 31) - 1) / d.ny || d.ny * pitch * esz > (1LL << 32) - 1) return XRFTHIP_UNSUPPORTED_LENGTH;
+        if ((d.in_stride_y * esz) % 16 != 0 || (d.in_stride_batch * esz) % 16 != 0) return XRFTHIP_UNSUPPORTED_LENGTH;
+    }
 
     if (d.inner > 1 || d.mid > 1) return create_inner_plan(plan, d);
 
@@ -1127,6 +1147,10 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         appendf(s, "xrfthip plan: ndim=%d batch=%lld ny=%lld nx=%lld dtype=%d mode=%d detrend=%d flags=0x%x width=%lld nx_out=%lld mirror=%d group=%d ws=%zuB\n",
                 d.ndim, (long long)d.batch, (long long)d.ny, (long long)d.nx, d.dtype, d.out_mode, d.detrend, d.flags,
                 plan->width, plan->nx_out, (int)plan->mirror, plan->G, plan->ws_bytes);
+    // a strided plan: said on the line of the pass that reads the caller's input, by every family that family_reads_strided() names (empty on a dense plan)
+    std::string in_note_;
+    if (in_strided(plan)) appendf(in_note_, "; input read where it lies: in pitch %lld / slab %lld", in_pitch(plan), in_slab(plan));
+    const char* in_note = in_note_.c_str();
     switch (plan->family) {
     case Family::FusedInner: {
         auto rads = [](const NGeo& g) { std::string t; for (int i = 0; i < g.np; ++i) t += (i ? "x" : "") + std::to_string(g.r[i]); return t; };
@@ -1162,21 +1186,21 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         for (int r : plan->g_ry) rys += (rys.empty() ? "" : "x") + std::to_string(r);
         if (plan->g_one_d)
             appendf(s, "  [fastg rows] one pass, one %d-thread workgroup per %d rows of %lld samples%s: in LDS, radices from the plan (x: %d = %s), a mean / line per row in the "
-                       "workgroup, output gathered in output order through the digit-reversal table, lds=%zuB\n",
+                       "workgroup, output gathered in output order through the digit-reversal table, lds=%zuB%s\n",
                     (int)fastg_threads(plan), plan->g_rows, (long long)plan->d.nx, plan->g_packed ? " packed in pairs" : plan->cplx_in ? " (complex input)" : " (an odd length: complex sequences)", plan->g_n,
-                    rxs.empty() ? "1" : rxs.c_str(), plan->g_lds);
+                    rxs.empty() ? "1" : rxs.c_str(), plan->g_lds, in_note);
         else if (plan->g_packed)
             appendf(s, "  [fastg] one pass, one %d-thread workgroup per %lld x %lld slab: the half spectrum (%lld rows of %lld + 1 complex) in LDS, radices from the plan "
                        "(x: %lld = %s on packed rows, y: %lld = %s), exact plane detrend in the workgroup, output gathered in output order through the digit-reversal "
-                       "tables, lds=%zuB\n",
+                       "tables, lds=%zuB%s\n",
                     (int)fastg_threads(plan), (long long)plan->d.ny, (long long)plan->d.nx, (long long)plan->d.ny, (long long)plan->d.nx / 2, (long long)plan->d.nx / 2,
-                    rxs.empty() ? "1" : rxs.c_str(), (long long)plan->d.ny, rys.c_str(), plan->g_lds);
+                    rxs.empty() ? "1" : rxs.c_str(), (long long)plan->d.ny, rys.c_str(), plan->g_lds, in_note);
         else
             appendf(s, "  [fastg] one pass, one %d-thread workgroup per %lld x %lld slab (complex input or an odd row length: the rows as complex sequences): the spectrum (%lld rows of %lld complex) "
                        "in LDS, radices from the plan (x: %lld = %s, y: %lld = %s), exact plane detrend in the workgroup, output gathered in output order through the "
-                       "digit-reversal tables, lds=%zuB\n",
+                       "digit-reversal tables, lds=%zuB%s\n",
                     (int)fastg_threads(plan), (long long)plan->d.ny, (long long)plan->d.nx, (long long)plan->d.ny, (long long)plan->d.nx, (long long)plan->d.nx,
-                    rxs.c_str(), (long long)plan->d.ny, rys.c_str(), plan->g_lds);
+                    rxs.c_str(), (long long)plan->d.ny, rys.c_str(), plan->g_lds, in_note);
         if (plan->d.out_mode == XRFTHIP_OUT_CROSS)
             appendf(s, "  [fastg cross spectrum] both fields' tiles in the workgroup's LDS, F0 conj(F1) on the way out\n");
         if (plan->d.flags & XRFTHIP_ISO)
@@ -1188,8 +1212,8 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         const SGeomRt G = sgeom(plan->d.ny, plan->d.nx);
         appendf(s, "  [fasts] one pass, one %d-thread workgroup per %lld x %lld slab (%d fit a CU): the packed columns' transform, their split and the rows' "
                    "transform in registers (32 complex per thread, r32x%lld / r32x%lld, three LDS exchanges in halves), exact plane detrend in the workgroup, |F|^2 "
-                   "rows staged in LDS and written whole with the fftshift and the Hermitian mirror, lds=%zuB; 8 algorithmic bytes per sample through memory\n",
-                G.thr, (long long)plan->d.ny, (long long)plan->d.nx, G.per_cu, (long long)plan->d.ny / 32, (long long)plan->d.nx / 32, G.lds);
+                   "rows staged in LDS and written whole with the fftshift and the Hermitian mirror, lds=%zuB; 8 algorithmic bytes per sample through memory%s\n",
+                G.thr, (long long)plan->d.ny, (long long)plan->d.nx, G.per_cu, (long long)plan->d.ny / 32, (long long)plan->d.nx / 32, G.lds, in_note);
         break;
     }
     case Family::FastYCFourStep: {
@@ -1235,10 +1259,10 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         const long long nxr = plan->d.nx;
         appendf(s, "  [fastr] one pass, one %lld-thread workgroup per %lld-sample row (grid %lld): the packed %lld-point complex transform in registers (32 per thread, "
                    "r32x%dx%d, LDS exchanges%s), real split through the LDS, lds=%zuB; per-row detrend + window + full (or half) spectrum; "
-                   "12 algorithmic bytes per sample through memory\n",
+                   "12 algorithmic bytes per sample through memory%s\n",
                 nxr / 64, nxr, plan->tune_rgrid > 0 ? std::min<long long>(plan->tune_rgrid, plan->d.batch) : (long long)plan->d.batch, nxr / 2,
                 nxr >= 32768 ? 32 : nxr == 4096 ? 8 : 16, nxr == 65536 ? 32 : nxr <= 8192 ? 8 : 16, nxr == 65536 ? " in halves" : "",
-                nxr == 65536 ? kFastRLds : nxr == 32768 ? R2Geom<32, 16>::LDS : nxr == 16384 ? R2Geom<16, 16>::LDS : nxr == 8192 ? R2Geom<16, 8>::LDS : R2Geom<8, 8>::LDS);
+                nxr == 65536 ? kFastRLds : nxr == 32768 ? R2Geom<32, 16>::LDS : nxr == 16384 ? R2Geom<16, 16>::LDS : nxr == 8192 ? R2Geom<16, 8>::LDS : R2Geom<8, 8>::LDS, in_note);
         break;
     }
     case Family::FastMX: {
@@ -1303,8 +1327,8 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
             const MGeomRt R = mgeom(plan->ynx, plan->dbl);
             appendf(rs_, "table kernel, %d thr, %d rows/unit (FFT%lld r%dx%dx%d)", R.thr_r1, plan->n_rpu, (long long)plan->ynx, R.r0, R.r1, R.r2);
         }
-        appendf(s, "  [fastn] cols: %s -> W2[slab][%d/%d][%d][%d][%d] complex -> fit -> rows: %s, trend added back in the spectral domain, fftshift + mirror rows\n",
-                cs_.c_str(), plan->y_nrow_pad, plan->n_rk, plan->n_nxb, plan->n_rk, plan->n_cw, rs_.c_str());
+        appendf(s, "  [fastn] cols: %s -> W2[slab][%d/%d][%d][%d][%d] complex -> fit -> rows: %s, trend added back in the spectral domain, fftshift + mirror rows%s\n",
+                cs_.c_str(), plan->y_nrow_pad, plan->n_rk, plan->n_nxb, plan->n_rk, plan->n_cw, rs_.c_str(), in_note);
         if (plan->n_blue_m)
             appendf(s, "  [fastn Bluestein] the %lld-point columns as a circular convolution of %d inside the tile (chirp products, two forward transforms)\n", (long long)plan->yny, plan->n_blue_m);
         if ((plan->d.flags & XRFTHIP_ISO) && plan->nbins > 0)
@@ -1315,9 +1339,9 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
     }
     case Family::FastM: {
         const MGeomRt C = mgeom_cols(plan->yny, plan->ynx, plan->dbl), R = mgeom(plan->ynx, plan->dbl);
-        appendf(s, "  [fastm] cols: %d thr, %d packed column pairs (FFT%lld r%dx%dx%d in LDS), lds=%zuB -> W2[slab][%d/%d][nx/%d][%d][%d] complex -> fit -> rows: %d thr, %d rows/unit (FFT%lld r%dx%dx%d), lds=%zuB, trend added back in the spectral domain, fftshift + mirror rows\n",
+        appendf(s, "  [fastm] cols: %d thr, %d packed column pairs (FFT%lld r%dx%dx%d in LDS), lds=%zuB -> W2[slab][%d/%d][nx/%d][%d][%d] complex -> fit -> rows: %d thr, %d rows/unit (FFT%lld r%dx%dx%d), lds=%zuB, trend added back in the spectral domain, fftshift + mirror rows%s\n",
                 C.thr, C.g, (long long)plan->yny, C.r0, C.r1, C.r2, C.lds_cols, plan->y_nrow_pad, fastm_rk2(plan->yny, plan->ynx, plan->d.out_mode >= XRFTHIP_OUT_CROSS, plan->dbl), fastm_cw(plan->yny, plan->ynx, plan->dbl), fastm_rk2(plan->yny, plan->ynx, plan->d.out_mode >= XRFTHIP_OUT_CROSS, plan->dbl), fastm_cw(plan->yny, plan->ynx, plan->dbl),
-                R.thr_r1, R.g_r1, (long long)plan->ynx, R.r0, R.r1, R.r2, R.lds_r1);
+                R.thr_r1, R.g_r1, (long long)plan->ynx, R.r0, R.r1, R.r2, R.lds_r1, in_note);
         if ((plan->d.flags & XRFTHIP_ISO) && plan->nbins > 0)
             appendf(s, "  [fastm radial sums] %s\n", fastm_iso_gather(plan) ? "fused into the row pass: radial map, per-bin gather from the spectra in LDS, no atomics"
                                                    : fastm_iso_fused(plan) ? "fused into the row pass: int64 fixed-point tables behind the transforms' LDS"
@@ -1329,9 +1353,9 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         const YGeomRt C = ycols_geom(plan->yny), R = yrows_geom(plan->ynx, fs);
         if (fs) appendf(s, "  [fasty four-step] %lld samples = [%lld][%lld]: columns = step 1 (half spectrum k1 <= %lld), rows x W_N^(i2 k1) = step 2, transposed stores + Hermitian mirror\n",
                                   (long long)plan->d.nx, (long long)plan->yny, (long long)plan->ynx, (long long)plan->yny / 2);
-        appendf(s, "  [fasty] cols: %d thr, %d x 2 packed column pairs (FFT%lld r16x16x%lld, column-local detrend fused), %d columns/unit, lds=%zuB -> W2[slab][%d/%d][nx/%d][2][%d][%d] -> rows: %d thr, %d rows/unit (FFT%lld r16x16x%lld), lds=%zuB, |F|^2 + fftshift + mirror rows\n",
+        appendf(s, "  [fasty] cols: %d thr, %d x 2 packed column pairs (FFT%lld r16x16x%lld, column-local detrend fused), %d columns/unit, lds=%zuB -> W2[slab][%d/%d][nx/%d][2][%d][%d] -> rows: %d thr, %d rows/unit (FFT%lld r16x16x%lld), lds=%zuB, |F|^2 + fftshift + mirror rows%s\n",
                 C.thr, C.gxy, (long long)plan->d.ny, (long long)plan->d.ny / 256, C.cw, C.lds, plan->y_nrow_pad, C.rk, C.cw, C.rk, 2 * C.gxy,
-                R.thr, R.rk, (long long)plan->d.nx, (long long)plan->d.nx / 256, R.lds);
+                R.thr, R.rk, (long long)plan->d.nx, (long long)plan->d.nx / 256, R.lds, in_note);
         if ((plan->d.flags & XRFTHIP_ISO) && plan->ytcodes.p)
             appendf(s, "  [fasty radial sums] fused into the row pass (runs of equal bins from the staged rows, int64 fixed-point tables), bin codes: %s\n",
                     plan->ytfirst_on ? "radial map: per-bin gather, no atomics" : plan->ytcodes_compact ? "compact (radial map: first bin + step mask per 16 samples)" : "full (4 bytes per sample)");
@@ -1356,6 +1380,7 @@ int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1,
     const bool cross = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
     const bool iso = (d.flags & XRFTHIP_ISO) != 0;
     if (cross && !d_in1) return XRFTHIP_BAD_ARG;
+    if (in_strided(P) && ((((uintptr_t)d_in0) & 15) || (cross && (((uintptr_t)d_in1) & 15)))) return XRFTHIP_BAD_ARG;  // (a strided plan's vector loads: 16-byte aligned fields)
     if (!d_out && !(d.flags & XRFTHIP_NO_SPECTRUM_OUT)) return XRFTHIP_BAD_ARG;
     if (iso && (!d_iso || !P->binmap.p)) return d_iso ? XRFTHIP_MISSING_TABLE : XRFTHIP_BAD_ARG;
     const bool inner = inner_layout(P);  // (always a workspace)

@@ -37,7 +37,7 @@ class SpectralPlan:
 
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
-                 slabs_per_group=0, inner=1, mid=1):
+                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         if dtype not in _DTYPES:
@@ -50,8 +50,10 @@ class SpectralPlan:
         self.nbins = int(nbins)
         self.inner = max(int(inner), 1)  # > 1: (batch, ny, nx, inner) arrays, the transform axes are not the trailing ones
         self.mid = max(int(mid), 1)      # > 1: (batch, ny, mid, nx, inner): independent elements between the two transform axes
+        # input strides in elements (0 = dense): the plan reads a box of a larger array where it lies (xrfthip_desc.in_stride_y / in_stride_batch)
+        self.in_stride_y, self.in_stride_batch = int(in_stride_y), int(in_stride_batch)
         d = _lib.Desc(C.sizeof(_lib.Desc), self.ndim, self.batch, self.ny, self.nx, _DTYPES[dtype], self.out_mode,
-                      int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid)
+                      int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
         for axis, w in ((0, window_y), (1, window_x)):
             if w is not None:
@@ -114,15 +116,27 @@ class SpectralPlan:
         real = self.out_mode in (_lib.OUT_POWER, _lib.OUT_PHASE) or (self.flags & _lib.C2R_X)
         return _REAL_OF[self.dtype] if real else _CPLX_OF[self.dtype]
 
+    def _layout_ok(self, t):
+        """Does the memory layout of ``t`` match the plan's: contiguous, or -- a plan with input strides -- a view (..., ny, nx) whose last stride is 1, whose row
+        stride is the plan's, whose leading dims collapse to ONE batch stride equal to the plan's, and whose first element is 16-byte aligned."""
+        if not (self.in_stride_y or self.in_stride_batch):
+            return t.is_contiguous()
+        sy, sb = strides_of(t, self.ndim)
+        if sy is None or t.data_ptr() % 16:
+            return False
+        want_y = self.in_stride_y or self.nx
+        want_b = self.in_stride_batch or self.ny * self.nx
+        return (self.ndim == 1 or self.ny == 1 or sy == want_y) and (self.batch <= 1 or sb == want_b)
+
     def execute(self, in0, in1=None, out=None, iso=None):
-        """``in0``/``in1``: contiguous tensors of shape (batch, ny, nx) (any leading shape that flattens to it).
-        Returns (out, iso); either may be None depending on the flags."""
+        """``in0``/``in1``: contiguous tensors of shape (batch, ny, nx) (any leading shape that flattens to it); a plan made with ``in_stride_y`` /
+        ``in_stride_batch`` takes the view with exactly those strides instead (see ``strides_of``).  Returns (out, iso); either may be None depending on the flags."""
         dev = in0.device
         nx_in = self.nx // 2 + 1 if (self.flags & _lib.C2R_X) else self.nx
-        if in0.dtype != self.dtype or not in0.is_contiguous() or in0.numel() != self.batch * self.ny * nx_in * self.inner * self.mid:
+        if in0.dtype != self.dtype or not self._layout_ok(in0) or in0.numel() != self.batch * self.ny * nx_in * self.inner * self.mid:
             raise ValueError("in0 does not match the plan (dtype / contiguity / size)")
         if self.out_mode in (_lib.OUT_CROSS, _lib.OUT_PHASE):
-            if in1 is None or in1.dtype != self.dtype or not in1.is_contiguous() or in1.numel() != in0.numel():
+            if in1 is None or in1.dtype != self.dtype or not self._layout_ok(in1) or in1.numel() != in0.numel():
                 raise ValueError("in1 does not match the plan")
         want_out = not (self.flags & _lib.NO_SPECTRUM_OUT)
         if want_out and out is None:
@@ -154,6 +168,31 @@ class SpectralPlan:
             _lib.check(self._dll.xrfthip_exec(self._h, _ptr(in0), _ptr(in1), _ptr(out if want_out else None), _ptr(iso),
                                               _ptr(ws), ws.numel(), stream))
         return (out if want_out else None), iso
+
+
+def strides_of(t, ndim):
+    """(row stride, batch stride) in elements of a tensor whose last ``ndim`` dims are the transform axes, as xrfthip_desc.in_stride_y / in_stride_batch describe it:
+    the last stride is 1 and the leading dims collapse to one batch stride (size-1 dims aside).  (None, None) when the view has no such description.  A batch
+    of one reports the dense batch stride; a 1-D transform the row length as its row stride."""
+    if t.dim() < ndim or t.stride(-1) != 1 and t.shape[-1] > 1:
+        return None, None
+    nx = t.shape[-1]
+    ny = t.shape[-2] if ndim == 2 else 1
+    sy = t.stride(-2) if (ndim == 2 and ny > 1) else nx
+    lead = [(n, s) for n, s in zip(t.shape[:t.dim() - ndim], t.stride()[:t.dim() - ndim]) if n > 1]
+    sb = None
+    for n, s in reversed(lead):  # innermost leading dim first: each outer stride must be (extent x stride) of the dim inside it
+        if sb is None:
+            sb, span = s, n * s
+        elif s != span:
+            return None, None
+        else:
+            span = n * s
+    if sb is None:
+        sb = ny * sy
+    if sy < nx or sb <= 0:
+        return None, None
+    return int(sy), int(sb)
 
 
 # One grow-only scratch buffer per (device, stream), shared by every plan: work on one stream is ordered, so plans never
