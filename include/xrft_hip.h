@@ -165,6 +165,22 @@ typedef struct xrfthip_desc {
      * capability apart: the status of xrfthip_plan_create does (an older library answers XRFTHIP_BAD_ARG to the larger struct_size). */
     int64_t in_stride_y;
     int64_t in_stride_batch;
+    /* The last stage of a power / cross spectrum over THREE axes (t, y, x) of a real field (xrft.power_spectrum(da, dim=["time", "y", "x"]), xrft/xrft.py:685-835; numpy's
+     * fftn over three axes, xrft.py:439-447): the columns of an XRFTHIP_AXIS_Y plan are the HALF spectrum of a real herm_ny x herm_nx grid -- what a two-axis plan with
+     * XRFTHIP_HALF_X and out_mode COMPLEX wrote, unshifted -- and the plan transforms them along t, takes |F|^2 * scale (POWER) or F0 conj(F1) * scale (CROSS, d_in1 = the
+     * second field's half spectrum) and writes the FULL result, the redundant half from the Hermitian twin (-kt, -ky, -kx): the conjugate for CROSS.
+     *   herm_ny, herm_nx   the real grid (0, 0 = off: both or neither); d_in0 / d_in1 are [batch][nt][herm_ny][herm_nx/2 + 1] complex,
+     *                      d_out is real (POWER) or complex (CROSS) [batch][nt][herm_ny][herm_nx], every element written exactly once
+     * Valid with XRFTHIP_AXIS_Y, ndim = 2, ny = nt, nx = herm_ny * (herm_nx/2 + 1), dtype C64 | C128, out_mode POWER | CROSS, no detrend.  Flags: XRFTHIP_SHIFT_Y fftshifts
+     * the result along t and XRFTHIP_ISHIFT_Y rotates the input rows along t, as on every AXIS_Y plan; XRFTHIP_SHIFT_X here means "fftshift the two Hermitian axes of the
+     * result" (the reference shifts all transform axes or none, xrft.py:446-447).  A window along t (axis 0) multiplies the source rows.
+     * XRFTHIP_BAD_ARG: one of the two fields without the other or a negative one; any other flag, in_stride_*, inner / mid, a detrend, out_mode COMPLEX | PHASE, real input, an
+     * nx that is not herm_ny * (herm_nx/2 + 1); xrfthip_plan_set_phase (the twin of a sample at a Nyquist index does not carry the conjugate phase factor) and a window on
+     * axis 1.  XRFTHIP_UNSUPPORTED_LENGTH means "the caller composes the stages": an nt with a prime factor above 13, or whose tile of 128 output bytes per row does not fit
+     * the LDS (nt above ~600).  One pass, no workspace, no sums: repeated calls return identical bits.
+     * Descriptors with the struct_size of the four earlier versions are accepted (0, 0).  As with the strides, the status of xrfthip_plan_create tells the capability. */
+    int64_t herm_ny;
+    int64_t herm_nx;
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;
@@ -216,7 +232,8 @@ typedef enum xrfthip_kernel_kind {
     XRFTHIP_K_FASTG = 8,      /* one pass over a small slab, lengths as data */
     XRFTHIP_K_FASTS = 9,      /* one pass over a small float32 slab in registers */
     XRFTHIP_K_FASTR = 10,     /* one pass over a long float32 row in registers */
-    XRFTHIP_K_COMPOSITE = 11  /* xrfthip_desc.inner / .mid: two one-axis plans */
+    XRFTHIP_K_COMPOSITE = 11, /* xrfthip_desc.inner / .mid: two one-axis plans */
+    XRFTHIP_K_FASTH = 12      /* xrfthip_desc.herm_ny / herm_nx: the last pass of a three-axis spectrum, half spectrum in, full result out */
 } xrfthip_kernel_kind;
 int xrfthip_plan_kernel_info(const xrfthip_plan* plan, int32_t* kind, int32_t* per_workgroup);
 

@@ -933,6 +933,115 @@ def _fft_nd(da, dims, spacing_tol, real_dim, shift, detrend_, window, true_phase
     return cur
 
 
+def _nd_scale(da, dims, window, scaling, window_correction, spacings):
+    """What multiplies |F|^2 (or F1 conj F2) of a spectrum over the dims ``dims`` beyond the (prod dx)^2 of the transforms: / window factor, x prod(dk)^(1|2)
+    (xrft.py:745-748); ``spacings``: the frequency spacings in the order of ``dims``."""
+    scale = 1.0
+    if scaling != "false_density":
+        if window_correction:
+            if window is None:
+                raise ValueError("window_correction can only be applied when windowing is turned on.")
+            vecs = [_window_vector(window, da.sizes[d]) for d in dims]
+            if scaling == "density":
+                scale /= float(np.prod([(v ** 2).mean() for v in vecs]))
+            elif scaling == "spectrum":
+                scale /= float(np.prod([v.mean() for v in vecs])) ** 2
+            else:
+                raise ValueError("Unknown {} scaling flag".format(scaling))
+        fs = float(math.prod(spacings))
+        if scaling == "density":
+            scale *= fs
+        elif scaling == "spectrum":
+            scale *= fs ** 2
+        else:
+            raise ValueError("Unknown {} scaling flag".format(scaling))
+    return scale
+
+
+# power_spectrum / cross_spectrum over the trailing THREE axes of real data take the fused route (_spectrum_3d_fused); False: the composition of _fft_nd stages
+# and the elementwise tail, as before round 9 -- the tests and scripts/bench_three_axes.py compare the two on one build
+_FUSE_THREE_AXES = True
+
+
+def _spectrum_3d_fused(da, da2, dims, scaling, window_correction, true_phase, kw):
+    """Frequency-wavenumber spectra -- ``power_spectrum(da, dim=["time", "y", "x"])``, ``cross_spectrum`` of two such fields -- of real float32 / float64 data whose
+    three transform dims are the trailing three axes (any order in ``dim``): detrend as before, the two-axis plan over the last two axes in memory with the HALF
+    spectrum as its complex output (XRFTHIP_HALF_X: 4 bytes per point written instead of 8), then ONE plan (xrfthip_desc.herm_ny / herm_nx, csrc/fasth.h) that
+    transforms along the first of the three, takes |F|^2 or F1 conj(F2) and writes the full shifted result, the redundant half from the Hermitian twin.  The
+    composition moved ~48 bytes per point behind the first stage's intermediate and held two full complex arrays; this moves ~12 and holds the half spectrum.
+    Returns None where the route does not apply (the caller composes as before): a descending coordinate (FLIP), two fields that differ in dtype, dims, spacing or lag
+    (a true-phase factor: the twin of a Nyquist sample does not carry its conjugate), a length either stage does not take."""
+    if len(dims) != 3 or len(da.dims) < 3 or set(dims) != set(da.dims[-3:]) or kw["chunks_to_segments"] or kw["detrend"] not in (None, "constant", "linear"):
+        return None
+    if da2 is not None and (tuple(da2.dims) != tuple(da.dims) or tuple(da2.shape) != tuple(da.shape)):
+        return None
+    pt, py, px = da.dims[-3:]
+    nt, ny, nx = (da.sizes[d] for d in (pt, py, px))
+    nxh = nx // 2 + 1
+    if min(nt, ny, nx) < 2 or ny * nx > (1 << 31) - 1 or nt * ny * nxh > (1 << 31) - 1 or ny * nxh > (1 << 30):
+        return None
+    def real_dtype(data):  # float32 / float64 as it lies (anything else -- integers, float16, complex -- keeps the composition and its conversions)
+        dt = data.dtype if isinstance(data, torch.Tensor) else {"float32": torch.float32, "float64": torch.float64}.get(np.asarray(data).dtype.name)
+        return dt if dt in (torch.float32, torch.float64) else None
+
+    if real_dtype(da.data) is None or (da2 is not None and real_dtype(da2.data) != real_dtype(da.data)):
+        return None
+    order = [dims[-2], dims[-1], dims[0]]  # the stages of the composition: their labels, in their order
+
+    def analyze(a):
+        ca = _analyze(a, kw["spacing_tol"], dims[-2:], None, kw["shift"], None, kw["window"], true_phase, False, kw["prefix"], None)
+        cb = _analyze(a, kw["spacing_tol"], [dims[0]], None, kw["shift"], None, kw["window"], true_phase, False, kw["prefix"], None)
+        info = {}
+        for c in (ca, cb):
+            for i, d in enumerate(c.dim):
+                info[d] = dict(dx=c.delta_x[i], lag=c.lag_x[i], rev=c.reversed[i], win=None if c.windows is None else c.windows[i],
+                               name=c.swap[d], coord=c.new_coords[c.swap[d]])
+        return info
+
+    info = analyze(da)
+    if any(v["rev"] for v in info.values()) or any("spacing" not in v["coord"].attrs for v in info.values()):
+        return None
+    amp = math.prod([info[d]["dx"] for d in order]) ** 2
+    if da2 is not None:
+        info2 = analyze(da2)
+        if any(v["rev"] for v in info2.values()) or any(info[d]["dx"] != info2[d]["dx"] or info[d]["lag"] != info2[d]["lag"] for d in dims):
+            return None
+    scale = amp * _nd_scale(da, dims, kw["window"], scaling, window_correction, [float(info[d]["coord"].attrs["spacing"]) for d in dims])
+    cur, cur2 = da, da2
+    if kw["detrend"] is not None:
+        cur = from_any(detrend(da, dims, kw["detrend"]))
+        cur2 = None if da2 is None else from_any(detrend(da2, dims, kw["detrend"]))
+    t = _to_device(cur.data).contiguous()
+    t2 = None if cur2 is None else _to_device(cur2.data).contiguous()
+    batch = t.numel() // (nt * ny * nx)
+    ish = (_lib.ISHIFT_Y | _lib.ISHIFT_X) if true_phase else 0  # (the reference ifftshifts the windowed input, xrft.py:436-441; the lags' phase factors cancel in the product)
+    kw1 = dict(ndim=2, batch=batch * nt, ny=ny, nx=nx, dtype=t.dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=_lib.HALF_X | ish, scale=1.0,
+               window_y=info[py]["win"], window_x=info[px]["win"], phase_y=None, phase_x=None)
+    kw2 = dict(ndim=2, batch=batch, ny=nt, nx=ny * nxh, dtype=engine._CPLX_OF[t.dtype], out_mode=_lib.OUT_POWER if da2 is None else _lib.OUT_CROSS,
+               detrend=_lib.DETREND_NONE, flags=_lib.AXIS_Y | ((_lib.SHIFT_Y | _lib.SHIFT_X) if kw["shift"] else 0) | (_lib.ISHIFT_Y if true_phase else 0),
+               scale=float(scale), window_y=info[pt]["win"], window_x=None, phase_y=None, phase_x=None, herm_ny=ny, herm_nx=nx)
+    try:
+        plan1 = _get_plan(**kw1)
+        plan2 = _get_plan(**kw2)  # (the newest plan of the call: describe() shows [fasth])
+    except _lib.XrftHipError as e:
+        if e.status != _lib.UNSUPPORTED_LENGTH:
+            raise
+        return None
+    h, _ = plan1.execute(t)
+    h2 = None if t2 is None else plan1.execute(t2)[0]
+    out, _ = plan2.execute(h.reshape(batch, nt, ny * nxh), None if h2 is None else h2.reshape(batch, nt, ny * nxh))
+    del h, h2
+    final = [info[d]["name"] if d in info else d for d in da.dims]
+    coords = {k: v._clone(k) for k, v in da.coords.items() if k not in dims}
+    for d in order:
+        cv = info[d]["coord"]
+        attrs = dict(cv.attrs)
+        if true_phase:
+            attrs["direct_lag"] = info[d]["lag"]  # xrft.py:469
+        coords[info[d]["name"]] = Coordinate(cv.dims, cv.values, attrs, info[d]["name"])
+    return DataArray(out.reshape(tuple(da.shape)), final, coords, None, None)
+
+
 def _spectrum_nd(da, da2, dims, real_dim, scaling, window_correction, true_phase, kwargs, one_at_a_time=False):
     """power_spectrum / cross_spectrum over more than two axes: N-D transform(s), then the elementwise tail."""
     if "density" in kwargs:
@@ -946,6 +1055,10 @@ def _spectrum_nd(da, da2, dims, real_dim, scaling, window_correction, true_phase
     if unknown:
         raise TypeError(f"fft() got an unexpected keyword argument {sorted(unknown)[0]!r}")
     kw.update({k: v for k, v in kwargs.items() if k != "real"})
+    if _FUSE_THREE_AXES and real_dim is None and not one_at_a_time:
+        fused = _spectrum_3d_fused(da, da2, dims, scaling, window_correction, true_phase, kw)
+        if fused is not None:
+            return fused
     f1 = _fft_nd(da, dims, kw["spacing_tol"], real_dim, kw["shift"], kw["detrend"], kw["window"], true_phase, True,
                  kw["chunks_to_segments"], kw["prefix"], one_at_a_time)
     f2 = None
@@ -956,25 +1069,7 @@ def _spectrum_nd(da, da2, dims, real_dim, scaling, window_correction, true_phase
             raise ValueError("The two datasets have different dimensions")
     pf = kw["prefix"]
     new = [pf + d if d[: len(pf)] != pf else d[len(pf):] for d in dims]  # xrft.py:186
-    scale = 1.0
-    if scaling != "false_density":
-        if window_correction:
-            if kw["window"] is None:
-                raise ValueError("window_correction can only be applied when windowing is turned on.")
-            vecs = [_window_vector(kw["window"], da.sizes[d]) for d in dims]
-            if scaling == "density":
-                scale /= float(np.prod([(v ** 2).mean() for v in vecs]))
-            elif scaling == "spectrum":
-                scale /= float(np.prod([v.mean() for v in vecs])) ** 2
-            else:
-                raise ValueError("Unknown {} scaling flag".format(scaling))
-        fs = float(math.prod([float(f1[n].attrs["spacing"]) for n in new]))
-        if scaling == "density":
-            scale *= fs
-        elif scaling == "spectrum":
-            scale *= fs ** 2
-        else:
-            raise ValueError("Unknown {} scaling flag".format(scaling))
+    scale = _nd_scale(da, dims, kw["window"], scaling, window_correction, [float(f1[n].attrs["spacing"]) for n in new])
     a = _to_device(f1.data).contiguous()
     b = None
     if f2 is not None:

@@ -374,6 +374,60 @@ int run_fastgy(const xrfthip_plan* P, const void* in, const void* in_b, void* ou
     return XRFTHIP_OK;
 }
 
+// The herm form of FastGY (gy_herm): the last pass of a three-axis power / cross spectrum (xrfthip_desc.herm_ny / herm_nx; fasth.h).  G columns of the half spectrum per workgroup = 128 bytes of
+// an output row (32 float32 powers, 16 float64 powers or complex64 products, 8 complex128 products): in every precision and mode the tile is 256 nt bytes, so any
+// smooth nt up to ~600 fits.  A descriptor with these fields is served here or not at all: the caller composes the stages (XRFTHIP_UNSUPPORTED_LENGTH).
+int try_fasth(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    if (!herm_plan(P)) return kDeclined;
+    if (env_ll("XRFTHIP_FASTG", 1) == 0 || d.ny < 2 || d.ny > 65535) return XRFTHIP_UNSUPPORTED_LENGTH;
+    std::vector<int> rt;
+    if (!fastg_factor(d.ny, rt) || (int)rt.size() > kFastGMaxPasses) return XRFTHIP_UNSUPPORTED_LENGTH;  // (Bluestein / Rader along t: not carried over)
+    for (int r : rt) if (r > 16) return XRFTHIP_UNSUPPORTED_LENGTH;
+    const bool cross = d.out_mode == XRFTHIP_OUT_CROSS;
+    const int G = (int)(128 / (cross ? P->csize : P->rsize));
+    const long long pts = (long long)G * (cross ? 2 : 1) * d.ny;  // threads by the points of the tile, as fastgy_try
+    const int thr = pts <= 1024 ? 64 : pts <= 2048 ? 128 : 256;
+    const size_t lds = (((size_t)d.ny * G * (cross ? 2 : 1) * P->csize + 15) & ~(size_t)15) + (size_t)d.ny * (P->csize + P->rsize + 2) + 16;
+    if (lds > kLdsMax - 1024) return XRFTHIP_UNSUPPORTED_LENGTH;
+    if ((d.nx + G - 1) / G > 0x7fffffffLL / std::max<long long>(d.batch, 1)) return XRFTHIP_UNSUPPORTED_LENGTH;  // (units of a launch)
+    P->family = P->chosen = Family::FastGY; P->gy_herm = true;
+    P->g_ry = rt; P->h_G = G; P->h_thr = thr; P->h_lds = lds;
+    int rc = plan_twiddle(P, P->g_twy, d.ny, d.ny);
+    if (!rc) rc = fastg_rev(rt, (int)d.ny, P->g_revy, P->g_hrevy);
+    return rc;
+}
+
+int run_fasth(const xrfthip_plan* P, const void* in, const void* in_b, void* out, hipStream_t st) {
+    const xrfthip_desc& d = P->d;
+    const bool cross = d.out_mode == XRFTHIP_OUT_CROSS;
+    FastH p{};
+    p.in = in; p.in_b = in_b; p.out = out;
+    p.nt = (int)d.ny; p.ny = (int)d.herm_ny; p.nx = (int)d.herm_nx; p.nxh = (int)(d.herm_nx / 2 + 1); p.ncol = (int)d.nx;
+    p.G = P->h_G; p.lg = ilog2i(P->h_G);
+    p.lch = p.lg - ilog2i((int)(16 / (cross ? P->csize : P->rsize)));
+    p.nblk = (p.ncol + p.G - 1) / p.G;
+    p.nunits = d.batch * p.nblk;
+    p.nrt = (int)P->g_ry.size();
+    for (int i = 0; i < p.nrt; ++i) p.rt[i] = P->g_ry[(size_t)i];
+    p.tw_t = P->g_twy.p; p.rev_t = (const unsigned*)P->g_revy.p;
+    p.win_t = P->win[0].p;
+    p.ishift_in = (d.flags & XRFTHIP_ISHIFT_Y) ? (int)(d.ny / 2) : 0;
+    p.shift_t = (d.flags & XRFTHIP_SHIFT_Y) ? (int)(d.ny / 2) : 0;
+    p.shift_y = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.herm_ny / 2) : 0;  // (SHIFT_X of a herm plan: the two Hermitian axes)
+    p.shift_x = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.herm_nx / 2) : 0;
+    p.scale = d.scale;
+    const dim3 grid((unsigned)std::min<long long>(p.nunits, 0x7fffffffLL)), blk((unsigned)P->h_thr);
+    xrfthip_plan::ProfRec* rec = prof_begin(P, "fasth_last", st);
+#define GH_(TT) do { if (cross) { auto k = &fasth_kernel<TT, true>; XRFT_LAUNCH(k, grid, blk, P->h_lds, st, p); } \
+                     else { auto k = &fasth_kernel<TT, false>; XRFT_LAUNCH(k, grid, blk, P->h_lds, st, p); } } while (0)
+    if (P->dbl) GH_(double); else GH_(float);
+#undef GH_
+    prof_end(rec, st);
+    HIP_TRY(hipGetLastError());
+    return XRFTHIP_OK;
+}
+
 // threads per slab.  The passes are chains of LDS round trips, so it is the number of waves in flight on a CU that sets the rate, and that is
 // bounded twice: by the registers (float32: 105 -> 4 waves per SIMD, 16 per CU; float64: 153 -> 3 and 12) and by how many slabs' LDS a CU holds.
 // Take the workgroup of 1, 2, 4, 8 or 16 waves (whole waves per SIMD, or the second workgroup does not fit beside the first) that keeps most
@@ -494,5 +548,6 @@ void set_attrs_fastg() {
     SETF((fastgy_kernel<float, 0, 1>)); SETF((fastgy_kernel<float, 1, 1>)); SETF((fastgy_kernel<double, 0, 1>)); SETF((fastgy_kernel<double, 1, 1>));
     SETF((fastgy_kernel<float, 0, 2>)); SETF((fastgy_kernel<float, 1, 2>)); SETF((fastgy_kernel<double, 0, 2>)); SETF((fastgy_kernel<double, 1, 2>));
     SETF((fastgy_kernel<float, 0, 3>)); SETF((fastgy_kernel<float, 1, 3>)); SETF((fastgy_kernel<double, 0, 3>)); SETF((fastgy_kernel<double, 1, 3>));
+    SETF((fasth_kernel<float, false>)); SETF((fasth_kernel<float, true>)); SETF((fasth_kernel<double, false>)); SETF((fasth_kernel<double, true>));
 #undef SETF
 }

@@ -8,8 +8,9 @@
 //                    (FastY, FastY1D, FastYC, FastYCFourStep)
 //   host_fastm.cpp   the mixed-radix pipeline on the lat/lon lengths (fastm.h), its run-time-radix form (fastn.h), the one-axis table kernels
 //                    (FastM, FastN, FastMY, FastMX)
-//   host_fastg.cpp   the one-pass lengths-as-data kernels (fastg.h): small slabs, one axis of any smooth length, Rader / Bluestein tables
-//                    (FastG, FastGY)
+//   host_fastg.cpp   the one-pass lengths-as-data kernels (fastg.h): small slabs, one axis of any smooth length, Rader / Bluestein tables;
+//                    the last pass of a three-axis spectrum (fasth.h)
+//                    (FastG, FastGY; the herm form of FastGY)
 //   host_rows.cpp    the register-resident one-pass kernels: small float32 slabs (fasts.h), long rows and complex rows (fastr.h)
 //                    (FastS, FastR, FastRComplex, FastRRows)
 //   host_inner.cpp   two transform axes that are not the trailing pair (xrfthip_desc.inner / .mid): the fused passes and the composite plan
@@ -54,6 +55,7 @@
 #include "fasts.h"
 #include "tile_fft.h"
 #include "fastg.h"
+#include "fasth.h"
 #ifdef XRFT_SPLIT_TUS  /* the library built from several translation units: the fasty / fastm kernels are instantiated in inst_g*.cpp */
 namespace xrft {
 #define XRFT_KW extern template __global__
@@ -325,7 +327,8 @@ enum class Family {
     FusedInner,      // ... or the two fused passes where the axes lie (fastn.h)
     FastS,           // one pass over a small float32 slab in registers (fasts.h)
     FastG,           // one pass over a small slab, or groups of rows (g_one_d), lengths as data (fastg.h)
-    FastGY,          // one pass along one axis that is not the contiguous one, or along rows with one Rader prime (gy_rows) (fastg.h)
+    FastGY,          // one pass along one axis that is not the contiguous one, or along rows with one Rader prime (gy_rows) (fastg.h); gy_herm: its Hermitian form --
+                     // xrfthip_desc.herm_ny / herm_nx, the last pass of a three-axis spectrum: half spectrum in, full power / cross result out (fasth.h)
     FastMX,          // short rows, table lengths (fastm.h, fastm_xonly_kernel)
     FastMY,          // one axis that is not the contiguous one, table lengths (fastm.h, fastm_yonly_kernel)
     FastR,           // one pass over a long real float32 row in registers (fastr.h)
@@ -406,6 +409,10 @@ struct xrfthip_plan {
     size_t gy_lds = 0;
     DevBuf gy_bluec, gy_blueb;
     size_t g_lds = 0;
+    // FastGY, gy_herm: the last pass of a three-axis power / cross spectrum (fasth.h, its own launcher run_fasth): h_G columns of the half spectrum per workgroup; radices, twiddles and digit reversal of nt in g_ry / g_twy / g_revy
+    bool gy_herm = false;
+    int h_G = 0, h_thr = 0;
+    size_t h_lds = 0;
     // FastS: ONE pass for a small real float32 slab that fits the registers of a CU: 256 x 256 power spectra (fasts.h)
     DevBuf tw_sy, tw_sx, s_tfirst;
     long long tune_sstagger = 0;  // XRFTHIP_FASTS_STAGGER: classes << 8 | steps of 3.4 us between the classes of a resident set of slab workgroups
@@ -518,6 +525,7 @@ int rader_maps(int n, int p, const std::vector<int>& rq_, const std::vector<int>
 int run_detrend_inner(int32_t dtype, int32_t ndim, long long batch, long long ny, long long nx, long long inner, int32_t kind, const void* in, void* out, char* ws, hipStream_t st, long long mid = 1);
 int run_fastg(const xrfthip_plan* P, const void* in, const void* in_b, void* out, double* iso, hipStream_t st);
 int run_fastgy(const xrfthip_plan* P, const void* in, const void* in_b, void* out, hipStream_t st);
+int run_fasth(const xrfthip_plan* P, const void* in, const void* in_b, void* out, hipStream_t st);
 int run_fastm(const xrfthip_plan* P, const void* in, const void* in1, void* out, double* iso, char* ws, hipStream_t st);
 int run_fastmx(const xrfthip_plan* P, const void* in, const void* in1, void* out, hipStream_t st);
 int run_fastmy(const xrfthip_plan* P, const void* in, const void* in1, void* out, hipStream_t st);
@@ -550,6 +558,7 @@ bool fasty_fits(const xrfthip_plan* P);
 int fasty_tables(xrfthip_plan* P);
 
 // the families' try_* (xrfthip_plan_create calls them in this order; the first that does not return kDeclined decides)
+int try_fasth(xrfthip_plan* P);
 int try_fasts(xrfthip_plan* P);
 int try_fastyc(xrfthip_plan* P);
 int try_fastr(xrfthip_plan* P);
@@ -568,6 +577,7 @@ inline bool fasty_len(long long n) { return n == 256 || n == 512 || n == 1024 ||
 inline bool fastm_pipeline(const xrfthip_plan* P) { return P->family == Family::FastM || P->family == Family::FastN; }  // fastm.h / fastn.h two passes
 inline bool two_pass_y(const xrfthip_plan* P) { return fastm_pipeline(P) || P->family == Family::FastY || P->family == Family::FastY1D; }  // columns -> [fit] -> rows
 inline bool inner_layout(const xrfthip_plan* P) { return P->family == Family::FusedInner || P->family == Family::Composite; }  // (no tile passes of their own)
+inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (xrfthip_desc.herm_ny / herm_nx: the herm form of FastGY or no plan -- no generic passes either)
 inline bool dbl_phase_tables(const xrfthip_plan* P) {  // the families that read float64 phase / window-spectrum tables in a float64 plan
     const Family f = P->family;
     return P->dbl && (f == Family::FastM || f == Family::FastN || f == Family::FastMY || f == Family::FastMX || f == Family::FastG || f == Family::FastGY || f == Family::FusedInner);

@@ -714,7 +714,8 @@ int finalize_plan(xrfthip_plan* P) {
             if (cross_iso_phase(P)) { settle_family(P, true); break; }
             [[fallthrough]];
         case Family::FastGY: case Family::FastS: case Family::FastR: case Family::FastRComplex: case Family::FastRRows: case Family::FastYC: case Family::FastMX: case Family::FastMY:
-            if (phase) rc = fast_phase_tables(P);
+            if (phase && !P->gy_herm)  // (the herm form: no phase table, no other family to hand the plan to)
+                rc = fast_phase_tables(P);
             break;
         case Family::FastYCFourStep: {
             if (phase) rc = fast_phase_tables(P);
@@ -856,8 +857,11 @@ int xrfthip_last_hip_error(void) { return g_last_hip_error; }
 int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // (a descriptor of the version before `inner` was appended is accepted: inner = 1)
     // (... and of the versions before `mid` and before the input strides: mid = 1, strides 0)
-    constexpr uint32_t kOldDescSize = (uint32_t)offsetof(xrfthip_desc, inner), kOldDescSize2 = (uint32_t)offsetof(xrfthip_desc, mid), kOldDescSize3 = (uint32_t)offsetof(xrfthip_desc, in_stride_y);
-    if (!plan || !desc || (desc->struct_size != sizeof(xrfthip_desc) && desc->struct_size != kOldDescSize && desc->struct_size != kOldDescSize2 && desc->struct_size != kOldDescSize3)) return XRFTHIP_BAD_ARG;
+    // (... and of the version before herm_ny / herm_nx: 0, 0)
+    constexpr uint32_t kOldDescSize = (uint32_t)offsetof(xrfthip_desc, inner), kOldDescSize2 = (uint32_t)offsetof(xrfthip_desc, mid), kOldDescSize3 = (uint32_t)offsetof(xrfthip_desc, in_stride_y),
+                       kOldDescSize4 = (uint32_t)offsetof(xrfthip_desc, herm_ny);
+    if (!plan || !desc || (desc->struct_size != sizeof(xrfthip_desc) && desc->struct_size != kOldDescSize && desc->struct_size != kOldDescSize2 && desc->struct_size != kOldDescSize3 &&
+                           desc->struct_size != kOldDescSize4)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);
     dcopy.struct_size = sizeof(xrfthip_desc);
@@ -891,7 +895,15 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (d.ndim == 1 && (d.flags & (XRFTHIP_SHIFT_Y | XRFTHIP_ISHIFT_Y | XRFTHIP_FLIP_Y))) return XRFTHIP_BAD_ARG;
     if ((d.flags & (XRFTHIP_FLIP0_Y | XRFTHIP_FLIP0_X)) && d.out_mode != XRFTHIP_OUT_CROSS && d.out_mode != XRFTHIP_OUT_PHASE) return XRFTHIP_BAD_ARG;
     if ((d.flags & XRFTHIP_FLIP0_Y) && d.ndim == 1) return XRFTHIP_BAD_ARG;
-    if ((d.flags & XRFTHIP_AXIS_Y) && (d.ndim != 2 || (d.flags & XRFTHIP_FLIP0_X) || (d.flags & (XRFTHIP_SHIFT_X | XRFTHIP_ISHIFT_X | XRFTHIP_FLIP_X |
+    // herm_ny / herm_nx: the columns of an AXIS_Y plan are the half spectrum of a real herm_ny x herm_nx grid (the last pass of a three-axis spectrum, fasth.h)
+    const bool herm = d.herm_ny != 0 || d.herm_nx != 0;
+    if (herm) {
+        if (d.herm_ny < 1 || d.herm_nx < 1 || d.herm_nx > (1LL << 30) || d.herm_ny > (1LL << 30)) return XRFTHIP_BAD_ARG;
+        if (!(d.flags & XRFTHIP_AXIS_Y) || (d.flags & ~(XRFTHIP_AXIS_Y | XRFTHIP_SHIFT_Y | XRFTHIP_ISHIFT_Y | XRFTHIP_SHIFT_X))) return XRFTHIP_BAD_ARG;
+        if (d.ndim != 2 || !cplx_in || (d.out_mode != XRFTHIP_OUT_POWER && d.out_mode != XRFTHIP_OUT_CROSS) || d.detrend) return XRFTHIP_BAD_ARG;
+        if (d.nx != d.herm_ny * (d.herm_nx / 2 + 1) || d.inner > 1 || d.mid > 1 || d.in_stride_y || d.in_stride_batch) return XRFTHIP_BAD_ARG;
+    }
+    if ((d.flags & XRFTHIP_AXIS_Y) && (d.ndim != 2 || (d.flags & XRFTHIP_FLIP0_X) || (d.flags & ((herm ? 0u : XRFTHIP_SHIFT_X) | XRFTHIP_ISHIFT_X | XRFTHIP_FLIP_X |
                                                                     XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT | XRFTHIP_C2R_X)))) return XRFTHIP_BAD_ARG;  // (PHASE_IN: only where fastgy takes the plan, below)
     // AXIS_Y with HALF_X / REALDIM_X2 (ABI 0.1.4): real_dim along the ONE transformed axis -- ny / 2 + 1 rows per slab, unshifted; the one-pass kernels only (below)
     if ((d.flags & XRFTHIP_AXIS_Y) && (d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2)) &&
@@ -924,6 +936,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     P->csize = 2 * P->rsize;
     P->nxh = cplx_in ? d.nx : d.nx / 2 + 1;
     P->nx_out = ((d.flags & XRFTHIP_HALF_X) && !(d.flags & XRFTHIP_AXIS_Y)) ? d.nx / 2 + 1 : d.nx;  // (AXIS_Y: the half is along y)
+    if (herm) P->nx_out = d.herm_ny * d.herm_nx;  // (the full grid behind every row along t)
     // width of the intermediate: the half spectrum for real input, unless the row does not fit one LDS tile
     // (four-step along x computes every kx) -- decided inside build_x through P->width.
     P->width = P->nxh;
@@ -935,12 +948,13 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     }
     P->mirror = !cplx_in && !(d.flags & (XRFTHIP_HALF_X | XRFTHIP_AXIS_Y)) && P->width == d.nx / 2 + 1 && d.nx > 1;
     // the families in order of precedence: the first whose try_* does not decline serves the plan (its tables built); none: the generic passes
-    static int (*const kTry[])(xrfthip_plan*) = {try_fasts, try_fastyc, try_fastr, try_fasty, try_fast1d, try_fastm, try_fastmx, try_fastmy, try_fastgy, try_fastg, try_fastn};
+    static int (*const kTry[])(xrfthip_plan*) = {try_fasth, try_fasts, try_fastyc, try_fastr, try_fasty, try_fast1d, try_fastm, try_fastmx, try_fastmy, try_fastgy, try_fastg, try_fastn};
     int rc = kDeclined;
     if (!env_ll("XRFTHIP_NO_FAST", 0))
         for (auto try_family : kTry)
             if ((rc = try_family(P)) != kDeclined) break;
     if (rc == kDeclined) rc = XRFTHIP_OK;
+    if (!rc && herm && !P->gy_herm) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family reads a half spectrum as columns: the caller composes the stages)
     const bool one_axis = P->family == Family::FastGY || P->family == Family::FastMY;
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_PHASE_IN) && !one_axis) rc = XRFTHIP_BAD_ARG;  // (the generic column tiles have no input phase)
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_HALF_X) && !one_axis) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (... and no half output: the caller transposes)
@@ -948,7 +962,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
         set_kernel_attrs_once();
         // nbins must be known before tiles are sized (the LDS histogram shares the tile's allocation): ISO plans are
         // (re)built in xrfthip_plan_set_binmap.  Build now for everything else.
-        if (!(d.flags & XRFTHIP_ISO)) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
+        if (!(d.flags & XRFTHIP_ISO) && !herm) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
     }
     if (!rc) rc = finalize_plan(P);
     if (rc) { delete P; return rc; }
@@ -963,6 +977,7 @@ int xrfthip_plan_destroy(xrfthip_plan* plan) {
 
 int xrfthip_plan_set_window(xrfthip_plan* plan, int axis, const double* h_window, int64_t n) {
     if (!plan || axis < 0 || axis > 1) return XRFTHIP_BAD_ARG;
+    if (herm_plan(plan) && axis == 1) return XRFTHIP_BAD_ARG;  // (the two-axis stage that wrote the half spectrum windowed y and x)
     if (h_window && n != (axis == 0 ? plan->d.ny : plan->d.nx)) return XRFTHIP_BAD_ARG;
     if (plan->sub_x) return xrfthip_plan_set_window(axis == 0 ? plan->sub_y : plan->sub_x, (axis == 1 && plan->sub_x_1d) ? 1 : 0, h_window, n);  // (each one-axis plan transforms its "y"; a 1-D x stage its x)
     if (axis == 0) plan->host_win_y.assign(h_window ? h_window : nullptr, h_window ? h_window + n : nullptr);
@@ -973,7 +988,7 @@ int xrfthip_plan_set_window(xrfthip_plan* plan, int axis, const double* h_window
 }
 
 int xrfthip_plan_set_phase(xrfthip_plan* plan, int axis, const double* h_phase, int64_t n) {
-    if (!plan || axis < 0 || axis > 1) return XRFTHIP_BAD_ARG;
+    if (!plan || axis < 0 || axis > 1 || herm_plan(plan)) return XRFTHIP_BAD_ARG;  // (herm: the twin of a sample at a Nyquist index does not carry the conjugate factor)
     // an input phase of a c2r transform covers the stored half of the x axis only
     const int64_t want = axis == 0 ? plan->d.ny : ((plan->d.flags & XRFTHIP_C2R_X) ? plan->d.nx / 2 + 1 : plan->d.nx);
     if (h_phase && n != want) return XRFTHIP_BAD_ARG;
@@ -1125,7 +1140,8 @@ int xrfthip_plan_kernel_info(const xrfthip_plan* plan, int32_t* kind, int32_t* p
         case Family::FastYC: case Family::FastYCFourStep: case Family::FastY: case Family::FastY1D: k = XRFTHIP_K_FASTY; break;
         case Family::FastR: case Family::FastRComplex: case Family::FastRRows: k = XRFTHIP_K_FASTR; n = 1; break;
         case Family::FastMX: { k = XRFTHIP_K_FASTM_X; const MGeomRt C = mxgeom(P->d.nx, P->dbl); n = (two || (P->cplx_in && !(P->d.flags & XRFTHIP_C2R_X))) ? C.g : 2 * C.g; break; }
-        case Family::FastGY: k = P->gy_rows ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG_Y; n = ((P->cplx_in || two) ? 1 : 2) * P->gy_G; break;
+        case Family::FastGY: if (P->gy_herm) { k = XRFTHIP_K_FASTH; n = P->h_G; break; }
+            k = P->gy_rows ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG_Y; n = ((P->cplx_in || two) ? 1 : 2) * P->gy_G; break;
         case Family::FastMY: { k = XRFTHIP_K_FASTM_Y; const MGeomRt C = mygeom(P->d.ny, P->dbl); n = ((P->cplx_in || two) ? 1 : 2) * C.g; break; }
         case Family::FastM: k = XRFTHIP_K_FASTM; n = plan_cw(P); break;
         case Family::FastN: k = XRFTHIP_K_FASTN; n = plan_cw(P); break;
@@ -1272,6 +1288,18 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         break;
     }
     case Family::FastGY: {
+        if (plan->gy_herm) {  // (the Hermitian form: the last pass of a three-axis spectrum, fasth.h)
+            std::string rts;
+            for (int r : plan->g_ry) rts += (rts.empty() ? "" : "x") + std::to_string(r);
+            const bool cross = plan->d.out_mode == XRFTHIP_OUT_CROSS;
+            appendf(s, "  [fasth] the last pass of a three-axis %s spectrum: %d thr, %d columns of the half spectrum [%lld][%lld][%lld + 1] per workgroup%s, the radices from the plan "
+                       "(t: %lld = %s in LDS), lds=%zuB: window + transform along t + %s, ",
+                    cross ? "cross" : "power", plan->h_thr, plan->h_G, (long long)d.ny, (long long)d.herm_ny, (long long)d.herm_nx / 2, cross ? " of each of the two fields" : "",
+                    (long long)d.ny, rts.c_str(), plan->h_lds, cross ? "F0 conj(F1)" : "|F|^2");
+            appendf(s, "every sample and its Hermitian twin stored as 16-byte pieces of 128-byte runs of the full [%lld][%lld][%lld] result, non-temporal\n",
+                    (long long)d.ny, (long long)d.herm_ny, (long long)d.herm_nx);
+            break;
+        }
         std::string rys;
         for (int r : plan->g_ry) rys += (rys.empty() ? "" : "x") + std::to_string(r);
         const bool onecol = plan->cplx_in || plan->d.out_mode == XRFTHIP_OUT_CROSS || plan->d.out_mode == XRFTHIP_OUT_PHASE;
@@ -1384,7 +1412,7 @@ int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1,
     if (!d_out && !(d.flags & XRFTHIP_NO_SPECTRUM_OUT)) return XRFTHIP_BAD_ARG;
     if (iso && (!d_iso || !P->binmap.p)) return d_iso ? XRFTHIP_MISSING_TABLE : XRFTHIP_BAD_ARG;
     const bool inner = inner_layout(P);  // (always a workspace)
-    if (!inner && P->passes.empty()) return XRFTHIP_MISSING_TABLE;
+    if (!inner && !herm_plan(P) && P->passes.empty()) return XRFTHIP_MISSING_TABLE;
     if (ws_bytes < P->ws_bytes || (!d_workspace && (inner || P->ws_bytes))) return XRFTHIP_WORKSPACE_TOO_SMALL;
     if (d.batch == 0) return XRFTHIP_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -1402,7 +1430,7 @@ int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1,
         case Family::FastYC: case Family::FastYCFourStep: return run_fastyc(P, d_in0, out, ws, st);
         case Family::FastR: case Family::FastRComplex: case Family::FastRRows: return run_fastr(P, d_in0, out, st);
         case Family::FastMX: return run_fastmx(P, d_in0, d_in1, out, st);
-        case Family::FastGY: return run_fastgy(P, d_in0, d_in1, out, st);
+        case Family::FastGY: return P->gy_herm ? run_fasth(P, d_in0, d_in1, out, st) : run_fastgy(P, d_in0, d_in1, out, st);
         case Family::FastMY: return run_fastmy(P, d_in0, d_in1, out, st);
         case Family::FastM: case Family::FastN: return run_fastm(P, d_in0, d_in1, out, (double*)d_iso, ws, st);
         case Family::FastY: case Family::FastY1D: return run_fasty(P, (const float*)d_in0, (const float*)d_in1, out, (double*)d_iso, ws, st);

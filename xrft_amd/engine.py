@@ -37,7 +37,7 @@ class SpectralPlan:
 
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
-                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0):
+                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         if dtype not in _DTYPES:
@@ -52,8 +52,13 @@ class SpectralPlan:
         self.mid = max(int(mid), 1)      # > 1: (batch, ny, mid, nx, inner): independent elements between the two transform axes
         # input strides in elements (0 = dense): the plan reads a box of a larger array where it lies (xrfthip_desc.in_stride_y / in_stride_batch)
         self.in_stride_y, self.in_stride_batch = int(in_stride_y), int(in_stride_batch)
+        # the last pass of a three-axis spectrum (xrfthip_desc.herm_ny / herm_nx): (batch, nt, herm_ny, herm_nx/2 + 1) complex in, the full (batch, nt, herm_ny, herm_nx) out
+        self.herm_ny, self.herm_nx = int(herm_ny), int(herm_nx)
+        if self.herm_ny or self.herm_nx:
+            self.nx_out = self.herm_ny * self.herm_nx
         d = _lib.Desc(C.sizeof(_lib.Desc), self.ndim, self.batch, self.ny, self.nx, _DTYPES[dtype], self.out_mode,
-                      int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch)
+                      int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
+                      self.herm_ny, self.herm_nx)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
         for axis, w in ((0, window_y), (1, window_x)):
             if w is not None:
@@ -143,6 +148,8 @@ class SpectralPlan:
             shape = (self.batch, self.ny_out, self.nx_out) + ((self.inner,) if self.inner > 1 else ())
             if self.mid > 1:
                 shape = (self.batch, self.ny_out, self.mid, self.nx_out, self.inner)
+            if self.herm_ny:
+                shape = (self.batch, self.ny, self.herm_ny, self.herm_nx)
             out = torch.empty(shape, dtype=self.out_dtype(), device=dev)
         elif want_out:  # a caller's buffer (graph capture, composed passes): held to the plan before the device sees its pointer
             need = self.batch * self.ny_out * self.nx_out * self.inner * self.mid
