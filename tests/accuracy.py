@@ -99,6 +99,25 @@ def radial_map(ny, nx):
     return np.minimum(np.floor(np.hypot(ky, kx)).astype(np.int32), nb - 1), nb
 
 
+def herm_kw(shape, cdtype, mode, flags=0, batch=2):
+    """make() arguments of the last pass of a three-axis spectrum (herm_ny / herm_nx): the transform along t of the half spectrum of a (nt, ny, nx) grid."""
+    nt, ny, nx = shape
+    return dict(batch=batch, ny=nt, nx=ny * (nx // 2 + 1), dtype=cdtype, out_mode=mode, flags=L.AXIS_Y | flags, herm_ny=ny, herm_nx=nx)
+
+
+def herm_full(v, hny, hnx, conj):
+    """[batch][nt][hny (hnx/2 + 1)] values on the stored half of a real grid's spectrum -> the full [batch][nt][hny][hnx] result of a herm_ny / herm_nx plan: the
+    columns kx > hnx/2 from the twin (-kt, -ky, -kx), conjugated for a cross spectrum."""
+    b, nt = v.shape[:2]
+    nxh = hnx // 2 + 1
+    h = v.reshape(b, nt, hny, nxh)
+    full = np.empty((b, nt, hny, hnx), dtype=h.dtype)
+    full[..., :nxh] = h
+    tw = h[:, (-np.arange(nt)) % nt][:, :, (-np.arange(hny)) % hny][..., hnx - np.arange(nxh, hnx)]
+    full[..., nxh:] = np.conj(tw) if conj else tw
+    return full
+
+
 def family(p):
     """(kernel kind, the first family tag describe prints)"""
     line = p.describe().splitlines()[1]
@@ -182,9 +201,12 @@ def detrended(a, axes, kind):
 
 
 def reference(kw, x0, x1=None, binmap=None, nbins=0, phase_x=None):
-    """What a make(**kw) plan computes (scale 1), in float64 / complex128 from the float64 image of its input(s).  Returns (out, iso)."""
+    """What a make(**kw) plan computes (scale 1), in float64 / complex128 from the float64 image of its input(s).  Returns (out, iso).
+    A herm descriptor (herm_ny / herm_nx): the transform along t of the complex half-spectrum input, |F|^2 or F0 conj(F1), expanded to the
+    full grid by herm_full, with the plan's rotations (the other descriptors of the ladder carry none)."""
     shape, axes, half = _axes(kw)
     flags, mode, det = kw.get("flags", 0), kw.get("out_mode", L.OUT_POWER), kw.get("detrend", L.DETREND_NONE)
+    herm = kw.get("herm_ny", 0) > 0
     if flags & L.C2R_X:  # irfftn: the half spectrum [.., nx/2 + 1] in, nx real samples out, unnormalised (the caller folds 1/N into scale)
         s = [shape[k] for k in axes]
         a = np.asarray(x0, dtype=np.complex128).reshape(shape[:-1] + (shape[-1] // 2 + 1,))
@@ -193,6 +215,8 @@ def reference(kw, x0, x1=None, binmap=None, nbins=0, phase_x=None):
     def fwd(x):
         a = np.asarray(x).reshape(shape)
         a = a.astype(np.complex128 if np.iscomplexobj(a) else np.float64)
+        if herm and flags & L.ISHIFT_Y:
+            a = np.fft.ifftshift(a, axes=1)
         a = detrended(a, axes, det)
         if flags & L.PHASE_IN:
             a = a * np.asarray(phase_x, dtype=np.complex128)
@@ -220,6 +244,12 @@ def reference(kw, x0, x1=None, binmap=None, nbins=0, phase_x=None):
         if w is not None:
             c = c * w
         out = c if mode == L.OUT_CROSS else np.angle(c)
+    if herm:
+        out = herm_full(out, kw["herm_ny"], kw["herm_nx"], mode == L.OUT_CROSS)
+        if flags & L.SHIFT_Y:
+            out = np.fft.fftshift(out, axes=1)
+        if flags & L.SHIFT_X:  # (of a herm plan: the two Hermitian axes)
+            out = np.fft.fftshift(out, axes=(2, 3))
     iso = None
     if flags & L.ISO:
         bm = np.asarray(binmap).ravel()
@@ -305,6 +335,11 @@ MODES = [
     ("fastyc-four-step-small", dict(ndim=1, nx=65536, dtype=C64, out_mode=L.OUT_COMPLEX), {}, L.K_FASTY, "fasty complex rows, four-step"),
     ("fast1d-small", dict(ndim=1, nx=65536, detrend=L.DETREND_LINEAR), {"XRFTHIP_FASTR": "0"}, L.K_FASTY, "fasty four-step"),
     ("fasty-small", dict(ny=256, nx=512), {}, L.K_FASTY, "fasty"),
+    # the last pass of a three-axis spectrum on the half spectrum of a (nt, ny, nx) grid: the smallest shapes at which the twin indexing (kx = 0, the Nyquist
+    # column, an odd ny) and the 128-byte runs with a ragged last block can go wrong; the tone / impulse / Nyquist signals lie along t (the one transform axis)
+    ("fasth-power-f32", herm_kw((8, 6, 10), C64, L.OUT_POWER, L.SHIFT_Y | L.SHIFT_X), {}, L.K_FASTH, "fasth"),
+    ("fasth-cross-f64", herm_kw((12, 4, 6), C128, L.OUT_CROSS), {}, L.K_FASTH, "fasth"),
+    ("fasth-power-odd", herm_kw((15, 5, 7), C64, L.OUT_POWER), {}, L.K_FASTH, "fasth"),  # (odd Hermitian axes, no Nyquist column; 15 = 5 x 3: two radices)
 ]
 
 # xrfthip Family (csrc/plan.h) -> the (kernel kind, describe tag) forms it shows; every Family has a ladder case (test_every_family_is_executed)
@@ -326,6 +361,7 @@ FAMILY_FORMS = {
     "FastY1D": {(L.K_FASTY, "fasty four-step")},
     "FastM": {(L.K_FASTM, "fastm")},
     "FastN": {(L.K_FASTN, "fastn")},
+    "FastH": {(L.K_FASTH, "fasth")},
 }
 
 

@@ -25,6 +25,7 @@ from xrft_amd import _lib, api  # noqa: E402
 from xrft_amd import _lib as L  # noqa: E402
 
 import accuracy as A  # noqa: E402
+from accuracy import herm_full, herm_kw  # noqa: E402
 import cases  # noqa: E402
 
 # (nt, ny, nx): a small even cube; all odd (no Nyquist column, twins for kx = 1 .. (nx - 1) / 2); all even; column blocks that straddle rows ky; nt = 2 x 3 x 5
@@ -207,24 +208,6 @@ def half_spectra(shape, batch, cdtype, seed=4):
     return [torch.from_numpy(np.ascontiguousarray(v)).to(cdtype).reshape(batch, nt, ny * (nx // 2 + 1)) for v in h]
 
 
-def herm_full(v, hny, hnx, conj):
-    """[batch][nt][hny (hnx/2 + 1)] values on the stored half of a real grid's spectrum -> the full [batch][nt][hny][hnx] result of a herm_ny / herm_nx plan: the
-    columns kx > hnx/2 from the twin (-kt, -ky, -kx), conjugated for a cross spectrum."""
-    b, nt = v.shape[:2]
-    nxh = hnx // 2 + 1
-    h = v.reshape(b, nt, hny, nxh)
-    full = np.empty((b, nt, hny, hnx), dtype=h.dtype)
-    full[..., :nxh] = h
-    tw = h[:, (-np.arange(nt)) % nt][:, :, (-np.arange(hny)) % hny][..., hnx - np.arange(nxh, hnx)]
-    full[..., nxh:] = np.conj(tw) if conj else tw
-    return full
-
-
-def herm_kw(shape, cdtype, mode, flags=0, batch=2):
-    nt, ny, nx = shape
-    return dict(batch=batch, ny=nt, nx=ny * (nx // 2 + 1), dtype=cdtype, out_mode=mode, flags=L.AXIS_Y | flags, herm_ny=ny, herm_nx=nx)
-
-
 @pytest.mark.parametrize("flags", [0, L.SHIFT_Y | L.SHIFT_X, L.SHIFT_X | L.ISHIFT_Y], ids=["plain", "shifted", "yx-shifted-ishift"])
 @pytest.mark.parametrize("mode", [L.OUT_POWER, L.OUT_CROSS], ids=["power", "cross"])
 @pytest.mark.parametrize("cdtype", [A.C64, A.C128], ids=["c64", "c128"])
@@ -247,7 +230,8 @@ def test_no_stale_output_and_identical_repeats(shape, cdtype, mode, flags):
     x0, x1 = (h.to(torch.complex128).numpy() * w for h in (h0, h1))
     if flags & L.ISHIFT_Y:
         x0, x1 = (np.fft.ifftshift(x, axes=1) for x in (x0, x1))
-    ref, _ = A.reference(kw, x0, x1)  # (the one-axis transform and the product on the stored half: tests/accuracy.py knows AXIS_Y, not the Hermitian fields)
+    plain = {k: v for k, v in kw.items() if not k.startswith("herm_")}
+    ref, _ = A.reference(plain, x0, x1)  # (the one-axis transform and the product on the stored half; the twins and the rotations are applied here, apart from A.reference's own herm form)
     ref = herm_full(ref, ny, nx, mode == L.OUT_CROSS)
     if flags & L.SHIFT_Y:
         ref = np.fft.fftshift(ref, axes=1)

@@ -3,7 +3,7 @@
 // ---------------------------------------------------------------------------------------------------------------
 // one pass over small slabs of any smooth shape (fastg.h): the lengths as data
 // ---------------------------------------------------------------------------------------------------------------
-int fastg_rev(const std::vector<int>& radix, int n, DevBuf& buf, std::vector<unsigned>& host) {  // rev[k] = position of frequency k after the DIF passes (as build_tables)
+static int fastg_rev(const std::vector<int>& radix, int n, DevBuf& buf, std::vector<unsigned>& host) {  // rev[k] = position of frequency k after the DIF passes (as build_tables)
     std::vector<unsigned> rev((size_t)std::max(n, 1));
     for (int pos = 0; pos < n; ++pos) {
         if (radix.empty()) { rev[(size_t)pos] = (unsigned)pos; continue; }  // (no passes: the identity)
@@ -20,7 +20,7 @@ int fastg_rev(const std::vector<int>& radix, int n, DevBuf& buf, std::vector<uns
     host = rev;
     return buf.upload(rev.data(), rev.size() * sizeof(unsigned));
 }
-template <typename T> int fastg_setup_t(xrfthip_plan* P) {
+template <typename T> static int fastg_setup_t(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
     const int n = P->g_n, ny = P->g_one_d ? P->g_rows : (int)d.ny;
     int rc = build_twiddle<T>(P->g_twx, n, n);
@@ -33,13 +33,13 @@ template <typename T> int fastg_setup_t(xrfthip_plan* P) {
 // the radices of one axis of the lengths-as-data one-pass kernels (fastg.h): the 2^a 3^b 5^c choice of `factorize` where the length is that smooth (unchanged
 // plans), else -- prime factors 7, 11, 13: weekly data, 77, 91, 364 = 52 weeks, 1001 -- the butterflies of tile_fft.h's dft_prime (numpy's pocketfft
 // hard-codes 7 and 11).  False: another prime factor.
-bool fastg_factor(long long n, std::vector<int>& out) {
+static bool fastg_factor(long long n, std::vector<int>& out) {
     bool gen = false;
     if (factorize(n, out, gen) == XRFTHIP_OK && !gen) return true;
     if (n == 7 || n == 11 || n == 13 || n == 14) { out.assign(1, (int)n); return true; }
     return fastn_factor(n, 16, out);
 }
-bool fastg_try(xrfthip_plan* P) {  // can the slab's half spectrum live in the LDS of one workgroup, and are both lengths smooth?
+static bool fastg_try(xrfthip_plan* P) {  // can the slab's half spectrum live in the LDS of one workgroup, and are both lengths smooth?
     const xrfthip_desc& d = P->d;
     const bool one_d = d.ndim == 1;
     if ((d.ndim != 2 && !one_d) || d.nx < 3 || (!one_d && d.ny < 2) || d.nx > (one_d ? 16384 : 4096) || d.ny > 4096) return false;
@@ -77,7 +77,7 @@ bool fastg_try(xrfthip_plan* P) {  // can the slab's half spectrum live in the L
 }
 // fastg radial sums: per bin the LDS positions of its samples, in (ky, kx) order -- any bin map (a sample with kx > nx/2 lives at its Hermitian twin's
 // position: |F|^2 is the same)
-int fastg_build_iso(xrfthip_plan* P, const int32_t* bm) {
+static int fastg_build_iso(xrfthip_plan* P, const int32_t* bm) {
     const int ny = (int)P->d.ny, nx = (int)P->d.nx, n = P->g_n, rs = P->g_rs, nb = P->nbins;
     const bool packed = P->g_packed;
     const bool cross = P->d.out_mode == XRFTHIP_OUT_CROSS;  // (bit 15 of a position: the sample is the conjugate of the stored product)
@@ -129,7 +129,7 @@ bool rader_split(long long n, bool allow17, int& p_out, std::vector<int>& rq, st
     return false;
 }
 
-bool fastgy_try(xrfthip_plan* P, bool rows) {
+static bool fastgy_try(xrfthip_plan* P, bool rows = false) {
     const xrfthip_desc& d = P->d;
     const bool two_f = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
     const long long N = rows ? d.nx : d.ny;  // the transform length
@@ -189,7 +189,7 @@ bool fastgy_try(xrfthip_plan* P, bool rows) {
 }
 // the tables of the prime-factor / Rader form (fastg.h, FastGY::rad_p): the row of every input sample and of every frequency, the transformed kernel
 // B = FFT_(p-1)(W_p^(g^m)) / (p - 1) at the row the forward passes (radices rp) leave each frequency
-int rader_maps(int n, int p, const std::vector<int>& rq_, const std::vector<int>& rp_, std::vector<unsigned>& pin, std::vector<unsigned>& pout, std::vector<double>& bre, std::vector<double>& bim) {
+static int rader_maps(int n, int p, const std::vector<int>& rq_, const std::vector<int>& rp_, std::vector<unsigned>& pin, std::vector<unsigned>& pout, std::vector<double>& bre, std::vector<double>& bim) {
     const int q = n / p, P1 = p - 1;
     auto powmod = [](long long b, long long e, long long m) { long long r = 1; b %= m; while (e > 0) { if (e & 1) r = r * b % m; b = b * b % m; e >>= 1; } return r; };
     int g = 0;  // the smallest generator of the units mod p
@@ -235,7 +235,7 @@ int rader_maps(int n, int p, const std::vector<int>& rq_, const std::vector<int>
     }
     return XRFTHIP_OK;
 }
-template <typename T> int fastgy_rader_tables(xrfthip_plan* P) {
+template <typename T> static int fastgy_rader_tables(xrfthip_plan* P) {
     const int n = (int)P->gy_n, p = P->gy_rad_p, P1 = p - 1;
     std::vector<unsigned> pin, pout;
     std::vector<double> bre, bim;
@@ -277,7 +277,7 @@ template <typename T> int fastn_rader_tables(xrfthip_plan* P) {
     return rc;
 }
 // the tables of the Bluestein form: c[k] = exp(i pi k^2 / n), k < n, and FFT_m(chirp kernel) / m at the row the forward passes leave each frequency
-template <typename T> int fastgy_blue_tables(xrfthip_plan* P) {
+template <typename T> static int fastgy_blue_tables(xrfthip_plan* P) {
     const long long N = P->d.ny;
     const int m = P->gy_blue_m;
     const long double pi = 3.14159265358979323846264338327950288L;
@@ -330,12 +330,13 @@ int try_fastgy(xrfthip_plan* P) {
     return rc;
 }
 
-int run_fastgy(const xrfthip_plan* P, const void* in, const void* in_b, void* out, hipStream_t st) {
+static int run_fastgy(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
     FastGY p{};
-    p.in = in; p.out = out;
+    p.in = a.in0; p.out = a.out;
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
-    p.in_b = in_b; p.two = two ? 1 : 0; p.angle = d.out_mode == XRFTHIP_OUT_PHASE ? 1 : 0;
+    p.in_b = a.in1; p.two = two ? 1 : 0; p.angle = d.out_mode == XRFTHIP_OUT_PHASE ? 1 : 0;
     const bool rows = P->gy_rows;  // (the contiguous axis of a 1-D plan: "columns" are the batch's rows)
     const int ax = rows ? 1 : 0;
     p.ny = (int)P->gy_n; p.nx = rows ? (int)d.batch : (int)d.nx; p.G = P->gy_G; p.lg = ilog2i(P->gy_G);
@@ -374,7 +375,7 @@ int run_fastgy(const xrfthip_plan* P, const void* in, const void* in_b, void* ou
     return XRFTHIP_OK;
 }
 
-// The herm form of FastGY (gy_herm): the last pass of a three-axis power / cross spectrum (xrfthip_desc.herm_ny / herm_nx; fasth.h).  G columns of the half spectrum per workgroup = 128 bytes of
+// FastH: the last pass of a three-axis power / cross spectrum (xrfthip_desc.herm_ny / herm_nx; fasth.h).  G columns of the half spectrum per workgroup = 128 bytes of
 // an output row (32 float32 powers, 16 float64 powers or complex64 products, 8 complex128 products): in every precision and mode the tile is 256 nt bytes, so any
 // smooth nt up to ~600 fits.  A descriptor with these fields is served here or not at all: the caller composes the stages (XRFTHIP_UNSUPPORTED_LENGTH).
 int try_fasth(xrfthip_plan* P) {
@@ -391,18 +392,19 @@ int try_fasth(xrfthip_plan* P) {
     const size_t lds = (((size_t)d.ny * G * (cross ? 2 : 1) * P->csize + 15) & ~(size_t)15) + (size_t)d.ny * (P->csize + P->rsize + 2) + 16;
     if (lds > kLdsMax - 1024) return XRFTHIP_UNSUPPORTED_LENGTH;
     if ((d.nx + G - 1) / G > 0x7fffffffLL / std::max<long long>(d.batch, 1)) return XRFTHIP_UNSUPPORTED_LENGTH;  // (units of a launch)
-    P->family = P->chosen = Family::FastGY; P->gy_herm = true;
+    P->family = P->chosen = Family::FastH;
     P->g_ry = rt; P->h_G = G; P->h_thr = thr; P->h_lds = lds;
     int rc = plan_twiddle(P, P->g_twy, d.ny, d.ny);
     if (!rc) rc = fastg_rev(rt, (int)d.ny, P->g_revy, P->g_hrevy);
     return rc;
 }
 
-int run_fasth(const xrfthip_plan* P, const void* in, const void* in_b, void* out, hipStream_t st) {
+static int run_fasth(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
     const bool cross = d.out_mode == XRFTHIP_OUT_CROSS;
     FastH p{};
-    p.in = in; p.in_b = in_b; p.out = out;
+    p.in = a.in0; p.in_b = a.in1; p.out = a.out;
     p.nt = (int)d.ny; p.ny = (int)d.herm_ny; p.nx = (int)d.herm_nx; p.nxh = (int)(d.herm_nx / 2 + 1); p.ncol = (int)d.nx;
     p.G = P->h_G; p.lg = ilog2i(P->h_G);
     p.lch = p.lg - ilog2i((int)(16 / (cross ? P->csize : P->rsize)));
@@ -433,7 +435,7 @@ int run_fasth(const xrfthip_plan* P, const void* in, const void* in_b, void* out
 // Take the workgroup of 1, 2, 4, 8 or 16 waves (whole waves per SIMD, or the second workgroup does not fit beside the first) that keeps most
 // waves resident, the smaller one on a tie: a 50 x 50 slab is a 128-thread workgroup, eight to a CU; 96 x 96: 256 threads, four to a CU;
 // 150 x 150 fills the LDS alone and brings 1024 threads (512 in float64).  Measured: profiles/r04_small_slabs.txt
-long long fastg_threads(const xrfthip_plan* P) {
+static long long fastg_threads(const xrfthip_plan* P) {
     const long long maxthr = P->dbl ? fastg_max_threads<double>() : fastg_max_threads<float>();
     const long long forced = env_ll("XRFTHIP_FASTG_THREADS", 0);
     if (forced >= 64 && forced <= maxthr && forced % 64 == 0) return forced;
@@ -467,10 +469,11 @@ int try_fastg(xrfthip_plan* P) {
     return rc;
 }
 
-int run_fastg(const xrfthip_plan* P, const void* in, const void* in_b, void* out, double* iso, hipStream_t st) {
+static int run_fastg(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
     FastG p{};
-    p.in = in; p.in_b = in_b; p.out = out; p.nslabs = d.batch;
+    p.in = a.in0; p.in_b = a.in1; p.out = a.out; p.nslabs = d.batch;  // (out: null when the spectrum is not stored)
     p.ny = P->g_one_d ? P->g_rows : (int)d.ny; p.nx = (int)d.nx; p.n = P->g_n; p.rs = P->g_rs; p.packed = P->g_packed ? 1 : 0;
     p.one_d = P->g_one_d ? 1 : 0; p.nrows = d.batch; p.nred = P->g_nred;
     p.cin = P->cplx_in ? 1 : 0;
@@ -489,10 +492,8 @@ int run_fastg(const xrfthip_plan* P, const void* in, const void* in_b, void* out
     p.tw_x = P->g_twx.p; p.tw_y = P->g_twy.p; p.tw_r = P->g_twr.p;
     p.rev_x = (const unsigned*)P->g_revx.p; p.rev_y = (const unsigned*)P->g_revy.p;
     if (d.flags & XRFTHIP_ISO) {
-        p.iso = iso; p.nbins = P->nbins;
+        p.iso = a.iso; p.nbins = P->nbins;
         p.iso_pos = (const unsigned short*)P->g_isopos.p; p.iso_start = (const unsigned*)P->g_isostart.p;
-        if (d.flags & XRFTHIP_NO_SPECTRUM_OUT) out = nullptr;
-        p.out = out;
     }
     const bool win = P->win[0].p || P->win[1].p;
     p.win_y = win ? (P->win[0].p ? P->win[0].p : P->ones4096.p) : nullptr;
@@ -526,14 +527,91 @@ int run_fastg(const xrfthip_plan* P, const void* in, const void* in_b, void* out
 }
 
 
-template int fastg_setup_t<float>(xrfthip_plan*);
-template int fastg_setup_t<double>(xrfthip_plan*);
-template int fastgy_rader_tables<float>(xrfthip_plan*);
-template int fastgy_rader_tables<double>(xrfthip_plan*);
+// ---------------------------------------------------------------------------------------------------------------
+// the rows of FastG, FastGY and FastH (plan.h, FamilyOps)
+// ---------------------------------------------------------------------------------------------------------------
+static void describe_fastg(const xrfthip_plan* plan, std::string& s, const char* in_note) {
+    std::string rxs, rys;
+    for (int r : plan->g_rx) rxs += (rxs.empty() ? "" : "x") + std::to_string(r);
+    for (int r : plan->g_ry) rys += (rys.empty() ? "" : "x") + std::to_string(r);
+    if (plan->g_one_d)
+        appendf(s, "  [fastg rows] one pass, one %d-thread workgroup per %d rows of %lld samples%s: in LDS, radices from the plan (x: %d = %s), a mean / line per row in the "
+                   "workgroup, output gathered in output order through the digit-reversal table, lds=%zuB%s\n",
+                (int)fastg_threads(plan), plan->g_rows, (long long)plan->d.nx, plan->g_packed ? " packed in pairs" : plan->cplx_in ? " (complex input)" : " (an odd length: complex sequences)", plan->g_n,
+                rxs.empty() ? "1" : rxs.c_str(), plan->g_lds, in_note);
+    else if (plan->g_packed)
+        appendf(s, "  [fastg] one pass, one %d-thread workgroup per %lld x %lld slab: the half spectrum (%lld rows of %lld + 1 complex) in LDS, radices from the plan "
+                   "(x: %lld = %s on packed rows, y: %lld = %s), exact plane detrend in the workgroup, output gathered in output order through the digit-reversal "
+                   "tables, lds=%zuB%s\n",
+                (int)fastg_threads(plan), (long long)plan->d.ny, (long long)plan->d.nx, (long long)plan->d.ny, (long long)plan->d.nx / 2, (long long)plan->d.nx / 2,
+                rxs.empty() ? "1" : rxs.c_str(), (long long)plan->d.ny, rys.c_str(), plan->g_lds, in_note);
+    else
+        appendf(s, "  [fastg] one pass, one %d-thread workgroup per %lld x %lld slab (complex input or an odd row length: the rows as complex sequences): the spectrum (%lld rows of %lld complex) "
+                   "in LDS, radices from the plan (x: %lld = %s, y: %lld = %s), exact plane detrend in the workgroup, output gathered in output order through the "
+                   "digit-reversal tables, lds=%zuB%s\n",
+                (int)fastg_threads(plan), (long long)plan->d.ny, (long long)plan->d.nx, (long long)plan->d.ny, (long long)plan->d.nx, (long long)plan->d.nx,
+                rxs.c_str(), (long long)plan->d.ny, rys.c_str(), plan->g_lds, in_note);
+    if (plan->d.out_mode == XRFTHIP_OUT_CROSS)
+        appendf(s, "  [fastg cross spectrum] both fields' tiles in the workgroup's LDS, F0 conj(F1) on the way out\n");
+    if (plan->d.flags & XRFTHIP_ISO)
+        appendf(s, "  [fastg radial sums] in the same pass: per bin the LDS positions of its samples (any bin map), a bin per wave, float64, a fixed shuffle tree -- no atomics%s\n",
+                (plan->d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? "; the spectrum is not stored" : "");
+}
+static void describe_fastgy(const xrfthip_plan* plan, std::string& s, const char*) {
+    std::string rys;
+    for (int r : plan->g_ry) rys += (rys.empty() ? "" : "x") + std::to_string(r);
+    const bool onecol = plan->cplx_in || plan->d.out_mode == XRFTHIP_OUT_CROSS || plan->d.out_mode == XRFTHIP_OUT_PHASE;
+    if (plan->gy_rows)
+        appendf(s, "  [fastg rows Rader] one pass along the contiguous axis, %d thr, %d sequences (%s) per workgroup, lanes along the samples, lds=%zuB: per-row detrend + window + transform%s\n",
+                plan->gy_thr, plan->gy_G, plan->cplx_in ? "complex rows" : onecol ? "a row of each of the two fields" : "pairs of rows", plan->gy_lds, (plan->d.flags & XRFTHIP_INVERSE) ? "; inverse (conj in, conj out)" : "");
+    else
+    appendf(s, "  [fastg y-only] one pass, %d thr, %d %s per workgroup (%d bytes of a row), the radices from the plan (y: %lld = %s in LDS), lds=%zuB: "
+               "per-column detrend + window + transform%s, in place in memory order%s\n",
+            plan->gy_thr, plan->gy_G, plan->cplx_in ? "complex columns" : onecol ? "columns of each of the two fields" : "packed column pairs",
+            (int)((plan->cplx_in ? plan->csize : onecol ? plan->rsize : 2 * plan->rsize) * (size_t)plan->gy_G), (long long)(plan->gy_blue_m ? plan->gy_blue_m : plan->d.ny), rys.c_str(), plan->gy_lds,
+            onecol ? "" : " + both columns' spectra", (plan->d.flags & XRFTHIP_INVERSE) ? "; inverse (conj in, conj out)" : "");
+    if (plan->gy_rad_p) {
+        std::string rps;
+        for (int r : plan->gy_rp) rps += (rps.empty() ? "" : "x") + std::to_string(r);
+        appendf(s, "  [fastg %s Rader] %lld = %lld x %d: the prime-factor form, no twiddles between the two dimensions; along the prime %d a cyclic convolution of %d = %s points "
+                   "(forward passes, * the transformed kernel, inverse passes) inside the tile\n", plan->gy_rows ? "rows:" : "y-only",
+                (long long)plan->gy_n, (long long)(plan->gy_n / plan->gy_rad_p), plan->gy_rad_p, plan->gy_rad_p, plan->gy_rad_p - 1, rps.c_str());
+    }
+    if (plan->gy_blue_m)
+        appendf(s, "  [fastg y-only Bluestein] %lld points as a circular convolution of %d inside the tile (chirp products, forward and inverse passes)%s\n",
+                (long long)plan->d.ny, plan->gy_blue_m, plan->gy_tw_lds ? "" : "; twiddles from memory");
+}
+static void describe_fasth(const xrfthip_plan* plan, std::string& s, const char*) {
+    const xrfthip_desc& d = plan->d;
+    std::string rts;
+    for (int r : plan->g_ry) rts += (rts.empty() ? "" : "x") + std::to_string(r);
+    const bool cross = plan->d.out_mode == XRFTHIP_OUT_CROSS;
+    appendf(s, "  [fasth] the last pass of a three-axis %s spectrum: %d thr, %d columns of the half spectrum [%lld][%lld][%lld + 1] per workgroup%s, the radices from the plan "
+               "(t: %lld = %s in LDS), lds=%zuB: window + transform along t + %s, ",
+            cross ? "cross" : "power", plan->h_thr, plan->h_G, (long long)d.ny, (long long)d.herm_ny, (long long)d.herm_nx / 2, cross ? " of each of the two fields" : "",
+            (long long)d.ny, rts.c_str(), plan->h_lds, cross ? "F0 conj(F1)" : "|F|^2");
+    appendf(s, "every sample and its Hermitian twin stored as 16-byte pieces of 128-byte runs of the full [%lld][%lld][%lld] result, non-temporal\n",
+            (long long)d.ny, (long long)d.herm_ny, (long long)d.herm_nx);
+}
+static int finalize_fastg(xrfthip_plan* P) {
+    if (cross_iso_phase(P)) { settle_family(P, true); return XRFTHIP_OK; }
+    return fast_phase_tables(P);
+}
+// (slabs and row groups; a group of rows is indexed with 32 bits)
+static bool fastg_strided_if(const xrfthip_plan* P) { return !P->g_one_d || (long long)P->g_rows * in_slab(P) <= 0x7fffffffLL; }
+static void info_fastg(const xrfthip_plan* P, int32_t* k, int32_t* n) { *k = P->g_one_d ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG; *n = P->g_one_d ? P->g_rows : 1; }
+static void info_fastgy(const xrfthip_plan* P, int32_t* k, int32_t* n) { *k = P->gy_rows ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG_Y; *n = ((P->cplx_in || plan_two(P)) ? 1 : 2) * P->gy_G; }
+static void info_fasth(const xrfthip_plan* P, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTH; *n = P->h_G; }
+static bool fastgy_uses_bluestein(const xrfthip_plan* P) { return P->gy_blue_m > 0; }
+// (the entries in the order of struct FamilyOps: family, run, describe, kernel_info, finalize, layout, binmap, uses_bluestein, reads_strided, strided_if, dbl_tables)
+#ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
+const FamilyOps kOpsFastG = {Family::FastG, run_fastg, describe_fastg, info_fastg, finalize_fastg, layout_one_pass, fastg_build_iso, nullptr, true, fastg_strided_if, true};  // (any bin map: per-bin position lists)
+const FamilyOps kOpsFastGY = {Family::FastGY, run_fastgy, describe_fastgy, info_fastgy, fast_phase_tables, layout_one_pass, nullptr, fastgy_uses_bluestein, false, nullptr, true};
+const FamilyOps kOpsFastH = {Family::FastH, run_fasth, describe_fasth, info_fasth, nullptr, layout_one_pass};  // (no phase table, no other family to hand the plan to)
+#endif
+
 template int fastn_rader_tables<float>(xrfthip_plan*);
 template int fastn_rader_tables<double>(xrfthip_plan*);
-template int fastgy_blue_tables<float>(xrfthip_plan*);
-template int fastgy_blue_tables<double>(xrfthip_plan*);
 
 // kernels of this unit that take more than 64 KB of dynamic LDS (the one-pass lengths-as-data kernels): called once through set_kernel_attrs_once()
 void set_attrs_fastg() {

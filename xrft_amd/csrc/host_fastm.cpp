@@ -3,19 +3,20 @@
 // ---------------------------------------------------------------------------------------------------------------
 // mixed-radix float64 form of the y-first pipeline (fastm.h)
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T, int N, int GOV = 0> MGeomRt mgeom_t() {
+struct MGeomRt { int thr, g; size_t lds_cols, lds_rows; int r0, r1, r2; int thr_r1, g_r1; size_t lds_r1; };  // geometry of a table kernel as the host needs it; *_r1: pass 2 of one field
+template <typename T, int N, int GOV = 0> static MGeomRt mgeom_t() {
     typedef MGeom<T, N, GOV> M;
     typedef typename M::template Rows<M::GR1> R1;
     return {M::THR, M::G, M::LDS, M::LDS_ROWS, M::R0, M::R1, M::R2, R1::THR, M::GR1, R1::LDS};
 }
-bool fastm_len(long long n, bool dbl) {
+static bool fastm_len(long long n, bool dbl) {
 #define X_(NN) if (n == NN) return true;
     XRFT_M_LATLON(X_)
     if (dbl) { XRFT_M_POW2(X_) } else { XRFT_M_F32ONLY(X_) }
 #undef X_
     return false;
 }
-MGeomRt mgeom(long long n, bool dbl) {
+static MGeomRt mgeom(long long n, bool dbl) {
     if (dbl) {
 #define X_(NN) if (n == NN) return mgeom_t<double, NN>();
         XRFT_M_LATLON(X_) XRFT_M_POW2(X_)
@@ -27,14 +28,14 @@ MGeomRt mgeom(long long n, bool dbl) {
     return mgeom_t<float, 360>();
 }
 // pass 1 with four float32 sequences per workgroup (fastm_cols_kernel, GOV = 4) when the rows divide into its 8-column blocks
-bool fastm_wide(long long ny, long long nx, bool dbl) {
+static bool fastm_wide(long long ny, long long nx, bool dbl) {
     if (dbl || (nx & 7) != 0) return false;
 #define X_(NN) if (ny == NN) return true;
     XRFT_M_WIDE32(X_)
 #undef X_
     return false;
 }
-MGeomRt mgeom_cols(long long ny, long long nx, bool dbl) {  // geometry of pass 1 of an (ny, nx) slab
+static MGeomRt mgeom_cols(long long ny, long long nx, bool dbl) {  // geometry of pass 1 of an (ny, nx) slab
     if (fastm_wide(ny, nx, dbl)) {
 #define X_(NN) if (ny == NN) return mgeom_t<float, NN, 4>();
         XRFT_M_WIDE32(X_)
@@ -43,23 +44,22 @@ MGeomRt mgeom_cols(long long ny, long long nx, bool dbl) {  // geometry of pass 
     return mgeom(ny, dbl);
 }
 // layout of the intermediate: CW = 2 G columns of a pass-1 workgroup, RK rows per 128-byte line
-int fastm_cw(long long ny, long long nx, bool dbl) { return 2 * mgeom_cols(ny, nx, dbl).g; }
-int fastm_rk(long long ny, long long nx, bool dbl) { const int lb = fastm_cw(ny, nx, dbl) * (dbl ? 16 : 8); return lb >= 128 ? 1 : 128 / lb; }
-int fastm_rpu(long long nx, bool two, bool dbl) { const MGeomRt r = mgeom(nx, dbl); return two ? r.g / 2 : r.g_r1; }  // 
+static int fastm_cw(long long ny, long long nx, bool dbl) { return 2 * mgeom_cols(ny, nx, dbl).g; }
+static int fastm_rk(long long ny, long long nx, bool dbl) { const int lb = fastm_cw(ny, nx, dbl) * (dbl ? 16 : 8); return lb >= 128 ? 1 : 128 / lb; }
+static int fastm_rpu(long long nx, bool two, bool dbl) { const MGeomRt r = mgeom(nx, dbl); return two ? r.g / 2 : r.g_r1; }  // 
 // rows per line of the intermediate for a (ny, nx) plan: a whole 128-byte line of pass 1's CW columns, but never more rows than
 // one pass-2 workgroup owns (long float32 sequences: two per workgroup = 4 columns = 32 bytes per row, pass 2 takes 2 rows -> 64-byte pieces)
-int fastm_rk2(long long ny, long long nx, bool two, bool dbl) { return std::max(1, std::min(fastm_rk(ny, nx, dbl), fastm_rpu(nx, two, dbl))); }
+static int fastm_rk2(long long ny, long long nx, bool two, bool dbl) { return std::max(1, std::min(fastm_rk(ny, nx, dbl), fastm_rpu(nx, two, dbl))); }
 // ... of a plan: the table's geometry, or what fastn_setup chose when either pass runs on the run-time-radix kernels (fastn.h)
-bool plan_two(const xrfthip_plan* P) { return P->d.out_mode == XRFTHIP_OUT_CROSS || P->d.out_mode == XRFTHIP_OUT_PHASE; }
-int plan_cw(const xrfthip_plan* P) { return P->family == Family::FastN ? P->n_cw : fastm_cw(P->yny, P->ynx, P->dbl); }
-int plan_rk2(const xrfthip_plan* P) { return P->family == Family::FastN ? P->n_rk : fastm_rk2(P->yny, P->ynx, plan_two(P), P->dbl); }
-int plan_nxb(const xrfthip_plan* P) { return P->family == Family::FastN ? P->n_nxb : (int)(P->ynx / fastm_cw(P->yny, P->ynx, P->dbl)); }
+static int plan_cw(const xrfthip_plan* P) { return P->family == Family::FastN ? P->n_cw : fastm_cw(P->yny, P->ynx, P->dbl); }
+static int plan_rk2(const xrfthip_plan* P) { return P->family == Family::FastN ? P->n_rk : fastm_rk2(P->yny, P->ynx, plan_two(P), P->dbl); }
+static int plan_nxb(const xrfthip_plan* P) { return P->family == Family::FastN ? P->n_nxb : (int)(P->ynx / fastm_cw(P->yny, P->ynx, P->dbl)); }
 
 // radial sums inside pass 2 when the per-bin tables fit behind the transforms' LDS (64 KB of dynamic LDS per workgroup); otherwise
 // the spectrum is stored and summed by run_radial_sums
 // a radial bin map (fastm_build_tfirst) is gathered per bin without atomics or tables; a cross spectrum with a true-phase factor keeps
 // the general path (the factor of a sample and of its Hermitian twin differ)
-bool fastm_iso_gather(const xrfthip_plan* P) {
+static bool fastm_iso_gather(const xrfthip_plan* P) {
     return fastm_pipeline(P) && (P->d.flags & XRFTHIP_ISO) && P->nbins >= 1 && P->ytfirst_on && !(P->d.out_mode == XRFTHIP_OUT_CROSS && P->fph_on);
 }
 bool fastm_iso_fused(const xrfthip_plan* P) {
@@ -72,7 +72,7 @@ bool fastm_iso_fused(const xrfthip_plan* P) {
 }
 
 // copies of the per-bin tables in pass 2 (a power of two <= 8, whatever fits the 64 KB)
-int fastm_iso_ncopy(const xrfthip_plan* P) {
+static int fastm_iso_ncopy(const xrfthip_plan* P) {
     if (fastm_iso_gather(P)) return 1;
     const bool cx = P->d.out_mode == XRFTHIP_OUT_CROSS;
     const MGeomRt R = mgeom(P->ynx, P->dbl);
@@ -83,7 +83,6 @@ int fastm_iso_ncopy(const xrfthip_plan* P) {
 }
 
 // rows per pass-2 workgroup of this plan: two fields share a workgroup's sequences (MRowsG in fastm.h)
-int fastm_gather_rpu(const xrfthip_plan* P) { return fastm_rows_rpu(P); }
 int fastm_rows_rpu(const xrfthip_plan* P) {
     if (P->family == Family::FastN) return P->n_rpu;
     const bool two = P->d.out_mode == XRFTHIP_OUT_CROSS || P->d.out_mode == XRFTHIP_OUT_PHASE;
@@ -140,7 +139,7 @@ bool fastn_factor(long long n, int maxr, std::vector<int>& out, int need_last) {
 }
 
 // the geometry of one n-point transform held in LDS with g sequences per workgroup (fastn.h, NGeo); blue: the Bluestein plan's natural layout is its intermediate layout
-void fastn_geom(long long n, const std::vector<int>& rad, int g, int maxthr, bool blue, NGeo& o, int thr_force, int thr_pref) {
+static void fastn_geom(long long n, const std::vector<int>& rad, int g, int maxthr, bool blue, NGeo& o, int thr_force = 0, int thr_pref = 0) {
     o = NGeo{};
     o.n = (int)n; o.np = (int)rad.size();
     long long L = n;
@@ -191,7 +190,7 @@ template <typename T> int fastn_upload_twm(const NGeo& g, DevBuf& buf, bool blue
 }
 
 // Bluestein tables of pass 1: c[k] = exp(i pi k^2 / n), k < n, and FFT_m(chirp) / m in natural order
-template <typename T> int fastn_blue_tables(xrfthip_plan* P) {
+template <typename T> static int fastn_blue_tables(xrfthip_plan* P) {
     const long long N = P->d.ny;
     const int m = P->n_blue_m;
     const long double pi = 3.14159265358979323846264338327950288L;
@@ -219,7 +218,6 @@ size_t fastn_lds(const NGeo& g, size_t csize, bool cols) {
 // registers (128 per lane in float32 -> 16 waves per CU, 168 in float64 -> 12): the thread count is a divisor of that budget -- 512 (columns) / 256 (rows) in
 // float32, 192 / 256 / 384 in float64; 576- or 320-thread workgroups leave a CU half empty (profiles/r05_fastn_threads.txt) -- and the factorisation is the one
 // with the fewest passes whose LAST radix is large enough for one last-pass butterfly per thread at that count (a thread loops over the other passes' butterflies).
-size_t fastn_lds(const NGeo& g, size_t csize, bool cols);
 bool fastn_pick(long long n, int g, bool blue, bool dbl, bool cols, int maxr, int thr_force, NGeo& out) {
     const int maxthr = dbl ? fastn_max_threads<double>() : fastn_max_threads<float>();
     std::vector<int> base, r;
@@ -249,10 +247,9 @@ bool fastn_pick(long long n, int g, bool blue, bool dbl, bool cols, int maxr, in
     return false;
 }
 
-bool rader_split(long long n, bool allow17, int& p_out, std::vector<int>& rq, std::vector<int>& rp);
 // Decide which kernel runs each pass of a y-first plan on (ny, nx) and the layout of the intermediate between them.  Returns false when the plan stays
 // with the other paths (a length the butterflies do not factor and the chirp convolution does not fit, sequences that do not fit the LDS).
-bool fastn_setup(xrfthip_plan* P) {
+static bool fastn_setup(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
     const bool dbl = P->dbl, two = plan_two(P);
     const size_t cs = P->csize;
@@ -409,7 +406,7 @@ bool fastn_setup(xrfthip_plan* P) {
     return true;
 }
 
-FastN fastn_wrap(const xrfthip_plan* P, const FastM& m, bool cols) {
+static FastN fastn_wrap(const xrfthip_plan* P, const FastM& m, bool cols) {
     FastN n{};
     n.f = m;
     n.g = (NGeoPtr)(cols ? P->n_c.geo_dev.p : P->n_r.geo_dev.p);
@@ -450,7 +447,7 @@ void fastn_launch_cols(const xrfthip_plan* P, const FastM& m, hipStream_t st) {
 #undef NC_
 }
 
-void fastn_launch_rows(const xrfthip_plan* P, const FastM& m, long long gc, bool fused, hipStream_t st) {
+static void fastn_launch_rows(const xrfthip_plan* P, const FastM& m, long long gc, bool fused, hipStream_t st) {
     const FastN n = fastn_wrap(P, m, false);
     const xrfthip_desc& d = P->d;
     const NGeo& hg = P->n_r.geo;
@@ -467,7 +464,7 @@ void fastn_launch_rows(const xrfthip_plan* P, const FastM& m, long long gc, bool
 #undef NR_
 }
 
-FastM fastm_params(const xrfthip_plan* P, const void* in, void* out, char* ws, long long g0, long long gc, int slot, long long slot_slabs) {
+static FastM fastm_params(const xrfthip_plan* P, const void* in, void* out, char* ws, long long g0, long long gc, int slot, long long slot_slabs) {
     const xrfthip_desc& d = P->d;
     const size_t slab_pts = (size_t)P->yny * P->ynx, s0 = (size_t)slot * slot_slabs;
     FastM p{};
@@ -501,7 +498,7 @@ FastM fastm_params(const xrfthip_plan* P, const void* in, void* out, char* ws, l
     return p;
 }
 
-void fastm_launch_cols(const xrfthip_plan* P, const FastM& p, long long gc, hipStream_t st) {
+static void fastm_launch_cols(const xrfthip_plan* P, const FastM& p, long long gc, hipStream_t st) {
     const xrfthip_desc& d = P->d;
     const MGeomRt C = mgeom_cols(P->yny, P->ynx, P->dbl);
     const bool wide = fastm_wide(P->yny, P->ynx, P->dbl);
@@ -545,7 +542,7 @@ void fastm_launch_cols(const xrfthip_plan* P, const FastM& p, long long gc, hipS
     }
 }
 
-void fastm_launch_rows(const xrfthip_plan* P, const FastM& p, long long gc, hipStream_t st) {
+static void fastm_launch_rows(const xrfthip_plan* P, const FastM& p, long long gc, hipStream_t st) {
     const xrfthip_desc& d = P->d;
     const MGeomRt R = mgeom(P->ynx, P->dbl);
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
@@ -621,8 +618,10 @@ int try_fastn(xrfthip_plan* P) {
     return rc;
 }
 
-int run_fastm(const xrfthip_plan* P, const void* in, const void* in1, void* out, double* iso, char* ws, hipStream_t st) {
+static int run_fastm(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    const void *in = a.in0, *in1 = a.in1;
+    void* out = a.out; double* iso = a.iso; char* ws = a.ws; hipStream_t st = a.stream;
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
     const bool iso_on = (d.flags & XRFTHIP_ISO) != 0;
     for (long long g0 = 0; g0 < d.batch; g0 += P->G) {
@@ -660,18 +659,18 @@ int run_fastm(const xrfthip_plan* P, const void* in, const void* in1, void* out,
 }
 
 // one transform axis, not the contiguous one: pass 1 alone (fastm_yonly_kernel)
-bool fastmy_len(long long n, bool dbl) {
+static bool fastmy_len(long long n, bool dbl) {
 #define X_(NN) if (n == NN) return true;
     XRFT_M_LATLON(X_) XRFT_M_POW2(X_) XRFT_M_YONLY(X_)
     if (!dbl) { XRFT_M_F32ONLY(X_) XRFT_M_F32_1AX(X_) }
 #undef X_
     return n == 2048 || n == 4096;
 }
-template <typename T, int N> MGeomRt mygeom_t() {  // (the y-only kernel's own geometry: at least two sequences per workgroup)
+template <typename T, int N> static MGeomRt mygeom_t() {  // (the y-only kernel's own geometry: at least two sequences per workgroup)
     typedef typename MYGeom<T, N>::type M;
     return {M::THR, M::G, M::LDS, M::LDS_ROWS, M::R0, M::R1, M::R2, 0, 0, 0};
 }
-MGeomRt mygeom(long long n, bool dbl) {
+static MGeomRt mygeom(long long n, bool dbl) {
     if (n == 4096) return dbl ? mygeom_t<double, 4096>() : mygeom_t<float, 4096>();
     if (n == 2048 && dbl) return mygeom_t<double, 2048>();
     if (!dbl) {
@@ -703,12 +702,13 @@ int try_fastmy(xrfthip_plan* P) {
     return rc;
 }
 
-int run_fastmy(const xrfthip_plan* P, const void* in, const void* in1, void* out, hipStream_t st) {
+static int run_fastmy(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
     const MGeomRt C = mygeom(d.ny, P->dbl);
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
     FastM p{};
-    p.in = in; p.in_b = in1; p.out = out;
+    p.in = a.in0; p.in_b = a.in1; p.out = a.out;
     p.angle = d.out_mode == XRFTHIP_OUT_PHASE ? 1 : 0;
     p.tw_y = P->tw_fy.p;
     p.win_y = P->win[0].p ? P->win[0].p : P->ones4096.p;
@@ -742,8 +742,8 @@ int run_fastmy(const xrfthip_plan* P, const void* in, const void* in1, void* out
 
 // one transform axis, the contiguous one, short rows: rows packed in pairs (fastm_xonly_kernel).  Rows are contiguous whatever the
 // number of sequences per workgroup, so the lengths that leave room for one pair only (4096; 2048 in float64) are taken too.
-bool fastmx_len(long long n, bool dbl) { return fastmy_len(n, dbl); }
-MGeomRt mxgeom(long long n, bool dbl) {
+static bool fastmx_len(long long n, bool dbl) { return fastmy_len(n, dbl); }
+static MGeomRt mxgeom(long long n, bool dbl) {
     if (n == 4096) return dbl ? mgeom_t<double, 4096>() : mgeom_t<float, 4096>();
     if (dbl && n == 2048) return mgeom_t<double, 2048>();
     return mygeom(n, dbl);
@@ -763,12 +763,13 @@ int try_fastmx(xrfthip_plan* P) {
     return rc;
 }
 
-int run_fastmx(const xrfthip_plan* P, const void* in, const void* in1, void* out, hipStream_t st) {
+static int run_fastmx(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
     const MGeomRt C = mxgeom(d.nx, P->dbl);
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
     FastM p{};
-    p.in = in; p.in_b = in1; p.out = out;
+    p.in = a.in0; p.in_b = a.in1; p.out = a.out;
     p.angle = d.out_mode == XRFTHIP_OUT_PHASE ? 1 : 0;
     p.tw_x = P->tw_fx.p;
     p.win_x = P->win[1].p ? P->win[1].p : P->ones4096.p;
@@ -802,11 +803,114 @@ int run_fastmx(const xrfthip_plan* P, const void* in, const void* in1, void* out
     return XRFTHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the rows of FastM, FastN, FastMX and FastMY (plan.h, FamilyOps)
+// ---------------------------------------------------------------------------------------------------------------
+// fastm: is the bin map a radial one (see fastm_rows_kernel, ISO)?  If so: first[ky][b] = the smallest |kx| <= nx/2 whose bin is >= b
+// (nx/2 + 1 if none), b = 0 .. nbins, and the unit windows.  Any nx (the lengths of the table are even; odd ones would work).
+static int fastm_build_tfirst(xrfthip_plan* P, const int32_t* bm) {
+    const int ny = (int)P->yny, nx = (int)P->ynx, nyh = ny / 2, H = nx / 2, HM = (nx - 1) / 2;
+    bool radial = env_ll("XRFTHIP_ISO_GATHER", 1) != 0 && P->nbins < 65535 && H + 1 < 65535;
+    for (int ky = 0; ky <= nyh && radial; ++ky) {
+        const int32_t* r = bm + (size_t)ky * nx;
+        const bool twin = ky != 0 && 2 * ky != ny;
+        const int32_t* t = bm + (size_t)(twin ? ny - ky : ky) * nx;
+        for (int m = 0; m <= H; ++m) {
+            const int32_t c = r[m];
+            if (c < 0 || c >= P->nbins || (m > 0 && c < r[m - 1]) || (m >= 1 && m <= HM && r[nx - m] != c)) { radial = false; break; }
+            if (twin && (t[m] != c || t[(nx - m) % nx] != c)) { radial = false; break; }
+        }
+    }
+    P->ytfirst_on = radial;
+    if (!radial) return XRFTHIP_OK;
+    std::vector<uint16_t> f((size_t)(nyh + 1) * (P->nbins + 1), (uint16_t)(H + 1));
+    for (int ky = 0; ky <= nyh; ++ky) {
+        const int32_t* r = bm + (size_t)ky * nx;
+        uint16_t* dst = f.data() + (size_t)ky * (P->nbins + 1);
+        int m = 0;
+        for (int b = 0; b <= P->nbins; ++b) {
+            while (m <= H && r[m] < b) ++m;
+            dst[b] = (uint16_t)m;
+        }
+    }
+    int rc = P->ytfirst.upload(f.data(), f.size() * sizeof(uint16_t));
+    if (!rc) rc = build_unit_windows(P, bm, fastm_rows_rpu(P));
+    return rc;
+}
+static void describe_fastm(const xrfthip_plan* plan, std::string& s, const char* in_note) {
+    const MGeomRt C = mgeom_cols(plan->yny, plan->ynx, plan->dbl), R = mgeom(plan->ynx, plan->dbl);
+    appendf(s, "  [fastm] cols: %d thr, %d packed column pairs (FFT%lld r%dx%dx%d in LDS), lds=%zuB -> W2[slab][%d/%d][nx/%d][%d][%d] complex -> fit -> rows: %d thr, %d rows/unit (FFT%lld r%dx%dx%d), lds=%zuB, trend added back in the spectral domain, fftshift + mirror rows%s\n",
+            C.thr, C.g, (long long)plan->yny, C.r0, C.r1, C.r2, C.lds_cols, plan->y_nrow_pad, fastm_rk2(plan->yny, plan->ynx, plan->d.out_mode >= XRFTHIP_OUT_CROSS, plan->dbl), fastm_cw(plan->yny, plan->ynx, plan->dbl), fastm_rk2(plan->yny, plan->ynx, plan->d.out_mode >= XRFTHIP_OUT_CROSS, plan->dbl), fastm_cw(plan->yny, plan->ynx, plan->dbl),
+            R.thr_r1, R.g_r1, (long long)plan->ynx, R.r0, R.r1, R.r2, R.lds_r1, in_note);
+    if ((plan->d.flags & XRFTHIP_ISO) && plan->nbins > 0)
+        appendf(s, "  [fastm radial sums] %s\n", fastm_iso_gather(plan) ? "fused into the row pass: radial map, per-bin gather from the spectra in LDS, no atomics"
+                                               : fastm_iso_fused(plan) ? "fused into the row pass: int64 fixed-point tables behind the transforms' LDS"
+                                                                       : "a pass over the stored spectrum (the tables do not fit beside the transforms)");
+}
+static void describe_fastn(const xrfthip_plan* plan, std::string& s, const char* in_note) {
+    auto rads = [](const NGeo& g) { std::string t; for (int i = 0; i < g.np; ++i) t += (i ? "x" : "") + std::to_string(g.r[i]); return t; };
+    std::string cs_, rs_;
+    if (plan->n_c.rt) {
+        const NGeo& g = plan->n_c.geo;
+        if (plan->n_rad_p) {
+            std::string a, b;
+            for (int r : plan->n_rq) a += (a.empty() ? "" : "x") + std::to_string(r);
+            for (int r : plan->n_rp) b += (b.empty() ? "" : "x") + std::to_string(r);
+            appendf(cs_, "lengths as data, %d thr, %d packed column pairs (FFT%d = %d r%s x prime %d: the prime-factor form, Rader's cyclic convolution of %d = %s points along the prime, in LDS), lds=%zuB",
+                    g.thr, g.g, g.n, g.n / plan->n_rad_p, a.c_str(), plan->n_rad_p, plan->n_rad_p - 1, b.c_str(), plan->n_c.lds);
+        } else
+        appendf(cs_, "lengths as data, %d thr, %d packed column pairs (FFT%d r%s in LDS%s), lds=%zuB", g.thr, g.g, g.n, rads(g).c_str(),
+                plan->n_blue_m ? ": a chirp convolution" : "", plan->n_c.lds);
+    } else {
+        const MGeomRt C = mgeom_cols(plan->yny, plan->ynx, plan->dbl);
+        appendf(cs_, "table kernel, %d thr, %d packed column pairs (FFT%lld r%dx%dx%d)", C.thr, C.g, (long long)plan->yny, C.r0, C.r1, C.r2);
+    }
+    if (plan->n_r.rt) {
+        const NGeo& g = plan->n_r.geo;
+        appendf(rs_, "lengths as data, %d thr, %d rows/unit (FFT%d r%s), lds=%zuB", g.thr, plan->n_rpu, g.n, rads(g).c_str(), plan->n_r.lds);
+    } else {
+        const MGeomRt R = mgeom(plan->ynx, plan->dbl);
+        appendf(rs_, "table kernel, %d thr, %d rows/unit (FFT%lld r%dx%dx%d)", R.thr_r1, plan->n_rpu, (long long)plan->ynx, R.r0, R.r1, R.r2);
+    }
+    appendf(s, "  [fastn] cols: %s -> W2[slab][%d/%d][%d][%d][%d] complex -> fit -> rows: %s, trend added back in the spectral domain, fftshift + mirror rows%s\n",
+            cs_.c_str(), plan->y_nrow_pad, plan->n_rk, plan->n_nxb, plan->n_rk, plan->n_cw, rs_.c_str(), in_note);
+    if (plan->n_blue_m)
+        appendf(s, "  [fastn Bluestein] the %lld-point columns as a circular convolution of %d inside the tile (chirp products, two forward transforms)\n", (long long)plan->yny, plan->n_blue_m);
+    if ((plan->d.flags & XRFTHIP_ISO) && plan->nbins > 0)
+        appendf(s, "  [fastn radial sums] %s\n", fastm_iso_gather(plan) ? "fused into the row pass: radial map, per-bin gather from the spectra in LDS, no atomics"
+                                               : fastm_iso_fused(plan) ? "fused into the row pass: int64 fixed-point tables behind the transforms' LDS"
+                                                                       : "a pass over the stored spectrum");
+}
+static void describe_fastmx(const xrfthip_plan* plan, std::string& s, const char*) {
+    const MGeomRt C = mxgeom(plan->d.nx, plan->dbl);
+    appendf(s, "  [fastm x-only] %d thr, %d row pairs per workgroup (FFT%lld r%dx%dx%d in LDS), lds=%zuB: per-row detrend + window + transform + full (or half) spectrum in one pass\n",
+            C.thr, C.g, (long long)plan->d.nx, C.r0, C.r1, C.r2, C.lds_cols);
+}
+static void describe_fastmy(const xrfthip_plan* plan, std::string& s, const char*) {
+    const MGeomRt C = mygeom(plan->d.ny, plan->dbl);
+    appendf(s, "  [fastm y-only] %d thr, %d packed column pairs (FFT%lld r%dx%dx%d in LDS), lds=%zuB: per-column detrend + window + transform + both halves of the spectrum in one pass, in place in memory order\n",
+            C.thr, C.g, (long long)plan->d.ny, C.r0, C.r1, C.r2, C.lds_cols);
+}
+static void info_fastm(const xrfthip_plan* P, int32_t* k, int32_t* n) { *k = P->family == Family::FastN ? XRFTHIP_K_FASTN : XRFTHIP_K_FASTM; *n = plan_cw(P); }
+static void info_fastmx(const xrfthip_plan* P, int32_t* k, int32_t* n) {
+    *k = XRFTHIP_K_FASTM_X;
+    const MGeomRt C = mxgeom(P->d.nx, P->dbl);
+    *n = (plan_two(P) || (P->cplx_in && !(P->d.flags & XRFTHIP_C2R_X))) ? C.g : 2 * C.g;
+}
+static void info_fastmy(const xrfthip_plan* P, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTM_Y; *n = ((P->cplx_in || plan_two(P)) ? 1 : 2) * mygeom(P->d.ny, P->dbl).g; }
+static bool fastn_uses_bluestein(const xrfthip_plan* P) { return P->n_blue_m > 0; }
+// (the entries in the order of struct FamilyOps: family, run, describe, kernel_info, finalize, layout, binmap, uses_bluestein, reads_strided, strided_if, dbl_tables, two_pass_y, fastm_pipeline;
+//  a radial bin map: the fused radial sums are gathered per bin, fastm_rows_kernel)
+#ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
+const FamilyOps kOpsFastM = {Family::FastM, run_fastm, describe_fastm, info_fastm, two_pass_tables, layout_passes, fastm_build_tfirst, nullptr, true, nullptr, true, true, true};
+const FamilyOps kOpsFastN = {Family::FastN, run_fastm, describe_fastn, info_fastm, two_pass_tables, layout_passes, fastm_build_tfirst, fastn_uses_bluestein, true, nullptr, true, true, true};
+const FamilyOps kOpsFastMX = {Family::FastMX, run_fastmx, describe_fastmx, info_fastmx, fast_phase_tables, layout_passes, nullptr, nullptr, false, nullptr, true};
+const FamilyOps kOpsFastMY = {Family::FastMY, run_fastmy, describe_fastmy, info_fastmy, fast_phase_tables, layout_passes, nullptr, nullptr, false, nullptr, true};
+#endif
+
 
 template int fastn_upload_twm<float>(const NGeo&, DevBuf&, bool);
 template int fastn_upload_twm<double>(const NGeo&, DevBuf&, bool);
-template int fastn_blue_tables<float>(xrfthip_plan*);
-template int fastn_blue_tables<double>(xrfthip_plan*);
 
 // kernels of this unit that take more than 64 KB of dynamic LDS (the mixed-radix and run-time-radix kernels): called once through set_kernel_attrs_once()
 void set_attrs_fastm() {

@@ -4,6 +4,7 @@
 // (rolling the input by n/2 -- xrft.py:436-441 -- is that sign in the spectrum; in a cross spectrum the two signs cancel)
 int fast_phase_tables(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
+    if (d.out_mode == XRFTHIP_OUT_POWER) return XRFTHIP_OK;  // (the complex modes only)
     P->fph_on = false;
     for (int ax = 0; ax < 2; ++ax) {
         const long long n = ax == 0 ? d.ny : d.nx;
@@ -43,15 +44,15 @@ bool cross_iso_phase(const xrfthip_plan* P) {
 // ---------------------------------------------------------------------------------------------------------------
 // two-pass "y first" pipeline (fasty.h): full float32 power spectra of power-of-two slabs
 // ---------------------------------------------------------------------------------------------------------------
-template <int NY> YGeomRt ycols_geom_t() {
+template <int NY> static YGeomRt ycols_geom_t() {
     typedef YCols<NY> Y;
     return {Y::THR, Y::GY, Y::CW, Y::RK, Y::LBS, (size_t)(Y::GY * YLds<NY, Y::GY>::GSTR + 16 * P2<NY>::R3) * sizeof(cf) + (size_t)(Y::THR / 64) * Y::GY * 8 * sizeof(double)};
 }
-template <int NX, bool FS = false> YGeomRt yrows_geom_t() {
+template <int NX, bool FS = false> static YGeomRt yrows_geom_t() {
     typedef YRows<NX, FS> R;
     return {R::THR, R::GX, 0, R::RPU, 0, (size_t)(R::GX * YLds<NX, R::GX>::GSTR + 16 * P2<NX>::R3) * sizeof(cf)};
 }
-int ycols_gstr(long long ny) {  // complex elements of LDS per packed column pair of pass 1 (YLds<NY, GY>::GSTR)
+static int ycols_gstr(long long ny) {  // complex elements of LDS per packed column pair of pass 1 (YLds<NY, GY>::GSTR)
     switch (ny) { case 4096: return YLds<4096, YCols<4096>::GY>::GSTR; case 2048: return YLds<2048, YCols<2048>::GY>::GSTR; case 1024: return YLds<1024, YCols<1024>::GY>::GSTR;
                   case 512: return YLds<512, YCols<512>::GY>::GSTR; default: return YLds<256, YCols<256>::GY>::GSTR; }
 }
@@ -65,12 +66,11 @@ YGeomRt yrows_geom(long long nx, bool fs) {  // .rk = rows per workgroup; fs: th
                   case 512: return yrows_geom_t<512>(); default: return yrows_geom_t<256>(); }
 }
 long long fasty_rows_gx(const xrfthip_plan* P) { return yrows_geom(P->ynx, P->family == Family::FastY1D).gxy; }
-int ilog2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 // Four-step 1-D with a window w[n], n = nx i1 + i2: the slab-shaped float32 window table pass 1 reads, and -- column i2 of the view has
 // its own window w[nx i1 + i2] -- the per-column transforms FFT_i1(w) and FFT_i1(w (i1 - ibar)) as tables [i2][k1 < nrow_pad] that carry
 // the residual line back in pass 2 (fasty_rows_kernel, W2D).  Host, once per plan: nx transforms of ny points each.
-int fasty_window_spectra_1d(xrfthip_plan* P) {
+static int fasty_window_spectra_1d(xrfthip_plan* P) {
     const int ny = (int)P->yny, nx = (int)P->ynx, nyh = ny / 2, nent = P->y_nrow_pad;
     const std::vector<double>& w = P->host_win_x;
     if ((long long)w.size() != (long long)ny * nx) return XRFTHIP_BAD_ARG;
@@ -101,7 +101,7 @@ int fasty_window_spectra_1d(xrfthip_plan* P) {
 }
 
 // FFT_y(wy) and FFT_y(wy (i - ibar)) for ky < nrow_pad (zero beyond ny/2): what pass 2 needs to add the residual trend back
-int fasty_window_spectra(xrfthip_plan* P) {
+static int fasty_window_spectra(xrfthip_plan* P) {
     const int ny = (int)P->yny, nyh = ny / 2;
     std::vector<double> r0((size_t)ny), i0((size_t)ny, 0.0), r1((size_t)ny), i1((size_t)ny, 0.0);
     for (int i = 0; i < ny; ++i) {
@@ -183,44 +183,12 @@ int build_unit_windows(xrfthip_plan* P, const int32_t* bm, int rpu) {
     return rcf;
 }
 
-// fastm: is the bin map a radial one (see fastm_rows_kernel, ISO)?  If so: first[ky][b] = the smallest |kx| <= nx/2 whose bin is >= b
-// (nx/2 + 1 if none), b = 0 .. nbins, and the unit windows.  Any nx (the lengths of the table are even; odd ones would work).
-int fastm_build_tfirst(xrfthip_plan* P, const int32_t* bm) {
-    const int ny = (int)P->yny, nx = (int)P->ynx, nyh = ny / 2, H = nx / 2, HM = (nx - 1) / 2;
-    bool radial = env_ll("XRFTHIP_ISO_GATHER", 1) != 0 && P->nbins < 65535 && H + 1 < 65535;
-    for (int ky = 0; ky <= nyh && radial; ++ky) {
-        const int32_t* r = bm + (size_t)ky * nx;
-        const bool twin = ky != 0 && 2 * ky != ny;
-        const int32_t* t = bm + (size_t)(twin ? ny - ky : ky) * nx;
-        for (int m = 0; m <= H; ++m) {
-            const int32_t c = r[m];
-            if (c < 0 || c >= P->nbins || (m > 0 && c < r[m - 1]) || (m >= 1 && m <= HM && r[nx - m] != c)) { radial = false; break; }
-            if (twin && (t[m] != c || t[(nx - m) % nx] != c)) { radial = false; break; }
-        }
-    }
-    P->ytfirst_on = radial;
-    if (!radial) return XRFTHIP_OK;
-    std::vector<uint16_t> f((size_t)(nyh + 1) * (P->nbins + 1), (uint16_t)(H + 1));
-    for (int ky = 0; ky <= nyh; ++ky) {
-        const int32_t* r = bm + (size_t)ky * nx;
-        uint16_t* dst = f.data() + (size_t)ky * (P->nbins + 1);
-        int m = 0;
-        for (int b = 0; b <= P->nbins; ++b) {
-            while (m <= H && r[m] < b) ++m;
-            dst[b] = (uint16_t)m;
-        }
-    }
-    int rc = P->ytfirst.upload(f.data(), f.size() * sizeof(uint16_t));
-    if (!rc) rc = build_unit_windows(P, bm, fastm_gather_rpu(P));
-    return rc;
-}
-
 // the bin map as pass 2 reads it (fasty_rows_kernel).  Full form: [ky < nrow_pad][kx] in natural order,
 // value = (bin of (ky, kx) + 1) | (bin of the mirror (-ky, -kx) + 1) << 16; rows beyond ny/2 and unbinned samples are 0.
 // Compact form, when the map has the structure of a radial one (every sample of rows 0 .. ny/2 binned; along a half row the bin
 // never decreases / never increases and moves by at most one per sample; the mirror sample is in the same bin except on the
 // self-mirrored rows 0 and ny/2): [ky][kx / 16] = (first sample's bin + 1) | step mask << 16 -- 1/16 of the bytes.
-int fasty_build_tcodes(xrfthip_plan* P, const int32_t* bm) {
+static int fasty_build_tcodes(xrfthip_plan* P, const int32_t* bm) {
     const int ny = (int)P->yny, nx = (int)P->ynx, nyh = ny / 2;
     bool compact = env_ll("XRFTHIP_ISO_COMPACT", 1) != 0 && nx % 32 == 0;
     for (int ky = 0; ky <= nyh && compact; ++ky)
@@ -302,7 +270,7 @@ int fasty_build_tcodes(xrfthip_plan* P, const int32_t* bm) {
     return P->ytcodes.upload(t.data(), t.size() * sizeof(uint32_t));
 }
 // the radial-sum tables of one round share the transforms' LDS with the staged half of the workgroup's rows: they must fit the other half
-bool fasty_iso_tables_fit(const xrfthip_plan* P, int nbins) {
+static bool fasty_iso_tables_fit(const xrfthip_plan* P, int nbins) {
     const YGeomRt R = yrows_geom(P->ynx);
     const size_t half = (size_t)R.gxy * (size_t)(P->ynx + P->ynx / 16) * 4;  // GX rows of floats = GX / 2 rows of complex
     const size_t hw = P->d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1;
@@ -311,7 +279,7 @@ bool fasty_iso_tables_fit(const xrfthip_plan* P, int nbins) {
 
 // Workgroups of `kernel` the whole device holds at once (a persistent launch's grid): the occupancy calculator's count per CU times the CUs,
 // asked once per kernel.
-long long resident_workgroups(const void* kernel, int threads, size_t lds) {
+static long long resident_workgroups(const void* kernel, int threads, size_t lds) {
     static std::mutex mu;
     static std::map<const void*, long long> memo;
     std::lock_guard<std::mutex> lock(mu);
@@ -326,7 +294,7 @@ long long resident_workgroups(const void* kernel, int threads, size_t lds) {
     return n;
 }
 
-void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof) {
+static void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof) {
     const xrfthip_desc& d = P->d;
     const YGeomRt C = ycols_geom(P->yny);
     xrfthip_plan::ProfRec* rec = prof ? prof_begin(P, "fasty_cols", st) : nullptr;
@@ -356,7 +324,7 @@ void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long gc, hipS
     }
 }
 
-void fasty_launch_rows(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof) {
+static void fasty_launch_rows(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof) {
     const xrfthip_desc& d = P->d;
     const YGeomRt R = yrows_geom(P->ynx, P->family == Family::FastY1D);
     const bool iso_on = (d.flags & XRFTHIP_ISO) != 0;
@@ -428,7 +396,7 @@ void fasty_launch_rows(const xrfthip_plan* P, const FastY& p, long long gc, hipS
 }
 
 // parameter block of one group of slabs [g0, g0 + gc): the intermediate and the fit tables sit in ring slot `slot` (of slot_slabs slabs each)
-FastY fasty_params(const xrfthip_plan* P, const float* in, void* out, double* iso, char* ws, long long g0, long long gc, int slot, long long slot_slabs) {
+static FastY fasty_params(const xrfthip_plan* P, const float* in, void* out, double* iso, char* ws, long long g0, long long gc, int slot, long long slot_slabs) {
     // (slot 0 = field 0 / the only field, slot 1 = field 1 of a cross spectrum: its own intermediate and fit tables)
     const xrfthip_desc& d = P->d;
     const size_t slab_pts = (size_t)P->yny * P->ynx;
@@ -554,8 +522,10 @@ int try_fastyc(xrfthip_plan* P) {
     return rc ? rc : plan_ones(P, 4096);
 }
 
-int run_fasty(const xrfthip_plan* P, const float* in, const float* in1, void* out, double* iso, char* ws, hipStream_t st) {
+static int run_fasty(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    const float *in = (const float*)a.in0, *in1 = (const float*)a.in1;
+    void* out = a.out; double* iso = a.iso; char* ws = a.ws; hipStream_t st = a.stream;
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
     for (long long g0 = 0; g0 < d.batch; g0 += P->G) {
         const long long gc = std::min<long long>(P->G, d.batch - g0);
@@ -578,8 +548,9 @@ int run_fasty(const xrfthip_plan* P, const float* in, const float* in1, void* ou
 }
 
 // the two-pass pipeline on complex float32 slabs (fasty_c2c.h): columns -> rows, group by group
-int run_fastyc(const xrfthip_plan* P, const void* in, void* out, char* ws, hipStream_t st) {
+static int run_fastyc(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d0 = P->d;
+    const void* in = a.in0; void* out = a.out; char* ws = a.ws; hipStream_t st = a.stream;
     // (the four-step form: every batch entry is ONE sequence of d.nx points, transformed as the [d.nx / 256][256] view)
     const bool fs = P->family == Family::FastYCFourStep;
     struct { long long batch, ny, nx; uint32_t flags; int out_mode; double scale; } d{d0.batch, fs ? d0.nx / 256 : d0.ny, fs ? 256 : d0.nx, d0.flags, d0.out_mode, d0.scale};
@@ -644,6 +615,110 @@ int run_fastyc(const xrfthip_plan* P, const void* in, void* out, char* ws, hipSt
     }
     return XRFTHIP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// the rows of FastY, FastY1D, FastYC and FastYCFourStep (plan.h, FamilyOps)
+// ---------------------------------------------------------------------------------------------------------------
+// the tables of the two y-first passes that depend on a window / a phase (FastY, FastM, FastN; the fused inner passes)
+int two_pass_tables(xrfthip_plan* P) {
+    const int rc = fasty_window_spectra(P);
+    return rc ? rc : fast_phase_tables(P);
+}
+static int finalize_fast1d(xrfthip_plan* P) {
+    P->fast1d_win = !P->host_win_x.empty();  // (a window rides on a slab-shaped table)
+    const int rc = P->fast1d_win ? fasty_window_spectra_1d(P) : fasty_window_spectra(P);
+    return rc ? rc : fast_phase_tables(P);
+}
+static int finalize_fastyc_four_step(xrfthip_plan* P) {
+    int rc = fast_phase_tables(P);
+    if (rc) return rc;
+    // a window has no separable form over the view; an input phase (PHASE_IN: the lag's factor on the source samples) must be one -- exp(i theta n) is:
+    // row factor ph[256 i1], column factor ph[i2] / ph[0]; checked, else the generic passes take the plan
+    bool ok = P->host_win_x.empty() && !P->win[1].p;
+    if (ok && (P->d.flags & XRFTHIP_PHASE_IN) && P->fph_on) {
+        const std::vector<double>& h = P->host_phase[1];
+        const long long n = P->d.nx, vy = n / 256;
+        ok = (long long)h.size() >= 2 * n;
+        std::vector<cf> py((size_t)vy), px(256);
+        if (ok) {
+            const double r0 = h[0], i0 = h[1], m0 = r0 * r0 + i0 * i0;
+            for (long long i1 = 0; i1 < vy; ++i1) { py[(size_t)i1].re = (float)h[(size_t)(512 * i1)]; py[(size_t)i1].im = (float)h[(size_t)(512 * i1 + 1)]; }
+            for (int i2 = 0; i2 < 256; ++i2) {  // ph[i2] conj(ph[0]) / |ph[0]|^2
+                const double re = h[(size_t)(2 * i2)], im = h[(size_t)(2 * i2 + 1)];
+                px[(size_t)i2].re = (float)((re * r0 + im * i0) / m0); px[(size_t)i2].im = (float)((im * r0 - re * i0) / m0);
+            }
+            double worst = 0.0;
+            for (long long nn = 0; nn < n; ++nn) {  // (every product: one O(n) host pass when the table is set; a sample let a single wrong entry through)
+                const long long i1 = nn / 256; const int i2 = (int)(nn % 256);
+                const double yr = h[(size_t)(512 * i1)], yi = h[(size_t)(512 * i1 + 1)], xr = (h[(size_t)(2 * i2)] * r0 + h[(size_t)(2 * i2 + 1)] * i0) / m0, xi = (h[(size_t)(2 * i2 + 1)] * r0 - h[(size_t)(2 * i2)] * i0) / m0;
+                worst = std::max(worst, std::hypot(yr * xr - yi * xi - h[(size_t)(2 * nn)], yr * xi + yi * xr - h[(size_t)(2 * nn + 1)]));
+            }
+            ok = worst < 1e-9 && m0 > 0.0;
+        }
+        if (ok) {
+            rc = P->fph[0].upload(py.data(), py.size() * sizeof(cf));
+            if (!rc) rc = P->fs_phx.upload(px.data(), px.size() * sizeof(cf));
+        }
+    }
+    if (!rc && !ok) settle_family(P, true);  // (the generic four-step passes)
+    return rc;
+}
+// the tiled intermediate of one group of slabs
+static void layout_fastyc(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    long long G = d.slabs_per_group > 0 ? d.slabs_per_group : (P->tune_fast_group > 0 ? P->tune_fast_group : std::max<long long>(1, (32LL * 4096 * 4096) / (d.ny * d.nx)));
+    G = std::max<long long>(1, std::min<long long>(G, std::max<long long>(d.batch, 1)));
+    P->G = (int)G;
+    P->off_w = 0;
+    size_t w2_cols = (size_t)d.nx;  // complex columns of the intermediate per row
+    if (d.flags & XRFTHIP_C2R_X) { const size_t cw = 2 * (size_t)ycols_geom(d.ny).gxy; w2_cols = (size_t)d.nx / 2 + cw; }  // (+ the block of the Nyquist column)
+    P->ws_bytes = (((size_t)G * (size_t)d.ny * w2_cols * sizeof(cf)) + 255) & ~(size_t)255;
+}
+static int fasty_binmap(xrfthip_plan* P, const int32_t* bm) {
+    const int rc = fasty_build_tcodes(P, bm);
+    if (!rc && !P->ytfirst_on && !fasty_iso_tables_fit(P, P->nbins)) settle_family(P, true);  // (any map: the atomic tables alias half of the transforms' LDS)
+    return rc;
+}
+static void describe_fasty(const xrfthip_plan* plan, std::string& s, const char* in_note) {
+    const bool fs = plan->family == Family::FastY1D;
+    const YGeomRt C = ycols_geom(plan->yny), R = yrows_geom(plan->ynx, fs);
+    if (fs) appendf(s, "  [fasty four-step] %lld samples = [%lld][%lld]: columns = step 1 (half spectrum k1 <= %lld), rows x W_N^(i2 k1) = step 2, transposed stores + Hermitian mirror\n",
+                              (long long)plan->d.nx, (long long)plan->yny, (long long)plan->ynx, (long long)plan->yny / 2);
+    appendf(s, "  [fasty] cols: %d thr, %d x 2 packed column pairs (FFT%lld r16x16x%lld, column-local detrend fused), %d columns/unit, lds=%zuB -> W2[slab][%d/%d][nx/%d][2][%d][%d] -> rows: %d thr, %d rows/unit (FFT%lld r16x16x%lld), lds=%zuB, |F|^2 + fftshift + mirror rows%s\n",
+            C.thr, C.gxy, (long long)plan->d.ny, (long long)plan->d.ny / 256, C.cw, C.lds, plan->y_nrow_pad, C.rk, C.cw, C.rk, 2 * C.gxy,
+            R.thr, R.rk, (long long)plan->d.nx, (long long)plan->d.nx / 256, R.lds, in_note);
+    if ((plan->d.flags & XRFTHIP_ISO) && plan->ytcodes.p)
+        appendf(s, "  [fasty radial sums] fused into the row pass (runs of equal bins from the staged rows, int64 fixed-point tables), bin codes: %s\n",
+                plan->ytfirst_on ? "radial map: per-bin gather, no atomics" : plan->ytcodes_compact ? "compact (radial map: first bin + step mask per 16 samples)" : "full (4 bytes per sample)");
+}
+static void describe_fastyc(const xrfthip_plan* plan, std::string& s, const char*) {
+    const YGeomRt C = ycols_geom(plan->d.ny), R = yrows_geom(plan->d.nx);
+    if (plan->d.flags & XRFTHIP_C2R_X) {
+        const YGeomRt R2 = yrows_geom(plan->d.nx / 2);
+        appendf(s, "  [fasty complex] cols: %d thr, %d x 2 adjacent complex columns of the half spectrum (FFT%lld, inverse: conjugate in / out) + one block for the Nyquist column, "
+                   "%d columns/unit -> W2 -> rows: %d thr, %d rows/unit: the half spectrum of a row back to %lld real samples (FFT%lld on the packed row), whole rows out; "
+                   "16 B per point through memory\n", C.thr, C.gxy, (long long)plan->d.ny, 2 * C.gxy, R2.thr, R2.rk, (long long)plan->d.nx, (long long)plan->d.nx / 2);
+    } else
+    appendf(s, "  [fasty complex] cols: %d thr, %d x 2 adjacent complex columns (FFT%lld, %s), %d columns/unit -> W2[slab][%lld/%d][nx/%d][%d][%d] -> rows: %d thr, %d rows/unit "
+               "(FFT%lld), whole rows out (scale, %sfftshift); 32 B per point through memory\n",
+            C.thr, C.gxy, (long long)plan->d.ny, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse: conjugate in / out" : "forward", 2 * C.gxy, (long long)plan->d.ny,
+            std::max(1, 16 / (2 * C.gxy)), 2 * C.gxy, std::max(1, 16 / (2 * C.gxy)), 2 * C.gxy, R.thr, R.rk, (long long)plan->d.nx, plan->fph_on ? "phase, " : "");
+}
+static void describe_fastyc_four_step(const xrfthip_plan* plan, std::string& s, const char*) {
+    const YGeomRt C = ycols_geom(plan->d.nx / 256), R = yrows_geom(256);
+    appendf(s, "  [fasty complex rows, four-step] two passes over the [%lld][256] view of every %lld-point sequence: cols: %d thr, FFT%lld along the view's rows index (input rotation / lag phase / "
+               "conjugation on load) -> W2 in whole lines -> rows: %d thr, %d rows/unit x W_N^(i2 k1), FFT256, stored transposed (X[k1 + %lld k2]: runs of %d samples)%s; 32 bytes per point through memory\n",
+            (long long)plan->d.nx / 256, (long long)plan->d.nx, C.thr, (long long)plan->d.nx / 256, R.thr, R.rk, (long long)plan->d.nx / 256, R.rk / 2,
+            (plan->d.flags & XRFTHIP_INVERSE) ? "; inverse: conjugate in / out" : "");
+}
+static void info_fasty(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTY; *n = 0; }
+// (the entries in the order of struct FamilyOps: family, run, describe, kernel_info, finalize, layout, binmap, uses_bluestein, reads_strided, strided_if, dbl_tables, two_pass_y)
+#ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
+const FamilyOps kOpsFastY = {Family::FastY, run_fasty, describe_fasty, info_fasty, two_pass_tables, layout_passes, fasty_binmap, nullptr, true, nullptr, false, true};
+const FamilyOps kOpsFastY1D = {Family::FastY1D, run_fasty, describe_fasty, info_fasty, finalize_fast1d, layout_passes, nullptr, nullptr, false, nullptr, false, true};
+const FamilyOps kOpsFastYC = {Family::FastYC, run_fastyc, describe_fastyc, info_fasty, fast_phase_tables, layout_fastyc};
+const FamilyOps kOpsFastYCFourStep = {Family::FastYCFourStep, run_fastyc, describe_fastyc_four_step, info_fasty, finalize_fastyc_four_step, layout_fastyc};
+#endif
 
 
 // kernels of this unit that take more than 64 KB of dynamic LDS (the y-first float32 kernels): called once through set_kernel_attrs_once()

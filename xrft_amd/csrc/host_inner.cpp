@@ -3,7 +3,8 @@
 // ---------------------------------------------------------------------------------------------------------------
 // xrfthip_desc.inner > 1 as two fused passes (fastn.h, round 5): 16 bytes per sample through memory where the composite of two one-axis plans moves 32
 // ---------------------------------------------------------------------------------------------------------------
-int fusedi_tables(xrfthip_plan* P) {  // what depends on the windows / phases: called from finalize_plan
+static void fusedi_layout(xrfthip_plan* P);
+static int fusedi_tables(xrfthip_plan* P) {  // what depends on the windows / phases: the row's finalize (its workspace layout does not depend on the tables)
     const xrfthip_desc& d = P->d;
     const long long ne = std::max<long long>(d.inner, std::max<long long>(d.mid, 1)), ncol = d.nx * ne;
     const long long sx = d.mid > 1 ? 1 : d.inner, se = d.mid > 1 ? d.nx : 1;
@@ -12,13 +13,11 @@ int fusedi_tables(xrfthip_plan* P) {  // what depends on the windows / phases: c
         const double w = P->host_win_x.empty() ? 1.0 : P->host_win_x[(size_t)x];
         for (long long e = 0; e < ne; ++e) wexp[(size_t)(x * sx + e * se)] = w;
     }
-    int rc = upload_real_table(P, P->winx_exp, wexp.data(), ncol, 0);
-    if (!rc) rc = fasty_window_spectra(P);
-    if (!rc && d.out_mode != XRFTHIP_OUT_POWER) rc = fast_phase_tables(P);
-    return rc;
+    const int rc = upload_real_table(P, P->winx_exp, wexp.data(), ncol, 0);
+    return rc ? rc : two_pass_tables(P);
 }
 
-xrfthip_plan* create_fused_inner(const xrfthip_desc& d) {
+static xrfthip_plan* create_fused_inner(const xrfthip_desc& d) {
     if (env_ll("XRFTHIP_NO_FAST", 0) || !env_ll("XRFTHIP_FASTN", 1) || !env_ll("XRFTHIP_FUSED_INNER", 1)) return nullptr;
     // (the independent elements innermost, or between the two axes -- not both)
     if (d.ndim != 2 || !((d.mid <= 1 && d.inner >= 2) || (d.mid >= 2 && d.inner <= 1)) || (d.dtype != XRFTHIP_F32 && d.dtype != XRFTHIP_F64)) return nullptr;
@@ -128,7 +127,7 @@ xrfthip_plan* create_fused_inner(const xrfthip_desc& d) {
 
 // workspace: the intermediate of one group of slabs, the column sums, the plane corrections -- and, with radial sums, their per-(slab, element, row ky) partial table
 // (known once the bin map has arrived: xrfthip_plan_set_binmap lays the workspace out again)
-void fusedi_layout(xrfthip_plan* P) {
+static void fusedi_layout(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
     const bool crossm = d.out_mode == XRFTHIP_OUT_CROSS;
     const long long ne = std::max<long long>(d.inner, std::max<long long>(d.mid, 1)), ncol = d.nx * ne;
@@ -151,7 +150,7 @@ void fusedi_layout(xrfthip_plan* P) {
 // binned, along a row the bin depends on |kx| only and never decreases with it, the Hermitian twin (-ky, -kx) of a sample in the sample's bin (pd.cut of
 // sqrt(ky^2 + kx^2) is, for any spacings: xrft.py:975-981).  Builds first[ky][b] = the smallest |kx| <= nx/2 of row ky whose bin is >= b (nx/2 + 1 if none), b = 0 .. nbins,
 // the bins each row reaches and the rows that reach each bin.  Any other map: XRFTHIP_BAD_ARG (there is no other path to the sums where the axes lie).
-int fusedi_build_iso(xrfthip_plan* P, const int32_t* bm) {
+static int fusedi_build_iso(xrfthip_plan* P, const int32_t* bm) {
     const int ny = (int)P->d.ny, nx = (int)P->d.nx, nyh = ny / 2, H = nx / 2, HM = (nx - 1) / 2, nb = P->nbins;
     if (nb >= 65535 || H + 1 >= 65535) return XRFTHIP_BAD_ARG;
     for (int ky = 0; ky <= nyh; ++ky) {
@@ -196,8 +195,10 @@ int fusedi_build_iso(xrfthip_plan* P, const int32_t* bm) {
     return rc;
 }
 
-int run_fused_inner(const xrfthip_plan* P, const void* in, const void* in1, void* out, double* iso, char* ws, hipStream_t st) {
+static int run_fused_inner(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    const void *in = a.in0, *in1 = a.in1;
+    void* out = a.out; double* iso = a.iso; char* ws = a.ws; hipStream_t st = a.stream;
     const bool midlay = d.mid >= 2, crossm = d.out_mode == XRFTHIP_OUT_CROSS;
     const long long ne = midlay ? d.mid : d.inner, ncol = d.nx * ne;
     const int sx = midlay ? 1 : (int)d.inner, se = midlay ? (int)d.nx : 1;
@@ -343,8 +344,9 @@ int create_inner_plan(xrfthip_plan** plan, const xrfthip_desc& d) {
     return XRFTHIP_OK;
 }
 
-int run_inner_plan(const xrfthip_plan* P, const void* in, void* out, char* ws, hipStream_t st) {
+static int run_inner_plan(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    const void* in = a.in0; void* out = a.out; char* ws = a.ws; hipStream_t st = a.stream;
     const void* cur = in;
     if (d.detrend) {
         int rc = run_detrend_inner(d.dtype, 2, d.batch * d.mid, d.ny, d.nx, d.inner, d.detrend, in, ws + P->off_det, ws + P->off_dws, st, d.mid);
@@ -356,3 +358,43 @@ int run_inner_plan(const xrfthip_plan* P, const void* in, void* out, char* ws, h
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the rows of FusedInner and Composite (plan.h, FamilyOps): a header of their own in describe, a workspace laid out when the plan is created
+// ---------------------------------------------------------------------------------------------------------------
+static void describe_fused_inner(const xrfthip_plan* plan, std::string& s, const char*) {
+    const xrfthip_desc& d = plan->d;
+    auto rads = [](const NGeo& g) { std::string t; for (int i = 0; i < g.np; ++i) t += (i ? "x" : "") + std::to_string(g.r[i]); return t; };
+    const NGeo &gc = plan->n_c.geo, &gr = plan->n_r.geo;
+    appendf(s, "xrfthip plan: [batch %lld][ny %lld][mid %lld][nx %lld][inner %lld] dtype=%d mode=%d detrend=%d flags=0x%x ws=%zuB\n"
+               "  [inner layout] [fastn fused] two passes where the axes lie, no transposed copy: cols: the [ny][mid nx inner] view, %d thr, %d packed column pairs (FFT%d r%s), lds=%zuB -> "
+               "W2[slab][%d/%d][%d][%d][%d] complex -> fit per (slab, inner element) -> rows: %d thr, %d independent elements of one row ky per workgroup (FFT%d r%s), lds=%zuB, plane added "
+               "back in the spectral domain, (ky, kx, e) and its Hermitian twin stored as runs of %d elements\n",
+            (long long)d.batch, (long long)d.ny, (long long)plan->mid, (long long)d.nx, (long long)plan->inner, d.dtype, d.out_mode, d.detrend, d.flags, plan->ws_bytes,
+            gc.thr, gc.g, gc.n, plan->n_rad_p ? ("Rader, prime " + std::to_string(plan->n_rad_p)).c_str() : rads(gc).c_str(), plan->n_c.lds, plan->y_nrow_pad, plan->n_rk, plan->n_nxb, plan->n_rk, plan->n_cw, gr.thr, gr.g, gr.n, rads(gr).c_str(), plan->n_r.lds, gr.g);
+    if (d.flags & XRFTHIP_ISO)
+        appendf(s, "  [inner layout] [fastn fused iso] the row pass gathers, per element and bin the row reaches, the bin's samples from LDS in float64 (one thread, a fixed order, no atomics) "
+                   "-> partial[slab][element][ky][%d bins] (%zuB per slab) -> added over ky in order: per-element radial sums%s\n",
+                plan->nbins, (size_t)(d.ny / 2 + 1) * (size_t)std::max<long long>(plan->inner, plan->mid) * (size_t)plan->nbins * (d.out_mode == XRFTHIP_OUT_CROSS ? 16 : 8),
+                (d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? "; the spectrum is not stored" : "");
+}
+static void describe_composite(const xrfthip_plan* plan, std::string& s, const char*) {
+    const xrfthip_desc& d = plan->d;
+    appendf(s, "xrfthip plan: [batch %lld][ny %lld][mid %lld][nx %lld][inner %lld] dtype=%d mode=%d detrend=%d flags=0x%x ws=%zuB\n  [inner layout] no transposed copy: %sx where it lies, then y\n",
+            (long long)d.batch, (long long)d.ny, (long long)plan->mid, (long long)d.nx, (long long)plan->inner, d.dtype, d.out_mode, d.detrend, d.flags, plan->ws_bytes,
+            d.detrend ? "detrend pass (plane per (batch, inner) element), " : "");
+    for (const xrfthip_plan* sp : {plan->sub_x, plan->sub_y}) {
+        std::vector<char> tmp(4096);
+        xrfthip_plan_describe(sp, tmp.data(), tmp.size());
+        s += "  ";
+        for (const char* c = tmp.data(); *c; ++c) { s += *c; if (*c == '\n' && c[1]) s += "  "; }
+    }
+}
+static void info_fused_inner(const xrfthip_plan* P, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTN; *n = P->n_cw; }
+static void info_composite(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTHIP_K_COMPOSITE; *n = 0; }
+static bool composite_uses_bluestein(const xrfthip_plan* P) { return xrfthip_plan_uses_bluestein(P->sub_x) || xrfthip_plan_uses_bluestein(P->sub_y); }
+// (the entries in the order of struct FamilyOps: family, run, describe, kernel_info, finalize, layout, binmap, uses_bluestein, reads_strided, strided_if, dbl_tables, two_pass_y, fastm_pipeline, inner_layout;
+//  FusedInner's bin map: a radial map, or XRFTHIP_BAD_ARG)
+#ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
+const FamilyOps kOpsFusedInner = {Family::FusedInner, run_fused_inner, describe_fused_inner, info_fused_inner, fusedi_tables, nullptr, fusedi_build_iso, nullptr, false, nullptr, true, false, false, true};
+const FamilyOps kOpsComposite = {Family::Composite, run_inner_plan, describe_composite, info_composite, nullptr, nullptr, nullptr, composite_uses_bluestein, false, nullptr, false, false, false, true};
+#endif

@@ -1,20 +1,21 @@
 #include "plan.h"
 
 // one pass over small float32 slabs (fasts.h): resident workgroups walk the slabs
-template <int RY, int RX> SGeomRt sgeom_t() {
+struct SGeomRt { int thr; size_t lds; int per_cu; size_t lds_iso; };
+template <int RY, int RX> static SGeomRt sgeom_t() {
     typedef SGeom<RY, RX> G;
     const int by_lds = (int)((160 * 1024) / G::LDS);
     return {G::T, G::LDS, std::max(1, std::min(by_lds, (int)G::PER_CU)), G::LDS_ISO};
 }
-SGeomRt sgeom(long long ny, long long nx) {
+static SGeomRt sgeom(long long ny, long long nx) {
 #define SG_(A, B) if (ny == 32 * A && nx == 32 * B) return sgeom_t<A, B>();
     SG_(2, 2) SG_(2, 4) SG_(2, 8) SG_(4, 2) SG_(4, 4) SG_(4, 8) SG_(8, 2) SG_(8, 4) SG_(8, 8)
 #undef SG_
     return {0, 0, 0, 0};
 }
 // fasts: is the bin map a radial one (see fasts_power_kernel, ISO)?  If so: first[ky][b] = the smallest |kx| <= nx/2 of row ky whose bin is
-// >= b (nx/2 + 1 if none), ky <= ny/2, b = 0 .. nbins.  Otherwise the plan leaves the one-pass path.
-int fasts_build_tfirst(xrfthip_plan* P, const int32_t* bm) {
+// >= b (nx/2 + 1 if none), ky <= ny/2, b = 0 .. nbins.  Otherwise the plan leaves the one-pass path: FastY's tables (and FastY's reaction to the map) or the generic passes.
+static int fasts_build_tfirst(xrfthip_plan* P, const int32_t* bm) {
     const int ny = (int)P->d.ny, nx = (int)P->d.nx, nyh = ny / 2, H = nx / 2;
     bool radial = P->nbins <= sgeom(ny, nx).thr && P->nbins >= 1;
     for (int ky = 0; ky <= nyh && radial; ++ky) {
@@ -27,7 +28,10 @@ int fasts_build_tfirst(xrfthip_plan* P, const int32_t* bm) {
             if (twin && (t[m] != c || t[(nx - m) % nx] != c)) { radial = false; break; }
         }
     }
-    if (!radial) { settle_family(P, true); return XRFTHIP_OK; }
+    if (!radial) {
+        settle_family(P, true);
+        return P->chosen == Family::FastY ? family_ops(Family::FastY).binmap(P, bm) : XRFTHIP_OK;
+    }
     std::vector<uint16_t> f((size_t)(nyh + 1) * (P->nbins + 1), (uint16_t)(H + 1));
     for (int ky = 0; ky <= nyh; ++ky) {
         const int32_t* r = bm + (size_t)ky * nx;
@@ -59,10 +63,11 @@ int try_fasts(xrfthip_plan* P) {
     return rc;
 }
 
-int run_fasts(const xrfthip_plan* P, const void* in, void* out, double* iso, hipStream_t st) {
+static int run_fasts(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
     FastS p{};
-    p.in = (const float*)in; p.out = (float*)out;
+    p.in = (const float*)a.in0; p.out = (float*)a.out;
     p.tw_y = (const cf*)P->tw_sy.p; p.tw_x = (const cf*)P->tw_sx.p;
     const bool win = P->win[0].p || P->win[1].p;
     p.win_y = win ? (const float*)(P->win[0].p ? P->win[0].p : P->ones4096.p) : nullptr;
@@ -85,7 +90,7 @@ int run_fasts(const xrfthip_plan* P, const void* in, void* out, double* iso, hip
     const dim3 grid((unsigned)std::min<long long>(g, 0x7fffffffLL)), blk((unsigned)G.thr);
     xrfthip_plan::ProfRec* rec = prof_begin(P, "fasts_slab", st);
     const int isom = (d.flags & XRFTHIP_ISO) ? ((d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? 2 : 1) : 0;
-    p.iso = iso; p.tfirst = (const unsigned short*)P->s_tfirst.p; p.nbins = P->nbins;
+    p.iso = a.iso; p.tfirst = (const unsigned short*)P->s_tfirst.p; p.nbins = P->nbins;
     const bool cplx = d.out_mode == XRFTHIP_OUT_COMPLEX;
     p.ph_y = (const cf*)P->fph[0].p; p.ph_x = (const cf*)P->fph[1].p; p.ph_on = (cplx && P->fph_on) ? 1 : 0;
 #define SLS_(A, B, SS) do { \
@@ -151,8 +156,9 @@ int try_fastr(xrfthip_plan* P) {
 }
 
 // one pass over 65536-sample float32 rows (fastr.h): a 1024-thread workgroup per row, or a resident set walking the rows
-int run_fastr(const xrfthip_plan* P, const void* in, void* out, hipStream_t st) {
+static int run_fastr(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
+    const void* in = a.in0; void* out = a.out; hipStream_t st = a.stream;
     const bool cin = P->family == Family::FastRComplex;
     if (P->family == Family::FastRRows) {  // complex rows of 256 .. 4096 points: the row pass of the complex two-pass pipeline on the input's own rows
         const bool c2r = (d.flags & XRFTHIP_C2R_X) != 0;
@@ -255,6 +261,50 @@ int run_fastr(const xrfthip_plan* P, const void* in, void* out, hipStream_t st) 
     HIP_TRY(hipGetLastError());
     return XRFTHIP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// the rows of FastS, FastR, FastRComplex and FastRRows (plan.h, FamilyOps)
+// ---------------------------------------------------------------------------------------------------------------
+static void describe_fasts(const xrfthip_plan* plan, std::string& s, const char* in_note) {
+    const SGeomRt G = sgeom(plan->d.ny, plan->d.nx);
+    appendf(s, "  [fasts] one pass, one %d-thread workgroup per %lld x %lld slab (%d fit a CU): the packed columns' transform, their split and the rows' "
+               "transform in registers (32 complex per thread, r32x%lld / r32x%lld, three LDS exchanges in halves), exact plane detrend in the workgroup, |F|^2 "
+               "rows staged in LDS and written whole with the fftshift and the Hermitian mirror, lds=%zuB; 8 algorithmic bytes per sample through memory%s\n",
+            G.thr, (long long)plan->d.ny, (long long)plan->d.nx, G.per_cu, (long long)plan->d.ny / 32, (long long)plan->d.nx / 32, G.lds, in_note);
+}
+static void describe_fastr(const xrfthip_plan* plan, std::string& s, const char* in_note) {
+    const long long nxr = plan->d.nx;
+    appendf(s, "  [fastr] one pass, one %lld-thread workgroup per %lld-sample row (grid %lld): the packed %lld-point complex transform in registers (32 per thread, "
+               "r32x%dx%d, LDS exchanges%s), real split through the LDS, lds=%zuB; per-row detrend + window + full (or half) spectrum; "
+               "12 algorithmic bytes per sample through memory%s\n",
+            nxr / 64, nxr, plan->tune_rgrid > 0 ? std::min<long long>(plan->tune_rgrid, plan->d.batch) : (long long)plan->d.batch, nxr / 2,
+            nxr >= 32768 ? 32 : nxr == 4096 ? 8 : 16, nxr == 65536 ? 32 : nxr <= 8192 ? 8 : 16, nxr == 65536 ? " in halves" : "",
+            nxr == 65536 ? kFastRLds : nxr == 32768 ? R2Geom<32, 16>::LDS : nxr == 16384 ? R2Geom<16, 16>::LDS : nxr == 8192 ? R2Geom<16, 8>::LDS : R2Geom<8, 8>::LDS, in_note);
+}
+static void describe_fastr_complex(const xrfthip_plan* plan, std::string& s, const char*) {
+    appendf(s, "  [fastr complex rows] one pass, one %lld-thread workgroup per %lld-point complex row: the %s transform in registers (32 per thread, two LDS "
+               "exchanges), natural order through the LDS, lds=%zuB; 16 algorithmic bytes per point through memory\n",
+            (long long)plan->d.nx / 32, (long long)plan->d.nx, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse" : "forward",
+            plan->d.nx == 16384 ? R2Geom<32, 16>::LDS : plan->d.nx == 8192 ? R2Geom<16, 16>::LDS : plan->d.nx == 4096 ? R2Geom<16, 8>::LDS : R2Geom<8, 8>::LDS);
+}
+static void describe_fastr_rows(const xrfthip_plan* plan, std::string& s, const char*) {
+    const bool c2r = (plan->d.flags & XRFTHIP_C2R_X) != 0;
+    const YGeomRt R = yrows_geom(c2r ? plan->d.nx / 2 : plan->d.nx);
+    if (c2r) appendf(s, "  [fasty complex rows] one pass: %d thr, %d rows/unit of the row-major half spectrum back to %lld real samples each (FFT%lld on the packed row; two rows per "
+                        "thread through one LDS buffer), whole rows out; 8 algorithmic bytes per sample through memory\n", R.thr, R.rk, (long long)plan->d.nx, (long long)plan->d.nx / 2);
+    else
+    appendf(s, "  [fasty complex rows] one pass: %d thr, %d rows/unit of the row-major input (FFT%lld, %s; two rows per thread through one LDS buffer), whole rows out; "
+               "16 algorithmic bytes per point through memory\n", R.thr, R.rk, (long long)plan->d.nx, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse" : "forward");
+}
+static void info_fasts(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTS; *n = 1; }
+static void info_fastr(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTR; *n = 1; }
+// (the entries in the order of struct FamilyOps: family, run, describe, kernel_info, finalize, layout, binmap, uses_bluestein, reads_strided)
+#ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
+const FamilyOps kOpsFastS = {Family::FastS, run_fasts, describe_fasts, info_fasts, fast_phase_tables, layout_one_pass, fasts_build_tfirst, nullptr, true};
+const FamilyOps kOpsFastR = {Family::FastR, run_fastr, describe_fastr, info_fastr, fast_phase_tables, layout_one_pass, nullptr, nullptr, true};
+const FamilyOps kOpsFastRComplex = {Family::FastRComplex, run_fastr, describe_fastr_complex, info_fastr, fast_phase_tables, layout_one_pass};
+const FamilyOps kOpsFastRRows = {Family::FastRRows, run_fastr, describe_fastr_rows, info_fastr, fast_phase_tables, layout_one_pass};
+#endif
 
 
 // kernels of this unit that take more than 64 KB of dynamic LDS (the register-resident one-pass kernels): called once through set_kernel_attrs_once()

@@ -1,16 +1,19 @@
 #pragma once
 // plan.h -- what the host side of libxrft_hip.so shares between its translation units (not part of the C ABI: include/xrft_hip.h is):
-// the plan (struct xrfthip_plan), device tables, the small host helpers, and the declarations of the per-family host functions.
+// the plan (struct xrfthip_plan), device tables, the small host helpers, the table of per-family host operations (struct FamilyOps: one row
+// per Family, defined in the unit that owns the family) and the few host functions more than one unit calls.
 //
 //   xrft_hip.cpp     the plan builder (xrfthip_plan_create: descriptor checks, then the families' try_* in order of precedence), the generic
-//                    tile passes (tile_fft.h), workspace layout, xrfthip_exec's dispatch, describe / profiling, the C ABI of the plan
+//                    tile passes (tile_fft.h) and their workspace layout, the table of rows (family_ops), profiling, the C ABI of the plan:
+//                    finalize / set_binmap / kernel_info / describe / exec go through the plan's row
+//                    (Generic)
 //   host_fasty.cpp   the y-first float32 two-pass pipeline (fasty.h, fasty_iso.h) and its complex form (fasty_c2c.h): try_*, tables, launchers
 //                    (FastY, FastY1D, FastYC, FastYCFourStep)
 //   host_fastm.cpp   the mixed-radix pipeline on the lat/lon lengths (fastm.h), its run-time-radix form (fastn.h), the one-axis table kernels
 //                    (FastM, FastN, FastMY, FastMX)
 //   host_fastg.cpp   the one-pass lengths-as-data kernels (fastg.h): small slabs, one axis of any smooth length, Rader / Bluestein tables;
 //                    the last pass of a three-axis spectrum (fasth.h)
-//                    (FastG, FastGY; the herm form of FastGY)
+//                    (FastG, FastGY, FastH)
 //   host_rows.cpp    the register-resident one-pass kernels: small float32 slabs (fasts.h), long rows and complex rows (fastr.h)
 //                    (FastS, FastR, FastRComplex, FastRRows)
 //   host_inner.cpp   two transform axes that are not the trailing pair (xrfthip_desc.inner / .mid): the fused passes and the composite plan
@@ -23,7 +26,8 @@
 //     The x pass reads the user's array (detrend / window / flip / ifftshift fused into its loads) and the last pass writes the
 //     user's output (fftshift / phase / scaling / |F|^2 / cross / mirror fused into its stores); the only intermediate is the
 //     half spectrum of ONE group of slabs, re-used for every group.
-//   * the specialised families above, each with its own launcher (run_fast*): enum class Family, one value per plan.
+//   * the specialised families above: enum class Family, one value per plan; each family's launcher, describe text, workspace layout and
+//     reactions to the plan's tables are its row of FamilyOps.
 // Nothing allocates or synchronises in exec.
 #include <algorithm>
 #include <functional>
@@ -327,8 +331,7 @@ enum class Family {
     FusedInner,      // ... or the two fused passes where the axes lie (fastn.h)
     FastS,           // one pass over a small float32 slab in registers (fasts.h)
     FastG,           // one pass over a small slab, or groups of rows (g_one_d), lengths as data (fastg.h)
-    FastGY,          // one pass along one axis that is not the contiguous one, or along rows with one Rader prime (gy_rows) (fastg.h); gy_herm: its Hermitian form --
-                     // xrfthip_desc.herm_ny / herm_nx, the last pass of a three-axis spectrum: half spectrum in, full power / cross result out (fasth.h)
+    FastGY,          // one pass along one axis that is not the contiguous one, or along rows with one Rader prime (gy_rows) (fastg.h)
     FastMX,          // short rows, table lengths (fastm.h, fastm_xonly_kernel)
     FastMY,          // one axis that is not the contiguous one, table lengths (fastm.h, fastm_yonly_kernel)
     FastR,           // one pass over a long real float32 row in registers (fastr.h)
@@ -340,7 +343,9 @@ enum class Family {
     FastY1D,         // ... as the two steps of a four-step transform of one long real sequence
     FastM,           // the two y-first passes, table lengths (fastm.h)
     FastN,           // ... with the lengths as data (fastn.h; either pass may still be a table kernel)
+    FastH,           // xrfthip_desc.herm_ny / herm_nx, the last pass of a three-axis spectrum: half spectrum in, full power / cross result out (fasth.h)
 };
+constexpr int kFamilyCount = (int)Family::FastH + 1;  // (FastH is the last value: a value added behind it moves this line, and the table of rows with it)
 constexpr int kDeclined = 1;  // a try_* that does not take the descriptor (XRFTHIP_OK: taken, its tables built; < 0: an error)
 
 }  // namespace xrfth
@@ -409,8 +414,8 @@ struct xrfthip_plan {
     size_t gy_lds = 0;
     DevBuf gy_bluec, gy_blueb;
     size_t g_lds = 0;
-    // FastGY, gy_herm: the last pass of a three-axis power / cross spectrum (fasth.h, its own launcher run_fasth): h_G columns of the half spectrum per workgroup; radices, twiddles and digit reversal of nt in g_ry / g_twy / g_revy
-    bool gy_herm = false;
+    // FastH: the last pass of a three-axis power / cross spectrum (fasth.h): h_G columns of the half spectrum per workgroup.  It shares FastG's fields for the
+    // radices, twiddles and digit reversal of nt: g_ry, g_twy, g_revy, g_hrevy
     int h_G = 0, h_thr = 0;
     size_t h_lds = 0;
     // FastS: ONE pass for a small real float32 slab that fits the registers of a CU: 256 x 256 power spectra (fasts.h)
@@ -460,102 +465,77 @@ struct xrfthip_plan {
 };
 
 
-// geometry of the specialised kernels as the host needs it (describe, launchers, workspace layout)
+// geometry of the y-first float32 kernels as the host needs it (host_fasty.cpp; host_rows.cpp runs their row pass on the input's own rows)
 struct YGeomRt { int thr, gxy, cw, rk, lbs; size_t lds; };
-struct MGeomRt { int thr, g; size_t lds_cols, lds_rows; int r0, r1, r2; int thr_r1, g_r1; size_t lds_r1; };  // *_r1: pass 2 of one field
-struct SGeomRt { int thr; size_t lds; int per_cu; size_t lds_iso; };
 
-// ---- host functions shared by the translation units of the library (xrft_hip.cpp, host_*.cpp, ops.cpp)
-FastM fastm_params(const xrfthip_plan* P, const void* in, void* out, char* ws, long long g0, long long gc, int slot, long long slot_slabs);
-FastN fastn_wrap(const xrfthip_plan* P, const FastM& m, bool cols);
-FastY fasty_params(const xrfthip_plan* P, const float* in, void* out, double* iso, char* ws, long long g0, long long gc, int slot, long long slot_slabs);
-MGeomRt mgeom(long long n, bool dbl);
-MGeomRt mgeom_cols(long long ny, long long nx, bool dbl);
-MGeomRt mxgeom(long long n, bool dbl);
-MGeomRt mygeom(long long n, bool dbl);
-SGeomRt sgeom(long long ny, long long nx);
-YGeomRt ycols_geom(long long ny);
-YGeomRt yrows_geom(long long nx, bool fs = false);
-bool fastg_factor(long long n, std::vector<int>& out);
-bool fastg_try(xrfthip_plan* P);
-bool fastgy_try(xrfthip_plan* P, bool rows = false);
-bool cross_iso_phase(const xrfthip_plan* P);
-bool fastm_iso_fused(const xrfthip_plan* P);
-bool fastm_iso_gather(const xrfthip_plan* P);
-bool fastm_len(long long n, bool dbl);
-bool fastm_wide(long long ny, long long nx, bool dbl);
-bool fastmx_len(long long n, bool dbl);
-bool fastmy_len(long long n, bool dbl);
-bool fastn_factor(long long n, int maxr, std::vector<int>& out, int need_last = 0);
-bool fastn_pick(long long n, int g, bool blue, bool dbl, bool cols, int maxr, int thr_force, NGeo& out);
-bool fastn_setup(xrfthip_plan* P);
-bool fasty_iso_tables_fit(const xrfthip_plan* P, int nbins);
-bool plan_two(const xrfthip_plan* P);
-bool rader_split(long long n, bool allow17, int& p_out, std::vector<int>& rq, std::vector<int>& rp);
-int build_unit_windows(xrfthip_plan* P, const int32_t* bm, int rpu);
-int create_inner_plan(xrfthip_plan** plan, const xrfthip_desc& d);
-int fast_phase_tables(xrfthip_plan* P);
-int fastg_build_iso(xrfthip_plan* P, const int32_t* bm);
-int fastg_rev(const std::vector<int>& radix, int n, DevBuf& buf, std::vector<unsigned>& host);
-int fastm_build_tfirst(xrfthip_plan* P, const int32_t* bm);
-int fastm_cw(long long ny, long long nx, bool dbl);
-int fastm_gather_rpu(const xrfthip_plan* P);
-int fastm_iso_ncopy(const xrfthip_plan* P);
-int fastm_rk(long long ny, long long nx, bool dbl);
-int fastm_rk2(long long ny, long long nx, bool two, bool dbl);
-int fastm_rows_rpu(const xrfthip_plan* P);
-int fastm_rpu(long long nx, bool two, bool dbl);
-int fasts_build_tfirst(xrfthip_plan* P, const int32_t* bm);
-int fasty_build_tcodes(xrfthip_plan* P, const int32_t* bm);
-int fasty_window_spectra(xrfthip_plan* P);
-int fasty_window_spectra_1d(xrfthip_plan* P);
-int finalize_plan(xrfthip_plan* P);
-int fusedi_build_iso(xrfthip_plan* P, const int32_t* bm);
-int fusedi_tables(xrfthip_plan* P);
-void fusedi_layout(xrfthip_plan* P);
-int ilog2i(int v);
-int inner_chunk_cap(long long batch, long long i2);
-int inner_chunks(long long ny, long long batch, long long i2);
-int iso_bin_window(bool cplx);
-int iso_chunk_count(long long total);
-int plan_cw(const xrfthip_plan* P);
-int plan_nxb(const xrfthip_plan* P);
-int plan_rk2(const xrfthip_plan* P);
-int rader_maps(int n, int p, const std::vector<int>& rq_, const std::vector<int>& rp_, std::vector<unsigned>& pin, std::vector<unsigned>& pout, std::vector<double>& bre, std::vector<double>& bim);
-int run_detrend_inner(int32_t dtype, int32_t ndim, long long batch, long long ny, long long nx, long long inner, int32_t kind, const void* in, void* out, char* ws, hipStream_t st, long long mid = 1);
-int run_fastg(const xrfthip_plan* P, const void* in, const void* in_b, void* out, double* iso, hipStream_t st);
-int run_fastgy(const xrfthip_plan* P, const void* in, const void* in_b, void* out, hipStream_t st);
-int run_fasth(const xrfthip_plan* P, const void* in, const void* in_b, void* out, hipStream_t st);
-int run_fastm(const xrfthip_plan* P, const void* in, const void* in1, void* out, double* iso, char* ws, hipStream_t st);
-int run_fastmx(const xrfthip_plan* P, const void* in, const void* in1, void* out, hipStream_t st);
-int run_fastmy(const xrfthip_plan* P, const void* in, const void* in1, void* out, hipStream_t st);
-int run_fastr(const xrfthip_plan* P, const void* in, void* out, hipStream_t st);
-int run_fasts(const xrfthip_plan* P, const void* in, void* out, double* iso, hipStream_t st);
-int run_fasty(const xrfthip_plan* P, const float* in, const float* in1, void* out, double* iso, char* ws, hipStream_t st);
-int run_fastyc(const xrfthip_plan* P, const void* in, void* out, char* ws, hipStream_t st);
-int run_fused_inner(const xrfthip_plan* P, const void* in, const void* in1, void* out, double* iso, char* ws, hipStream_t st);
-int run_inner_plan(const xrfthip_plan* P, const void* in, void* out, char* ws, hipStream_t st);
-int run_radial_sums(int32_t dtype, const void* spec, const int32_t* d_binmap, long long bc, long long ny, long long nxo, int sy, int sx, int nbins, int chunks, double* part, double* iso, hipStream_t st);
+// What xrfthip_exec hands a family's launcher: the caller's buffers (out: null when the spectrum is not stored), the workspace, the stream.
+struct ExecArgs { const void* in0; const void* in1; void* out; double* iso; char* ws; hipStream_t stream; };
+
+// One row per Family: the host side of a kernel family, defined in the unit that owns it (the file map above) and found through family_ops().
+// A null entry: nothing to do / no / none.
+struct FamilyOps {
+    Family family;                                                         // the row's own place in the table (checked once, set_kernel_attrs_once)
+    int (*run)(const xrfthip_plan*, const ExecArgs&);                      // the launcher: neither allocates, nor synchronises, nor reads the environment
+    void (*describe)(const xrfthip_plan*, std::string&, const char* in_note);  // the family's lines of xrfthip_plan_describe (in_note: the strided-input note, "" on a dense plan)
+    void (*kernel_info)(const xrfthip_plan*, int32_t* kind, int32_t* per_workgroup);
+    int (*finalize)(xrfthip_plan*) = nullptr;                              // the tables that depend on windows / phases; may hand the plan on (settle_family)
+    void (*layout)(xrfthip_plan*) = nullptr;                               // G and the workspace offsets (null: the family laid out its own when it was created)
+    int (*binmap)(xrfthip_plan*, const int32_t*) = nullptr;                // the reaction to a bin map, looked up by `chosen`; may hand the plan on
+    bool (*uses_bluestein)(const xrfthip_plan*) = nullptr;
+    bool reads_strided = false;                                            // real input addressed as in + slab * in_stride_batch + y * in_stride_y + x ...
+    bool (*strided_if)(const xrfthip_plan*) = nullptr;                     // ... where this holds, too
+    bool dbl_tables = false;                                               // float64 phase / window-spectrum tables in a float64 plan
+    bool two_pass_y = false;                                               // columns -> [fit] -> rows: the y-first intermediate, per-column sums and corrections
+    bool fastm_pipeline = false;                                           // ... of fastm.h / fastn.h
+    bool inner_layout = false;                                             // xrfthip_desc.inner / .mid: a header and a workspace of their own, no tile passes
+};
+const FamilyOps& family_ops(Family f);
+extern const FamilyOps kOpsComposite, kOpsFusedInner, kOpsFastS, kOpsFastG, kOpsFastGY, kOpsFastMX, kOpsFastMY, kOpsFastR, kOpsFastRComplex, kOpsFastRRows, kOpsFastYC,
+    kOpsFastYCFourStep, kOpsFastY, kOpsFastY1D, kOpsFastM, kOpsFastN, kOpsFastH;
+
+// ---- host functions more than one translation unit of the library calls (xrft_hip.cpp, host_*.cpp, ops.cpp)
+// xrft_hip.cpp
+void appendf(std::string& s, const char* fmt, ...);  // (describe)
 int upload_real_table(xrfthip_plan* P, DevBuf& buf, const double* h, int64_t n, int cplx);
-int ycols_gstr(long long ny);
-long long fastg_threads(const xrfthip_plan* P);
-long long fasty_rows_gx(const xrfthip_plan* P);
-long long resident_workgroups(const void* kernel, int threads, size_t lds);
-size_t detrend_inner_ws(bool cplx, long long batch, long long inner);
-size_t fastn_lds(const NGeo& g, size_t csize, bool cols);
-void fastm_launch_cols(const xrfthip_plan* P, const FastM& p, long long gc, hipStream_t st);
-void fastm_launch_rows(const xrfthip_plan* P, const FastM& p, long long gc, hipStream_t st);
-void fastn_geom(long long n, const std::vector<int>& rad, int g, int maxthr, bool blue, NGeo& o, int thr_force = 0, int thr_pref = 0);
-void fastn_launch_cols(const xrfthip_plan* P, const FastM& m, hipStream_t st);
-void fastn_launch_rows(const xrfthip_plan* P, const FastM& m, long long gc, bool fused, hipStream_t st);
-void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof);
-void fasty_launch_rows(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof);
-void layout_workspace(xrfthip_plan* P);
-void settle_family(xrfthip_plan* P, bool decline = false);
 int plan_twiddle(xrfthip_plan* P, DevBuf& buf, long long N, long long count);
 int plan_ones(xrfthip_plan* P, long long n);
+void settle_family(xrfthip_plan* P, bool decline = false);
+void layout_one_pass(xrfthip_plan* P);  // the layout entry of the rows: no workspace ...
+void layout_passes(xrfthip_plan* P);    // ... or the generic passes' / the two y-first passes' workspace
+int iso_chunk_count(long long total);
+int run_radial_sums(int32_t dtype, const void* spec, const int32_t* d_binmap, long long bc, long long ny, long long nxo, int sy, int sx, int nbins, int chunks, double* part, double* iso, hipStream_t st);
+xrfthip_plan::ProfRec* prof_begin(const xrfthip_plan* P, const std::string& label, hipStream_t st);
+void prof_end(xrfthip_plan::ProfRec* r, hipStream_t st);
+// host_fasty.cpp
+bool cross_iso_phase(const xrfthip_plan* P);
+int fast_phase_tables(xrfthip_plan* P);
+int two_pass_tables(xrfthip_plan* P);
+YGeomRt ycols_geom(long long ny);
+YGeomRt yrows_geom(long long nx, bool fs = false);
+long long fasty_rows_gx(const xrfthip_plan* P);
+int build_unit_windows(xrfthip_plan* P, const int32_t* bm, int rpu);
 bool fasty_fits(const xrfthip_plan* P);
 int fasty_tables(xrfthip_plan* P);
+// host_fastm.cpp
+bool fastm_iso_fused(const xrfthip_plan* P);
+int fastm_rows_rpu(const xrfthip_plan* P);
+bool fastn_factor(long long n, int maxr, std::vector<int>& out, int need_last = 0);
+bool fastn_pick(long long n, int g, bool blue, bool dbl, bool cols, int maxr, int thr_force, NGeo& out);
+size_t fastn_lds(const NGeo& g, size_t csize, bool cols);
+void fastn_launch_cols(const xrfthip_plan* P, const FastM& m, hipStream_t st);
+template <typename T> int fastn_upload_twm(const NGeo& g, DevBuf& buf, bool blue = false);  // (both precisions instantiated where it is defined)
+// host_fastg.cpp
+bool rader_split(long long n, bool allow17, int& p_out, std::vector<int>& rq, std::vector<int>& rp);
+template <typename T> int fastn_rader_tables(xrfthip_plan* P);  // (both precisions instantiated where it is defined)
+// host_inner.cpp, ops.cpp
+int create_inner_plan(xrfthip_plan** plan, const xrfthip_desc& d);
+size_t detrend_inner_ws(bool cplx, long long batch, long long inner);
+int run_detrend_inner(int32_t dtype, int32_t ndim, long long batch, long long ny, long long nx, long long inner, int32_t kind, const void* in, void* out, char* ws, hipStream_t st, long long mid = 1);
+// the kernels of each unit that take more than 64 KB of dynamic LDS (set_kernel_attrs_once)
+void set_attrs_fasty();
+void set_attrs_fastm();
+void set_attrs_fastg();
+void set_attrs_rows();
 
 // the families' try_* (xrfthip_plan_create calls them in this order; the first that does not return kDeclined decides)
 int try_fasth(xrfthip_plan* P);
@@ -572,42 +552,21 @@ int try_fastg(xrfthip_plan* P);
 int try_fastn(xrfthip_plan* P);
 
 inline bool fasty_len(long long n) { return n == 256 || n == 512 || n == 1024 || n == 2048 || n == 4096; }  // the lengths of fasty.h / fasty_c2c.h
+inline bool plan_two(const xrfthip_plan* P) { return P->d.out_mode == XRFTHIP_OUT_CROSS || P->d.out_mode == XRFTHIP_OUT_PHASE; }
+inline int ilog2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-// sets of families
-inline bool fastm_pipeline(const xrfthip_plan* P) { return P->family == Family::FastM || P->family == Family::FastN; }  // fastm.h / fastn.h two passes
-inline bool two_pass_y(const xrfthip_plan* P) { return fastm_pipeline(P) || P->family == Family::FastY || P->family == Family::FastY1D; }  // columns -> [fit] -> rows
-inline bool inner_layout(const xrfthip_plan* P) { return P->family == Family::FusedInner || P->family == Family::Composite; }  // (no tile passes of their own)
-inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (xrfthip_desc.herm_ny / herm_nx: the herm form of FastGY or no plan -- no generic passes either)
-inline bool dbl_phase_tables(const xrfthip_plan* P) {  // the families that read float64 phase / window-spectrum tables in a float64 plan
-    const Family f = P->family;
-    return P->dbl && (f == Family::FastM || f == Family::FastN || f == Family::FastMY || f == Family::FastMX || f == Family::FastG || f == Family::FastGY || f == Family::FusedInner);
-}
+// sets of families: each a lookup of the plan's row
+inline bool fastm_pipeline(const xrfthip_plan* P) { return family_ops(P->family).fastm_pipeline; }
+inline bool two_pass_y(const xrfthip_plan* P) { return family_ops(P->family).two_pass_y; }
+inline bool inner_layout(const xrfthip_plan* P) { return family_ops(P->family).inner_layout; }
+inline bool dbl_phase_tables(const xrfthip_plan* P) { return P->dbl && family_ops(P->family).dbl_tables; }
+inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's
 // input take them: pass 1 of the two-pass families, the load of the one-pass families.  The intermediate and the output are dense.
 inline bool in_strided(const xrfthip_plan* P) { return P->d.in_stride_y != 0 || P->d.in_stride_batch != 0; }
 inline long long in_pitch(const xrfthip_plan* P) { return P->d.in_stride_y ? P->d.in_stride_y : P->d.nx; }               // elements between rows (real-input families: rows of nx)
 inline long long in_slab(const xrfthip_plan* P) { return P->d.in_stride_batch ? P->d.in_stride_batch : P->d.ny * P->d.nx; }  // elements between slabs
-inline bool family_reads_strided(const xrfthip_plan* P) {  // the families taught to address in + slab * in_stride_batch + y * in_stride_y + x (real input)
-    switch (P->family) {
-        case Family::FastY: case Family::FastM: case Family::FastN: case Family::FastS: case Family::FastR: return !P->cplx_in;
-        // (slabs and row groups; the complex-input forms are kernels of their own; a group of rows is indexed with 32 bits)
-        case Family::FastG: return !P->cplx_in && (!P->g_one_d || (long long)P->g_rows * in_slab(P) <= 0x7fffffffLL);
-        default: return false;
-    }
+inline bool family_reads_strided(const xrfthip_plan* P) {  // (the complex-input forms are kernels of their own)
+    const FamilyOps& o = family_ops(P->family);
+    return o.reads_strided && !P->cplx_in && (!o.strided_if || o.strided_if(P));
 }
-void prof_end(xrfthip_plan::ProfRec* r, hipStream_t st);
-xrfthip_plan* create_fused_inner(const xrfthip_desc& d);
-xrfthip_plan::ProfRec* prof_begin(const xrfthip_plan* P, const std::string& label, hipStream_t st);
-
-void set_attrs_fasty();
-void set_attrs_fastm();
-void set_attrs_fastg();
-void set_attrs_rows();
-
-// templates whose two precisions are instantiated where they are defined (host_fastm.cpp / host_fastg.cpp)
-template <typename T> int fastn_upload_twm(const NGeo& g, DevBuf& buf, bool blue = false);
-template <typename T> int fastn_blue_tables(xrfthip_plan* P);
-template <typename T> int fastg_setup_t(xrfthip_plan* P);
-template <typename T> int fastgy_rader_tables(xrfthip_plan* P);
-template <typename T> int fastn_rader_tables(xrfthip_plan* P);
-template <typename T> int fastgy_blue_tables(xrfthip_plan* P);

@@ -438,6 +438,8 @@ void set_kernel_attrs_once() {
     static bool done = false;
     if (done) return;
     done = true;
+    for (int f = 0; f < kFamilyCount; ++f)  // every row at its own place in the table
+        if (family_ops((Family)f).family != (Family)f) { std::fprintf(stderr, "xrfthip: the row of Family %d is misplaced\n", f); std::abort(); }
     const int m = (int)kLdsMax;
     // the generic tile kernels live in this unit; every family sets its own (host_*.cpp)
 #define SETA(TT, A, B, C) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_fft_kernel<TT, A, B, C, sizeof(TT) == 8 ? 512 : 1024, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, m)
@@ -488,15 +490,6 @@ void launch_tile(const Pass& ps, int grid, hipStream_t st) {
 #undef L_
 }
 
-void appendf(std::string& s, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    s += buf;
-}
-
 void describe_passes(std::string& s, const std::vector<Pass>& v, const char* name) {
     for (const Pass& p : v) {
         appendf(s, "  [%s] %-16s n=%d radix=", name, p.label.c_str(), p.g.n);
@@ -507,6 +500,15 @@ void describe_passes(std::string& s, const std::vector<Pass>& v, const char* nam
 }
 
 }  // namespace
+
+void appendf(std::string& s, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    s += buf;
+}
 
 int upload_real_table(xrfthip_plan* P, DevBuf& buf, const double* h, int64_t n, int cplx) {
     if (!h) { buf.clear(); return XRFTHIP_OK; }
@@ -542,7 +544,7 @@ int iso_chunk_count(long long total) {
     return (int)c;
 }
 // bins per launch: the int64 sums and the exponent table of a window of bins share 64 KB of LDS
-int iso_bin_window(bool cplx) { return (int)((64 * 1024) / (cplx ? 24 : 16)); }  // (+ 4 bytes per bin: the non-finite flags)
+static int iso_bin_window(bool cplx) { return (int)((64 * 1024) / (cplx ? 24 : 16)); }  // (+ 4 bytes per bin: the non-finite flags)
 
 // radial sums of `bc` stored spectra [bc][ny][nxo] (rows / columns rotated by sy / sx) -> iso[bc][nbins (x2)], bit-reproducible
 int run_radial_sums(int32_t dtype, const void* spec, const int32_t* d_binmap, long long bc, long long ny, long long nxo, int sy, int sx,
@@ -573,27 +575,16 @@ int run_radial_sums(int32_t dtype, const void* spec, const int32_t* d_binmap, lo
     return XRFTHIP_OK;
 }
 
-void layout_workspace(xrfthip_plan* P) {
+// the one-pass families (registers + LDS): no intermediate
+void layout_one_pass(xrfthip_plan* P) {
+    P->G = (int)std::max<long long>(1, std::min<long long>(P->d.batch, 1 << 30));
+    P->ws_bytes = 0;
+}
+
+// the generic passes' layout (Generic, FastMX, FastMY) and, for the two y-first passes (two_pass_y), their intermediate, per-column sums and corrections
+void layout_passes(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
-    bool fast = false;  // the two y-first passes: their intermediate, per-column sums and corrections (else the generic passes' layout)
-    switch (P->family) {
-        case Family::FastR: case Family::FastRComplex: case Family::FastRRows: case Family::FastS: case Family::FastG: case Family::FastGY:
-            P->G = (int)std::max<long long>(1, std::min<long long>(d.batch, 1 << 30)); P->ws_bytes = 0;  // one pass, registers + LDS: no intermediate
-            return;
-        case Family::FastYC: case Family::FastYCFourStep: {  // the tiled intermediate of one group of slabs
-            long long G = d.slabs_per_group > 0 ? d.slabs_per_group : (P->tune_fast_group > 0 ? P->tune_fast_group : std::max<long long>(1, (32LL * 4096 * 4096) / (d.ny * d.nx)));
-            G = std::max<long long>(1, std::min<long long>(G, std::max<long long>(d.batch, 1)));
-            P->G = (int)G;
-            P->off_w = 0;
-            size_t w2_cols = (size_t)d.nx;  // complex columns of the intermediate per row
-            if (d.flags & XRFTHIP_C2R_X) { const size_t cw = 2 * (size_t)ycols_geom(d.ny).gxy; w2_cols = (size_t)d.nx / 2 + cw; }  // (+ the block of the Nyquist column)
-            P->ws_bytes = (((size_t)G * (size_t)d.ny * w2_cols * sizeof(cf)) + 255) & ~(size_t)255;
-            return;
-        }
-        case Family::FastY: case Family::FastY1D: case Family::FastM: case Family::FastN: fast = true; break;
-        case Family::Generic: case Family::FastMX: case Family::FastMY: break;
-        case Family::Composite: case Family::FusedInner: break;  // (never here: they lay out their own workspace)
-    }
+    const bool fast = two_pass_y(P);
     long long G = d.slabs_per_group > 0 ? d.slabs_per_group : P->tune_group;
     size_t slab_w = (size_t)d.ny * std::max(P->width, P->w_cols) * P->csize;
     if (fast) {
@@ -704,68 +695,14 @@ static int run_moments(const xrfthip_plan* P, const void* in, long long g0, long
 // Everything xrfthip_exec needs beyond the caller's buffers is built HERE, when the plan is created or one of its tables is
 // set: window spectra and phase tables of the specialised paths (device allocations + blocking copies) and the workspace
 // layout.  xrfthip_exec itself takes the plan as const: no allocation, no copy, no synchronisation, no getenv.
-int finalize_plan(xrfthip_plan* P) {
-    const bool phase = P->d.out_mode != XRFTHIP_OUT_POWER;  // (the complex modes: the combined phase tables, fast_phase_tables)
-    int rc = XRFTHIP_OK;
-    switch (P->chosen) {
-        case Family::FusedInner: return fusedi_tables(P);  // (its workspace layout does not depend on the tables)
-        case Family::Generic: case Family::Composite: break;
-        case Family::FastG:
-            if (cross_iso_phase(P)) { settle_family(P, true); break; }
-            [[fallthrough]];
-        case Family::FastGY: case Family::FastS: case Family::FastR: case Family::FastRComplex: case Family::FastRRows: case Family::FastYC: case Family::FastMX: case Family::FastMY:
-            if (phase && !P->gy_herm)  // (the herm form: no phase table, no other family to hand the plan to)
-                rc = fast_phase_tables(P);
-            break;
-        case Family::FastYCFourStep: {
-            if (phase) rc = fast_phase_tables(P);
-            if (rc) break;
-            // a window has no separable form over the view; an input phase (PHASE_IN: the lag's factor on the source samples) must be one -- exp(i theta n) is:
-            // row factor ph[256 i1], column factor ph[i2] / ph[0]; checked, else the generic passes take the plan
-            bool ok = P->host_win_x.empty() && !P->win[1].p;
-            if (ok && (P->d.flags & XRFTHIP_PHASE_IN) && P->fph_on) {
-                const std::vector<double>& h = P->host_phase[1];
-                const long long n = P->d.nx, vy = n / 256;
-                ok = (long long)h.size() >= 2 * n;
-                std::vector<cf> py((size_t)vy), px(256);
-                if (ok) {
-                    const double r0 = h[0], i0 = h[1], m0 = r0 * r0 + i0 * i0;
-                    for (long long i1 = 0; i1 < vy; ++i1) { py[(size_t)i1].re = (float)h[(size_t)(512 * i1)]; py[(size_t)i1].im = (float)h[(size_t)(512 * i1 + 1)]; }
-                    for (int i2 = 0; i2 < 256; ++i2) {  // ph[i2] conj(ph[0]) / |ph[0]|^2
-                        const double re = h[(size_t)(2 * i2)], im = h[(size_t)(2 * i2 + 1)];
-                        px[(size_t)i2].re = (float)((re * r0 + im * i0) / m0); px[(size_t)i2].im = (float)((im * r0 - re * i0) / m0);
-                    }
-                    double worst = 0.0;
-                    for (long long nn = 0; nn < n; ++nn) {  // (every product: one O(n) host pass when the table is set; a sample let a single wrong entry through)
-                        const long long i1 = nn / 256; const int i2 = (int)(nn % 256);
-                        const double yr = h[(size_t)(512 * i1)], yi = h[(size_t)(512 * i1 + 1)], xr = (h[(size_t)(2 * i2)] * r0 + h[(size_t)(2 * i2 + 1)] * i0) / m0, xi = (h[(size_t)(2 * i2 + 1)] * r0 - h[(size_t)(2 * i2)] * i0) / m0;
-                        worst = std::max(worst, std::hypot(yr * xr - yi * xi - h[(size_t)(2 * nn)], yr * xi + yi * xr - h[(size_t)(2 * nn + 1)]));
-                    }
-                    ok = worst < 1e-9 && m0 > 0.0;
-                }
-                if (ok) {
-                    rc = P->fph[0].upload(py.data(), py.size() * sizeof(cf));
-                    if (!rc) rc = P->fs_phx.upload(px.data(), px.size() * sizeof(cf));
-                }
-            }
-            if (!rc && !ok) settle_family(P, true);  // (the generic four-step passes)
-            break;
-        }
-        case Family::FastM: case Family::FastN: case Family::FastY:
-            rc = fasty_window_spectra(P);
-            if (!rc && phase) rc = fast_phase_tables(P);
-            break;
-        case Family::FastY1D:
-            P->fast1d_win = !P->host_win_x.empty();  // (a window rides on a slab-shaped table)
-            rc = P->fast1d_win ? fasty_window_spectra_1d(P) : fasty_window_spectra(P);
-            if (!rc && phase) rc = fast_phase_tables(P);
-            break;
-    }
+static int finalize_plan(xrfthip_plan* P) {
+    const auto finalize = family_ops(P->chosen).finalize;
+    const int rc = finalize ? finalize(P) : XRFTHIP_OK;
     if (rc) return rc;
     settle_family(P);
     // a strided plan runs the family the dense descriptor gets, or none: never a slower family because of the strides (the caller copies)
     if (in_strided(P) && !family_reads_strided(P)) return XRFTHIP_UNSUPPORTED_LENGTH;
-    layout_workspace(P);
+    if (const auto layout = family_ops(P->family).layout) layout(P);
     return XRFTHIP_OK;
 }
 
@@ -829,6 +766,56 @@ static int run_pipeline(const xrfthip_plan* P, const std::vector<Pass>& passes, 
         if (rc) return rc;
     }
     return XRFTHIP_OK;
+}
+
+// ---------------------------------------------------------------- Generic: the tile passes' row, and the table of rows
+static int run_generic(const xrfthip_plan* P, const ExecArgs& a) {
+    const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
+    const bool cross = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
+    const bool det = d.detrend != XRFTHIP_DETREND_NONE;
+    double* acc = (double*)(a.ws + P->off_acc);
+    double* coef = (double*)(a.ws + P->off_coef);
+    for (long long g0 = 0; g0 < d.batch; g0 += P->G) {
+        const long long gc = std::min<long long>(P->G, d.batch - g0);
+        int rc;
+        if (cross) {
+            if (det) {
+                rc = P->dbl ? run_moments<double>(P, a.in0, g0, gc, acc, coef, st) : run_moments<float>(P, a.in0, g0, gc, acc, coef, st);
+                if (rc) return rc;
+            }
+            rc = P->dbl ? run_pipeline<double>(P, P->passes_f0, a.in0, nullptr, nullptr, a.ws, det ? coef : nullptr, g0, gc, st)
+                        : run_pipeline<float>(P, P->passes_f0, a.in0, nullptr, nullptr, a.ws, det ? coef : nullptr, g0, gc, st);
+            if (rc) return rc;
+        }
+        const void* in_main = cross ? a.in1 : a.in0;
+        double* acc_m = cross ? acc + (size_t)P->G * P->mom_chunks * 6 : acc;
+        double* coef_m = cross ? coef + d.batch * ((d.flags & XRFTHIP_AXIS_Y) ? d.nx : 1) * 6 : coef;
+        if (det) {
+            rc = P->dbl ? run_moments<double>(P, in_main, g0, gc, acc_m, coef_m, st) : run_moments<float>(P, in_main, g0, gc, acc_m, coef_m, st);
+            if (rc) return rc;
+        }
+        rc = P->dbl ? run_pipeline<double>(P, P->passes, in_main, a.out, a.iso, a.ws, det ? coef_m : nullptr, g0, gc, st)
+                    : run_pipeline<float>(P, P->passes, in_main, a.out, a.iso, a.ws, det ? coef_m : nullptr, g0, gc, st);
+        if (rc) return rc;
+    }
+    return XRFTHIP_OK;
+}
+static bool generic_uses_bluestein(const xrfthip_plan* P) {
+    for (const Pass& ps : P->passes) if (ps.g.blue_n > 0) return true;
+    for (const Pass& ps : P->passes_f0) if (ps.g.blue_n > 0) return true;
+    return false;
+}
+static void generic_info(const xrfthip_plan*, int32_t* kind, int32_t* n) { *kind = XRFTHIP_K_GENERIC; *n = 0; }
+// (describe: the header and the passes' lines that xrfthip_plan_describe prints for every plan with tile passes)
+static const FamilyOps kOpsGeneric = {Family::Generic, run_generic, nullptr, generic_info, nullptr, layout_passes, nullptr, generic_uses_bluestein};
+
+const FamilyOps& family_ops(Family f) {
+    static const FamilyOps* const kRows[] = {  // in the order of enum class Family
+        &kOpsGeneric, &kOpsComposite, &kOpsFusedInner, &kOpsFastS, &kOpsFastG, &kOpsFastGY, &kOpsFastMX, &kOpsFastMY, &kOpsFastR, &kOpsFastRComplex, &kOpsFastRRows,
+        &kOpsFastYC, &kOpsFastYCFourStep, &kOpsFastY, &kOpsFastY1D, &kOpsFastM, &kOpsFastN, &kOpsFastH};
+    static_assert(sizeof kRows / sizeof kRows[0] == kFamilyCount, "one row of FamilyOps per Family");
+    return *kRows[(int)f];
 }
 
 // =====================================================================================================
@@ -954,7 +941,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
         for (auto try_family : kTry)
             if ((rc = try_family(P)) != kDeclined) break;
     if (rc == kDeclined) rc = XRFTHIP_OK;
-    if (!rc && herm && !P->gy_herm) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family reads a half spectrum as columns: the caller composes the stages)
+    if (!rc && herm && P->family != Family::FastH) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family reads a half spectrum as columns: the caller composes the stages)
     const bool one_axis = P->family == Family::FastGY || P->family == Family::FastMY;
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_PHASE_IN) && !one_axis) rc = XRFTHIP_BAD_ARG;  // (the generic column tiles have no input phase)
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_HALF_X) && !one_axis) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (... and no half output: the caller transposes)
@@ -962,7 +949,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
         set_kernel_attrs_once();
         // nbins must be known before tiles are sized (the LDS histogram shares the tile's allocation): ISO plans are
         // (re)built in xrfthip_plan_set_binmap.  Build now for everything else.
-        if (!(d.flags & XRFTHIP_ISO) && !herm) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
+        if (!(d.flags & XRFTHIP_ISO) && P->family != Family::FastH) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
     }
     if (!rc) rc = finalize_plan(P);
     if (rc) { delete P; return rc; }
@@ -1005,27 +992,9 @@ int xrfthip_plan_set_binmap(xrfthip_plan* plan, const int32_t* h_binmap, int64_t
     int rc = plan->binmap.upload(h_binmap, (size_t)ny * nx_out * sizeof(int32_t));
     if (rc) return rc;
     plan->nbins = nbins;
-    if (plan->family == Family::FusedInner) return fusedi_build_iso(plan, h_binmap);  // (a radial map, or XRFTHIP_BAD_ARG; no tile passes to rebuild)
-    switch (plan->chosen) {
-        case Family::FastS:  // a radial map within the workgroup's reach: the sums are taken from the staged rows (fasts.h); else FastY's tables or the generic passes
-            rc = fasts_build_tfirst(plan, h_binmap);
-            if (rc || plan->chosen != Family::FastY) break;
-            [[fallthrough]];
-        case Family::FastY:
-            rc = fasty_build_tcodes(plan, h_binmap);
-            if (!rc && !plan->ytfirst_on && !fasty_iso_tables_fit(plan, nbins)) settle_family(plan, true);  // (any map: the atomic tables alias half of the transforms' LDS)
-            break;
-        case Family::FastG:  // any map: per-bin position lists (fastg.h)
-            rc = fastg_build_iso(plan, h_binmap);
-            break;
-        case Family::FastM: case Family::FastN:  // a radial map: the fused radial sums are gathered per bin (fastm_rows_kernel)
-            rc = fastm_build_tfirst(plan, h_binmap);
-            break;
-        case Family::Generic: case Family::Composite: case Family::FusedInner: case Family::FastGY: case Family::FastMX: case Family::FastMY:
-        case Family::FastR: case Family::FastRComplex: case Family::FastRRows: case Family::FastYC: case Family::FastYCFourStep: case Family::FastY1D:
-            break;
-    }
-    if (rc) return rc;
+    const FamilyOps& ops = family_ops(plan->chosen);
+    if (ops.binmap) rc = ops.binmap(plan, h_binmap);
+    if (rc || ops.inner_layout) return rc;  // (FusedInner: no tile passes to rebuild)
     plan->passes.clear();
     plan->passes_f0.clear();
     int rcb = plan->dbl ? build_plan_t<double>(*plan) : build_plan_t<float>(*plan);
@@ -1112,41 +1081,13 @@ int xrfthip_plan_profile_read(xrfthip_plan* plan, char* buf, size_t buflen) {
 
 int xrfthip_plan_uses_bluestein(const xrfthip_plan* plan) {
     if (!plan) return 0;
-    switch (plan->family) {
-        case Family::Composite: return xrfthip_plan_uses_bluestein(plan->sub_x) || xrfthip_plan_uses_bluestein(plan->sub_y);
-        case Family::FastGY: return plan->gy_blue_m > 0;
-        case Family::FastN: return plan->n_blue_m > 0;
-        case Family::Generic: break;
-        case Family::FusedInner: case Family::FastS: case Family::FastG: case Family::FastMX: case Family::FastMY: case Family::FastR: case Family::FastRComplex:
-        case Family::FastRRows: case Family::FastYC: case Family::FastYCFourStep: case Family::FastY: case Family::FastY1D: case Family::FastM:
-            return 0;  // (the generic passes of such a plan never run)
-    }
-    for (const Pass& ps : plan->passes) if (ps.g.blue_n > 0) return 1;
-    for (const Pass& ps : plan->passes_f0) if (ps.g.blue_n > 0) return 1;
-    return 0;
+    const auto uses = family_ops(plan->family).uses_bluestein;
+    return uses && uses(plan);
 }
 
 int xrfthip_plan_kernel_info(const xrfthip_plan* plan, int32_t* kind, int32_t* per_workgroup) {
     if (!plan || !kind || !per_workgroup) return XRFTHIP_BAD_ARG;
-    const xrfthip_plan* P = plan;
-    const bool two = P->d.out_mode == XRFTHIP_OUT_CROSS || P->d.out_mode == XRFTHIP_OUT_PHASE;
-    int k = XRFTHIP_K_GENERIC, n = 0;
-    switch (P->family) {
-        case Family::Generic: break;
-        case Family::Composite: k = XRFTHIP_K_COMPOSITE; break;
-        case Family::FusedInner: k = XRFTHIP_K_FASTN; n = P->n_cw; break;
-        case Family::FastG: k = P->g_one_d ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG; n = P->g_one_d ? P->g_rows : 1; break;
-        case Family::FastS: k = XRFTHIP_K_FASTS; n = 1; break;
-        case Family::FastYC: case Family::FastYCFourStep: case Family::FastY: case Family::FastY1D: k = XRFTHIP_K_FASTY; break;
-        case Family::FastR: case Family::FastRComplex: case Family::FastRRows: k = XRFTHIP_K_FASTR; n = 1; break;
-        case Family::FastMX: { k = XRFTHIP_K_FASTM_X; const MGeomRt C = mxgeom(P->d.nx, P->dbl); n = (two || (P->cplx_in && !(P->d.flags & XRFTHIP_C2R_X))) ? C.g : 2 * C.g; break; }
-        case Family::FastGY: if (P->gy_herm) { k = XRFTHIP_K_FASTH; n = P->h_G; break; }
-            k = P->gy_rows ? XRFTHIP_K_FASTG_ROWS : XRFTHIP_K_FASTG_Y; n = ((P->cplx_in || two) ? 1 : 2) * P->gy_G; break;
-        case Family::FastMY: { k = XRFTHIP_K_FASTM_Y; const MGeomRt C = mygeom(P->d.ny, P->dbl); n = ((P->cplx_in || two) ? 1 : 2) * C.g; break; }
-        case Family::FastM: k = XRFTHIP_K_FASTM; n = plan_cw(P); break;
-        case Family::FastN: k = XRFTHIP_K_FASTN; n = plan_cw(P); break;
-    }
-    *kind = k; *per_workgroup = n;
+    family_ops(plan->family).kernel_info(plan, kind, per_workgroup);
     return XRFTHIP_OK;
 }
 
@@ -1167,229 +1108,7 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
     std::string in_note_;
     if (in_strided(plan)) appendf(in_note_, "; input read where it lies: in pitch %lld / slab %lld", in_pitch(plan), in_slab(plan));
     const char* in_note = in_note_.c_str();
-    switch (plan->family) {
-    case Family::FusedInner: {
-        auto rads = [](const NGeo& g) { std::string t; for (int i = 0; i < g.np; ++i) t += (i ? "x" : "") + std::to_string(g.r[i]); return t; };
-        const NGeo &gc = plan->n_c.geo, &gr = plan->n_r.geo;
-        appendf(s, "xrfthip plan: [batch %lld][ny %lld][mid %lld][nx %lld][inner %lld] dtype=%d mode=%d detrend=%d flags=0x%x ws=%zuB\n"
-                   "  [inner layout] [fastn fused] two passes where the axes lie, no transposed copy: cols: the [ny][mid nx inner] view, %d thr, %d packed column pairs (FFT%d r%s), lds=%zuB -> "
-                   "W2[slab][%d/%d][%d][%d][%d] complex -> fit per (slab, inner element) -> rows: %d thr, %d independent elements of one row ky per workgroup (FFT%d r%s), lds=%zuB, plane added "
-                   "back in the spectral domain, (ky, kx, e) and its Hermitian twin stored as runs of %d elements\n",
-                (long long)d.batch, (long long)d.ny, (long long)plan->mid, (long long)d.nx, (long long)plan->inner, d.dtype, d.out_mode, d.detrend, d.flags, plan->ws_bytes,
-                gc.thr, gc.g, gc.n, plan->n_rad_p ? ("Rader, prime " + std::to_string(plan->n_rad_p)).c_str() : rads(gc).c_str(), plan->n_c.lds, plan->y_nrow_pad, plan->n_rk, plan->n_nxb, plan->n_rk, plan->n_cw, gr.thr, gr.g, gr.n, rads(gr).c_str(), plan->n_r.lds, gr.g);
-        if (d.flags & XRFTHIP_ISO)
-            appendf(s, "  [inner layout] [fastn fused iso] the row pass gathers, per element and bin the row reaches, the bin's samples from LDS in float64 (one thread, a fixed order, no atomics) "
-                       "-> partial[slab][element][ky][%d bins] (%zuB per slab) -> added over ky in order: per-element radial sums%s\n",
-                    plan->nbins, (size_t)(d.ny / 2 + 1) * (size_t)std::max<long long>(plan->inner, plan->mid) * (size_t)plan->nbins * (d.out_mode == XRFTHIP_OUT_CROSS ? 16 : 8),
-                    (d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? "; the spectrum is not stored" : "");
-        break;
-    }
-    case Family::Composite:
-        appendf(s, "xrfthip plan: [batch %lld][ny %lld][mid %lld][nx %lld][inner %lld] dtype=%d mode=%d detrend=%d flags=0x%x ws=%zuB\n  [inner layout] no transposed copy: %sx where it lies, then y\n",
-                (long long)d.batch, (long long)d.ny, (long long)plan->mid, (long long)d.nx, (long long)plan->inner, d.dtype, d.out_mode, d.detrend, d.flags, plan->ws_bytes,
-                d.detrend ? "detrend pass (plane per (batch, inner) element), " : "");
-        for (const xrfthip_plan* sp : {plan->sub_x, plan->sub_y}) {
-            std::vector<char> tmp(4096);
-            xrfthip_plan_describe(sp, tmp.data(), tmp.size());
-            s += "  ";
-            for (const char* c = tmp.data(); *c; ++c) { s += *c; if (*c == '\n' && c[1]) s += "  "; }
-        }
-        break;
-    case Family::Generic: break;
-    case Family::FastG: {
-        std::string rxs, rys;
-        for (int r : plan->g_rx) rxs += (rxs.empty() ? "" : "x") + std::to_string(r);
-        for (int r : plan->g_ry) rys += (rys.empty() ? "" : "x") + std::to_string(r);
-        if (plan->g_one_d)
-            appendf(s, "  [fastg rows] one pass, one %d-thread workgroup per %d rows of %lld samples%s: in LDS, radices from the plan (x: %d = %s), a mean / line per row in the "
-                       "workgroup, output gathered in output order through the digit-reversal table, lds=%zuB%s\n",
-                    (int)fastg_threads(plan), plan->g_rows, (long long)plan->d.nx, plan->g_packed ? " packed in pairs" : plan->cplx_in ? " (complex input)" : " (an odd length: complex sequences)", plan->g_n,
-                    rxs.empty() ? "1" : rxs.c_str(), plan->g_lds, in_note);
-        else if (plan->g_packed)
-            appendf(s, "  [fastg] one pass, one %d-thread workgroup per %lld x %lld slab: the half spectrum (%lld rows of %lld + 1 complex) in LDS, radices from the plan "
-                       "(x: %lld = %s on packed rows, y: %lld = %s), exact plane detrend in the workgroup, output gathered in output order through the digit-reversal "
-                       "tables, lds=%zuB%s\n",
-                    (int)fastg_threads(plan), (long long)plan->d.ny, (long long)plan->d.nx, (long long)plan->d.ny, (long long)plan->d.nx / 2, (long long)plan->d.nx / 2,
-                    rxs.empty() ? "1" : rxs.c_str(), (long long)plan->d.ny, rys.c_str(), plan->g_lds, in_note);
-        else
-            appendf(s, "  [fastg] one pass, one %d-thread workgroup per %lld x %lld slab (complex input or an odd row length: the rows as complex sequences): the spectrum (%lld rows of %lld complex) "
-                       "in LDS, radices from the plan (x: %lld = %s, y: %lld = %s), exact plane detrend in the workgroup, output gathered in output order through the "
-                       "digit-reversal tables, lds=%zuB%s\n",
-                    (int)fastg_threads(plan), (long long)plan->d.ny, (long long)plan->d.nx, (long long)plan->d.ny, (long long)plan->d.nx, (long long)plan->d.nx,
-                    rxs.c_str(), (long long)plan->d.ny, rys.c_str(), plan->g_lds, in_note);
-        if (plan->d.out_mode == XRFTHIP_OUT_CROSS)
-            appendf(s, "  [fastg cross spectrum] both fields' tiles in the workgroup's LDS, F0 conj(F1) on the way out\n");
-        if (plan->d.flags & XRFTHIP_ISO)
-            appendf(s, "  [fastg radial sums] in the same pass: per bin the LDS positions of its samples (any bin map), a bin per wave, float64, a fixed shuffle tree -- no atomics%s\n",
-                    (plan->d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? "; the spectrum is not stored" : "");
-        break;
-    }
-    case Family::FastS: {
-        const SGeomRt G = sgeom(plan->d.ny, plan->d.nx);
-        appendf(s, "  [fasts] one pass, one %d-thread workgroup per %lld x %lld slab (%d fit a CU): the packed columns' transform, their split and the rows' "
-                   "transform in registers (32 complex per thread, r32x%lld / r32x%lld, three LDS exchanges in halves), exact plane detrend in the workgroup, |F|^2 "
-                   "rows staged in LDS and written whole with the fftshift and the Hermitian mirror, lds=%zuB; 8 algorithmic bytes per sample through memory%s\n",
-                G.thr, (long long)plan->d.ny, (long long)plan->d.nx, G.per_cu, (long long)plan->d.ny / 32, (long long)plan->d.nx / 32, G.lds, in_note);
-        break;
-    }
-    case Family::FastYCFourStep: {
-        const YGeomRt C = ycols_geom(plan->d.nx / 256), R = yrows_geom(256);
-        appendf(s, "  [fasty complex rows, four-step] two passes over the [%lld][256] view of every %lld-point sequence: cols: %d thr, FFT%lld along the view's rows index (input rotation / lag phase / "
-                   "conjugation on load) -> W2 in whole lines -> rows: %d thr, %d rows/unit x W_N^(i2 k1), FFT256, stored transposed (X[k1 + %lld k2]: runs of %d samples)%s; 32 bytes per point through memory\n",
-                (long long)plan->d.nx / 256, (long long)plan->d.nx, C.thr, (long long)plan->d.nx / 256, R.thr, R.rk, (long long)plan->d.nx / 256, R.rk / 2,
-                (plan->d.flags & XRFTHIP_INVERSE) ? "; inverse: conjugate in / out" : "");
-        break;
-    }
-    case Family::FastYC: {
-        const YGeomRt C = ycols_geom(plan->d.ny), R = yrows_geom(plan->d.nx);
-        if (plan->d.flags & XRFTHIP_C2R_X) {
-            const YGeomRt R2 = yrows_geom(plan->d.nx / 2);
-            appendf(s, "  [fasty complex] cols: %d thr, %d x 2 adjacent complex columns of the half spectrum (FFT%lld, inverse: conjugate in / out) + one block for the Nyquist column, "
-                       "%d columns/unit -> W2 -> rows: %d thr, %d rows/unit: the half spectrum of a row back to %lld real samples (FFT%lld on the packed row), whole rows out; "
-                       "16 B per point through memory\n", C.thr, C.gxy, (long long)plan->d.ny, 2 * C.gxy, R2.thr, R2.rk, (long long)plan->d.nx, (long long)plan->d.nx / 2);
-        } else
-        appendf(s, "  [fasty complex] cols: %d thr, %d x 2 adjacent complex columns (FFT%lld, %s), %d columns/unit -> W2[slab][%lld/%d][nx/%d][%d][%d] -> rows: %d thr, %d rows/unit "
-                   "(FFT%lld), whole rows out (scale, %sfftshift); 32 B per point through memory\n",
-                C.thr, C.gxy, (long long)plan->d.ny, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse: conjugate in / out" : "forward", 2 * C.gxy, (long long)plan->d.ny,
-                std::max(1, 16 / (2 * C.gxy)), 2 * C.gxy, std::max(1, 16 / (2 * C.gxy)), 2 * C.gxy, R.thr, R.rk, (long long)plan->d.nx, plan->fph_on ? "phase, " : "");
-        break;
-    }
-    case Family::FastRRows: {
-        const bool c2r = (plan->d.flags & XRFTHIP_C2R_X) != 0;
-        const YGeomRt R = yrows_geom(c2r ? plan->d.nx / 2 : plan->d.nx);
-        if (c2r) appendf(s, "  [fasty complex rows] one pass: %d thr, %d rows/unit of the row-major half spectrum back to %lld real samples each (FFT%lld on the packed row; two rows per "
-                            "thread through one LDS buffer), whole rows out; 8 algorithmic bytes per sample through memory\n", R.thr, R.rk, (long long)plan->d.nx, (long long)plan->d.nx / 2);
-        else
-        appendf(s, "  [fasty complex rows] one pass: %d thr, %d rows/unit of the row-major input (FFT%lld, %s; two rows per thread through one LDS buffer), whole rows out; "
-                   "16 algorithmic bytes per point through memory\n", R.thr, R.rk, (long long)plan->d.nx, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse" : "forward");
-        break;
-    }
-    case Family::FastRComplex: {
-        appendf(s, "  [fastr complex rows] one pass, one %lld-thread workgroup per %lld-point complex row: the %s transform in registers (32 per thread, two LDS "
-                   "exchanges), natural order through the LDS, lds=%zuB; 16 algorithmic bytes per point through memory\n",
-                (long long)plan->d.nx / 32, (long long)plan->d.nx, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse" : "forward",
-                plan->d.nx == 16384 ? R2Geom<32, 16>::LDS : plan->d.nx == 8192 ? R2Geom<16, 16>::LDS : plan->d.nx == 4096 ? R2Geom<16, 8>::LDS : R2Geom<8, 8>::LDS);
-        break;
-    }
-    case Family::FastR: {
-        const long long nxr = plan->d.nx;
-        appendf(s, "  [fastr] one pass, one %lld-thread workgroup per %lld-sample row (grid %lld): the packed %lld-point complex transform in registers (32 per thread, "
-                   "r32x%dx%d, LDS exchanges%s), real split through the LDS, lds=%zuB; per-row detrend + window + full (or half) spectrum; "
-                   "12 algorithmic bytes per sample through memory%s\n",
-                nxr / 64, nxr, plan->tune_rgrid > 0 ? std::min<long long>(plan->tune_rgrid, plan->d.batch) : (long long)plan->d.batch, nxr / 2,
-                nxr >= 32768 ? 32 : nxr == 4096 ? 8 : 16, nxr == 65536 ? 32 : nxr <= 8192 ? 8 : 16, nxr == 65536 ? " in halves" : "",
-                nxr == 65536 ? kFastRLds : nxr == 32768 ? R2Geom<32, 16>::LDS : nxr == 16384 ? R2Geom<16, 16>::LDS : nxr == 8192 ? R2Geom<16, 8>::LDS : R2Geom<8, 8>::LDS, in_note);
-        break;
-    }
-    case Family::FastMX: {
-        const MGeomRt C = mxgeom(plan->d.nx, plan->dbl);
-        appendf(s, "  [fastm x-only] %d thr, %d row pairs per workgroup (FFT%lld r%dx%dx%d in LDS), lds=%zuB: per-row detrend + window + transform + full (or half) spectrum in one pass\n",
-                C.thr, C.g, (long long)plan->d.nx, C.r0, C.r1, C.r2, C.lds_cols);
-        break;
-    }
-    case Family::FastGY: {
-        if (plan->gy_herm) {  // (the Hermitian form: the last pass of a three-axis spectrum, fasth.h)
-            std::string rts;
-            for (int r : plan->g_ry) rts += (rts.empty() ? "" : "x") + std::to_string(r);
-            const bool cross = plan->d.out_mode == XRFTHIP_OUT_CROSS;
-            appendf(s, "  [fasth] the last pass of a three-axis %s spectrum: %d thr, %d columns of the half spectrum [%lld][%lld][%lld + 1] per workgroup%s, the radices from the plan "
-                       "(t: %lld = %s in LDS), lds=%zuB: window + transform along t + %s, ",
-                    cross ? "cross" : "power", plan->h_thr, plan->h_G, (long long)d.ny, (long long)d.herm_ny, (long long)d.herm_nx / 2, cross ? " of each of the two fields" : "",
-                    (long long)d.ny, rts.c_str(), plan->h_lds, cross ? "F0 conj(F1)" : "|F|^2");
-            appendf(s, "every sample and its Hermitian twin stored as 16-byte pieces of 128-byte runs of the full [%lld][%lld][%lld] result, non-temporal\n",
-                    (long long)d.ny, (long long)d.herm_ny, (long long)d.herm_nx);
-            break;
-        }
-        std::string rys;
-        for (int r : plan->g_ry) rys += (rys.empty() ? "" : "x") + std::to_string(r);
-        const bool onecol = plan->cplx_in || plan->d.out_mode == XRFTHIP_OUT_CROSS || plan->d.out_mode == XRFTHIP_OUT_PHASE;
-        if (plan->gy_rows)
-            appendf(s, "  [fastg rows Rader] one pass along the contiguous axis, %d thr, %d sequences (%s) per workgroup, lanes along the samples, lds=%zuB: per-row detrend + window + transform%s\n",
-                    plan->gy_thr, plan->gy_G, plan->cplx_in ? "complex rows" : onecol ? "a row of each of the two fields" : "pairs of rows", plan->gy_lds, (plan->d.flags & XRFTHIP_INVERSE) ? "; inverse (conj in, conj out)" : "");
-        else
-        appendf(s, "  [fastg y-only] one pass, %d thr, %d %s per workgroup (%d bytes of a row), the radices from the plan (y: %lld = %s in LDS), lds=%zuB: "
-                   "per-column detrend + window + transform%s, in place in memory order%s\n",
-                plan->gy_thr, plan->gy_G, plan->cplx_in ? "complex columns" : onecol ? "columns of each of the two fields" : "packed column pairs",
-                (int)((plan->cplx_in ? plan->csize : onecol ? plan->rsize : 2 * plan->rsize) * (size_t)plan->gy_G), (long long)(plan->gy_blue_m ? plan->gy_blue_m : plan->d.ny), rys.c_str(), plan->gy_lds,
-                onecol ? "" : " + both columns' spectra", (plan->d.flags & XRFTHIP_INVERSE) ? "; inverse (conj in, conj out)" : "");
-        if (plan->gy_rad_p) {
-            std::string rps;
-            for (int r : plan->gy_rp) rps += (rps.empty() ? "" : "x") + std::to_string(r);
-            appendf(s, "  [fastg %s Rader] %lld = %lld x %d: the prime-factor form, no twiddles between the two dimensions; along the prime %d a cyclic convolution of %d = %s points "
-                       "(forward passes, * the transformed kernel, inverse passes) inside the tile\n", plan->gy_rows ? "rows:" : "y-only",
-                    (long long)plan->gy_n, (long long)(plan->gy_n / plan->gy_rad_p), plan->gy_rad_p, plan->gy_rad_p, plan->gy_rad_p - 1, rps.c_str());
-        }
-        if (plan->gy_blue_m)
-            appendf(s, "  [fastg y-only Bluestein] %lld points as a circular convolution of %d inside the tile (chirp products, forward and inverse passes)%s\n",
-                    (long long)plan->d.ny, plan->gy_blue_m, plan->gy_tw_lds ? "" : "; twiddles from memory");
-        break;
-    }
-    case Family::FastMY: {
-        const MGeomRt C = mygeom(plan->d.ny, plan->dbl);
-        appendf(s, "  [fastm y-only] %d thr, %d packed column pairs (FFT%lld r%dx%dx%d in LDS), lds=%zuB: per-column detrend + window + transform + both halves of the spectrum in one pass, in place in memory order\n",
-                C.thr, C.g, (long long)plan->d.ny, C.r0, C.r1, C.r2, C.lds_cols);
-        break;
-    }
-    case Family::FastN: {
-        auto rads = [](const NGeo& g) { std::string t; for (int i = 0; i < g.np; ++i) t += (i ? "x" : "") + std::to_string(g.r[i]); return t; };
-        std::string cs_, rs_;
-        if (plan->n_c.rt) {
-            const NGeo& g = plan->n_c.geo;
-            if (plan->n_rad_p) {
-                std::string a, b;
-                for (int r : plan->n_rq) a += (a.empty() ? "" : "x") + std::to_string(r);
-                for (int r : plan->n_rp) b += (b.empty() ? "" : "x") + std::to_string(r);
-                appendf(cs_, "lengths as data, %d thr, %d packed column pairs (FFT%d = %d r%s x prime %d: the prime-factor form, Rader's cyclic convolution of %d = %s points along the prime, in LDS), lds=%zuB",
-                        g.thr, g.g, g.n, g.n / plan->n_rad_p, a.c_str(), plan->n_rad_p, plan->n_rad_p - 1, b.c_str(), plan->n_c.lds);
-            } else
-            appendf(cs_, "lengths as data, %d thr, %d packed column pairs (FFT%d r%s in LDS%s), lds=%zuB", g.thr, g.g, g.n, rads(g).c_str(),
-                    plan->n_blue_m ? ": a chirp convolution" : "", plan->n_c.lds);
-        } else {
-            const MGeomRt C = mgeom_cols(plan->yny, plan->ynx, plan->dbl);
-            appendf(cs_, "table kernel, %d thr, %d packed column pairs (FFT%lld r%dx%dx%d)", C.thr, C.g, (long long)plan->yny, C.r0, C.r1, C.r2);
-        }
-        if (plan->n_r.rt) {
-            const NGeo& g = plan->n_r.geo;
-            appendf(rs_, "lengths as data, %d thr, %d rows/unit (FFT%d r%s), lds=%zuB", g.thr, plan->n_rpu, g.n, rads(g).c_str(), plan->n_r.lds);
-        } else {
-            const MGeomRt R = mgeom(plan->ynx, plan->dbl);
-            appendf(rs_, "table kernel, %d thr, %d rows/unit (FFT%lld r%dx%dx%d)", R.thr_r1, plan->n_rpu, (long long)plan->ynx, R.r0, R.r1, R.r2);
-        }
-        appendf(s, "  [fastn] cols: %s -> W2[slab][%d/%d][%d][%d][%d] complex -> fit -> rows: %s, trend added back in the spectral domain, fftshift + mirror rows%s\n",
-                cs_.c_str(), plan->y_nrow_pad, plan->n_rk, plan->n_nxb, plan->n_rk, plan->n_cw, rs_.c_str(), in_note);
-        if (plan->n_blue_m)
-            appendf(s, "  [fastn Bluestein] the %lld-point columns as a circular convolution of %d inside the tile (chirp products, two forward transforms)\n", (long long)plan->yny, plan->n_blue_m);
-        if ((plan->d.flags & XRFTHIP_ISO) && plan->nbins > 0)
-            appendf(s, "  [fastn radial sums] %s\n", fastm_iso_gather(plan) ? "fused into the row pass: radial map, per-bin gather from the spectra in LDS, no atomics"
-                                                   : fastm_iso_fused(plan) ? "fused into the row pass: int64 fixed-point tables behind the transforms' LDS"
-                                                                           : "a pass over the stored spectrum");
-        break;
-    }
-    case Family::FastM: {
-        const MGeomRt C = mgeom_cols(plan->yny, plan->ynx, plan->dbl), R = mgeom(plan->ynx, plan->dbl);
-        appendf(s, "  [fastm] cols: %d thr, %d packed column pairs (FFT%lld r%dx%dx%d in LDS), lds=%zuB -> W2[slab][%d/%d][nx/%d][%d][%d] complex -> fit -> rows: %d thr, %d rows/unit (FFT%lld r%dx%dx%d), lds=%zuB, trend added back in the spectral domain, fftshift + mirror rows%s\n",
-                C.thr, C.g, (long long)plan->yny, C.r0, C.r1, C.r2, C.lds_cols, plan->y_nrow_pad, fastm_rk2(plan->yny, plan->ynx, plan->d.out_mode >= XRFTHIP_OUT_CROSS, plan->dbl), fastm_cw(plan->yny, plan->ynx, plan->dbl), fastm_rk2(plan->yny, plan->ynx, plan->d.out_mode >= XRFTHIP_OUT_CROSS, plan->dbl), fastm_cw(plan->yny, plan->ynx, plan->dbl),
-                R.thr_r1, R.g_r1, (long long)plan->ynx, R.r0, R.r1, R.r2, R.lds_r1, in_note);
-        if ((plan->d.flags & XRFTHIP_ISO) && plan->nbins > 0)
-            appendf(s, "  [fastm radial sums] %s\n", fastm_iso_gather(plan) ? "fused into the row pass: radial map, per-bin gather from the spectra in LDS, no atomics"
-                                                   : fastm_iso_fused(plan) ? "fused into the row pass: int64 fixed-point tables behind the transforms' LDS"
-                                                                           : "a pass over the stored spectrum (the tables do not fit beside the transforms)");
-        break;
-    }
-    case Family::FastY: case Family::FastY1D: {
-        const bool fs = plan->family == Family::FastY1D;
-        const YGeomRt C = ycols_geom(plan->yny), R = yrows_geom(plan->ynx, fs);
-        if (fs) appendf(s, "  [fasty four-step] %lld samples = [%lld][%lld]: columns = step 1 (half spectrum k1 <= %lld), rows x W_N^(i2 k1) = step 2, transposed stores + Hermitian mirror\n",
-                                  (long long)plan->d.nx, (long long)plan->yny, (long long)plan->ynx, (long long)plan->yny / 2);
-        appendf(s, "  [fasty] cols: %d thr, %d x 2 packed column pairs (FFT%lld r16x16x%lld, column-local detrend fused), %d columns/unit, lds=%zuB -> W2[slab][%d/%d][nx/%d][2][%d][%d] -> rows: %d thr, %d rows/unit (FFT%lld r16x16x%lld), lds=%zuB, |F|^2 + fftshift + mirror rows%s\n",
-                C.thr, C.gxy, (long long)plan->d.ny, (long long)plan->d.ny / 256, C.cw, C.lds, plan->y_nrow_pad, C.rk, C.cw, C.rk, 2 * C.gxy,
-                R.thr, R.rk, (long long)plan->d.nx, (long long)plan->d.nx / 256, R.lds, in_note);
-        if ((plan->d.flags & XRFTHIP_ISO) && plan->ytcodes.p)
-            appendf(s, "  [fasty radial sums] fused into the row pass (runs of equal bins from the staged rows, int64 fixed-point tables), bin codes: %s\n",
-                    plan->ytfirst_on ? "radial map: per-bin gather, no atomics" : plan->ytcodes_compact ? "compact (radial map: first bin + step mask per 16 samples)" : "full (4 bytes per sample)");
-        break;
-    }
-    }
+    if (const auto describe = family_ops(plan->family).describe) describe(plan, s, in_note);
     if (!inner_layout(plan)) {
         describe_passes(s, plan->passes_f0, "f0");
         describe_passes(s, plan->passes, "main");
@@ -1412,54 +1131,14 @@ int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1,
     if (!d_out && !(d.flags & XRFTHIP_NO_SPECTRUM_OUT)) return XRFTHIP_BAD_ARG;
     if (iso && (!d_iso || !P->binmap.p)) return d_iso ? XRFTHIP_MISSING_TABLE : XRFTHIP_BAD_ARG;
     const bool inner = inner_layout(P);  // (always a workspace)
-    if (!inner && !herm_plan(P) && P->passes.empty()) return XRFTHIP_MISSING_TABLE;
+    if (!inner && P->family != Family::FastH && P->passes.empty()) return XRFTHIP_MISSING_TABLE;  // (the generic passes stand behind every other family)
     if (ws_bytes < P->ws_bytes || (!d_workspace && (inner || P->ws_bytes))) return XRFTHIP_WORKSPACE_TOO_SMALL;
     if (d.batch == 0) return XRFTHIP_OK;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)d_workspace;
     void* out = (d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? nullptr : d_out;
-    const bool det = d.detrend != XRFTHIP_DETREND_NONE;
-    double* acc = (double*)(ws + P->off_acc);
-    double* coef = (double*)(ws + P->off_coef);
     if (iso && !inner) HIP_TRY(hipMemsetAsync(d_iso, 0, (size_t)d.batch * P->nbins * (cross ? 16 : 8), st));
-    switch (P->family) {
-        case Family::FusedInner: return run_fused_inner(P, d_in0, d_in1, out, (double*)d_iso, ws, st);
-        case Family::Composite: return run_inner_plan(P, d_in0, d_out, ws, st);
-        case Family::FastG: return run_fastg(P, d_in0, d_in1, out, (double*)d_iso, st);
-        case Family::FastS: return run_fasts(P, d_in0, out, (double*)d_iso, st);
-        case Family::FastYC: case Family::FastYCFourStep: return run_fastyc(P, d_in0, out, ws, st);
-        case Family::FastR: case Family::FastRComplex: case Family::FastRRows: return run_fastr(P, d_in0, out, st);
-        case Family::FastMX: return run_fastmx(P, d_in0, d_in1, out, st);
-        case Family::FastGY: return P->gy_herm ? run_fasth(P, d_in0, d_in1, out, st) : run_fastgy(P, d_in0, d_in1, out, st);
-        case Family::FastMY: return run_fastmy(P, d_in0, d_in1, out, st);
-        case Family::FastM: case Family::FastN: return run_fastm(P, d_in0, d_in1, out, (double*)d_iso, ws, st);
-        case Family::FastY: case Family::FastY1D: return run_fasty(P, (const float*)d_in0, (const float*)d_in1, out, (double*)d_iso, ws, st);
-        case Family::Generic: break;
-    }
-    for (long long g0 = 0; g0 < d.batch; g0 += P->G) {
-        const long long gc = std::min<long long>(P->G, d.batch - g0);
-        int rc;
-        if (cross) {
-            if (det) {
-                rc = P->dbl ? run_moments<double>(P, d_in0, g0, gc, acc, coef, st) : run_moments<float>(P, d_in0, g0, gc, acc, coef, st);
-                if (rc) return rc;
-            }
-            rc = P->dbl ? run_pipeline<double>(P, P->passes_f0, d_in0, nullptr, nullptr, ws, det ? coef : nullptr, g0, gc, st)
-                        : run_pipeline<float>(P, P->passes_f0, d_in0, nullptr, nullptr, ws, det ? coef : nullptr, g0, gc, st);
-            if (rc) return rc;
-        }
-        const void* in_main = cross ? d_in1 : d_in0;
-        double* acc_m = cross ? acc + (size_t)P->G * P->mom_chunks * 6 : acc;
-        double* coef_m = cross ? coef + d.batch * ((d.flags & XRFTHIP_AXIS_Y) ? d.nx : 1) * 6 : coef;
-        if (det) {
-            rc = P->dbl ? run_moments<double>(P, in_main, g0, gc, acc_m, coef_m, st) : run_moments<float>(P, in_main, g0, gc, acc_m, coef_m, st);
-            if (rc) return rc;
-        }
-        rc = P->dbl ? run_pipeline<double>(P, P->passes, in_main, out, (double*)d_iso, ws, det ? coef_m : nullptr, g0, gc, st)
-                    : run_pipeline<float>(P, P->passes, in_main, out, (double*)d_iso, ws, det ? coef_m : nullptr, g0, gc, st);
-        if (rc) return rc;
-    }
-    return XRFTHIP_OK;
+    return family_ops(P->family).run(P, ExecArgs{d_in0, d_in1, out, (double*)d_iso, ws, st});
 }
 
 
