@@ -253,6 +253,53 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen);
 int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1, void* d_out, void* d_iso,
                  void* d_workspace, size_t ws_bytes, void* stream);
 
+/* A kept pass 1 (no new version number: the presence of the three symbols below tells the capability).  The auto and cross spectra of one pair of fields
+ * (coherence, transfer functions: xrft.cross_spectrum, then xrft.isotropic_power_spectrum of each field) are computed back to back, each by a plan of its own, and
+ * in the two-pass float32 family (XRFTHIP_K_FASTY) every one of those plans starts with the same column pass over the same field.  What that pass leaves for ONE
+ * field -- the tiled half spectrum, the per-column sums and lines, the detrend corrections -- is one self-contained "pass-1 block", and a plan can be told to
+ * write it into memory of the caller's, or to read it from there and launch neither the column kernel nor the fit kernel for that field.
+ *
+ * xrfthip_plan_pass1_bytes: the size of one field's block, a multiple of 256 -- or 0 where no block can be handed over: every kernel family other than FASTY's
+ *   two-pass slabs (the four-step 1-D form included), a plan whose batch runs in more than one group of slabs (xrfthip_desc.slabs_per_group < batch), tuning builds
+ *   whose column pass keeps rendezvous counters.  Ask after the plan's tables are set (a bin map can move a plan to another family).
+ * xrfthip_plan_pass1_signature: *sig = a 64-bit hash of everything but the input's values that decides the bytes of the block of `field` (0, or 1 = d_in1 of a
+ *   CROSS / PHASE plan): the column kernel's instantiation, ny, nx, batch, the rows of the intermediate and the kernel's geometry, the detrend kind, the values of
+ *   the two windows, the field's flip flags, the input strides, the tuning word and XRFTHIP_VERSION.  Two plans with equal signatures write bit-identical blocks
+ *   from the same input, whatever else differs between them (out_mode, shifts, scale, phases, ISO).  XRFTHIP_BAD_ARG where xrfthip_plan_pass1_bytes is 0.
+ *   Whether the input IS the same -- pointer, strides, contents unchanged since the block was written, the stream that orders writer and reader -- is the caller's
+ *   to know; xrft_amd/engine.py keeps a tag per block.
+ * xrfthip_exec_ex: xrfthip_exec with its arguments in a struct (struct_size = sizeof(xrfthip_exec_args)) and, per field, where pass 1 lives:
+ *   XRFTHIP_PASS1_PRIVATE  inside the workspace (xrfthip_exec is this for every field: same launches, same bytes)
+ *   XRFTHIP_PASS1_PRODUCE  run pass 1 as usual, but into pass1_block (xrfthip_plan_pass1_bytes bytes, 256-byte aligned)
+ *   XRFTHIP_PASS1_CONSUME  pass1_block holds the block a plan with the SAME signature produced from the same input, and every kernel that wrote it precedes this call
+ *                          in stream order: no column pass, no fit kernel for the field (the profiling records then show no "fasty_cols" launch for it)
+ *   With EVERY field of the plan in a mode other than PRIVATE the workspace needs only xrfthip_workspace_bytes(plan) - fields * xrfthip_plan_pass1_bytes(plan)
+ *   bytes (fields = 2 for CROSS / PHASE, else 1).  XRFTHIP_BAD_ARG: a mode above 2; a mode other than PRIVATE on a plan whose xrfthip_plan_pass1_bytes is 0 or on
+ *   field 1 of a one-field plan; a null block or one not 256-byte aligned; a block that overlaps [d_workspace, d_workspace + ws_bytes) or the other block.
+ *   Like xrfthip_exec it neither allocates, nor synchronises, nor reads the environment, and it only reads a consumed block. */
+#define XRFTHIP_PASS1_PRIVATE 0u
+#define XRFTHIP_PASS1_PRODUCE 1u
+#define XRFTHIP_PASS1_CONSUME 2u
+typedef struct xrfthip_exec_args {
+    uint32_t struct_size; /* = sizeof(xrfthip_exec_args) */
+    uint32_t reserved;
+    const void* d_in0; /* the arguments of xrfthip_exec */
+    const void* d_in1;
+    void* d_out;
+    void* d_iso;
+    void* d_workspace;
+    size_t ws_bytes;
+    void* stream;
+    struct {
+        void* pass1_block;   /* device memory, NULL with XRFTHIP_PASS1_PRIVATE */
+        uint32_t pass1_mode; /* XRFTHIP_PASS1_* */
+        uint32_t reserved;
+    } field[2]; /* [0]: d_in0, [1]: d_in1 */
+} xrfthip_exec_args;
+size_t xrfthip_plan_pass1_bytes(const xrfthip_plan* plan);
+int xrfthip_plan_pass1_signature(const xrfthip_plan* plan, int field, uint64_t* sig);
+int xrfthip_exec_ex(const xrfthip_plan* plan, const xrfthip_exec_args* args);
+
 /* Stand-alone detrend (xrft.detrend, detrend.py:11-97) over the last `ndim` axes: out = in - trend, same dtype.
  * d_workspace: >= xrfthip_detrend_workspace_bytes(batch) bytes. */
 size_t xrfthip_detrend_workspace_bytes(int64_t batch);

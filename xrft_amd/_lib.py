@@ -33,7 +33,9 @@ EXPORTS = [
     "xrfthip_detrend", "xrfthip_detrend3", "xrfthip_spectrum_tail", "xrfthip_spectrum_tail_axis", "xrfthip_gather_axis", "xrfthip_isotropize",
     "xrfthip_isotropize_workspace_bytes", "xrfthip_table_mul", "xrfthip_reduce_axis", "xrfthip_detrend_inner_workspace_bytes", "xrfthip_detrend_inner", "xrfthip_angle",
     "xrfthip_plan_uses_bluestein", "xrfthip_convert", "xrfthip_plan_kernel_info", "xrfthip_selftest_floor",
+    "xrfthip_plan_pass1_bytes", "xrfthip_plan_pass1_signature", "xrfthip_exec_ex",
 ]
+PASS1_PRIVATE, PASS1_PRODUCE, PASS1_CONSUME = 0, 1, 2  # xrfthip_exec_args.field[].pass1_mode
 
 
 class XrftHipUnavailable(RuntimeError):
@@ -58,6 +60,17 @@ class Desc(C.Structure):
         ("in_stride_batch", C.c_int64),  # elements between its slabs (0 = ny * nx); trailing-axes layout only, strides in multiples of 16 bytes
         ("herm_ny", C.c_int64),  # > 0 (both): the columns of an AXIS_Y plan are the half spectrum of a real herm_ny x herm_nx grid -- the last pass of a
         ("herm_nx", C.c_int64),  # three-axis power / cross spectrum: [batch][nt][herm_ny][herm_nx/2 + 1] complex in, the full [batch][nt][herm_ny][herm_nx] result out
+    ]
+
+
+class _ExecField(C.Structure):
+    _fields_ = [("pass1_block", C.c_void_p), ("pass1_mode", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ExecArgs(C.Structure):  # xrfthip_exec_args
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("d_in0", C.c_void_p), ("d_in1", C.c_void_p), ("d_out", C.c_void_p), ("d_iso", C.c_void_p),
+        ("d_workspace", C.c_void_p), ("ws_bytes", C.c_size_t), ("stream", C.c_void_p), ("field", _ExecField * 2),
     ]
 
 
@@ -98,6 +111,10 @@ def _bind(dll):
     dll.xrfthip_isotropize_workspace_bytes.argtypes = [i32, i64, i64, i64, i32]
     dll.xrfthip_isotropize.argtypes = [i32, i64, i64, i64, vp, vp, i32, vp, vp, sz, vp]
     dll.xrfthip_selftest_floor.argtypes = [vp, vp, vp, i64, i32, C.POINTER(C.c_double), vp]
+    dll.xrfthip_plan_pass1_bytes.restype = sz
+    dll.xrfthip_plan_pass1_bytes.argtypes = [vp]
+    dll.xrfthip_plan_pass1_signature.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]
+    dll.xrfthip_exec_ex.argtypes = [vp, C.POINTER(ExecArgs)]
     for name in EXPORTS:
         getattr(dll, name)  # AttributeError here = the .so does not export what the header declares
     return dll

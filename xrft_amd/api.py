@@ -663,6 +663,15 @@ def _execute_inner(c, da, mode, scale, extra_flags=0, da2=None, c2=None, iso=Non
     return out.reshape(shape)
 
 
+def _own_tensor(da, t):
+    """The caller's own device tensor behind ``t`` -- ``da.data`` when ``t`` is its memory, not a copy made for the call -- else None.  Only such a field takes part
+    in the reuse of the column pass (engine.reuse_column_pass): its identity and ``_version`` say whether it is unchanged since an earlier call."""
+    d = da.data
+    if isinstance(d, torch.Tensor) and d.device.type == _lib.device() and d.dtype == t.dtype and d.untyped_storage().data_ptr() == t.untyped_storage().data_ptr():
+        return d
+    return None
+
+
 def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
     k = _inplace_axis(c, da, iso) if (extra_flags & ~_lib.REALDIM_X2) == 0 else None
     if k is not None:
@@ -717,7 +726,7 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
             refused = skey in _STRIDED_REFUSED
         if not refused:
             try:
-                out, iso_out = _get_plan(binmap_key=bkey, **skw).execute(t, t2)
+                out, iso_out = _get_plan(binmap_key=bkey, **skw).execute(t, t2, sources=(_own_tensor(da, t),) if t2 is None else (_own_tensor(da, t), _own_tensor(da2, t2)))
                 return out, iso_out, other
             except _lib.XrftHipError as e:
                 if e.status != _lib.UNSUPPORTED_LENGTH:
@@ -742,7 +751,7 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
         raise _UnsupportedLength(f"transform length(s) {lens} not supported on the device: a length with a prime factor above 128 must be "
                          f"<= ~{lim} samples for {str(t.dtype).replace('torch.', '')} data (Bluestein inside one LDS tile) unless it is the only "
                          f"transform axis; transform the axes one at a time, or pad / crop the axis (e.g. xrft_amd.pad) to a smooth length") from e
-    out, iso_out = plan.execute(t, t2)
+    out, iso_out = plan.execute(t, t2, sources=(_own_tensor(da, t),) if t2 is None else (_own_tensor(da, t), _own_tensor(da2, t2)))
     return out, iso_out, other
 
 

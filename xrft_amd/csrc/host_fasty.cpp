@@ -522,22 +522,72 @@ int try_fastyc(xrfthip_plan* P) {
     return rc ? rc : plan_ones(P, 4096);
 }
 
+// ---- the pass-1 block (xrfthip_exec_ex): what the column pass and the fit kernel leave for ONE field -- intermediate, per-column sums and lines, corrections --
+// as one piece of memory outside the workspace, so that a second plan over the same field can read it instead of running the two kernels again.
+// Only where the whole batch is one group of slabs (the block is the field's, not a ring slot's) and pass 1 keeps no state beside it (the rendezvous counters).
+size_t fasty_pass1_bytes(const xrfthip_plan* P) {
+    if (P->family != Family::FastY || P->d.batch < 1 || P->G < P->d.batch || ((P->tune_y >> 21) & 1)) return 0;
+    if (((P->p1_w | P->p1_fit | P->p1_corr) & 255) || !P->p1_w) return 0;  // (the lengths of fasty.h leave whole 256-byte units: the workspace holds exactly these bytes per field)
+    return P->p1_w + P->p1_fit + P->p1_corr;
+}
+
+// Everything that decides the bytes of a field's block, hashed (FNV-1a, 64 bit): two plans with equal signatures leave identical blocks from the same input.
+namespace {
+struct Fnv {
+    uint64_t h = 1469598103934665603ull;
+    void bytes(const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } }
+    void num(long long v) { bytes(&v, sizeof v); }
+    void table(const std::vector<double>& t) { num((long long)t.size()); if (!t.empty()) bytes(t.data(), t.size() * sizeof(double)); }
+};
+}
+uint64_t fasty_pass1_signature(const xrfthip_plan* P, int field) {
+    const xrfthip_desc& d = P->d;
+    const YGeomRt C = ycols_geom(P->yny);
+    Fnv f;
+    f.num(XRFTHIP_VERSION); f.num(XRFT_YDBG); f.num((long long)sizeof(cf));
+    // the kernel: fasty_cols_kernel<NY, DET, W2D = false, STR>, then fasty_fit_kernel with a detrend
+    f.num(P->yny); f.num(d.detrend != 0); f.num(in_strided(P)); f.num(d.detrend);
+    f.num(d.ny); f.num(d.nx); f.num(d.batch); f.num(P->G); f.num(P->y_nrow_pad); f.num(d.dtype); f.num(d.ndim);
+    f.num(C.thr); f.num(C.gxy); f.num(C.cw); f.num(C.rk); f.num(C.lbs); f.num((long long)C.lds); f.num(ycols_gstr(P->yny));
+    f.num((long long)P->p1_w); f.num((long long)P->p1_fit); f.num((long long)P->p1_corr);
+    f.num(in_pitch(P)); f.num(in_slab(P));
+    // the field's own flip flags (fasty.h takes none today: a plan with one never reaches here)
+    const uint32_t fy = field == 0 && plan_two(P) ? XRFTHIP_FLIP0_Y : XRFTHIP_FLIP_Y, fx = field == 0 && plan_two(P) ? XRFTHIP_FLIP0_X : XRFTHIP_FLIP_X;
+    f.num((d.flags & fy) != 0); f.num((d.flags & fx) != 0);
+    // the tables pass 1 reads: the windows (the float32 tables are these values rounded; none = ones) -- win_x is the fit kernel's, too; W_ny^k follows from ny
+    f.table(P->host_win_y); f.table(P->host_win_x);
+    f.num(P->tune_y);
+    return f.h;
+}
+
 static int run_fasty(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
     const float *in = (const float*)a.in0, *in1 = (const float*)a.in1;
     void* out = a.out; double* iso = a.iso; char* ws = a.ws; hipStream_t st = a.stream;
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
+    // a field whose pass 1 lives in a block of the caller's (xrfthip_exec_ex: one group of slabs, g0 = 0): the three parts in the workspace's order
+    auto in_block = [&](FastY& q, int f) {
+        if (!a.p1_mode[f]) return;
+        q.w2 = reinterpret_cast<cf*>(a.p1_block[f]);
+        q.colfit = reinterpret_cast<double*>(a.p1_block[f] + P->p1_w);
+        q.corr = reinterpret_cast<const float*>(a.p1_block[f] + P->p1_w + P->p1_fit);
+    };
+    // ... and with every field there, the workspace is the plan's without the fields' shares: what lies behind them moves up
+    const bool compact = a.p1_mode[0] && (!two || a.p1_mode[1]);
     for (long long g0 = 0; g0 < d.batch; g0 += P->G) {
         const long long gc = std::min<long long>(P->G, d.batch - g0);
         FastY p = fasty_params(P, in, out, iso, ws, g0, gc, 0, P->G);
+        in_block(p, 0);
+        if (compact) p.iso_part = reinterpret_cast<double*>(ws + (P->off_isopart - (size_t)(two ? 2 : 1) * fasty_pass1_bytes(P)));
         if ((P->tune_y >> 21) & 1) {
             p.rdv = reinterpret_cast<unsigned*>(ws + P->off_rdv);
             HIP_TRY(hipMemsetAsync(p.rdv, 0, (size_t)gc * (size_t)std::max<long long>(P->ynx / 8, 1) * sizeof(unsigned), st));
         }
-        fasty_launch_cols(P, p, gc, st, true);
+        if (a.p1_mode[0] != XRFTHIP_PASS1_CONSUME) fasty_launch_cols(P, p, gc, st, true);
         if (two) {  // field 1 through the same column pass into its own intermediate; the row pass reads both
-            const FastY p1 = fasty_params(P, in1, out, iso, ws, g0, gc, 1, P->G);
-            fasty_launch_cols(P, p1, gc, st, true);
+            FastY p1 = fasty_params(P, in1, out, iso, ws, g0, gc, 1, P->G);
+            in_block(p1, 1);
+            if (a.p1_mode[1] != XRFTHIP_PASS1_CONSUME) fasty_launch_cols(P, p1, gc, st, true);
             p.w2b = p1.w2;
             p.corr_b = p1.corr;
         }

@@ -367,6 +367,9 @@ struct xrfthip_plan {
     std::vector<Pass> passes_f0;  // CROSS: field 0 -> raw F0 buffer
     // workspace layout (byte offsets)
     size_t off_acc = 0, off_coef = 0, off_w = 0, off_w2 = 0, off_f0 = 0, off_pt = 0, off_rowfit = 0, off_corr = 0, off_isopart = 0, off_isotmp = 0, off_rdv = 0, ws_bytes = 0;
+    // the two y-first passes: what pass 1 leaves for ONE field inside the workspace -- its share of the intermediate (off_w), of the per-column sums and lines (off_rowfit) and
+    // of the corrections (off_corr).  A pass-1 block handed in from outside (xrfthip_exec_ex) holds the three, in this order (layout_passes; fasty_pass1_bytes)
+    size_t p1_w = 0, p1_fit = 0, p1_corr = 0;
     int iso_chunks = 1;  // workgroups per slab of the generic radial-sum pass (partial sums added in order)
     std::string desc_text;
     Family family = Family::Generic;  // what xrfthip_exec runs
@@ -469,7 +472,8 @@ struct xrfthip_plan {
 struct YGeomRt { int thr, gxy, cw, rk, lbs; size_t lds; };
 
 // What xrfthip_exec hands a family's launcher: the caller's buffers (out: null when the spectrum is not stored), the workspace, the stream.
-struct ExecArgs { const void* in0; const void* in1; void* out; double* iso; char* ws; hipStream_t stream; };
+// p1_block / p1_mode: per field, xrfthip_exec_args.field (0 = private: pass 1 of the field writes into the workspace; only FastY takes anything else).
+struct ExecArgs { const void* in0; const void* in1; void* out; double* iso; char* ws; hipStream_t stream; char* p1_block[2] = {nullptr, nullptr}; uint32_t p1_mode[2] = {0, 0}; };
 
 // One row per Family: the host side of a kernel family, defined in the unit that owns it (the file map above) and found through family_ops().
 // A null entry: nothing to do / no / none.
@@ -516,6 +520,8 @@ long long fasty_rows_gx(const xrfthip_plan* P);
 int build_unit_windows(xrfthip_plan* P, const int32_t* bm, int rpu);
 bool fasty_fits(const xrfthip_plan* P);
 int fasty_tables(xrfthip_plan* P);
+size_t fasty_pass1_bytes(const xrfthip_plan* P);
+uint64_t fasty_pass1_signature(const xrfthip_plan* P, int field);
 // host_fastm.cpp
 bool fastm_iso_fused(const xrfthip_plan* P);
 int fastm_rows_rpu(const xrfthip_plan* P);

@@ -613,6 +613,7 @@ void layout_passes(xrfthip_plan* P) {
     const size_t nfit = (size_t)(fast ? 2 * P->ynx : d.ny);  // per-column sums + subtracted lines
     P->off_rowfit = off; if (fast) off = al(off + (size_t)G * nfit * 2 * sizeof(double) * nf);
     P->off_corr = off; if (fast) off = al(off + (size_t)G * nfit * 2 * sizeof(float) * nf);  // (16 bytes per column: fasty uses 8, fastm's float64 pairs all 16)
+    P->p1_w = fast ? (size_t)G * slab_w : 0; P->p1_fit = fast ? (size_t)G * nfit * 2 * sizeof(double) : 0; P->p1_corr = fast ? (size_t)G * nfit * 2 * sizeof(float) : 0;  // (one field's share of the three)
     P->off_isopart = off;
     if (fast && !fastm_pipeline(P) && (d.flags & XRFTHIP_ISO)) {  // per-workgroup partial radial sums of one group of slabs (reduced in order)
         const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
@@ -1119,11 +1120,23 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
     return (int)n;
 }
 
-int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1, void* d_out, void* d_iso,
-                 void* d_workspace, size_t ws_bytes, void* stream) {
-    if (!plan || !d_in0) return XRFTHIP_BAD_ARG;
+size_t xrfthip_plan_pass1_bytes(const xrfthip_plan* plan) {
+    if (!plan) return 0;
+    return fasty_pass1_bytes(plan);
+}
+
+int xrfthip_plan_pass1_signature(const xrfthip_plan* plan, int field, uint64_t* sig) {
+    if (!plan || !sig || field < 0 || field > (plan_two(plan) ? 1 : 0) || !fasty_pass1_bytes(plan)) return XRFTHIP_BAD_ARG;
+    *sig = fasty_pass1_signature(plan, field);
+    return XRFTHIP_OK;
+}
+
+int xrfthip_exec_ex(const xrfthip_plan* plan, const xrfthip_exec_args* args) {
+    if (!plan || !args || args->struct_size != sizeof(xrfthip_exec_args) || !args->d_in0) return XRFTHIP_BAD_ARG;
     const xrfthip_plan* P = plan;
     const xrfthip_desc& d = P->d;
+    const void *d_in0 = args->d_in0, *d_in1 = args->d_in1;
+    void *d_out = args->d_out, *d_iso = args->d_iso, *d_workspace = args->d_workspace;
     const bool cross = d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE;
     const bool iso = (d.flags & XRFTHIP_ISO) != 0;
     if (cross && !d_in1) return XRFTHIP_BAD_ARG;
@@ -1132,13 +1145,43 @@ int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1,
     if (iso && (!d_iso || !P->binmap.p)) return d_iso ? XRFTHIP_MISSING_TABLE : XRFTHIP_BAD_ARG;
     const bool inner = inner_layout(P);  // (always a workspace)
     if (!inner && P->family != Family::FastH && P->passes.empty()) return XRFTHIP_MISSING_TABLE;  // (the generic passes stand behind every other family)
-    if (ws_bytes < P->ws_bytes || (!d_workspace && (inner || P->ws_bytes))) return XRFTHIP_WORKSPACE_TOO_SMALL;
+    // pass-1 blocks: the fields of a plan that hands them over (fasty_pass1_bytes), whole, aligned, apart from each other and from the workspace
+    ExecArgs a{d_in0, d_in1, nullptr, (double*)d_iso, (char*)d_workspace, (hipStream_t)args->stream};
+    const int nf = cross ? 2 : 1;
+    int handed = 0;
+    for (int f = 0; f < 2; ++f) {
+        const uint32_t mode = args->field[f].pass1_mode;
+        if (mode > XRFTHIP_PASS1_CONSUME || (mode && f >= nf)) return XRFTHIP_BAD_ARG;
+        if (!mode) continue;
+        char* b = (char*)args->field[f].pass1_block;
+        if (!fasty_pass1_bytes(P) || !b || (((uintptr_t)b) & 255)) return XRFTHIP_BAD_ARG;
+        a.p1_block[f] = b; a.p1_mode[f] = mode;
+        ++handed;
+    }
+    // ... with every field handed over nothing of pass 1 lies in the workspace: it shrinks by the fields' shares (the remaining parts move up, run_fasty)
+    const size_t need = handed == nf ? P->ws_bytes - (size_t)nf * fasty_pass1_bytes(P) : P->ws_bytes;
+    if (args->ws_bytes < need || (!d_workspace && (inner || need))) return XRFTHIP_WORKSPACE_TOO_SMALL;
+    if (handed) {
+        const size_t pb = fasty_pass1_bytes(P);
+        auto apart = [](const char* x, size_t nx_, const char* y, size_t ny_) { return !nx_ || !ny_ || x + nx_ <= y || y + ny_ <= x; };
+        for (int f = 0; f < nf; ++f)
+            if (a.p1_block[f] && !apart(a.p1_block[f], pb, a.ws, args->ws_bytes)) return XRFTHIP_BAD_ARG;
+        if (a.p1_block[0] && a.p1_block[1] && !apart(a.p1_block[0], pb, a.p1_block[1], pb)) return XRFTHIP_BAD_ARG;
+    }
     if (d.batch == 0) return XRFTHIP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)d_workspace;
-    void* out = (d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? nullptr : d_out;
-    if (iso && !inner) HIP_TRY(hipMemsetAsync(d_iso, 0, (size_t)d.batch * P->nbins * (cross ? 16 : 8), st));
-    return family_ops(P->family).run(P, ExecArgs{d_in0, d_in1, out, (double*)d_iso, ws, st});
+    a.out = (d.flags & XRFTHIP_NO_SPECTRUM_OUT) ? nullptr : d_out;
+    if (iso && !inner) HIP_TRY(hipMemsetAsync(d_iso, 0, (size_t)d.batch * P->nbins * (cross ? 16 : 8), a.stream));
+    return family_ops(P->family).run(P, a);
+}
+
+// (the all-private case of xrfthip_exec_ex: every field's pass 1 inside the workspace)
+int xrfthip_exec(const xrfthip_plan* plan, const void* d_in0, const void* d_in1, void* d_out, void* d_iso,
+                 void* d_workspace, size_t ws_bytes, void* stream) {
+    xrfthip_exec_args args{};
+    args.struct_size = sizeof args;
+    args.d_in0 = d_in0; args.d_in1 = d_in1; args.d_out = d_out; args.d_iso = d_iso;
+    args.d_workspace = d_workspace; args.ws_bytes = ws_bytes; args.stream = stream;
+    return xrfthip_exec_ex(plan, &args);
 }
 
 

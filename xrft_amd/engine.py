@@ -6,8 +6,10 @@ arithmetic step runs inside libxrft_hip.so.
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 import threading
+import weakref
 
 import numpy as np
 import torch
@@ -40,6 +42,8 @@ class SpectralPlan:
                  slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
+        self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
+        self._pass1 = None
         if dtype not in _DTYPES:
             raise TypeError(f"unsupported dtype {dtype}")
         self.ndim, self.batch, self.ny, self.nx = int(ndim), int(batch), int(ny), int(nx)
@@ -102,6 +106,18 @@ class SpectralPlan:
         """True when an axis of the plan runs Bluestein's algorithm inside the tile kernels (a prime factor with no butterfly)."""
         return bool(self._dll.xrfthip_plan_uses_bluestein(self._h))
 
+    def pass1(self):
+        """(bytes of one field's pass-1 block, its signature per field) -- xrfthip_plan_pass1_bytes / _signature; (0, ()) where the plan hands no block over."""
+        if self._pass1 is None:
+            nb = int(self._dll.xrfthip_plan_pass1_bytes(self._h))
+            sigs = []
+            for f in range((2 if self.out_mode in (_lib.OUT_CROSS, _lib.OUT_PHASE) else 1) if nb else 0):
+                sig = C.c_uint64(0)
+                _lib.check(self._dll.xrfthip_plan_pass1_signature(self._h, f, C.byref(sig)))
+                sigs.append(int(sig.value))
+            self._pass1 = (nb if sigs else 0, tuple(sigs))
+        return self._pass1
+
     def set_profiling(self, enable=True):
         _lib.check(self._dll.xrfthip_plan_set_profiling(self._h, int(bool(enable))))
 
@@ -133,9 +149,11 @@ class SpectralPlan:
         want_b = self.in_stride_batch or self.ny * self.nx
         return (self.ndim == 1 or self.ny == 1 or sy == want_y) and (self.batch <= 1 or sb == want_b)
 
-    def execute(self, in0, in1=None, out=None, iso=None):
+    def execute(self, in0, in1=None, out=None, iso=None, sources=None):
         """``in0``/``in1``: contiguous tensors of shape (batch, ny, nx) (any leading shape that flattens to it); a plan made with ``in_stride_y`` /
-        ``in_stride_batch`` takes the view with exactly those strides instead (see ``strides_of``).  Returns (out, iso); either may be None depending on the flags."""
+        ``in_stride_batch`` takes the view with exactly those strides instead (see ``strides_of``).  Returns (out, iso); either may be None depending on the flags.
+        ``sources``: per field, the caller's OWN device tensor whose memory ``in0`` / ``in1`` is (not a copy made for this call), or None: only such fields
+        take part in the reuse of the column pass (``reuse_column_pass``)."""
         dev = in0.device
         nx_in = self.nx // 2 + 1 if (self.flags & _lib.C2R_X) else self.nx
         if in0.dtype != self.dtype or not self._layout_ok(in0) or in0.numel() != self.batch * self.ny * nx_in * self.inner * self.mid:
@@ -171,10 +189,80 @@ class SpectralPlan:
         with _stream_lock(dev, stream):
             # grown (and the outgrown buffer retired) only HERE, under the stream's lock: no other thread is between its look-up and
             # its enqueue on this stream, so the event recorded at retirement really follows every use of the old buffer
-            ws = _workspace(dev, stream, self.workspace_bytes)
-            _lib.check(self._dll.xrfthip_exec(self._h, _ptr(in0), _ptr(in1), _ptr(out if want_out else None), _ptr(iso),
-                                              _ptr(ws), ws.numel(), stream))
+            fields = (in0,) if in1 is None else (in0, in1)
+            if _takes_part(dev, sources, len(fields)) and self.pass1()[0]:
+                self._execute_blocks(dev, stream, fields, sources, out if want_out else None, iso)
+            else:
+                ws = _workspace(dev, stream, self.workspace_bytes)
+                _blocks_overwritten((str(dev), stream.value), 0, self.workspace_bytes)
+                _lib.check(self._dll.xrfthip_exec(self._h, _ptr(in0), _ptr(in1), _ptr(out if want_out else None), _ptr(iso),
+                                                  _ptr(ws), ws.numel(), stream))
         return (out if want_out else None), iso
+
+    def _execute_blocks(self, dev, stream, fields, sources, out, iso):
+        """xrfthip_exec_ex with every field's pass 1 in a block in front of the plan's private part of the stream's scratch: read from the block another plan left for
+        the same unchanged field (no column pass, no fit kernel), or written there for the calls that follow.  Called with _stream_lock(dev, stream) held."""
+        key = (str(dev), stream.value)
+        nb, sigs = self.pass1()
+        nf = len(fields)
+        private = self.workspace_bytes - nf * nb  # (every field in a block: xrfthip_exec_ex)
+        tags = [(t.data_ptr(), t.storage_offset(), tuple(t.shape), tuple(t.stride()), t.dtype, str(t.device), t._version, stream.value, sigs[f])
+                for f, t in enumerate(fields)]
+        ws = _WS.get(key)
+        slack = 0 if dev.type == "cuda" else 255  # (the emulated device's memory is the host's: 64-byte aligned; the blocks start on the first 256-byte boundary)
+        while True:
+            st = _BLOCKS.setdefault(key, {"gen": 0, "slots": []})
+            live = [s for s in st["slots"] if s["gen"] == st["gen"]]
+            # a block is read only if every item of its tag matches, the field's tensor is the very object it was written from, and ANOTHER plan wrote it:
+            # a call repeated on an unchanged array computes everything again
+            used, matched = [], {}
+            for f in range(nf):
+                for s in live:
+                    if (s["tag"] == tags[f] and s["ref"]() is sources[f] and s["producer"] != self._serial and s["bytes"] == nb
+                            and not any(s is m for m in matched.values())):
+                        matched[f] = s
+                        used.append((s["off"], s["off"] + nb))
+                        break
+            offs, at = {}, 0
+            for f in range(nf):  # the fields to compute: the lowest places the blocks read in this call leave free
+                if f in matched:
+                    offs[f] = matched[f]["off"]
+                    continue
+                while any(at < e and b < at + nb for b, e in used):
+                    at = min(e for b, e in used if at < e and b < at + nb)
+                offs[f] = at
+                used.append((at, at + nb))
+            end = max(e for _b, e in used)
+            new = [(offs[f], offs[f] + nb) for f in range(nf) if f not in matched]
+            # blocks of the same size this call neither reads nor writes (the other field of a pair): kept where the scratch has the room -- a call that reads a
+            # block may also grow the scratch for it, by no more than its own private part
+            keep = max([end] + [s["off"] + s["bytes"] for s in live if s["bytes"] == nb and not any(s is m for m in matched.values())
+                                and not any(s["off"] < e and b < s["off"] + s["bytes"] for b, e in new)])
+            have = ws.numel() - slack if ws is not None else 0
+            if keep + private <= have or (matched and keep > end):
+                want_bytes, start = keep + private, keep
+            else:
+                want_bytes, start = end + private, end
+            if want_bytes > have:
+                ws = _workspace(dev, stream, want_bytes + slack)  # (a new buffer: every block is gone with the old one -- lay the call out again)
+                continue
+            break
+        _PEAK[key] = max(_PEAK.get(key, 0), want_bytes)
+        for b, e in new + [(start, start + private)]:
+            _blocks_overwritten(key, b, e)
+        a = _lib.ExecArgs()
+        a.struct_size = C.sizeof(_lib.ExecArgs)
+        a.d_in0, a.d_in1 = fields[0].data_ptr(), (fields[1].data_ptr() if nf == 2 else None)
+        a.d_out, a.d_iso = (out.data_ptr() if out is not None else None), (iso.data_ptr() if iso is not None else None)
+        base = (ws.data_ptr() + 255) & ~255
+        a.d_workspace, a.ws_bytes, a.stream = base + start, max(private, 0), stream.value
+        for f in range(nf):
+            a.field[f].pass1_block = base + offs[f]
+            a.field[f].pass1_mode = _lib.PASS1_CONSUME if f in matched else _lib.PASS1_PRODUCE
+        _lib.check(self._dll.xrfthip_exec_ex(self._h, C.byref(a)))
+        for f in range(nf):
+            if f not in matched:
+                st["slots"].append({"off": offs[f], "bytes": nb, "gen": st["gen"], "tag": tags[f], "ref": weakref.ref(sources[f]), "producer": self._serial})
 
 
 def strides_of(t, ndim):
@@ -200,6 +288,43 @@ def strides_of(t, ndim):
     if sy < nx or sb <= 0:
         return None, None
     return int(sy), int(sb)
+
+
+_PLAN_SERIAL = itertools.count(1)
+
+# Reuse of the column pass.  The spectra of one pair of fields are computed back to back (xrft.cross_spectrum(a, b), then xrft.isotropic_power_spectrum(a) and (b)),
+# each call through a plan of its own that begins with the SAME column pass over the same field.  The stream's scratch therefore keeps up to two pass-1 blocks
+# (include/xrft_hip.h, xrfthip_exec_ex) in front of the running plan's private part, each with a tag: the field (data_ptr, storage offset, shape, strides, dtype,
+# device, tensor._version, the tensor object itself), the stream, the plan's pass-1 signature, the plan that wrote it, the generation of the scratch buffer.
+# A later call reads a block only when all of it matches and another plan wrote it.  Whatever writes a block's bytes (any exec on the scratch that reaches them), a
+# new scratch buffer and clear_plan_cache() drop the tags.
+_BLOCKS = {}   # (device, stream) -> {"gen": generation of the scratch buffer, "slots": [block, ...]}
+_PEAK = {}     # (device, stream) -> the most scratch bytes a call with blocks has asked for (bench scripts)
+_REUSE = [True]
+_CAPTURED = [False]
+
+
+def reuse_column_pass(enable=None):
+    """Switch the reuse of a field's column pass between spectral products (default on); ``reuse_column_pass(False)``: every call computes everything inside its
+    own workspace.  The results are bit-identical either way.  Returns the setting."""
+    if enable is not None:
+        _REUSE[0] = bool(enable)
+    return _REUSE[0]
+
+
+def _takes_part(dev, sources, nf):
+    if not _REUSE[0] or sources is None or len(sources) != nf or any(not isinstance(s, torch.Tensor) for s in sources):
+        return False
+    if dev.type == "cuda" and not _CAPTURED[0] and torch.cuda.is_current_stream_capturing():
+        _CAPTURED[0] = True  # a captured graph writes the scratch again whenever it is replayed, unseen from here: no block is trusted any more (until clear_workspaces)
+    return not _CAPTURED[0]
+
+
+def _blocks_overwritten(key, begin, end):
+    """Bytes [begin, end) of the stream's scratch are about to be written: the blocks they reach are gone."""
+    st = _BLOCKS.get(key)
+    if st and st["slots"]:
+        st["slots"] = [s for s in st["slots"] if s["gen"] == st["gen"] and (s["off"] >= end or s["off"] + s["bytes"] <= begin)]
 
 
 # One grow-only scratch buffer per (device, stream), shared by every plan: work on one stream is ordered, so plans never
@@ -236,6 +361,10 @@ def _workspace(dev, stream, nbytes):
                     ev.record(torch.cuda.current_stream(dev))
                     _WS_RETIRED.append((ws, ev))
             ws = _WS[key] = torch.empty(want, dtype=torch.uint8, device=dev)
+            st = _BLOCKS.get(key)
+            if st is not None:  # a new buffer: a new generation, no blocks
+                st["gen"] += 1
+                st["slots"] = []
         return ws
 
 
@@ -247,6 +376,9 @@ def clear_workspaces():
                 torch.cuda.synchronize()
             _WS.clear()
             _WS_RETIRED.clear()
+        _BLOCKS.clear()
+        _PEAK.clear()
+        _CAPTURED[0] = False
 
 
 def detrend(x, ndim, kind):
