@@ -60,7 +60,21 @@ typedef enum xrfthip_dtype { /* dtype of the input array; the arithmetic runs in
     XRFTHIP_F32 = 0,
     XRFTHIP_F64 = 1,
     XRFTHIP_C64 = 2,
-    XRFTHIP_C128 = 3
+    XRFTHIP_C128 = 3,
+    /* Real half-precision input, read where it lies at 2 bytes per sample and widened to float32 in registers (exact: every float16 / bfloat16 value is a float32
+     * value).  Accepted as xrfthip_desc.dtype and as dtype_in of xrfthip_convert only (no symbol and no version number tells the capability: an older library answers
+     * XRFTHIP_BAD_ARG).  A plan with one of them IS the float32 plan of the same descriptor -- same family, kernels behind the loads, workspace, tables, and
+     * float32 / complex64 output (d_iso float64 / complex128) -- and its result is bit-identical to that plan's on the widened samples, NaN payloads aside.
+     *   XRFTHIP_UNSUPPORTED_LENGTH ("the caller widens": xrfthip_convert to XRFTHIP_F32, then the float32 plan) from xrfthip_plan_create, or from the xrfthip_plan_set_*
+     *   call that moves the plan there: every family but the float32 ones that read 2-byte samples -- FASTY (two-pass slabs and the four-step 1-D form), FASTS, FASTR,
+     *   FASTG / FASTG_ROWS with real input -- hence also XRFTHIP_AXIS_Y, inner / mid, and a non-zero in_stride_y / in_stride_batch: a strided half view is NOT read
+     *   in place (copy it contiguous in half precision, 2 bytes per sample, or widen it).
+     *   XRFTHIP_BAD_ARG as for real float32 input: XRFTHIP_INVERSE, XRFTHIP_C2R_X, XRFTHIP_PHASE_IN, herm_ny / herm_nx (complex input only).
+     *   Alignment, in bytes: d_in0 (and d_in1) 16-byte aligned -- xrfthip_exec checks and answers XRFTHIP_UNSUPPORTED_LENGTH otherwise, reading nothing; the kernels issue
+     *   aligned 8-byte (FASTY: four samples) and 4-byte (two samples) vector loads, 2-byte loads only for an odd row length of FASTG, and touch no byte outside
+     *   [d_in, d_in + 2 * batch * ny * nx).  d_in0 and d_in1 of a CROSS / PHASE plan hold the same format. */
+    XRFTHIP_F16 = 4, /* IEEE binary16 */
+    XRFTHIP_BF16 = 5 /* bfloat16: the upper half of a float32 */
 } xrfthip_dtype;
 
 typedef enum xrfthip_out_mode {
@@ -346,7 +360,9 @@ int xrfthip_gather_axis(int32_t elem_bytes, int64_t outer, int64_t n_out, int64_
 int xrfthip_table_mul(int32_t dtype, int64_t batch, int64_t n_in, int64_t n_out, const void* d_in, const void* d_table, void* d_out, void* stream);
 
 /* d_out[e] = (precision of dtype_out) d_in[e], e < n: F32 <-> F64 or C64 <-> C128 (n counts real or complex elements of dtype_in's kind).
- * The precision change around float32 plans that run in float64 (Bluestein lengths, see xrfthip_plan_uses_bluestein). */
+ * The precision change around float32 plans that run in float64 (Bluestein lengths, see xrfthip_plan_uses_bluestein).
+ * F16 -> F32 and BF16 -> F32: the exact widening of half-precision samples, one pass (subnormals, +-0, +-inf exact; NaN -> NaN), for the calls a half plan declines
+ * with XRFTHIP_UNSUPPORTED_LENGTH.  d_in 2-byte aligned (4-byte: pairs of samples per load), d_out 4-byte aligned; no other direction. */
 int xrfthip_convert(int32_t dtype_in, int32_t dtype_out, int64_t n, const void* d_in, void* d_out, void* stream);
 
 /* d_out[o][i] = scale * sum_k d_in[o][k][i] over [outer][n][inner] -> [outer][inner], same dtype (F32|F64|C64|C128), accumulated in float64

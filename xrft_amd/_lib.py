@@ -13,6 +13,7 @@ LIB_NAME = "libxrft_hip.so"
 
 # ---- enums mirrored from include/xrft_hip.h
 F32, F64, C64, C128 = 0, 1, 2, 3
+F16, BF16 = 4, 5  # real half-precision input of a plan / of xrfthip_convert: read at 2 bytes per sample, computed in float32
 OUT_COMPLEX, OUT_POWER, OUT_CROSS, OUT_PHASE = 0, 1, 2, 3
 DETREND_NONE, DETREND_CONSTANT, DETREND_LINEAR = 0, 1, 2
 HALF_X, SHIFT_Y, SHIFT_X, ISHIFT_Y, ISHIFT_X, FLIP_Y, FLIP_X = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40

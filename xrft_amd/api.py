@@ -9,6 +9,10 @@ Device side (one fused plan per call): detrend, window, flip/ifftshift, FFT, fft
 Deviations from the reference, all documented in DESIGN.md:
   * float32 input is computed and returned in float32/complex64 (the reference promotes to float64 as soon as a
     float64 window or ``prod(dx)`` touches the data); isotropic results are returned in float64/complex128;
+  * float16 / bfloat16 input (numpy float16 arrays, torch float16 / bfloat16 tensors) is computed in float32 and returned as
+    float32/complex64, exactly what the call on ``x.float()`` returns: where a float32 kernel family reads 2-byte samples the
+    field is read where it lies (no widened copy), everywhere else it is widened once, exactly, on the device.  (torch half
+    tensors used to be widened to float64 and returned as float64/complex128.)
   * at most two transform dimensions (the reference also offers 3-D linear detrend / N-D fftn);
   * ``chunks_to_segments`` takes its segment length from ``DataArray.chunk({dim: n})`` metadata (no dask here).
 """
@@ -202,9 +206,17 @@ def _window_vector_uncached(window_type, n):
 # device plumbing
 # ------------------------------------------------------------------------------------------------------
 _TORCH_OK = (torch.float32, torch.float64, torch.complex64, torch.complex128)
+_TORCH_HALF = (torch.float16, torch.bfloat16)  # real half-precision fields: computed in float32 (the plan reads them where they lie, or engine.convert widens them once)
 
 
-def _to_device(data):
+def _widen_half(t):
+    """A float16 / bfloat16 device tensor as float32 (exact; the library's own one-pass kernel); anything else as it is."""
+    return engine.convert(t, torch.float32) if t.dtype in _TORCH_HALF else t
+
+
+def _to_device(data, keep_half=False):
+    """``data`` on the device in a dtype the library computes on.  Half-precision fields travel and arrive as 2-byte samples; ``keep_half``: returned as they are (the
+    two-trailing-axes route, whose plan may read them where they lie), else widened to float32 on the device."""
     dev = _lib.device()
     if isinstance(data, torch.Tensor):
         # the C library reads raw memory: materialise torch's lazy conjugate / negative views (x.conj(), x.mH)
@@ -212,7 +224,7 @@ def _to_device(data):
     else:
         a = np.asarray(data)
         if a.dtype == np.float16:
-            a = a.astype(np.float32)
+            pass  # uploaded as float16: 2 bytes per sample over the bus
         elif a.dtype.kind in "biu":
             a = a.astype(np.float64)  # numpy.fft promotes integers to float64
         elif a.dtype.kind not in "fc":
@@ -220,6 +232,9 @@ def _to_device(data):
         elif a.dtype.itemsize > 8 and a.dtype.kind == "f" or a.dtype.itemsize > 16:
             a = a.astype(np.complex128 if a.dtype.kind == "c" else np.float64)
         t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype in _TORCH_HALF:
+        t = t.to(dev)
+        return t if keep_half else _widen_half(t)
     if t.dtype not in _TORCH_OK:
         t = t.to(torch.float64 if not t.is_complex() else torch.complex128)
     return t.to(dev)
@@ -283,6 +298,7 @@ def clear_plan_cache():
     with _plan_lock:
         _plan_cache.clear()
         _STRIDED_REFUSED.clear()
+        _HALF_REFUSED.clear()
         _BLUE_TABLES.clear()
         _TWO_STAGE.clear()
     engine.clear_workspaces()
@@ -486,6 +502,7 @@ def _arrange(c, da):
 
 
 _STRIDED_REFUSED = OrderedDict()  # plan keys the library answered UNSUPPORTED_LENGTH to with input strides: those calls copy, without asking again
+_HALF_REFUSED = OrderedDict()     # ... and to with float16 / bfloat16 input: those calls widen the field once (engine.convert) and take the float32 plan
 
 
 def _view_strides(t, ndim):
@@ -504,16 +521,17 @@ def _view_strides(t, ndim):
     return (sy if ndim == 2 else 0), sb
 
 
-def _arrange_view(c, da, view_ok=True):
+def _arrange_view(c, da, view_ok=True, keep_half=False):
     """_arrange that leaves a box cut out of a larger array (``da.isel(y=slice(..), x=slice(..))``) where it lies when the transform dims are already the last
-    ones, in order, and the library can address the view (_view_strides): returns (tensor, other_dims, strides or None).  Everything else is made contiguous."""
-    t = _to_device(da.data)
+    ones, in order, and the library can address the view (_view_strides): returns (tensor, other_dims, strides or None).  Everything else is made contiguous.
+    ``keep_half``: a float16 / bfloat16 field stays in its 2-byte samples; a view of one is copied contiguous in half precision (half plans read dense input)."""
+    t = _to_device(da.data, keep_half)
     tdims = ([c.ydim] if c.ydim is not None else []) + [c.xdim]
     other = [d for d in da.dims if d not in tdims]
     order = other + tdims
     if tuple(order) != tuple(da.dims):
         t = t.permute([da.get_axis_num(d) for d in order])
-    elif view_ok:
+    elif view_ok and t.dtype not in _TORCH_HALF:
         st = _view_strides(t, len(tdims))
         if st is not None:
             return t, other, st
@@ -693,7 +711,7 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
         out = _execute_inner(c, da, _lib.OUT_CROSS, scale, 0, da2, c2)
         if out is not None:
             return engine.angle(out), None, None
-    t, other, strides = _arrange_view(c, da)  # (a qualifying view of a larger array stays where it lies: no contiguous copy)
+    t, other, strides = _arrange_view(c, da, keep_half=True)  # (a qualifying view of a larger array stays where it lies: no contiguous copy)
     ndim = len(c.dim)
     nx = da.sizes[c.xdim]
     ny = da.sizes[c.ydim] if c.ydim is not None else 1
@@ -704,9 +722,11 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
     flags |= extra_flags
     t2 = None
     if da2 is not None:
-        t2, other2, strides2 = _arrange_view(c2, da2)
+        t2, other2, strides2 = _arrange_view(c2, da2, keep_half=True)
         if t2.shape != t.shape or other2 != other:
             raise ValueError("The two datasets have different dimensions")
+        if t2.dtype != t.dtype and (t.dtype in _TORCH_HALF or t2.dtype in _TORCH_HALF):  # half with anything else: widened first, then promoted as ever
+            t, t2 = _widen_half(t), _widen_half(t2)
         if strides2 != strides or t2.dtype != t.dtype:  # one set of strides serves both fields: anything else is copied
             t, t2, strides = t.contiguous(), t2.contiguous(), None
         if t2.dtype != t.dtype:
@@ -718,6 +738,26 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
     if iso is not None:
         kw.update(binmap=iso["binmap"], nbins=iso["nbins"])
         bkey = iso.get("binmap_key")
+    if t.dtype in _TORCH_HALF:
+        # the plan that reads the 2-byte samples where they lie: the float32 plan of this call with a half loader, or UNSUPPORTED_LENGTH (a family without one, a
+        # field that is not 16-byte aligned): then the field is widened once and the float32 plan runs -- the same bits either way
+        hkey = _plan_key(bkey, kw)
+        with _plan_lock:
+            refused = hkey in _HALF_REFUSED
+        if not refused and t.data_ptr() % 16 == 0 and (t2 is None or t2.data_ptr() % 16 == 0):
+            try:
+                out, iso_out = _get_plan(binmap_key=bkey, **kw).execute(t, t2, sources=(_own_tensor(da, t),) if t2 is None else (_own_tensor(da, t), _own_tensor(da2, t2)))
+                return out, iso_out, other
+            except _lib.XrftHipError as e:
+                if e.status != _lib.UNSUPPORTED_LENGTH:
+                    raise
+                with _plan_lock:
+                    _HALF_REFUSED[hkey] = True
+                    while len(_HALF_REFUSED) > 64:
+                        _HALF_REFUSED.popitem(last=False)
+        t = _widen_half(t)
+        t2 = None if t2 is None else _widen_half(t2)
+        kw["dtype"] = t.dtype
     if strides is not None:
         # the plan that reads the view: the family of the dense plan of this shape, or UNSUPPORTED_LENGTH (then: the copy and the dense plan, exactly as before)
         skw = dict(kw, in_stride_y=strides[0], in_stride_batch=strides[1])

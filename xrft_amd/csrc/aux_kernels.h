@@ -5,6 +5,7 @@
 //   radial_binsum     isotropize of an existing spectrum                      xrft/xrft.py:895-906, 993-1004
 #pragma once
 #include "tile_fft.h"
+#include "half_in.h"
 
 namespace xrft {
 
@@ -438,6 +439,23 @@ __global__ void __launch_bounds__(256) plane_inner_apply_kernel(const T* __restr
 template <typename A, typename B>
 __global__ void __launch_bounds__(256) convert_kernel(const A* __restrict__ in, B* __restrict__ out, long long n) {
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) out[e] = (B)in[e];
+}
+
+// out[e] = (float) in[e] for float16 (bf = 0) / bfloat16 (bf = 1) samples, exact (half_in.h): one 4-byte load and one 8-byte store per pair of samples
+// (`in` 4-byte aligned: pairs; else sample by sample), the last sample of an odd count on its own
+static __global__ void __launch_bounds__(256) widen16_kernel(const unsigned short* __restrict__ in, float* __restrict__ out, long long n, int bf, int pairs) {
+    const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+    if (pairs) {
+        const long long np = n >> 1;
+        for (long long e = t0; e < np; e += step) {
+            float lo, hi;
+            xrft_widen2(reinterpret_cast<const unsigned*>(in)[e], bf, lo, hi);
+            out[2 * e] = lo; out[2 * e + 1] = hi;
+        }
+        if ((n & 1) && t0 == 0) out[n - 1] = xrft_load1_h16(reinterpret_cast<const char*>(in + (n - 1)), bf);
+    } else {
+        for (long long e = t0; e < n; e += step) out[e] = xrft_load1_h16(reinterpret_cast<const char*>(in + e), bf);
+    }
 }
 
 // out[e] = arg(a[e]) in [-pi, pi] (numpy.angle of a stored cross spectrum: xrft.cross_phase, xrft/xrft.py:838-874, where the fused

@@ -80,6 +80,7 @@ struct FastG {
     // and between its rows; fastg_kernel<.., STR> reads them, the dense kernels never do
     long long in_slab;
     int in_pitch;
+    int in_bf16;  // fastg_kernel<float, .., H16>: `in` / `in_b` hold 2-byte samples, bfloat16 (1) or float16 (0) (half_in.h); the other kernels never read it
 };
 
 // one radix pass over the COLUMNS of the tile: sequences of length len, element stride rs, ncols of them; lanes run along the columns
@@ -249,9 +250,12 @@ __device__ __forceinline__ void fastg_cols_pass(C2<T>* tile, int ncols, int len,
 // CIN: the complex-input forms (cin, inverse, c2r) -- kernels of their own: their branches cost the real-input forms registers
 // STR (real input only): the rows of the input are p.in_pitch elements apart, its slabs (one_d: its groups of ny rows) p.in_slab -- xrfthip_desc.in_stride_y /
 // in_stride_batch, multiples of 16 bytes; a template parameter, so that the dense kernels keep their code
-template <typename T, int MODE, bool CIN, bool STR = false>
+// H16 (real float32 plans, dense): the input is float16 / bfloat16: the packed rows' pair of samples per lane as ONE 4-byte load (consecutive lanes, consecutive
+// words), an odd row length's single samples as 2-byte loads (the float32 kernel loads one sample per lane there, too), widened in registers (half_in.h)
+template <typename T, int MODE, bool CIN, bool STR = false, bool H16 = false>
 __global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 3)) fastg_kernel(FastG p) {
     static_assert(!(STR && CIN), "the complex-input forms read dense input");  // (float64: three waves per SIMD = 168 registers)
+    static_assert(!H16 || (sizeof(T) == 4 && !CIN && !STR), "half input: real, dense, computed in float32");
     typedef C2<T> CT;
     XRFT_DYN_SMEM(smem_raw);
     CT* tile0 = reinterpret_cast<CT*>(smem_raw);
@@ -291,6 +295,7 @@ __global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
         const CT* __restrict__ src = (CIN && p.c2r) ? reinterpret_cast<const CT*>(p.in) + (size_t)slab * ny * (n + 1)  // (half spectra)
                                    : (CIN && p.cin) ? reinterpret_cast<const CT*>(p.in) + (size_t)slab * ny * nx  // (complex samples)
                                            : reinterpret_cast<const CT*>(reinterpret_cast<const T*>(f ? p.in_b : p.in) + (STR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * ny * nx));
+        const char* __restrict__ src16 = reinterpret_cast<const char*>(f ? p.in_b : p.in) + (size_t)slab * ny * nx * 2u;  // (H16: 2-byte samples)
         // ---- load; the plane's sums on the way (float64 per thread, then the threads in a fixed order)
         double s0 = 0.0, si = 0.0, sj = 0.0;
         const bool plane = p.detrend && !p.one_d;  // (the slab's plane; a 1-D transform fits a line per row below)
@@ -336,7 +341,9 @@ __global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
             const int p2 = STR ? p.in_pitch >> 1 : 0;  // (STR: pairs of samples per row of the input; a strided pitch is a multiple of 16 bytes)
             for (int e = tid; e < npk; e += nthr) {
                 const int i = fdiv(e, inv_n), m = e - i * n;
-                const CT z = src[STR ? i * p2 + m : e];
+                CT z;
+                if constexpr (H16) { const C2<float> zh = xrft_load2_h16(src16 + (size_t)e * 4u, p.in_bf16); z = mk<T>((T)zh.re, (T)zh.im); }
+                else z = src[STR ? i * p2 + m : e];
                 tile[i * rs + m] = z;
                 if (plane) {
                     const double u = (double)z.re + (double)z.im;
@@ -362,7 +369,9 @@ __global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
             const T* __restrict__ srcr = reinterpret_cast<const T*>(src);
             for (int e = tid; e < npk; e += nthr) {
                 const int i = fdiv(e, inv_n), m = e - i * n;
-                const T v = srcr[STR ? i * p.in_pitch + m : e];
+                T v;
+                if constexpr (H16) v = (T)xrft_load1_h16(src16 + (size_t)e * 2u, p.in_bf16);
+                else v = srcr[STR ? i * p.in_pitch + m : e];
                 tile[i * rs + m] = mk<T>(v, (T)0);
                 if (plane) {
                     s0 += (double)v;

@@ -7,11 +7,21 @@
 #pragma once
 #include <type_traits>
 #include "aux_kernels.h"
+#include "half_in.h"
 
 namespace xrft {
 
 typedef C2<float> cf;
 struct alignas(16) F4 { float x, y, z, w; };
+
+// four adjacent float16 / bfloat16 samples: one aligned 8-byte load, widened in registers (half_in.h)
+__device__ __forceinline__ F4 xrft_load4_h16(const char* src, int bf) {
+    const XrftU2 w = *reinterpret_cast<const XrftU2*>(src);
+    F4 r;
+    xrft_widen2(w.x, bf, r.x, r.y);
+    xrft_widen2(w.y, bf, r.z, r.w);
+    return r;
+}
 
 // a[k] *= w1^k for k = 1..15, powers built by a product tree of depth <= 4 (error ~ 4 ulp)
 template <typename T> __device__ __forceinline__ void twiddle16(C2<T>* a, C2<T> w1) {

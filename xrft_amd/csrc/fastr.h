@@ -48,6 +48,7 @@ struct FastR {
     int ph_in;         // ... `ph` multiplies the INPUT samples (by source index) instead of the output (the true-phase factor of xrft.ifft, xrft.py:596-606)
     int stagger;       // fastr_kernel: start delay of workgroup class c = (block / 8) % classes, c x (stagger & 0xff) x 3.4 us; classes = stagger >> 8 (0: none)
     long long in_row;  // fastr_kernel / fastr2_kernel<.., STR>: elements between the rows of `in` (xrfthip_desc.in_stride_batch: rows of a larger array read where they lie)
+    int in_bf16;       // fastr_kernel / fastr2_kernel<.., H16>: `in` holds 2-byte samples, bfloat16 (1) or float16 (0) (half_in.h); the float32 kernels never read it
 };
 
 constexpr int kFastRThreads = 1024;
@@ -192,8 +193,11 @@ __device__ __forceinline__ void fastr_stagger(int stagger) {
 }
 
 // (STR: the rows of the input are p.in_row elements apart -- rows of a larger array, xrfthip_desc.in_stride_batch; a template parameter: the dense kernels keep their code)
-template <int MODE, bool HALF, bool STR = false>
+// (H16: the input is float16 / bfloat16, dense: the same pair of samples per lane as ONE 4-byte load -- a wave reads 256 contiguous bytes per instruction --, widened in
+// registers, half_in.h; everything behind the loads is the float32 kernel)
+template <int MODE, bool HALF, bool STR = false, bool H16 = false>
 __global__ void __launch_bounds__(kFastRThreads) fastr_kernel(FastR p) {
+    static_assert(!(STR && H16), "half input is read dense");
     constexpr int N = 65536, M = N / 2, T = kFastRThreads;
     constexpr int A1 = 545, B1 = 17;  // exchange 1: element (k1, n1, n2') at k1 A1 + n1 B1 + n2' (8-byte elements)
     XRFT_DYN_SMEM(smem_raw);
@@ -212,9 +216,10 @@ __global__ void __launch_bounds__(kFastRThreads) fastr_kernel(FastR p) {
         XRFT_OPAQUE(tid);
         const int lo = tid & 31, hi = tid >> 5;
         const cf* __restrict__ src = reinterpret_cast<const cf*>(p.in + (STR ? (size_t)row * (size_t)p.in_row : (size_t)row * N)) + tid;
+        const char* __restrict__ src16 = reinterpret_cast<const char*>(p.in) + ((size_t)row * N + 2 * (size_t)tid) * 2u;
         cf a[32];
 #pragma unroll
-        for (int j = 0; j < 32; ++j) a[j] = src[j * T];  // z[n], n = tid + 1024 j: samples 2n, 2n + 1
+        for (int j = 0; j < 32; ++j) a[j] = H16 ? xrft_load2_h16(src16 + (unsigned)(j * T) * 4u, p.in_bf16) : src[j * T];  // z[n], n = tid + 1024 j: samples 2n, 2n + 1
         if (p.detrend) {
             // sums over the row of x and of (i - ibar) x in float64.  With u_j = x[2 n_j] + x[2 n_j + 1], n_j = tid + 1024 j and
             // c_j = 2 n_j - ibar = c_0 + 2048 j:   sum (i - ibar) x = c_0 sum u_j + 2048 sum j u_j + sum x[2 n_j + 1]  -- no per-sample
@@ -355,8 +360,9 @@ template <int R2, int R3> struct R2Geom {
     static constexpr int WPS = 4;  // (113-123 registers, none spilled: four waves per SIMD)
 };
 
-template <int R2, int R3, int MODE, bool HALF, bool STR = false>
+template <int R2, int R3, int MODE, bool HALF, bool STR = false, bool H16 = false>
 __global__ void __launch_bounds__((R2Geom<R2, R3>::T), (R2Geom<R2, R3>::WPS)) fastr2_kernel(FastR p) {
+    static_assert(!(STR && H16), "half input is read dense");
     typedef R2Geom<R2, R3> G;
     constexpr int T = G::T, M = G::M, N = G::N, K2 = G::K2, K3 = G::K3, S1 = G::S1, S2 = G::S2;
     constexpr float C64[32] = {
@@ -377,9 +383,10 @@ __global__ void __launch_bounds__((R2Geom<R2, R3>::T), (R2Geom<R2, R3>::WPS)) fa
         int tid = threadIdx.x;
         XRFT_OPAQUE(tid);
         const cf* __restrict__ src = reinterpret_cast<const cf*>(p.in + (STR ? (size_t)row * (size_t)p.in_row : (size_t)row * N)) + tid;
+        const char* __restrict__ src16 = reinterpret_cast<const char*>(p.in) + ((size_t)row * N + 2 * (size_t)tid) * 2u;  // (H16: 2-byte samples, half_in.h)
         cf a[32];
 #pragma unroll
-        for (int j = 0; j < 32; ++j) a[j] = src[j * T];  // z[n], n = tid + T j: samples 2n, 2n + 1
+        for (int j = 0; j < 32; ++j) a[j] = H16 ? xrft_load2_h16(src16 + (unsigned)(j * T) * 4u, p.in_bf16) : src[j * T];  // z[n], n = tid + T j: samples 2n, 2n + 1
         if (p.detrend) {  // (as in fastr_kernel: c_j = 2 n_j - ibar = c_0 + 2 T j)
             constexpr double IBAR = 0.5 * (N - 1);
             const double c0 = (double)(2 * tid) - IBAR;

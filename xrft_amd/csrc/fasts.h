@@ -51,6 +51,7 @@ struct FastS {
     // between its rows; the dense kernels never read the two
     long long in_slab;
     int in_pitch;
+    int in_bf16;  // fasts_power_kernel<.., H16>: `in` holds 2-byte samples, bfloat16 (1) or float16 (0) (half_in.h); the float32 kernels never read it
 };
 
 constexpr size_t fasts_max(size_t a, size_t b) { return a > b ? a : b; }
@@ -139,9 +140,12 @@ template <int R> __device__ __forceinline__ void fasts_split(cf* b, int c) {
 // 0: the complex spectrum (xrft.fft / dft; ISO = 0)
 // STR: the rows of the input are p.in_pitch elements apart, its slabs p.in_slab (multiples of 4, the base 16-byte aligned: the 8-byte loads stay aligned and inside
 // their rows); a template parameter, so that the dense kernels keep their code
-template <int RY, int RX, int ISO = 0, int MODE = 1, bool STR = false>
+// H16: the input is float16 / bfloat16 (dense): the same pair of columns per lane and row as ONE 4-byte load -- a wave reads 256 contiguous bytes per instruction --
+// widened in registers (half_in.h); everything behind the loads is the float32 kernel
+template <int RY, int RX, int ISO = 0, int MODE = 1, bool STR = false, bool H16 = false>
 __global__ void __launch_bounds__((SGeom<RY, RX>::T), (SGeom<RY, RX>::WPS)) fasts_power_kernel(FastS p) {
     static_assert(MODE == 1 || ISO == 0, "radial sums are of power spectra");
+    static_assert(!(STR && H16), "half input is read dense");
     typedef SGeom<RY, RX> G;
     constexpr int NY = G::NY, NX = G::NX, T = G::T, NXP = G::NXP, NROW = G::NROW, KGY = G::KGY, KGX = G::KGX;
     constexpr int P1 = G::P1, PX = G::PX, P3 = G::P3, PF = G::PF, HY = RY / 2, HX = RX / 2;
@@ -214,8 +218,12 @@ __global__ void __launch_bounds__((SGeom<RY, RX>::T), (SGeom<RY, RX>::WPS)) fast
         const int jp = tid % NXP, i0 = tid / NXP;  // packed column, first row
         cf a[32], b[32];
         if (have) {  // rows i0 + RY q, columns 2 jp, 2 jp + 1 (a uniform base + 32-bit offsets: no address pairs in registers)
-            const char* __restrict__ base = reinterpret_cast<const char*>(p.in + (STR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * NY * NX));
-            if (STR) {  // row i0 + RY q of the view, columns 2 jp, 2 jp + 1
+            const char* __restrict__ base = reinterpret_cast<const char*>(p.in) + (STR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * NY * NX) * (H16 ? 2u : 4u);
+            if (H16) {
+                const unsigned off = (unsigned)tid * 4u;
+#pragma unroll
+                for (int q = 0; q < 32; ++q) a[q] = xrft_load2_h16(base + (off + (unsigned)(q * T) * 4u), p.in_bf16);
+            } else if (STR) {  // row i0 + RY q of the view, columns 2 jp, 2 jp + 1
                 const unsigned rowb = (unsigned)p.in_pitch * 4u, off = (unsigned)i0 * rowb + (unsigned)jp * 8u, step = (unsigned)RY * rowb;
 #pragma unroll
                 for (int q = 0; q < 32; ++q) a[q] = *reinterpret_cast<const cf*>(base + (off + step * (unsigned)q));

@@ -140,6 +140,7 @@ struct FastY {
     unsigned* rdv;           // tune bit 21: one arrival counter per (slab, group of the column blocks that share the input's 128-byte lines), zeroed per launch
     long long in_slab;       // fasty_cols_kernel<.., STR>: elements between the slabs of `in` and between its rows (xrfthip_desc.in_stride_batch / in_stride_y):
     int in_pitch;            // a box of a larger field read where it lies; the dense kernels never read the two
+    int in_bf16;             // fasty_cols_kernel<.., H16>: `in` holds 2-byte samples, bfloat16 (1) or float16 (0) (half_in.h); the float32 kernels never read it
 };
 
 // phase-ablation bits for profiling builds (scripts/gpu_ablate_yf.sh compiles variants with -DXRFT_YDBG=bits); 0 in the product
@@ -251,9 +252,13 @@ template <int N> __device__ __forceinline__ int held_k(int u, int bb, int k3) {
 // table laid out like the slab, read at the samples' own offsets (w[nx i1 + i2]; shared by every slab: L2-resident).
 // STR: the input's rows are in_pitch elements apart and its slabs in_slab (a multiple of 4 each, the base 16-byte aligned: every float4 load stays aligned and inside
 // its row); a template parameter, so that the dense kernels keep their code.
-template <int NY, bool DET, bool W2D = false, bool STR = false>
+// H16: the input is float16 / bfloat16 (xrfthip_dtype XRFTHIP_F16 / XRFTHIP_BF16, dense): the same four columns per lane and row as ONE 8-byte load, widened in
+// registers (half_in.h; the base 8-byte aligned: xrfthip_exec asks for 16); everything behind the loads is the float32 kernel.
+template <int NY, bool DET, bool W2D = false, bool STR = false, bool H16 = false>
 __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : YCols<NY>::THR / 128)) fasty_cols_kernel(FastY p) {
     static_assert(!(STR && W2D), "the four-step form reads one dense sequence per slab");
+    static_assert(!(STR && H16), "half input is read dense (a strided half view is copied contiguous, in half precision)");
+    constexpr unsigned ESZ = H16 ? 2u : 4u;  // bytes per input sample
     typedef P2<NY> G;
     typedef YCols<NY> Y;
     constexpr int NT = G::NT, GY = Y::GY, THR = Y::THR, GSTR = YLds<NY, GY>::GSTR;
@@ -303,8 +308,9 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
     const int x0 = xb * Y::CW + 4 * g;
     // uniform 64-bit base + one 32-bit per-lane byte offset (a slab is < 4 GB): scalar-base loads, no 64-bit address per row
     const unsigned pitch = STR ? (unsigned)p.in_pitch : (unsigned)p.nx;  // elements between the input's rows
-    const char* __restrict__ src = reinterpret_cast<const char*>(p.in + (STR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * NY * p.nx) + (size_t)xb * Y::CW);
-    const unsigned off0 = ((unsigned)u * pitch + 4u * (unsigned)g) * 4u, rstep = (unsigned)NT * pitch * 4u;
+    const char* __restrict__ src = reinterpret_cast<const char*>(p.in) + ((STR ? (size_t)slab * (size_t)p.in_slab : (size_t)slab * NY * p.nx) + (size_t)xb * Y::CW) * ESZ;
+    const unsigned off0 = ((unsigned)u * pitch + 4u * (unsigned)g) * ESZ, rstep = (unsigned)NT * pitch * ESZ;
+    const unsigned woff0 = ((unsigned)u * pitch + 4u * (unsigned)g) * 4u, wrstep = (unsigned)NT * pitch * 4u;  // (the float32 window table of the four-step form: the same samples)
     F4 wx = {1.f, 1.f, 1.f, 1.f};
     if (!W2D) wx = *reinterpret_cast<const F4*>(p.win_x + x0);
     const char* __restrict__ wsrc = reinterpret_cast<const char*>(p.win2d + (size_t)xb * Y::CW);
@@ -329,16 +335,21 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
     float T[4] = {0.f, 0.f, 0.f, 0.f}, S[4] = {0.f, 0.f, 0.f, 0.f}, S2[4] = {0.f, 0.f, 0.f, 0.f};
     F4 rt[KREF], rb[KREF];
     if (DET) {
-        const unsigned offg = 16u * (unsigned)g, rowb = pitch * 4u;
+        const unsigned offg = 4u * ESZ * (unsigned)g, rowb = pitch * ESZ;
 #pragma unroll
         for (int k = 0; k < KREF; ++k) {
-            rt[k] = *reinterpret_cast<const F4*>(src + (offg + rowb * (unsigned)(ITOP - 1 + k)));
-            rb[k] = *reinterpret_cast<const F4*>(src + (offg + rowb * (unsigned)(IBOT - 1 + k)));
+            if (H16) {
+                rt[k] = xrft_load4_h16(src + (offg + rowb * (unsigned)(ITOP - 1 + k)), p.in_bf16);
+                rb[k] = xrft_load4_h16(src + (offg + rowb * (unsigned)(IBOT - 1 + k)), p.in_bf16);
+            } else {
+                rt[k] = *reinterpret_cast<const F4*>(src + (offg + rowb * (unsigned)(ITOP - 1 + k)));
+                rb[k] = *reinterpret_cast<const F4*>(src + (offg + rowb * (unsigned)(IBOT - 1 + k)));
+            }
         }
     }
     F4 raw[16];
 #pragma unroll
-    for (int q = 0; q < 16; ++q) raw[q] = xrft_load_pol(src + (off0 + rstep * (unsigned)q), (XRFT_YTUNE(p) & 4) != 0);
+    for (int q = 0; q < 16; ++q) raw[q] = H16 ? xrft_load4_h16(src + (off0 + rstep * (unsigned)q), p.in_bf16) : xrft_load_pol(src + (off0 + rstep * (unsigned)q), (XRFT_YTUNE(p) & 4) != 0);
     if (DET) {
         auto med3 = [](float x, float y, float z) { return fmaxf(fminf(x, y), fminf(fmaxf(x, y), z)); };
         const float mt[4] = {med3(rt[0].x, rt[1].x, rt[2].x), med3(rt[0].y, rt[1].y, rt[2].y), med3(rt[0].z, rt[1].z, rt[2].z), med3(rt[0].w, rt[1].w, rt[2].w)};
@@ -396,7 +407,7 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
         }
         if (W2D) {
             if ((q & 3) == 0) asm volatile("" ::: "memory");  // window loads in batches of four rows (all sixteen hoisted: 40 spilled registers at 4096)
-            const F4 ww = *reinterpret_cast<const F4*>(wsrc + (off0 + rstep * (unsigned)q));
+            const F4 ww = *reinterpret_cast<const F4*>(wsrc + (woff0 + wrstep * (unsigned)q));
             a[q] = mk<float>(v0 * ww.x, v1 * ww.y);
             b[q] = mk<float>(v2 * ww.z, v3 * ww.w);
         } else {

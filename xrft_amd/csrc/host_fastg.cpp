@@ -486,6 +486,7 @@ static int run_fastg(const xrfthip_plan* P, const ExecArgs& a) {
     // the input's own strides: a slab's rows in_pitch apart; one_d: the "slab" is a group of g_rows rows of the 1-D plan, in_stride_batch apart
     p.in_pitch = (int)(P->g_one_d ? in_slab(P) : in_pitch(P));
     p.in_slab = P->g_one_d ? (long long)P->g_rows * in_slab(P) : in_slab(P);
+    p.in_bf16 = P->in16 == 2 ? 1 : 0;
     p.nrx = (int)P->g_rx.size(); p.nry = (int)P->g_ry.size();
     for (int i = 0; i < p.nrx; ++i) p.rx[i] = P->g_rx[(size_t)i];
     for (int i = 0; i < p.nry; ++i) p.ry[i] = P->g_ry[(size_t)i];
@@ -517,10 +518,16 @@ static int run_fastg(const xrfthip_plan* P, const ExecArgs& a) {
 #define GL_(TT, MM) do { if (P->cplx_in) { auto k = &fastg_kernel<TT, (MM == 2 ? 1 : MM), true>; XRFT_LAUNCH(k, grid, blk, P->g_lds, st, p); } \
                          else if (in_strided(P)) { auto k = &fastg_kernel<TT, MM, false, true>; XRFT_LAUNCH(k, grid, blk, P->g_lds, st, p); } /* (a box of a larger field, read where it lies) */ \
                          else { auto k = &fastg_kernel<TT, MM, false>; XRFT_LAUNCH(k, grid, blk, P->g_lds, st, p); } } while (0)
+#define GH_(MM) do { auto k = &fastg_kernel<float, MM, false, false, true>; XRFT_LAUNCH(k, grid, blk, P->g_lds, st, p); } while (0)  /* (float16 / bfloat16 input, half_in.h) */
     const bool real_out = d.out_mode == XRFTHIP_OUT_POWER || (d.flags & XRFTHIP_C2R_X);  // (MODE 1: |F|^2, or the real samples of an irfftn)
-    if (P->dbl) { if (cross) GL_(double, 2); else if (!real_out) GL_(double, 0); else GL_(double, 1); }
+    if (in_half(P)) {
+        if (P->dbl || P->cplx_in || in_strided(P)) return XRFTHIP_UNSUPPORTED_LENGTH;  // (xrfthip_plan_create never makes such a plan)
+        if (cross) GH_(2); else if (!real_out) GH_(0); else GH_(1);
+    }
+    else if (P->dbl) { if (cross) GL_(double, 2); else if (!real_out) GL_(double, 0); else GL_(double, 1); }
     else { if (cross) GL_(float, 2); else if (!real_out) GL_(float, 0); else GL_(float, 1); }
 #undef GL_
+#undef GH_
     prof_end(rec, st);
     HIP_TRY(hipGetLastError());
     return XRFTHIP_OK;
@@ -621,6 +628,7 @@ void set_attrs_fastg() {
     SETF((fastg_kernel<float, 2, false>)); SETF((fastg_kernel<double, 2, false>));
     SETF((fastg_kernel<float, 0, false, true>)); SETF((fastg_kernel<float, 1, false, true>)); SETF((fastg_kernel<float, 2, false, true>));  // (strided input)
     SETF((fastg_kernel<double, 0, false, true>)); SETF((fastg_kernel<double, 1, false, true>)); SETF((fastg_kernel<double, 2, false, true>));
+    SETF((fastg_kernel<float, 0, false, false, true>)); SETF((fastg_kernel<float, 1, false, false, true>)); SETF((fastg_kernel<float, 2, false, false, true>));  // (float16 / bfloat16 input)
     SETF((fastg_kernel<float, 0, true>)); SETF((fastg_kernel<float, 1, true>)); SETF((fastg_kernel<double, 0, true>)); SETF((fastg_kernel<double, 1, true>));
     SETF((fastgy_kernel<float, 0, 0>)); SETF((fastgy_kernel<float, 1, 0>)); SETF((fastgy_kernel<double, 0, 0>)); SETF((fastgy_kernel<double, 1, 0>));
     SETF((fastgy_kernel<float, 0, 1>)); SETF((fastgy_kernel<float, 1, 1>)); SETF((fastgy_kernel<double, 0, 1>)); SETF((fastgy_kernel<double, 1, 1>));

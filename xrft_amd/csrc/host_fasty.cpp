@@ -305,7 +305,15 @@ static void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long g
                       else { auto k = &fasty_cols_kernel<NN, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
 #define YCS_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
                       else { auto k = &fasty_cols_kernel<NN, false, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
-    if (in_strided(P)) {  // a box of a larger field, read where it lies (FastY only: xrfthip_plan_create)
+#define YCH_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true, false, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
+                      else { auto k = &fasty_cols_kernel<NN, false, false, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
+#define YCHW_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true, true, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
+                       else { auto k = &fasty_cols_kernel<NN, false, true, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
+    if (in_half(P)) {  // float16 / bfloat16 input, dense (half_in.h): the 2-byte loaders of the same two forms
+        if (P->fast1d_win) { if (P->yny == 4096) YCHW_(4096); else if (P->yny == 2048) YCHW_(2048); else if (P->yny == 1024) YCHW_(1024); else if (P->yny == 512) YCHW_(512); else YCHW_(256); }
+        else if (P->yny == 4096) YCH_(4096); else if (P->yny == 2048) YCH_(2048); else if (P->yny == 1024) YCH_(1024); else if (P->yny == 512) YCH_(512); else YCH_(256);
+    }
+    else if (in_strided(P)) {  // a box of a larger field, read where it lies (FastY only: xrfthip_plan_create)
         if (P->yny == 4096) YCS_(4096); else if (P->yny == 2048) YCS_(2048); else if (P->yny == 1024) YCS_(1024); else if (P->yny == 512) YCS_(512); else YCS_(256);
     }
     else if (P->fast1d_win) {  // four-step 1-D with a window: the slab-shaped window table
@@ -315,6 +323,8 @@ static void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long g
 #undef YC_
 #undef YCW_
 #undef YCS_
+#undef YCH_
+#undef YCHW_
     prof_end(rec, st);
     if (d.detrend) {  // plane (2-D) or line through the whole sequence (four-step 1-D) from the per-column sums -> what pass 2 has to add back
         rec = prof ? prof_begin(P, "fasty_fit", st) : nullptr;
@@ -405,7 +415,8 @@ static FastY fasty_params(const xrfthip_plan* P, const float* in, void* out, dou
     const YGeomRt C = ycols_geom(P->yny);
     const size_t s0 = (size_t)slot * slot_slabs;  // first slab of the slot inside the workspace arrays
     FastY p{};
-    p.in = in + (in_strided(P) ? (size_t)g0 * (size_t)in_slab(P) : (size_t)g0 * slab_pts);
+    p.in = reinterpret_cast<const float*>(reinterpret_cast<const char*>(in) + (in_strided(P) ? (size_t)g0 * (size_t)in_slab(P) : (size_t)g0 * slab_pts) * (in_half(P) ? 2 : 4));
+    p.in_bf16 = P->in16 == 2 ? 1 : 0;
     p.in_slab = in_slab(P); p.in_pitch = (int)in_pitch(P);
     p.w2 = reinterpret_cast<cf*>(ws + P->off_w) + s0 * (size_t)P->y_nrow_pad * P->ynx;
     const size_t out_esz = (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_PHASE) ? sizeof(float) : sizeof(cf);
@@ -551,6 +562,7 @@ uint64_t fasty_pass1_signature(const xrfthip_plan* P, int field) {
     f.num(C.thr); f.num(C.gxy); f.num(C.cw); f.num(C.rk); f.num(C.lbs); f.num((long long)C.lds); f.num(ycols_gstr(P->yny));
     f.num((long long)P->p1_w); f.num((long long)P->p1_fit); f.num((long long)P->p1_corr);
     f.num(in_pitch(P)); f.num(in_slab(P));
+    if (in_half(P)) f.num(P->in16);  // (fasty_cols_kernel<.., H16> and the format it reads; a float32 plan's signature is what it was)
     // the field's own flip flags (fasty.h takes none today: a plan with one never reaches here)
     const uint32_t fy = field == 0 && plan_two(P) ? XRFTHIP_FLIP0_Y : XRFTHIP_FLIP_Y, fx = field == 0 && plan_two(P) ? XRFTHIP_FLIP0_X : XRFTHIP_FLIP_X;
     f.num((d.flags & fy) != 0); f.num((d.flags & fx) != 0);
@@ -775,7 +787,9 @@ const FamilyOps kOpsFastYCFourStep = {Family::FastYCFourStep, run_fastyc, descri
 void set_attrs_fasty() {
     const int m = (int)kLdsMax;
 #define SETF(K) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, m)
-#define SETY(NN) SETF((fasty_cols_kernel<NN, false>)); SETF((fasty_cols_kernel<NN, true>)); SETF((fasty_cols_kernel<NN, false, true>)); SETF((fasty_cols_kernel<NN, true, true>)); SETF((fasty_cols_kernel<NN, false, false, true>)); SETF((fasty_cols_kernel<NN, true, false, true>)); SETF((fasty_rows_kernel<NN, 1, false>)); SETF((fasty_rows_kernel<NN, 1, true>)); \
+#define SETY(NN) SETF((fasty_cols_kernel<NN, false>)); SETF((fasty_cols_kernel<NN, true>)); SETF((fasty_cols_kernel<NN, false, true>)); SETF((fasty_cols_kernel<NN, true, true>)); SETF((fasty_cols_kernel<NN, false, false, true>)); SETF((fasty_cols_kernel<NN, true, false, true>)); \
+                 SETF((fasty_cols_kernel<NN, false, false, false, true>)); SETF((fasty_cols_kernel<NN, true, false, false, true>)); SETF((fasty_cols_kernel<NN, false, true, false, true>)); SETF((fasty_cols_kernel<NN, true, true, false, true>)); /* (float16 / bfloat16 input) */ \
+                 SETF((fasty_rows_kernel<NN, 1, false>)); SETF((fasty_rows_kernel<NN, 1, true>)); \
                  SETF((fasty_rows_kernel<NN, 0, false>)); SETF((fasty_rows_kernel<NN, 2, false>)); SETF((fasty_rows_kernel<NN, 2, true>)); SETF((fasty_rows_kernel<NN, 3, false>))
     SETY(4096); SETY(2048); SETY(1024); SETY(512); SETY(256);
 #undef SETY

@@ -74,6 +74,7 @@ static int run_fasts(const xrfthip_plan* P, const ExecArgs& a) {
     p.win_x = win ? (const float*)(P->win[1].p ? P->win[1].p : P->ones4096.p) : nullptr;
     p.nslabs = d.batch;
     p.in_slab = in_slab(P); p.in_pitch = (int)in_pitch(P);
+    p.in_bf16 = P->in16 == 2 ? 1 : 0;
     p.detrend = d.detrend;
     p.shift_y = (d.flags & XRFTHIP_SHIFT_Y) ? (int)(d.ny / 2) : 0;
     p.shift_x = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0;
@@ -93,12 +94,13 @@ static int run_fasts(const xrfthip_plan* P, const ExecArgs& a) {
     p.iso = a.iso; p.tfirst = (const unsigned short*)P->s_tfirst.p; p.nbins = P->nbins;
     const bool cplx = d.out_mode == XRFTHIP_OUT_COMPLEX;
     p.ph_y = (const cf*)P->fph[0].p; p.ph_x = (const cf*)P->fph[1].p; p.ph_on = (cplx && P->fph_on) ? 1 : 0;
-#define SLS_(A, B, SS) do { \
-        if (cplx) { auto k = &fasts_power_kernel<A, B, 0, 0, SS>; XRFT_LAUNCH(k, grid, blk, G.lds, st, p); } \
-        else if (isom == 0) { auto k = &fasts_power_kernel<A, B, 0, 1, SS>; XRFT_LAUNCH(k, grid, blk, G.lds, st, p); } \
-        else if (isom == 1) { auto k = &fasts_power_kernel<A, B, 1, 1, SS>; XRFT_LAUNCH(k, grid, blk, G.lds_iso, st, p); } \
-        else { auto k = &fasts_power_kernel<A, B, 2, 1, SS>; XRFT_LAUNCH(k, grid, blk, G.lds_iso, st, p); } } while (0)
-#define SL_(A, B) if (d.ny == 32 * A && d.nx == 32 * B) { if (in_strided(P)) SLS_(A, B, true); else SLS_(A, B, false); }  /* (strided: a box of a larger field, read where it lies) */
+#define SLS_(A, B, SS, HI) do { \
+        if (cplx) { auto k = &fasts_power_kernel<A, B, 0, 0, SS, HI>; XRFT_LAUNCH(k, grid, blk, G.lds, st, p); } \
+        else if (isom == 0) { auto k = &fasts_power_kernel<A, B, 0, 1, SS, HI>; XRFT_LAUNCH(k, grid, blk, G.lds, st, p); } \
+        else if (isom == 1) { auto k = &fasts_power_kernel<A, B, 1, 1, SS, HI>; XRFT_LAUNCH(k, grid, blk, G.lds_iso, st, p); } \
+        else { auto k = &fasts_power_kernel<A, B, 2, 1, SS, HI>; XRFT_LAUNCH(k, grid, blk, G.lds_iso, st, p); } } while (0)
+    /* (strided: a box of a larger field, read where it lies; half: float16 / bfloat16 input, dense, half_in.h) */
+#define SL_(A, B) if (d.ny == 32 * A && d.nx == 32 * B) { if (in_half(P)) SLS_(A, B, false, true); else if (in_strided(P)) SLS_(A, B, true, false); else SLS_(A, B, false, false); }
     SL_(2, 2) SL_(2, 4) SL_(2, 8) SL_(4, 2) SL_(4, 4) SL_(4, 8) SL_(8, 2) SL_(8, 4) SL_(8, 8)
 #undef SL_
 #undef SLS_
@@ -203,6 +205,7 @@ static int run_fastr(const xrfthip_plan* P, const ExecArgs& a) {
     p.ph = (const cf*)P->fph[1].p; p.ph_on = (d.out_mode == XRFTHIP_OUT_COMPLEX && P->fph_on) ? 1 : 0;
     p.nrows = d.batch;
     p.in_row = in_slab(P);  // (ndim = 1: a slab is a row)
+    p.in_bf16 = P->in16 == 2 ? 1 : 0;
     p.detrend = d.detrend;
     p.half = (d.flags & XRFTHIP_HALF_X) ? 1 : 0;
     p.realdim2 = (d.flags & XRFTHIP_REALDIM_X2) ? 1 : 0;
@@ -235,13 +238,14 @@ static int run_fastr(const xrfthip_plan* P, const ExecArgs& a) {
 #else
 #define RK_(KK, LL) do { auto k = &KK; XRFT_LAUNCH(k, grid, blk, LL, st, p); } while (0)
 #endif
-#define RLS_(MM, HH, SS) do { \
-        if (d.nx == 65536) RK_((fastr_kernel<MM, HH, SS>), kFastRLds); \
-        else if (d.nx == 32768) RK_((fastr2_kernel<32, 16, MM, HH, SS>), (R2Geom<32, 16>::LDS)); \
-        else if (d.nx == 16384) RK_((fastr2_kernel<16, 16, MM, HH, SS>), (R2Geom<16, 16>::LDS)); \
-        else if (d.nx == 8192) RK_((fastr2_kernel<16, 8, MM, HH, SS>), (R2Geom<16, 8>::LDS)); \
-        else RK_((fastr2_kernel<8, 8, MM, HH, SS>), (R2Geom<8, 8>::LDS)); } while (0)
-#define RL_(MM, HH) do { if (in_strided(P)) RLS_(MM, HH, true); else RLS_(MM, HH, false); } while (0)  /* (strided: rows of a larger array, read where they lie) */
+#define RLS_(MM, HH, SS, HI) do { \
+        if (d.nx == 65536) RK_((fastr_kernel<MM, HH, SS, HI>), kFastRLds); \
+        else if (d.nx == 32768) RK_((fastr2_kernel<32, 16, MM, HH, SS, HI>), (R2Geom<32, 16>::LDS)); \
+        else if (d.nx == 16384) RK_((fastr2_kernel<16, 16, MM, HH, SS, HI>), (R2Geom<16, 16>::LDS)); \
+        else if (d.nx == 8192) RK_((fastr2_kernel<16, 8, MM, HH, SS, HI>), (R2Geom<16, 8>::LDS)); \
+        else RK_((fastr2_kernel<8, 8, MM, HH, SS, HI>), (R2Geom<8, 8>::LDS)); } while (0)
+    /* (strided: rows of a larger array, read where they lie; half: float16 / bfloat16 rows, dense, half_in.h) */
+#define RL_(MM, HH) do { if (in_half(P)) RLS_(MM, HH, false, true); else if (in_strided(P)) RLS_(MM, HH, true, false); else RLS_(MM, HH, false, false); } while (0)
 #define RC_(MM) do { \
         if (d.nx == 16384) RK_((fastc_kernel<32, 16, MM>), (R2Geom<32, 16>::LDS)); \
         else if (d.nx == 8192) RK_((fastc_kernel<16, 16, MM>), (R2Geom<16, 16>::LDS)); \
@@ -323,6 +327,14 @@ void set_attrs_rows() {
     SETF((fastr2_kernel<32, 16, 0, false, true>)); SETF((fastr2_kernel<32, 16, 0, true, true>)); SETF((fastr2_kernel<32, 16, 1, false, true>)); SETF((fastr2_kernel<32, 16, 1, true, true>));
     SETF((fastr2_kernel<16, 16, 0, false, true>)); SETF((fastr2_kernel<16, 16, 0, true, true>)); SETF((fastr2_kernel<16, 16, 1, false, true>)); SETF((fastr2_kernel<16, 16, 1, true, true>));
     SETF((fastr_kernel<0, false>)); SETF((fastr_kernel<0, true>)); SETF((fastr_kernel<1, false>)); SETF((fastr_kernel<1, true>));
+    // (float16 / bfloat16 input)
+    SETF((fasts_power_kernel<8, 8, 0, 0, false, true>)); SETF((fasts_power_kernel<8, 4, 0, 0, false, true>)); SETF((fasts_power_kernel<4, 8, 0, 0, false, true>));
+    SETF((fasts_power_kernel<8, 8, 0, 1, false, true>)); SETF((fasts_power_kernel<8, 8, 1, 1, false, true>)); SETF((fasts_power_kernel<8, 8, 2, 1, false, true>));
+    SETF((fasts_power_kernel<8, 4, 0, 1, false, true>)); SETF((fasts_power_kernel<8, 4, 1, 1, false, true>)); SETF((fasts_power_kernel<8, 4, 2, 1, false, true>));
+    SETF((fasts_power_kernel<4, 8, 0, 1, false, true>)); SETF((fasts_power_kernel<4, 8, 1, 1, false, true>)); SETF((fasts_power_kernel<4, 8, 2, 1, false, true>));
+    SETF((fastr_kernel<0, false, false, true>)); SETF((fastr_kernel<0, true, false, true>)); SETF((fastr_kernel<1, false, false, true>)); SETF((fastr_kernel<1, true, false, true>));
+    SETF((fastr2_kernel<32, 16, 0, false, false, true>)); SETF((fastr2_kernel<32, 16, 0, true, false, true>)); SETF((fastr2_kernel<32, 16, 1, false, false, true>)); SETF((fastr2_kernel<32, 16, 1, true, false, true>));
+    SETF((fastr2_kernel<16, 16, 0, false, false, true>)); SETF((fastr2_kernel<16, 16, 0, true, false, true>)); SETF((fastr2_kernel<16, 16, 1, false, false, true>)); SETF((fastr2_kernel<16, 16, 1, true, false, true>));
     SETF((fastc_kernel<32, 16, 0>)); SETF((fastc_kernel<32, 16, 1>)); SETF((fastc_kernel<16, 16, 0>)); SETF((fastc_kernel<16, 16, 1>));
     SETF((fastc_kernel<16, 8, 0>)); SETF((fastc_kernel<16, 8, 1>)); SETF((fastc_kernel<8, 8, 0>)); SETF((fastc_kernel<8, 8, 1>));
     SETF((fastr2_kernel<32, 16, 0, false>)); SETF((fastr2_kernel<32, 16, 0, true>)); SETF((fastr2_kernel<32, 16, 1, false>)); SETF((fastr2_kernel<32, 16, 1, true>));

@@ -18,6 +18,8 @@
     XRFT_KW void fasty_cols_kernel<NN, true>(FastY); XRFT_KW void fasty_cols_kernel<NN, false>(FastY); \
     XRFT_KW void fasty_cols_kernel<NN, true, true>(FastY); XRFT_KW void fasty_cols_kernel<NN, false, true>(FastY); \
     XRFT_KW void fasty_cols_kernel<NN, true, false, true>(FastY); XRFT_KW void fasty_cols_kernel<NN, false, false, true>(FastY);  /* (STR: strided input) */ \
+    XRFT_KW void fasty_cols_kernel<NN, true, false, false, true>(FastY); XRFT_KW void fasty_cols_kernel<NN, false, false, false, true>(FastY);  /* (H16: float16 / bfloat16 input) */ \
+    XRFT_KW void fasty_cols_kernel<NN, true, true, false, true>(FastY); XRFT_KW void fasty_cols_kernel<NN, false, true, false, true>(FastY); \
     XRFT_KW void fasty_rows_kernel<NN, 1, true>(FastY); XRFT_KW void fasty_rows_kernel<NN, 1, false>(FastY); \
     XRFT_KW void fasty_rows_kernel<NN, 2, true>(FastY); XRFT_KW void fasty_rows_kernel<NN, 2, false>(FastY); \
     XRFT_KW void fasty_rows_kernel<NN, 3, false>(FastY); XRFT_KW void fasty_rows_kernel<NN, 0, false>(FastY);

@@ -207,6 +207,16 @@ int xrfthip_detrend_inner(int32_t dtype, int32_t ndim, int64_t batch, int64_t ny
 
 int xrfthip_convert(int32_t dtype_in, int32_t dtype_out, int64_t n, const void* d_in, void* d_out, void* stream) {
     if (!d_in || !d_out || n < 0) return XRFTHIP_BAD_ARG;
+    if ((dtype_in == XRFTHIP_F16 || dtype_in == XRFTHIP_BF16) && dtype_out == XRFTHIP_F32) {  // exact widening: what a caller does when a half plan answers XRFTHIP_UNSUPPORTED_LENGTH
+        if (n == 0) return XRFTHIP_OK;
+        if ((((uintptr_t)d_in) & 1) || (((uintptr_t)d_out) & 3)) return XRFTHIP_BAD_ARG;
+        const int pairs = (((uintptr_t)d_in) & 3) == 0 ? 1 : 0;
+        const dim3 grid((unsigned)std::min<long long>(((pairs ? (n + 1) / 2 : n) + 255) / 256, 8LL * kCUs * 4)), block(256);
+        auto k = &widen16_kernel;
+        XRFT_LAUNCH(k, grid, block, 0, (hipStream_t)stream, (const unsigned short*)d_in, (float*)d_out, (long long)n, dtype_in == XRFTHIP_BF16 ? 1 : 0, pairs);
+        HIP_TRY(hipGetLastError());
+        return XRFTHIP_OK;
+    }
     const bool up = (dtype_in == XRFTHIP_F32 && dtype_out == XRFTHIP_F64) || (dtype_in == XRFTHIP_C64 && dtype_out == XRFTHIP_C128);
     const bool down = (dtype_in == XRFTHIP_F64 && dtype_out == XRFTHIP_F32) || (dtype_in == XRFTHIP_C128 && dtype_out == XRFTHIP_C64);
     if (!up && !down) return XRFTHIP_BAD_ARG;

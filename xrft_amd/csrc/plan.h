@@ -354,6 +354,8 @@ using namespace xrfth;
 struct xrfthip_plan {
     xrfthip_desc d{};
     bool dbl = false, cplx_in = false;
+    int in16 = 0;  // the input holds 2-byte real samples: 1 float16 (XRFTHIP_F16), 2 bfloat16 (XRFTHIP_BF16).  The plan is the float32 plan (d.dtype = XRFTHIP_F32) in everything but
+                   // the loads of the kernel that reads the caller's input (half_in.h); only the families half_family() names take it
     size_t rsize = 4, csize = 8;
     long long nxh = 0, width = 0, nx_out = 0, w_cols = 0;  // w_cols: columns of the row->column intermediate incl. tile padding
     bool mirror = false;
@@ -572,6 +574,14 @@ inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (t
 inline bool in_strided(const xrfthip_plan* P) { return P->d.in_stride_y != 0 || P->d.in_stride_batch != 0; }
 inline long long in_pitch(const xrfthip_plan* P) { return P->d.in_stride_y ? P->d.in_stride_y : P->d.nx; }               // elements between rows (real-input families: rows of nx)
 inline long long in_slab(const xrfthip_plan* P) { return P->d.in_stride_batch ? P->d.in_stride_batch : P->d.ny * P->d.nx; }  // elements between slabs
+// Half-precision input (xrfthip_plan::in16): read dense by the float32 families' own input pass -- the two y-first passes (and their four-step 1-D form), the register-
+// resident slabs and rows, the one-pass slabs and row groups with real input.  Every other family: XRFTHIP_UNSUPPORTED_LENGTH from xrfthip_plan_create or from the
+// xrfthip_plan_set_* call that moves the plan there (the caller widens with xrfthip_convert and takes the float32 plan).
+inline bool in_half(const xrfthip_plan* P) { return P->in16 != 0; }
+inline bool half_family(const xrfthip_plan* P) {
+    const Family f = P->family;
+    return !P->dbl && !P->cplx_in && (f == Family::FastY || f == Family::FastY1D || f == Family::FastS || f == Family::FastR || f == Family::FastG);
+}
 inline bool family_reads_strided(const xrfthip_plan* P) {  // (the complex-input forms are kernels of their own)
     const FamilyOps& o = family_ops(P->family);
     return o.reads_strided && !P->cplx_in && (!o.strided_if || o.strided_if(P));

@@ -703,6 +703,8 @@ static int finalize_plan(xrfthip_plan* P) {
     settle_family(P);
     // a strided plan runs the family the dense descriptor gets, or none: never a slower family because of the strides (the caller copies)
     if (in_strided(P) && !family_reads_strided(P)) return XRFTHIP_UNSUPPORTED_LENGTH;
+    // ... and a half plan a family that reads 2-byte samples, or none (the caller widens): no other kernel may ever see the 2-byte buffer
+    if (in_half(P) && !half_family(P)) return XRFTHIP_UNSUPPORTED_LENGTH;
     if (const auto layout = family_ops(P->family).layout) layout(P);
     return XRFTHIP_OK;
 }
@@ -864,6 +866,10 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
         if (dcopy.ndim == 1) dcopy.in_stride_y = 0;  // (one row per slab: nothing to stride over)
         if (dcopy.in_stride_y == 0 && dcopy.in_stride_batch == dcopy.ny * row) dcopy.in_stride_batch = 0;
     }
+    // float16 / bfloat16 input: the float32 plan of the same descriptor, its input pass reading 2-byte samples (half_in.h).  From here on the descriptor says XRFTHIP_F32
+    // -- every check, every table, the family and the workspace are the float32 plan's -- and in16 remembers what the input holds.
+    const int in16 = dcopy.dtype == XRFTHIP_F16 ? 1 : dcopy.dtype == XRFTHIP_BF16 ? 2 : 0;
+    if (in16) dcopy.dtype = XRFTHIP_F32;
     const xrfthip_desc& d = dcopy;
     if (d.ndim != 1 && d.ndim != 2) return XRFTHIP_BAD_ARG;
     if (d.batch < 0 || d.nx < 1 || d.ny < 1 || (d.ndim == 1 && d.ny != 1)) return XRFTHIP_BAD_ARG;
@@ -906,6 +912,8 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
         if ((d.in_stride_y * esz) % 16 != 0 || (d.in_stride_batch * esz) % 16 != 0) return XRFTHIP_UNSUPPORTED_LENGTH;
     }
 
+    // half input is read dense, by the trailing-axes families that half_family() names: everything else is "the caller widens" (xrfthip_convert, then the float32 plan)
+    if (in16 && (strided || d.inner > 1 || d.mid > 1 || (d.flags & XRFTHIP_AXIS_Y))) return XRFTHIP_UNSUPPORTED_LENGTH;
     if (d.inner > 1 || d.mid > 1) return create_inner_plan(plan, d);
 
     xrfthip_plan* P = new (std::nothrow) xrfthip_plan();
@@ -919,6 +927,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     P->tune_cols_grid = env_ll("XRFTHIP_FAST_COLS_GRID", kCUs);
     P->tune_max_grid = env_ll("XRFTHIP_MAX_GRID", 8 * kCUs * 4);
     P->cplx_in = cplx_in;
+    P->in16 = in16;
     P->dbl = d.dtype == XRFTHIP_F64 || d.dtype == XRFTHIP_C128;
     P->rsize = P->dbl ? 8 : 4;
     P->csize = 2 * P->rsize;
@@ -1108,6 +1117,7 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
     // a strided plan: said on the line of the pass that reads the caller's input, by every family that family_reads_strided() names (empty on a dense plan)
     std::string in_note_;
     if (in_strided(plan)) appendf(in_note_, "; input read where it lies: in pitch %lld / slab %lld", in_pitch(plan), in_slab(plan));
+    if (in_half(plan)) appendf(in_note_, "; %s input read where it lies (2 bytes per sample), widened to float32 in registers", plan->in16 == 2 ? "bfloat16" : "float16");
     const char* in_note = in_note_.c_str();
     if (const auto describe = family_ops(plan->family).describe) describe(plan, s, in_note);
     if (!inner_layout(plan)) {
@@ -1141,6 +1151,9 @@ int xrfthip_exec_ex(const xrfthip_plan* plan, const xrfthip_exec_args* args) {
     const bool iso = (d.flags & XRFTHIP_ISO) != 0;
     if (cross && !d_in1) return XRFTHIP_BAD_ARG;
     if (in_strided(P) && ((((uintptr_t)d_in0) & 15) || (cross && (((uintptr_t)d_in1) & 15)))) return XRFTHIP_BAD_ARG;  // (a strided plan's vector loads: 16-byte aligned fields)
+    if (in_half(P)) {  // (a half plan's vector loads: 16-byte aligned fields, else "the caller widens"; and never a kernel that reads 4-byte samples)
+        if (!half_family(P) || (((uintptr_t)d_in0) & 15) || (cross && (((uintptr_t)d_in1) & 15))) return XRFTHIP_UNSUPPORTED_LENGTH;
+    }
     if (!d_out && !(d.flags & XRFTHIP_NO_SPECTRUM_OUT)) return XRFTHIP_BAD_ARG;
     if (iso && (!d_iso || !P->binmap.p)) return d_iso ? XRFTHIP_MISSING_TABLE : XRFTHIP_BAD_ARG;
     const bool inner = inner_layout(P);  // (always a workspace)

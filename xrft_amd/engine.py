@@ -16,11 +16,12 @@ import torch
 
 from . import _lib
 
+_HALF = {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}  # real half-precision INPUT of a plan (the float32 plan reading 2-byte samples) and of convert(); nothing else takes it
 _DTYPES = {torch.float32: _lib.F32, torch.float64: _lib.F64, torch.complex64: _lib.C64, torch.complex128: _lib.C128}
 _REAL_OF = {torch.float32: torch.float32, torch.float64: torch.float64, torch.complex64: torch.float32,
-            torch.complex128: torch.float64}
+            torch.complex128: torch.float64, torch.float16: torch.float32, torch.bfloat16: torch.float32}
 _CPLX_OF = {torch.float32: torch.complex64, torch.float64: torch.complex128, torch.complex64: torch.complex64,
-            torch.complex128: torch.complex128}
+            torch.complex128: torch.complex128, torch.float16: torch.complex64, torch.bfloat16: torch.complex64}
 
 
 def _stream_handle(t):
@@ -44,7 +45,7 @@ class SpectralPlan:
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
         self._pass1 = None
-        if dtype not in _DTYPES:
+        if dtype not in _DTYPES and dtype not in _HALF:
             raise TypeError(f"unsupported dtype {dtype}")
         self.ndim, self.batch, self.ny, self.nx = int(ndim), int(batch), int(ny), int(nx)
         self.dtype, self.out_mode, self.flags = dtype, int(out_mode), int(flags)
@@ -60,7 +61,7 @@ class SpectralPlan:
         self.herm_ny, self.herm_nx = int(herm_ny), int(herm_nx)
         if self.herm_ny or self.herm_nx:
             self.nx_out = self.herm_ny * self.herm_nx
-        d = _lib.Desc(C.sizeof(_lib.Desc), self.ndim, self.batch, self.ny, self.nx, _DTYPES[dtype], self.out_mode,
+        d = _lib.Desc(C.sizeof(_lib.Desc), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
                       int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
                       self.herm_ny, self.herm_nx)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
@@ -448,8 +449,19 @@ _NARROWER = {v: k for k, v in _WIDER.items()}
 
 
 def convert(x, dtype, out=None):
-    """``x`` in the other precision (float32 <-> float64, complex64 <-> complex128) by the library's own kernel (xrfthip_convert)."""
+    """``x`` in the other precision (float32 <-> float64, complex64 <-> complex128) by the library's own kernel (xrfthip_convert); float16 / bfloat16 -> float32, exact:
+    the widening behind the calls a half plan declines."""
     dll = _lib.load()
+    if x.dtype in _HALF:
+        if dtype is not torch.float32:
+            raise TypeError(f"convert: {x.dtype} -> {dtype}")
+        x = x.contiguous()  # (a view: copied in half precision, 2 bytes per sample)
+        if out is None:
+            out = torch.empty(x.shape, dtype=dtype, device=x.device)
+        elif out.dtype is not dtype or out.numel() != x.numel() or not out.is_contiguous():
+            raise ValueError("convert: out does not match")
+        _lib.check(dll.xrfthip_convert(_HALF[x.dtype], _lib.F32, x.numel(), _ptr(x), _ptr(out), _stream_handle(x)))
+        return out
     if _WIDER.get(x.dtype) is not dtype and _NARROWER.get(x.dtype) is not dtype:
         raise TypeError(f"convert: {x.dtype} -> {dtype}")
     x = x.contiguous()
