@@ -1136,6 +1136,17 @@ def _spectrum_nd(da, da2, dims, real_dim, scaling, window_correction, true_phase
 # ------------------------------------------------------------------------------------------------------
 # public API
 # ------------------------------------------------------------------------------------------------------
+def _refuse_nonfinite(c):
+    """A least-squares line along ONE axis is scipy.signal.detrend in the reference (detrend.py:64-71), which refuses input that is not finite: the same refusal
+    here.  The price is one pass over the input and a device-to-host synchronisation per call with THIS detrend (not timed yet: profiles/r13_nonfinite.txt); the other
+    detrends and every transform let a NaN through, into its own transform alone.  Called before a plan is looked for, so the fallbacks of an unsupported length
+    are covered; transforms over more than two dims never take a one-axis line."""
+    if c.detrend == _lib.DETREND_LINEAR and len(c.dim) == 1:
+        t = c.da.data
+        if not (bool(np.isfinite(t).all()) if isinstance(t, np.ndarray) else bool(torch.isfinite(t).all())):
+            raise ValueError("array must not contain infs or NaNs")
+
+
 def fft(da, spacing_tol=1e-3, dim=None, real_dim=None, shift=True, detrend=None, window=None, true_phase=True,
         true_amplitude=True, chunks_to_segments=False, prefix="freq_", real=None):
     """Discrete Fourier transform of ``da`` along ``dim`` (reference: xrft/xrft.py:307-476; same arguments)."""
@@ -1146,6 +1157,7 @@ def fft(da, spacing_tol=1e-3, dim=None, real_dim=None, shift=True, detrend=None,
         return to_like(_fft_nd(da, nd, spacing_tol, real_dim if real is None else real, shift, detrend, window,
                                true_phase, true_amplitude, chunks_to_segments, prefix), src)
     c = _analyze(da, spacing_tol, dim, real_dim, shift, detrend, window, true_phase, chunks_to_segments, prefix, real)
+    _refuse_nonfinite(c)
     scale = math.prod(c.delta_x) if true_amplitude else 1.0  # xrft.py:471-472 (math.prod: the same left-to-right product as np.prod of a short list, a tenth of its call time)
     try:
         out, _, other = _execute(c, c.da, _lib.OUT_COMPLEX, scale)
@@ -1551,6 +1563,8 @@ def detrend(da, dim, detrend_type="constant"):
         raise NotImplementedError("Only 1D, 2D, and 3D detrending are implemented so far.")
     axes = [da.get_axis_num(d) for d in dim]
     t = _to_device(da.data)
+    if detrend_type == "linear" and len(dim) == 1 and not bool(torch.isfinite(t).all()):  # (scipy.signal.detrend's refusal, detrend.py:64-71; _refuse_nonfinite)
+        raise ValueError("array must not contain infs or NaNs")
     dim = [d for _, d in sorted(zip(axes, dim))]  # memory order: the fit does not depend on the order of the axes
     other = [d for d in da.dims if d not in dim]
     order = other + dim
@@ -1633,11 +1647,13 @@ def _spectrum(da, da2, dim, real_dim, scaling, window_correction, true_phase, kw
     kw.update(kwargs)
     c = _analyze(da, kw["spacing_tol"], dim, real_dim, kw["shift"], kw["detrend"], kw["window"], true_phase,
                  kw["chunks_to_segments"], kw["prefix"], kw["real"])
+    _refuse_nonfinite(c)
     c2 = None
     amp = math.prod(c.delta_x) ** 2
     if da2 is not None:
         c2 = _analyze(da2, kw["spacing_tol"], dim, real_dim, kw["shift"], kw["detrend"], kw["window"], true_phase,
                       kw["chunks_to_segments"], kw["prefix"], kw["real"])
+        _refuse_nonfinite(c2)
         if [c.swap.get(d, d) for d in c.rawdims] != [c2.swap.get(d, d) for d in c2.rawdims]:  # xrft.py:819-820
             raise ValueError("The two datasets have different dimensions")
         if c.N != c2.N or not np.allclose(c.delta_x, c2.delta_x, rtol=1e-12):

@@ -25,6 +25,7 @@
 // real fields; Bluestein inside the tile for a prime factor that has no butterfly.
 #pragma once
 #include "tile_fft.h"
+#include <limits>
 #include "fastr.h"  // fastr_store4 / fastr_store8
 
 namespace xrft {
@@ -686,6 +687,11 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fastgy_kernel(F
     C = G * cpg;
     const T sc = (T)p.scale;
     const double ibar = 0.5 * (ny - 1);
+    // real input, one field: the two columns (ROWS: rows) of a sequence are INDEPENDENT transforms, and a NaN / inf in one would fill the other's spectrum after the
+    // split.  A sample that is not finite enters the passes as 0 and marks its own column in coef[4 g + (0 | 2)] -- with a detrend that is the column's mean, not finite
+    // from its raw sum; without one a NaN stored there -- and a marked column is stored as NaN (fastn.h GUARD)
+    const bool guard = !one_col;
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
     for (long long unit = blockIdx.x; unit < p.nunits; unit += gridDim.x) {
         const long long b = unit / p.nblk;
         const int c0 = (int)(unit - b * p.nblk) * C;
@@ -695,6 +701,10 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fastgy_kernel(F
         const T* __restrict__ src = reinterpret_cast<const T*>(p.in) + (ROWS ? (size_t)(c0 + cpg * g) * ny : (size_t)b * ny * nx + c0 + cpg * g) * (p.cin ? 2 : 1);
         const size_t rowstep = ROWS ? (size_t)(p.cin ? 2 : 1) : (size_t)nx * (p.cin ? 2 : 1);  // (in T elements)
         __syncthreads();  // (the previous unit's output loop is done with the tile; the tables are in place)
+        if (guard && !p.detrend) {
+            if (tid < G) { coef[tid * 4] = 0.0; coef[tid * 4 + 2] = 0.0; }
+            __syncthreads();
+        }
         // ---- load (rows rq, rq + RQ, ... of sequence g); without a detrend the window rides along
         double s[4] = {0.0, 0.0, 0.0, 0.0};
         for (int i = rq; i < ny; i += RQ) {
@@ -707,6 +717,12 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fastgy_kernel(F
             }
             if (p.ph_in) z = cmul(z, reinterpret_cast<const CT*>(p.ph_y)[is]);
             if (p.inv) z.im = -z.im;
+            if (guard && !p.detrend) {
+                const bool f0 = fabs(z.re) <= std::numeric_limits<T>::max(), f1 = fabs(z.im) <= std::numeric_limits<T>::max();
+                // (every thread of the column that meets such a sample stores the same NaN: a same-value race, on purpose; coef was zeroed behind a barrier and is read after the passes)
+                if (!f0) { z.re = (T)0; coef[g * 4] = qnan; }
+                if (!f1) { z.im = (T)0; coef[g * 4 + 2] = qnan; }
+            }
             if (p.detrend) {
                 const double ri = (double)i - ibar;
                 s[0] += (double)z.re; s[2] += (double)z.im;
@@ -733,11 +749,12 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fastgy_kernel(F
             }
             __syncthreads();
             const double m0 = coef[g * 4], b0 = coef[g * 4 + 1], m1 = coef[g * 4 + 2], b1 = coef[g * 4 + 3];
+            const bool bad0 = guard && !(fabs(m0) <= std::numeric_limits<double>::max()), bad1 = guard && !(fabs(m1) <= std::numeric_limits<double>::max());
             for (int i = rq; i < ny; i += RQ) {  // (each thread revisits the elements it loaded)
                 const int slot = (RADER ? (int)pin[i] : i) * GS + g;
                 CT z = tile[slot];
                 const double ri = (double)i - ibar;
-                z = mk<T>((T)((double)z.re - fma(b0, ri, m0)), (T)((double)z.im - fma(b1, ri, m1)));
+                z = mk<T>(bad0 ? (T)0 : (T)((double)z.re - fma(b0, ri, m0)), bad1 ? (T)0 : (T)((double)z.im - fma(b1, ri, m1)));
                 if (p.win_y) { const T w = wys[i]; z = mk<T>(z.re * w, z.im * w); }
                 tile[slot] = z;
             }
@@ -813,6 +830,7 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fastgy_kernel(F
                 const CT zk = tile[(BLUE ? k : (int)revy[k]) * GS + (c >> 1)], zm = tile[(BLUE ? km : (int)revy[km]) * GS + (c >> 1)];
                 v = (c & 1) ? mk<T>((T)0.5 * (zk.im + zm.im), (T)0.5 * (zm.re - zk.re))   // (Zk - conj Zm) / 2i
                             : mk<T>((T)0.5 * (zk.re + zm.re), (T)0.5 * (zk.im - zm.im));  // (Zk + conj Zm) / 2
+                if (!(fabs(coef[(c >> 1) * 4 + 2 * (c & 1)]) <= std::numeric_limits<double>::max())) v = mk<T>((T)qnan, (T)qnan);  // (a marked column)
             }
             const size_t o = ROWS ? (size_t)col * nyo + orow : ((size_t)b * nyo + orow) * nx + col;
             const T sck = (p.realdim2 && k != 0 && 2 * k != ny) ? sc + sc : sc;

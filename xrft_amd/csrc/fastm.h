@@ -27,6 +27,7 @@
 #include "aux_kernels.h"
 #include "fasty.h"  // ilog2c
 #include "tile_fft.h"
+#include <limits>
 
 namespace xrft {
 
@@ -274,6 +275,48 @@ template <typename T, int N> __device__ __forceinline__ void mr_fill_tw1(C2<T>* 
     }
 }
 
+// The one-axis kernels below pack two INDEPENDENT real sequences (two columns, two rows; irfft: two half-spectrum rows) into one complex transform: a NaN / inf in
+// one would fill the other's spectrum after the split.  A sample that is not finite enters the transform as 0 and marks its own sequence (bit 0: the real part's,
+// bit 1: the imaginary part's); the marks of a sequence's threads meet in the detrend sums (a NaN added to the marked sum) or, without a detrend, as per-wave
+// words in the same LDS table; mr_marks reads them back once the transforms are done, and a marked sequence is stored as NaN.
+template <typename T> __device__ __forceinline__ bool mr_finite(T v) { return fabs(v) <= std::numeric_limits<T>::max(); }
+template <typename T> __device__ __forceinline__ unsigned mr_guard(C2<T>& z) {
+    const bool f0 = mr_finite<T>(z.re), f1 = mr_finite<T>(z.im);
+    z = mk<T>(f0 ? z.re : (T)0, f1 ? z.im : (T)0);
+    return (f0 ? 0u : 1u) | (f1 ? 0u : 2u);
+}
+// (no detrend) the marks of this wave's threads of sequence g -> word [wave][g] of the table
+template <int G> __device__ __forceinline__ void mr_marks_wave(double* part, unsigned bad, int tid, int g) {
+#pragma unroll
+    for (int m = G; m < 64; m <<= 1) bad |= (unsigned)__shfl_xor((int)bad, m);
+    if ((tid & 63) < G) reinterpret_cast<int*>(part)[(tid >> 6) * G + g] = (int)bad;
+}
+// after mr_fft_tail: thread g < G reads the marks of sequence g back from the table -- the detrend sums (a marked sum is NaN) or the per-wave words -- so that no thread
+// carries them in a register across the passes, and stores them where nothing is read any more: with a detrend in the unused first-moment slot of wave 0's entry g,
+// without one behind the words.  Ends with a barrier.  mr_mark: the mark of real sequence t = 2 g + (0 | 1).
+struct MrMarks { const int* p; int stride; };
+template <int G, int THR> __device__ __forceinline__ MrMarks mr_marks(double* part, bool det, int tid) {
+    int* w = reinterpret_cast<int*>(part);
+    int* fin = det ? w + 4 : w + (THR / 64) * G;
+    const int stride = det ? 8 : 2;
+    if (tid < G) {
+        unsigned bad = 0;
+        if (det) {
+            double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+            for (int v = 0; v < THR / 64; ++v) { t0 += part[(v * G + tid) * 4]; t1 += part[(v * G + tid) * 4 + 1]; }
+            bad = (mr_finite<double>(t0) ? 0u : 1u) | (mr_finite<double>(t1) ? 0u : 2u);
+        } else {
+#pragma unroll
+            for (int v = 0; v < THR / 64; ++v) bad |= (unsigned)w[v * G + tid];
+        }
+        fin[stride * tid] = (int)(bad & 1u); fin[stride * tid + 1] = (int)(bad >> 1);
+    }
+    __syncthreads();
+    return {fin, stride};
+}
+__device__ __forceinline__ bool mr_mark(const MrMarks& m, int t) { return m.p[m.stride * (t >> 1) + (t & 1)] != 0; }
+
 // ------------------------------------------------------------------------------------------------
 // pass 1: a workgroup owns CW = 2 G adjacent real columns of one slab (lane order (row, g), g fastest: the lanes of a row read
 // 16 G contiguous bytes); columns 2g, 2g+1 are the real and imaginary part of sequence g.     window: xrft.py:96-103, 430-433
@@ -484,6 +527,12 @@ __global__ void __launch_bounds__((MYGeom<T, NY>::type::THR), (MYGeom<T, NY>::ty
         }
     }
     constexpr double IBAR = 0.5 * (NY - 1);
+    const bool PAIR = !TWO && !CIN;  // columns 2g, 2g+1 are two independent sequences: a sample that is not finite stays in its own (mr_guard)
+    unsigned bad = 0;
+    if (PAIR) {
+#pragma unroll
+        for (int q = 0; q < R0; ++q) bad |= mr_guard<T>(a[q]);
+    }
     if (DET) {
         double s[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -492,6 +541,8 @@ __global__ void __launch_bounds__((MYGeom<T, NY>::type::THR), (MYGeom<T, NY>::ty
             s[0] += (double)a[q].re; s[1] += (double)a[q].im;
             s[2] = fma(ri, (double)a[q].re, s[2]); s[3] = fma(ri, (double)a[q].im, s[3]);
         }
+        if (bad & 1u) s[0] = std::numeric_limits<double>::quiet_NaN();
+        if (bad & 2u) s[1] = std::numeric_limits<double>::quiet_NaN();
 #pragma unroll
         for (int m = G; m < 64; m <<= 1)
 #pragma unroll
@@ -508,18 +559,21 @@ __global__ void __launch_bounds__((MYGeom<T, NY>::type::THR), (MYGeom<T, NY>::ty
             for (int c = 0; c < 4; ++c) tot[c] += part[(w * G + g) * 4 + c];
         // mean, and the slope of the least-squares line through (i - ibar): sum (i - ibar)^2 = n (n^2 - 1) / 12
         constexpr double INV_N = 1.0 / NY, INV_SII = 12.0 / ((double)NY * ((double)NY * NY - 1.0));
-        const double m0 = tot[0] * INV_N, m1 = tot[1] * INV_N;
+        if (PAIR) bad = (mr_finite<double>(tot[0]) ? 0u : 1u) | (mr_finite<double>(tot[1]) ? 0u : 2u);  // (the whole sequence's marks)
+        const double m0 = (bad & 1u) ? 0.0 : tot[0] * INV_N, m1 = (bad & 2u) ? 0.0 : tot[1] * INV_N;
         const double sl0 = p.detrend == 2 ? tot[2] * INV_SII : 0.0, sl1 = p.detrend == 2 ? tot[3] * INV_SII : 0.0;
 #pragma unroll
         for (int q = 0; q < R0; ++q) {
             const double ri = (double)(j + q * M0) - IBAR;
             a[q] = mk<T>((T)((double)a[q].re - fma(sl0, ri, m0)), (T)((double)a[q].im - fma(sl1, ri, m1)));
         }
-    }
+    } else if (PAIR) mr_marks_wave<G>(part, bad, tid, g);
 #pragma unroll
     for (int q = 0; q < R0; ++q) a[q] = cscale(a[q], wyv[q]);
     if (on) mr_pass0<T, NY>(a, lds + g * STR, j, w0);
     mr_fft_tail<T, NY, G, THR>(lds, tid, tw1);
+    MrMarks marks = {nullptr, 0};
+    if (PAIR) marks = mr_marks<G, THR>(part, DET, tid);
     // split the packed spectra (fastm_cols_kernel) and store rows ky and -ky of the result; lanes (ky, column), column fastest
     // (p.half -- real_dim along this axis, xrft.py:400-404: only k = 0 .. NY/2 is stored, NY/2 + 1 rows per slab, unshifted; p.realdim2: 0 < k < NY/2 counts twice, xrft.py:673-682)
     const int orows = p.half ? NY / 2 + 1 : NY;
@@ -552,6 +606,7 @@ __global__ void __launch_bounds__((MYGeom<T, NY>::type::THR), (MYGeom<T, NY>::ty
             CT o;
             if (TWO) o = cmulc(cscale(zk + zc, (T)0.5), cscale(mul_mi(zk - zc), (T)0.5));  // F0 conj(F1) of this column (xrft.py:825)
             else o = (col & 1) ? cscale(mul_mi(zk - zc), (T)0.5) : cscale(zk + zc, (T)0.5);
+            if (PAIR && mr_mark(marks, col)) o = mk<T>(std::numeric_limits<T>::quiet_NaN(), std::numeric_limits<T>::quiet_NaN());
             const int km = k == 0 ? 0 : NY - k;
             int rd = k + p.shift_y; if (rd >= NY) rd -= NY;
             int rm = km + p.shift_y; if (rm >= NY) rm -= NY;
@@ -614,6 +669,8 @@ __global__ void __launch_bounds__((MGeom<T, N>::THR), (MGeom<T, N>::WPS)) fastm_
     const T* __restrict__ wx = reinterpret_cast<const T*>(p.win_x);
     CT a[R0];
     T wv[R0];
+    const bool PAIR = !TWO && (!CIN || C2R);  // rows 2g, 2g+1 are two independent sequences: a sample that is not finite stays in its own (mr_guard)
+    unsigned bad = 0;
 #pragma unroll
     for (int q = 0; q < R0; ++q) {
         const int x = j + q * M0;
@@ -624,6 +681,8 @@ __global__ void __launch_bounds__((MGeom<T, N>::THR), (MGeom<T, N>::WPS)) fastm_
             CT B = hb ? (reinterpret_cast<const CT*>(p.in) + (size_t)rb * HW)[xs] : mk<T>((T)0, (T)0);
             if (p.ph_in) { const CT f = reinterpret_cast<const CT*>(p.ph_x)[xs]; A = cmul(A, f); B = cmul(B, f); }
             if (x == 0 || 2 * x == N) { A.im = (T)0; B.im = (T)0; }  // (numpy's irfft takes the real parts of the zero-frequency and Nyquist samples)
+            if (mr_guard<T>(A)) bad |= 1u;  // (a half-spectrum row that holds a value that is not finite -- where irfft reads it -- is marked whole)
+            if (mr_guard<T>(B)) bad |= 2u;
             if (2 * x > N) { A.im = -A.im; B.im = -B.im; }
             a[q] = mk<T>(A.re - B.im, -(A.im + B.re));  // conj(A + i B)
         } else if (CIN) {
@@ -635,6 +694,10 @@ __global__ void __launch_bounds__((MGeom<T, N>::THR), (MGeom<T, N>::WPS)) fastm_
         } else a[q] = mk<T>(ha ? sa[x] : (T)0, hb ? sb[x] : (T)0);
         wv[q] = wx[x];
     }
+    if (PAIR && !C2R) {  // (behind the loads, not between them: every load of the thread stays in flight at once)
+#pragma unroll
+        for (int q = 0; q < R0; ++q) bad |= mr_guard<T>(a[q]);
+    }
     constexpr double XBAR = 0.5 * (N - 1);
     if (DET) {
         double s[4] = {0.0, 0.0, 0.0, 0.0};
@@ -645,6 +708,8 @@ __global__ void __launch_bounds__((MGeom<T, N>::THR), (MGeom<T, N>::WPS)) fastm_
                 s[0] += (double)a[q].re; s[1] += (double)a[q].im;
                 s[2] = fma(ri, (double)a[q].re, s[2]); s[3] = fma(ri, (double)a[q].im, s[3]);
             }
+            if (bad & 1u) s[0] = std::numeric_limits<double>::quiet_NaN();
+            if (bad & 2u) s[1] = std::numeric_limits<double>::quiet_NaN();
         }
 #pragma unroll
         for (int m = G; m < 64; m <<= 1)
@@ -661,18 +726,21 @@ __global__ void __launch_bounds__((MGeom<T, N>::THR), (MGeom<T, N>::WPS)) fastm_
 #pragma unroll
             for (int c = 0; c < 4; ++c) tot[c] += part[(w * G + g) * 4 + c];
         constexpr double INV_N = 1.0 / N, INV_SII = 12.0 / ((double)N * ((double)N * N - 1.0));
-        const double m0 = tot[0] * INV_N, m1 = tot[1] * INV_N;
+        if (PAIR) bad = (mr_finite<double>(tot[0]) ? 0u : 1u) | (mr_finite<double>(tot[1]) ? 0u : 2u);  // (the whole sequence's marks)
+        const double m0 = (bad & 1u) ? 0.0 : tot[0] * INV_N, m1 = (bad & 2u) ? 0.0 : tot[1] * INV_N;
         const double sl0 = p.detrend == 2 ? tot[2] * INV_SII : 0.0, sl1 = p.detrend == 2 ? tot[3] * INV_SII : 0.0;
 #pragma unroll
         for (int q = 0; q < R0; ++q) {
             const double ri = (double)(j + q * M0) - XBAR;
             a[q] = mk<T>((T)((double)a[q].re - fma(sl0, ri, m0)), (T)((double)a[q].im - fma(sl1, ri, m1)));
         }
-    }
+    } else if (PAIR) mr_marks_wave<G>(part, bad, tid, g);
 #pragma unroll
     for (int q = 0; q < R0; ++q) a[q] = cscale(a[q], wv[q]);
     if (on) mr_pass0<T, N>(a, lds + g * STR, j, w0);
     mr_fft_tail<T, N, G, THR>(lds, tid, tw1);
+    MrMarks marks = {nullptr, 0};
+    if (PAIR) marks = mr_marks<G, THR>(part, DET, tid);
     // split and store: lanes run along k of one row
     const bool real_out = MODE == 1 || (MODE == 2 && p.angle) || C2R;
     const int W = p.half ? N / 2 + 1 : N;
@@ -684,7 +752,7 @@ __global__ void __launch_bounds__((MGeom<T, N>::THR), (MGeom<T, N>::WPS)) fastm_
         if (C2R) {  // sample k of row t: Re z (the even row of the pair) or Im z = -Im FFT(conj C)
             const CT zr = lds[(t >> 1) * STR + M::pn(k)];
             int ocr = k + p.shift_x; if (ocr >= N) ocr -= N;
-            reinterpret_cast<T*>(p.out)[(size_t)row * N + ocr] = ((t & 1) ? -zr.im : zr.re) * sc;
+            reinterpret_cast<T*>(p.out)[(size_t)row * N + ocr] = mr_mark(marks, t) ? std::numeric_limits<T>::quiet_NaN() : ((t & 1) ? -zr.im : zr.re) * sc;
             continue;
         }
         const CT* z = lds + ((TWO || CIN) ? t : (t >> 1)) * STR;
@@ -693,6 +761,7 @@ __global__ void __launch_bounds__((MGeom<T, N>::THR), (MGeom<T, N>::WPS)) fastm_
         if (CIN) { o = zk; if (p.inv) o.im = -o.im; }
         else if (TWO) o = cmulc(cscale(zk + zc, (T)0.5), cscale(mul_mi(zk - zc), (T)0.5));  // F0 conj(F1) of this row (xrft.py:825)
         else o = (t & 1) ? cscale(mul_mi(zk - zc), (T)0.5) : cscale(zk + zc, (T)0.5);
+        if (PAIR && mr_mark(marks, t)) o = mk<T>(std::numeric_limits<T>::quiet_NaN(), std::numeric_limits<T>::quiet_NaN());
         int oc = k + p.shift_x; if (oc >= N) oc -= N;  // (half output: shift_x = 0)
         const T f = (p.realdim2 && k != 0 && 2 * k != N) ? sc * (T)2 : sc;
         char* dst = reinterpret_cast<char*>(p.out) + ((size_t)row * W + oc) * (real_out ? sizeof(T) : sizeof(CT));

@@ -430,8 +430,8 @@ void fastn_launch_cols(const xrfthip_plan* P, const FastM& m, hipStream_t st) {
     const size_t lds = P->n_c.lds;
     int maxrad = 0;
     for (int i = 0; i < hg.np; ++i) maxrad = std::max(maxrad, hg.r[i]);
-    // (radial sums of an inner layout: a packed column pair holds two spectra -- a sample that is not finite must stay in its own, fastn.h GUARD)
-    const bool guard = P->family == Family::FusedInner && (P->d.flags & XRFTHIP_ISO);
+    // (an inner layout: a packed column pair holds two spectra -- a sample that is not finite must stay in its own, fastn.h GUARD)
+    const bool guard = P->family == Family::FusedInner;
     const bool str = in_strided(P) && P->family == Family::FastN;  // (a box of a larger field, read where it lies; the inner layouts are dense)
 #define NCS_(TT, CC) do { if (P->n_blue_m) { auto k = &fastn_cols_kernel<TT, 1, 16, false, true>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } \
                           else if (P->n_rad_p) { auto k = &fastn_cols_kernel<TT, 2, 16, false, true>; XRFT_LAUNCH(k, grid, blk, lds, st, n); } \
@@ -929,6 +929,8 @@ void set_attrs_fastm() {
                      SETF((fastn_rows_kernel<TT, 0, false, CC>)); SETF((fastn_rows_kernel<TT, 1, false, CC>)); SETF((fastn_rows_kernel<TT, 1, true, CC>)); SETF((fastn_rows_kernel<TT, 2, false, CC>)); \
                      SETF((fastn_rows_kernel<TT, 2, true, CC>)); SETF((fastn_rows_kernel<TT, 3, false, CC>))
     SETN(float, 16); SETN(float, 20); SETN(double, 16);
+    SETF((fastn_cols_kernel<float, 0, 16, true>)); SETF((fastn_cols_kernel<float, 0, 20, true>)); SETF((fastn_cols_kernel<float, 2, 16, true>));  // (GUARD: every fused inner-layout plan)
+    SETF((fastn_cols_kernel<double, 0, 16, true>)); SETF((fastn_cols_kernel<double, 2, 16, true>));
     SETF((fastn_irows_kernel<float, 0, 16>)); SETF((fastn_irows_kernel<float, 1, 16>)); SETF((fastn_irows_kernel<float, 0, 20>)); SETF((fastn_irows_kernel<float, 1, 20>));
     SETF((fastn_irows_kernel<double, 0, 16>)); SETF((fastn_irows_kernel<double, 1, 16>)); SETF((fastn_irows_kernel<double, 2, 16>));
     SETF((fastn_irows_kernel<float, 2, 16>)); SETF((fastn_irows_kernel<float, 2, 20>));
