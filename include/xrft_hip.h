@@ -124,6 +124,8 @@ typedef enum xrfthip_detrend_kind {
  * with REALDIM_X2 and POWER|CROSS 0 < ky < ny/2 counts twice.  Real input, no SHIFT_*, not together with HALF_X.  ny may be odd: ky = 0..(ny-1)/2 is stored
  * (numpy.fft.rfft's (ny-1)/2 + 1 rows, no Nyquist row), and every ky > 0 counts twice; XRFTHIP_UNSUPPORTED_LENGTH where only the composite of one-axis plans exists. */
 #define XRFTHIP_HALF_Y 0x10000u
+/* herm_ny / herm_nx descriptors only: the last pass writes the complex FIELD F itself (out_mode COMPLEX), not |F|^2 or F0 conj(F1) -- see herm_ny below. */
+#define XRFTHIP_HERM_FIELD 0x20000u
 
 typedef struct xrfthip_desc {
     uint32_t struct_size; /* = sizeof(xrfthip_desc) */
@@ -192,7 +194,15 @@ typedef struct xrfthip_desc {
      * nx that is not herm_ny * (herm_nx/2 + 1); xrfthip_plan_set_phase (the twin of a sample at a Nyquist index does not carry the conjugate phase factor) and a window on
      * axis 1.  XRFTHIP_UNSUPPORTED_LENGTH means "the caller composes the stages": an nt with a prime factor above 13, or whose tile of 128 output bytes per row does not fit
      * the LDS (nt above ~600).  One pass, no workspace, no sums: repeated calls return identical bits.
-     * Descriptors with the struct_size of the four earlier versions are accepted (0, 0).  As with the strides, the status of xrfthip_plan_create tells the capability. */
+     * Descriptors with the struct_size of the four earlier versions are accepted (0, 0).  As with the strides, the status of xrfthip_plan_create tells the capability.
+     * XRFTHIP_HERM_FIELD: the same pass writes the transform itself (xrft.fft(da, dim=["time", "y", "x"])): out_mode COMPLEX and nothing else (POWER | CROSS | PHASE
+     * with the flag: XRFTHIP_BAD_ARG, as is the flag on a descriptor without herm_ny / herm_nx); d_out is complex [batch][nt][herm_ny][herm_nx], F * scale, the
+     * columns 1 <= kx <= herm_nx - (herm_nx/2 + 1) also written as the twin conj(F) * scale at (-kt, -ky, herm_nx - kx).  Such a plan takes THREE output-phase tables,
+     * xrfthip_plan_set_phase with axis = 0 (t: ny entries), 1 (herm_ny entries) and 2 (herm_nx entries: the FULL x axis, the twins lie above herm_nx/2), each indexed by
+     * UNSHIFTED frequency index; an axis without a table counts as 1.  A twin is multiplied by the factors of its DESTINATION indices, not by the conjugate of its
+     * sample's (an index n/2 of an even n is its own twin: fftfreq gives it -1/(2 dx) both times); without tables the twin is the plain conjugate, bit for bit.
+     * axis 2 is XRFTHIP_BAD_ARG on every other plan; a window stays on axis 0 only.  The same lengths are declined (XRFTHIP_UNSUPPORTED_LENGTH); the tile is 128 nt
+     * bytes.  Without the flag every answer a herm descriptor gets is what it was: out_mode COMPLEX and xrfthip_plan_set_phase stay XRFTHIP_BAD_ARG. */
     int64_t herm_ny;
     int64_t herm_nx;
 } xrfthip_desc;
@@ -210,7 +220,8 @@ int xrfthip_plan_destroy(xrfthip_plan* plan);
 int xrfthip_plan_set_window(xrfthip_plan* plan, int axis, const double* h_window, int64_t n);
 /* h_phase: n interleaved (re,im) doubles indexed by UNSHIFTED frequency index: exp(-i 2 pi f_k lag)
  * (for CROSS: the net factor phase0 * conj(phase1)).  With XRFTHIP_PHASE_IN (inverse transforms) the table multiplies
- * the INPUT and is indexed by source position; a C2R_X plan then takes nx/2 + 1 entries on axis 1.  NULL clears. */
+ * the INPUT and is indexed by source position; a C2R_X plan then takes nx/2 + 1 entries on axis 1.  NULL clears.
+ * An XRFTHIP_HERM_FIELD plan: axis 0, 1, 2 = t, herm_ny, herm_nx (see xrfthip_desc.herm_ny); axis 2 is XRFTHIP_BAD_ARG on every other plan. */
 int xrfthip_plan_set_phase(xrfthip_plan* plan, int axis, const double* h_phase, int64_t n);
 /* h_binmap: [ny][nx_out] int32 bin codes indexed by UNSHIFTED frequency indices (nx_out = nx, or nx/2+1 with
  * HALF_X); negative = not binned.  The host computes it with the reference's float64 pd.cut expression.

@@ -24,6 +24,7 @@ UNSUPPORTED_LENGTH = -2
 AXIS_Y = 0x2000  # transform y of [batch][ny][nx] in place (a middle or first axis of the array), no transposed copy
 FLIP0_Y, FLIP0_X = 0x4000, 0x8000  # cross spectra: flip field 0 (FLIP_Y / FLIP_X then flip field 1)
 HALF_Y = 0x10000  # inner / mid layouts (ABI 0.1.6): real_dim along the FIRST of the two transform axes (ny / 2 + 1 rows out)
+HERM_FIELD = 0x20000  # herm_ny / herm_nx descriptors: the last pass writes the complex field F itself (out_mode COMPLEX), with three output-phase tables (axis 0, 1, 2)
 # xrfthip_kernel_kind (xrfthip_plan_kernel_info)
 K_GENERIC, K_FASTY, K_FASTM, K_FASTN, K_FASTM_Y, K_FASTM_X, K_FASTG_Y, K_FASTG_ROWS, K_FASTG, K_FASTS, K_FASTR, K_COMPOSITE, K_FASTH = range(13)
 
@@ -60,7 +61,7 @@ class Desc(C.Structure):
         ("in_stride_y", C.c_int64),      # elements between the rows of one slab of the input (0 = nx): a box of a larger field read where it lies
         ("in_stride_batch", C.c_int64),  # elements between its slabs (0 = ny * nx); trailing-axes layout only, strides in multiples of 16 bytes
         ("herm_ny", C.c_int64),  # > 0 (both): the columns of an AXIS_Y plan are the half spectrum of a real herm_ny x herm_nx grid -- the last pass of a
-        ("herm_nx", C.c_int64),  # three-axis power / cross spectrum: [batch][nt][herm_ny][herm_nx/2 + 1] complex in, the full [batch][nt][herm_ny][herm_nx] result out
+        ("herm_nx", C.c_int64),  # three-axis power / cross spectrum or (HERM_FIELD) transform: [batch][nt][herm_ny][herm_nx/2 + 1] complex in, the full [batch][nt][herm_ny][herm_nx] result out
     ]
 
 

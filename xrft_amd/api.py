@@ -1007,9 +1007,88 @@ def _nd_scale(da, dims, window, scaling, window_correction, spacings):
     return scale
 
 
-# power_spectrum / cross_spectrum over the trailing THREE axes of real data take the fused route (_spectrum_3d_fused); False: the composition of _fft_nd stages
-# and the elementwise tail, as before round 9 -- the tests and scripts/bench_three_axes.py compare the two on one build
+# power_spectrum / cross_spectrum and fft / dft over the trailing THREE axes of real data take the fused routes (_spectrum_3d_fused, _fft_3d_fused); False: the
+# composition of _fft_nd stages (and the elementwise tail), as before round 9 -- the tests and scripts/bench_three_axes.py compare the two on one build
 _FUSE_THREE_AXES = True
+
+
+def _real_dtype(data):
+    """float32 / float64 as it lies (anything else -- integers, float16, complex -- keeps the composition and its conversions)."""
+    dt = data.dtype if isinstance(data, torch.Tensor) else {"float32": torch.float32, "float64": torch.float64}.get(np.asarray(data).dtype.name)
+    return dt if dt in (torch.float32, torch.float64) else None
+
+
+def _three_axis_info(a, dims, spacing_tol, shift, window, true_phase, prefix):
+    """Per transform dim of a three-axis call what the composition's two stages derive (the last two listed dims, then the first): spacing, lag, a descending
+    coordinate, the window vector, the output coordinate and its name."""
+    ca = _analyze(a, spacing_tol, dims[-2:], None, shift, None, window, true_phase, False, prefix, None)
+    cb = _analyze(a, spacing_tol, [dims[0]], None, shift, None, window, true_phase, False, prefix, None)
+    info = {}
+    for c in (ca, cb):
+        for i, d in enumerate(c.dim):
+            info[d] = dict(dx=c.delta_x[i], lag=c.lag_x[i], rev=c.reversed[i], win=None if c.windows is None else c.windows[i],
+                           name=c.swap[d], coord=c.new_coords[c.swap[d]])
+    return info
+
+
+def _three_axis_labels(da, dims, order, info, true_phase, out):
+    """The composition's labels on the fused result: dims, the stages' coordinates in their order, spacing and (true_phase) direct_lag."""
+    final = [info[d]["name"] if d in info else d for d in da.dims]
+    coords = {k: v._clone(k) for k, v in da.coords.items() if k not in dims}
+    for d in order:
+        cv = info[d]["coord"]
+        attrs = dict(cv.attrs)
+        if true_phase:
+            attrs["direct_lag"] = info[d]["lag"]  # xrft.py:469
+        coords[info[d]["name"]] = Coordinate(cv.dims, cv.values, attrs, info[d]["name"])
+    return DataArray(out.reshape(tuple(da.shape)), final, coords, None, None)
+
+
+def _fft_3d_fused(da, dims, spacing_tol, shift, detrend_, window, true_phase, true_amplitude, chunks_to_segments, prefix):
+    """The frequency-wavenumber transform -- ``fft(da, dim=["time", "y", "x"])`` -- of real float32 / float64 data whose three transform dims are the trailing three
+    axes (any order in ``dim``): detrend as before, the two-axis plan over the last two axes in memory with the HALF spectrum as its complex output, then ONE plan
+    (xrfthip_desc.herm_ny / herm_nx with XRFTHIP_HERM_FIELD, csrc/fasth.h) that transforms along the first of the three and writes the full shifted complex result,
+    the redundant half as the conjugate of the Hermitian twin -- each element times the true-phase factors of its OWN indices (the twin of a sample at a Nyquist
+    index does not carry the conjugate factor).  20 bytes per point behind the detrend instead of the composition's 28, half its peak intermediate memory.
+    Returns None where the route does not apply (the caller composes as before): a descending coordinate (FLIP), a length either stage does not take."""
+    if len(dims) != 3 or len(da.dims) < 3 or set(dims) != set(da.dims[-3:]) or chunks_to_segments or detrend_ not in (None, "constant", "linear"):
+        return None
+    pt, py, px = da.dims[-3:]
+    nt, ny, nx = (da.sizes[d] for d in (pt, py, px))
+    nxh = nx // 2 + 1
+    if min(nt, ny, nx) < 2 or ny * nx > (1 << 31) - 1 or nt * ny * nxh > (1 << 31) - 1 or ny * nxh > (1 << 30) or _real_dtype(da.data) is None:
+        return None
+    order = [dims[-2], dims[-1], dims[0]]  # the stages of the composition: their labels, in their order
+    info = _three_axis_info(da, dims, spacing_tol, shift, window, true_phase, prefix)
+    if any(v["rev"] for v in info.values()):
+        return None
+    scale = math.prod([info[d]["dx"] for d in order]) if true_amplitude else 1.0  # xrft.py:471-472
+    ph = {d: None for d in dims}
+    if true_phase:  # xrft.py:462-469 -- indexed by unshifted frequency, as _flags_tables builds them
+        for d in dims:  # (memoised: the same table object on every call of a shape, identified by its key where the plan is looked up)
+            n, dx, lag = da.sizes[d], info[d]["dx"], info[d]["lag"]
+            ph[d] = _memoised(("phase3", int(n), float(dx), float(lag)), lambda: _ro(np.exp(-1j * 2.0 * np.pi * np.fft.fftfreq(n, dx) * lag)))
+    cur = da if detrend_ is None else from_any(detrend(da, dims, detrend_))
+    t = _to_device(cur.data).contiguous()
+    batch = t.numel() // (nt * ny * nx)
+    ish = (_lib.ISHIFT_Y | _lib.ISHIFT_X) if true_phase else 0  # (the reference ifftshifts the windowed input, xrft.py:436-441)
+    kw1 = dict(ndim=2, batch=batch * nt, ny=ny, nx=nx, dtype=t.dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=_lib.HALF_X | ish, scale=1.0,
+               window_y=info[py]["win"], window_x=info[px]["win"], phase_y=None, phase_x=None)
+    kw2 = dict(ndim=2, batch=batch, ny=nt, nx=ny * nxh, dtype=engine._CPLX_OF[t.dtype], out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE,
+               flags=_lib.AXIS_Y | _lib.HERM_FIELD | ((_lib.SHIFT_Y | _lib.SHIFT_X) if shift else 0) | (_lib.ISHIFT_Y if true_phase else 0),
+               scale=float(scale), window_y=info[pt]["win"], window_x=None, phase_y=ph[pt], phase_x=ph[py], phase_hx=ph[px], herm_ny=ny, herm_nx=nx)
+    try:
+        plan1 = _get_plan(**kw1)
+        plan2 = _get_plan(**kw2)  # (the newest plan of the call: describe() shows [fasth])
+    except _lib.XrftHipError as e:
+        if e.status != _lib.UNSUPPORTED_LENGTH:
+            raise
+        return None
+    h, _ = plan1.execute(t)
+    del t, cur  # (a detrended copy is not alive beside the result)
+    out, _ = plan2.execute(h.reshape(batch, nt, ny * nxh))
+    del h
+    return _three_axis_labels(da, dims, order, info, true_phase, out)
 
 
 def _spectrum_3d_fused(da, da2, dims, scaling, window_correction, true_phase, kw):
@@ -1029,23 +1108,12 @@ def _spectrum_3d_fused(da, da2, dims, scaling, window_correction, true_phase, kw
     nxh = nx // 2 + 1
     if min(nt, ny, nx) < 2 or ny * nx > (1 << 31) - 1 or nt * ny * nxh > (1 << 31) - 1 or ny * nxh > (1 << 30):
         return None
-    def real_dtype(data):  # float32 / float64 as it lies (anything else -- integers, float16, complex -- keeps the composition and its conversions)
-        dt = data.dtype if isinstance(data, torch.Tensor) else {"float32": torch.float32, "float64": torch.float64}.get(np.asarray(data).dtype.name)
-        return dt if dt in (torch.float32, torch.float64) else None
-
-    if real_dtype(da.data) is None or (da2 is not None and real_dtype(da2.data) != real_dtype(da.data)):
+    if _real_dtype(da.data) is None or (da2 is not None and _real_dtype(da2.data) != _real_dtype(da.data)):
         return None
     order = [dims[-2], dims[-1], dims[0]]  # the stages of the composition: their labels, in their order
 
     def analyze(a):
-        ca = _analyze(a, kw["spacing_tol"], dims[-2:], None, kw["shift"], None, kw["window"], true_phase, False, kw["prefix"], None)
-        cb = _analyze(a, kw["spacing_tol"], [dims[0]], None, kw["shift"], None, kw["window"], true_phase, False, kw["prefix"], None)
-        info = {}
-        for c in (ca, cb):
-            for i, d in enumerate(c.dim):
-                info[d] = dict(dx=c.delta_x[i], lag=c.lag_x[i], rev=c.reversed[i], win=None if c.windows is None else c.windows[i],
-                               name=c.swap[d], coord=c.new_coords[c.swap[d]])
-        return info
+        return _three_axis_info(a, dims, kw["spacing_tol"], kw["shift"], kw["window"], true_phase, kw["prefix"])
 
     info = analyze(da)
     if any(v["rev"] for v in info.values()) or any("spacing" not in v["coord"].attrs for v in info.values()):
@@ -1080,15 +1148,7 @@ def _spectrum_3d_fused(da, da2, dims, scaling, window_correction, true_phase, kw
     h2 = None if t2 is None else plan1.execute(t2)[0]
     out, _ = plan2.execute(h.reshape(batch, nt, ny * nxh), None if h2 is None else h2.reshape(batch, nt, ny * nxh))
     del h, h2
-    final = [info[d]["name"] if d in info else d for d in da.dims]
-    coords = {k: v._clone(k) for k, v in da.coords.items() if k not in dims}
-    for d in order:
-        cv = info[d]["coord"]
-        attrs = dict(cv.attrs)
-        if true_phase:
-            attrs["direct_lag"] = info[d]["lag"]  # xrft.py:469
-        coords[info[d]["name"]] = Coordinate(cv.dims, cv.values, attrs, info[d]["name"])
-    return DataArray(out.reshape(tuple(da.shape)), final, coords, None, None)
+    return _three_axis_labels(da, dims, order, info, true_phase, out)
 
 
 def _spectrum_nd(da, da2, dims, real_dim, scaling, window_correction, true_phase, kwargs, one_at_a_time=False):
@@ -1154,6 +1214,10 @@ def fft(da, spacing_tol=1e-3, dim=None, real_dim=None, shift=True, detrend=None,
     da = from_any(da)
     nd = _nd_dims(da, dim, real_dim, real)
     if nd is not None:
+        if _FUSE_THREE_AXES and real_dim is None and real is None:
+            fused = _fft_3d_fused(da, nd, spacing_tol, shift, detrend, window, true_phase, true_amplitude, chunks_to_segments, prefix)
+            if fused is not None:
+                return to_like(fused, src)
         return to_like(_fft_nd(da, nd, spacing_tol, real_dim if real is None else real, shift, detrend, window,
                                true_phase, true_amplitude, chunks_to_segments, prefix), src)
     c = _analyze(da, spacing_tol, dim, real_dim, shift, detrend, window, true_phase, chunks_to_segments, prefix, real)

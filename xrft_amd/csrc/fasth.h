@@ -17,6 +17,11 @@
 //          runs, so eight lanes write a whole 128-byte piece of a row with one 16-byte non-temporal store each (the result is read much later, by the
 //          caller); where a piece crosses a row end, the fftshift seam or the range of the twins, its samples are stored one by one.
 // No sums, no atomics: repeated calls return identical bits.
+//
+// FIELD: the transform those spectra are made of (xrft.fft(da, dim=["time", "y", "x"])): V = F scale [phase_t[kt] phase_y[ky] phase_x[kx]] (complex T), the twin
+// conj(F) scale times the phase factors of its DESTINATION indices (-kt, -ky, nx - kx) -- fftfreq gives the index n / 2 of an even n the frequency -1 / (2 dx) for
+// itself and for its own twin, so the rows kt = nt / 2 and ky = ny / 2 of the twins do not carry the conjugate factor (the twin columns never include kx = 0 or
+// nx / 2: along x phase[nx - kx] = conj(phase[kx]) holds for them).  Without phase tables the twin is the plain conjugate, bit for bit.
 #pragma once
 #include "fastg.h"
 
@@ -25,7 +30,7 @@ namespace xrft {
 struct FastH {
     const void* in;    // H[batch][nt][ny][nxh] complex T
     const void* in_b;  // CROSS: the second field's half spectrum (same layout); the result is F(in) conj F(in_b) (xrft.py:825)
-    void* out;         // [batch][nt][ny][nx] real T (POWER) or complex T (CROSS)
+    void* out;         // [batch][nt][ny][nx] real T (POWER) or complex T (CROSS, FIELD)
     long long nunits;  // batch x column blocks
     int nt, ny, nx, nxh, ncol, nblk;  // ncol = ny nxh columns of a batch entry; nblk = ceil(ncol / G)
     int G, lg, lch;    // columns per workgroup (a power of two = 128 bytes of an output row), its log2; log2 of the 16-byte pieces of a block's row
@@ -36,10 +41,13 @@ struct FastH {
     int ishift_in;     // tile row i is source row i + ishift_in (mod nt)
     int shift_t, shift_y, shift_x;  // 0 or n / 2 (xrft.py:446-447)
     double scale;
+    const void *ph_t, *ph_y, *ph_x;  // FIELD: the output phase factors by UNSHIFTED index, complex T [nt], [ny], [nx] (the full x axis: the twins lie above nx / 2); all three or none
 };
 
-template <typename T, bool CROSS> struct FastHOut { typedef T type; };
-template <typename T> struct FastHOut<T, true> { typedef C2<T> type; };
+enum { kFastHPower = 0, kFastHCross = 1, kFastHField = 2 };  // the output forms: |F|^2, F0 conj(F1), F
+
+template <typename T, int MODE> struct FastHOut { typedef C2<T> type; };
+template <typename T> struct FastHOut<T, kFastHPower> { typedef T type; };
 
 // BYTES (4 | 8 | 16) at dst, aligned like T only: non-temporal.  (A 16-byte store at 4-byte alignment is one global_store_dwordx4: gfx950 takes unaligned vector
 // accesses to global memory.)
@@ -62,18 +70,20 @@ __device__ __forceinline__ void fasth_store_nt(void* dst, const void* src) {
 #endif
 }
 
-template <typename T, bool CROSS>
-__device__ __forceinline__ typename FastHOut<T, CROSS>::type fasth_value(C2<T> a, C2<T> b, T sc) {
-    if constexpr (CROSS) { const C2<T> v = cmulc(a, b); return mk<T>(v.re * sc, v.im * sc); }  // F0 conj(F1)
+template <typename T, int MODE>
+__device__ __forceinline__ typename FastHOut<T, MODE>::type fasth_value(C2<T> a, C2<T> b, T sc) {
+    if constexpr (MODE == kFastHCross) { const C2<T> v = cmulc(a, b); return mk<T>(v.re * sc, v.im * sc); }  // F0 conj(F1)
+    else if constexpr (MODE == kFastHField) return mk<T>(a.re * sc, a.im * sc);                           // F
     else return (a.re * a.re + a.im * a.im) * sc;
 }
 template <typename T> __device__ __forceinline__ T fasth_twin(T v) { return v; }                   // |F|^2 of the twin
 template <typename T> __device__ __forceinline__ C2<T> fasth_twin(C2<T> v) { return cconj(v); }  // F0 conj(F1) of the twin: the conjugate, like a spectrum's
 
-template <typename T, bool CROSS>
+template <typename T, int MODE>
 __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fasth_kernel(FastH p) {
     typedef C2<T> CT;
-    typedef typename FastHOut<T, CROSS>::type OT;
+    typedef typename FastHOut<T, MODE>::type OT;
+    constexpr bool CROSS = MODE == kFastHCross, FIELD = MODE == kFastHField;
     constexpr int NF = CROSS ? 2 : 1, VW = 16 / (int)sizeof(OT);  // fields; samples of a 16-byte piece
     XRFT_DYN_SMEM(smem_raw);
     CT* tile = reinterpret_cast<CT*>(smem_raw);
@@ -133,7 +143,25 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fasth_kernel(Fa
             const CT* src = tile + (int)revt[kt] * GS + ch * VW;
             OT v[VW];
 #pragma unroll
-            for (int j = 0; j < VW; ++j) v[j] = fasth_value<T, CROSS>(src[j], src[(CROSS ? G : 0) + j], sc);
+            for (int j = 0; j < VW; ++j) v[j] = fasth_value<T, MODE>(src[j], src[(CROSS ? G : 0) + j], sc);
+            [[maybe_unused]] OT w[VW];  // FIELD: the twins' values
+            if constexpr (FIELD) {
+                const CT* __restrict__ pht = reinterpret_cast<const CT*>(p.ph_t);
+                const CT* __restrict__ phy = reinterpret_cast<const CT*>(p.ph_y);
+                const CT* __restrict__ phx = reinterpret_cast<const CT*>(p.ph_x);
+                int kyj = ky, kxj = kx;
+#pragma unroll
+                for (int j = 0; j < VW; ++j) {
+                    w[j] = cconj(v[j]);
+                    if (pht && j < nv) {  // (the tables: all three or none)
+                        if (kxj >= nxh) { kxj -= nxh; ++kyj; }
+                        if (kxj >= 1 && kxj <= nx - nxh)  // the twin carries the factors of where IT lies: (-kt, -ky, nx - kx)
+                            w[j] = cmul(w[j], cmul(cmul(pht[kt ? nt - kt : 0], phy[kyj ? ny - kyj : 0]), phx[nx - kxj]));
+                        v[j] = cmul(v[j], cmul(cmul(pht[kt], phy[kyj]), phx[kxj]));
+                        ++kxj;
+                    }
+                }
+            }
             int ot = kt + p.shift_t; if (ot >= nt) ot -= nt;
             int mt = (kt ? nt - kt : 0) + p.shift_t; if (mt >= nt) mt -= nt;  // the twin's row along t
             const size_t rowd = ((size_t)b * nt + ot) * ny, rowm = ((size_t)b * nt + mt) * ny;
@@ -168,7 +196,7 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fasth_kernel(Fa
                     int my = (ky ? ny - ky : 0) + p.shift_y; if (my >= ny) my -= ny;
                     OT r[VW];
 #pragma unroll
-                    for (int j = 0; j < VW; ++j) r[j] = fasth_twin(v[VW - 1 - j]);
+                    for (int j = 0; j < VW; ++j) { if constexpr (FIELD) r[j] = w[VW - 1 - j]; else r[j] = fasth_twin(v[VW - 1 - j]); }
                     fasth_store_nt<T, 16>(outp + (rowm + my) * nx + lo, r);
                     whole = true;
                 }
@@ -182,7 +210,8 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fasth_kernel(Fa
                         if (kxj >= 1 && kxj <= nx - nxh) {
                             int ox = nx - kxj + p.shift_x; if (ox >= nx) ox -= nx;
                             int my = (kyj ? ny - kyj : 0) + p.shift_y; if (my >= ny) my -= ny;
-                            const OT tw = fasth_twin(v[j]);
+                            OT tw;
+                            if constexpr (FIELD) tw = w[j]; else tw = fasth_twin(v[j]);
                             fasth_store_nt<T, (int)sizeof(OT)>(outp + (rowm + my) * nx + ox, &tw);
                         }
                         ++kxj;

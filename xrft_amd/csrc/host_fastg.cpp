@@ -377,7 +377,7 @@ static int run_fastgy(const xrfthip_plan* P, const ExecArgs& a) {
 
 // FastH: the last pass of a three-axis power / cross spectrum (xrfthip_desc.herm_ny / herm_nx; fasth.h).  G columns of the half spectrum per workgroup = 128 bytes of
 // an output row (32 float32 powers, 16 float64 powers or complex64 products, 8 complex128 products): in every precision and mode the tile is 256 nt bytes, so any
-// smooth nt up to ~600 fits.  A descriptor with these fields is served here or not at all: the caller composes the stages (XRFTHIP_UNSUPPORTED_LENGTH).
+// smooth nt up to ~600 fits; the field form (XRFTHIP_HERM_FIELD: the complex transform itself, 16 complex64 / 8 complex128 columns) holds one field's columns, 128 nt bytes.  A descriptor with these fields is served here or not at all: the caller composes the stages (XRFTHIP_UNSUPPORTED_LENGTH).
 int try_fasth(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
     if (!herm_plan(P)) return kDeclined;
@@ -385,8 +385,8 @@ int try_fasth(xrfthip_plan* P) {
     std::vector<int> rt;
     if (!fastg_factor(d.ny, rt) || (int)rt.size() > kFastGMaxPasses) return XRFTHIP_UNSUPPORTED_LENGTH;  // (Bluestein / Rader along t: not carried over)
     for (int r : rt) if (r > 16) return XRFTHIP_UNSUPPORTED_LENGTH;
-    const bool cross = d.out_mode == XRFTHIP_OUT_CROSS;
-    const int G = (int)(128 / (cross ? P->csize : P->rsize));
+    const bool cross = d.out_mode == XRFTHIP_OUT_CROSS, cout = cross || d.out_mode == XRFTHIP_OUT_COMPLEX;  // (cout: complex output, cross or field)
+    const int G = (int)(128 / (cout ? P->csize : P->rsize));
     const long long pts = (long long)G * (cross ? 2 : 1) * d.ny;  // threads by the points of the tile, as fastgy_try
     const int thr = pts <= 1024 ? 64 : pts <= 2048 ? 128 : 256;
     const size_t lds = (((size_t)d.ny * G * (cross ? 2 : 1) * P->csize + 15) & ~(size_t)15) + (size_t)d.ny * (P->csize + P->rsize + 2) + 16;
@@ -399,15 +399,30 @@ int try_fasth(xrfthip_plan* P) {
     return rc;
 }
 
+// XRFTHIP_HERM_FIELD: the three output-phase tables in the plan's precision -- all three (ones where an axis has none) or none (FamilyOps::finalize)
+static int fasth_phase_tables(xrfthip_plan* P) {
+    if (!herm_field_plan(P)) return XRFTHIP_OK;
+    const long long n3[3] = {P->d.ny, P->d.herm_ny, P->d.herm_nx};
+    const bool any = !P->h_host_ph[0].empty() || !P->h_host_ph[1].empty() || !P->h_host_ph[2].empty();
+    for (int ax = 0; ax < 3; ++ax) {
+        if (!any) { P->h_ph[ax].clear(); continue; }
+        std::vector<double> t = P->h_host_ph[ax];
+        if (t.empty()) { t.assign((size_t)(2 * n3[ax]), 0.0); for (long long k = 0; k < n3[ax]; ++k) t[(size_t)(2 * k)] = 1.0; }
+        const int rc = upload_real_table(P, P->h_ph[ax], t.data(), n3[ax], 1);
+        if (rc) return rc;
+    }
+    return XRFTHIP_OK;
+}
+
 static int run_fasth(const xrfthip_plan* P, const ExecArgs& a) {
     const xrfthip_desc& d = P->d;
     hipStream_t st = a.stream;
-    const bool cross = d.out_mode == XRFTHIP_OUT_CROSS;
+    const bool cross = d.out_mode == XRFTHIP_OUT_CROSS, field = d.out_mode == XRFTHIP_OUT_COMPLEX;
     FastH p{};
     p.in = a.in0; p.in_b = a.in1; p.out = a.out;
     p.nt = (int)d.ny; p.ny = (int)d.herm_ny; p.nx = (int)d.herm_nx; p.nxh = (int)(d.herm_nx / 2 + 1); p.ncol = (int)d.nx;
     p.G = P->h_G; p.lg = ilog2i(P->h_G);
-    p.lch = p.lg - ilog2i((int)(16 / (cross ? P->csize : P->rsize)));
+    p.lch = p.lg - ilog2i((int)(16 / ((cross || field) ? P->csize : P->rsize)));
     p.nblk = (p.ncol + p.G - 1) / p.G;
     p.nunits = d.batch * p.nblk;
     p.nrt = (int)P->g_ry.size();
@@ -419,10 +434,12 @@ static int run_fasth(const xrfthip_plan* P, const ExecArgs& a) {
     p.shift_y = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.herm_ny / 2) : 0;  // (SHIFT_X of a herm plan: the two Hermitian axes)
     p.shift_x = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.herm_nx / 2) : 0;
     p.scale = d.scale;
+    if (field && P->h_ph[0].p) { p.ph_t = P->h_ph[0].p; p.ph_y = P->h_ph[1].p; p.ph_x = P->h_ph[2].p; }
     const dim3 grid((unsigned)std::min<long long>(p.nunits, 0x7fffffffLL)), blk((unsigned)P->h_thr);
     xrfthip_plan::ProfRec* rec = prof_begin(P, "fasth_last", st);
-#define GH_(TT) do { if (cross) { auto k = &fasth_kernel<TT, true>; XRFT_LAUNCH(k, grid, blk, P->h_lds, st, p); } \
-                     else { auto k = &fasth_kernel<TT, false>; XRFT_LAUNCH(k, grid, blk, P->h_lds, st, p); } } while (0)
+#define GH_(TT) do { if (cross) { auto k = &fasth_kernel<TT, kFastHCross>; XRFT_LAUNCH(k, grid, blk, P->h_lds, st, p); } \
+                     else if (field) { auto k = &fasth_kernel<TT, kFastHField>; XRFT_LAUNCH(k, grid, blk, P->h_lds, st, p); } \
+                     else { auto k = &fasth_kernel<TT, kFastHPower>; XRFT_LAUNCH(k, grid, blk, P->h_lds, st, p); } } while (0)
     if (P->dbl) GH_(double); else GH_(float);
 #undef GH_
     prof_end(rec, st);
@@ -592,11 +609,12 @@ static void describe_fasth(const xrfthip_plan* plan, std::string& s, const char*
     const xrfthip_desc& d = plan->d;
     std::string rts;
     for (int r : plan->g_ry) rts += (rts.empty() ? "" : "x") + std::to_string(r);
-    const bool cross = plan->d.out_mode == XRFTHIP_OUT_CROSS;
-    appendf(s, "  [fasth] the last pass of a three-axis %s spectrum: %d thr, %d columns of the half spectrum [%lld][%lld][%lld + 1] per workgroup%s, the radices from the plan "
+    const bool cross = plan->d.out_mode == XRFTHIP_OUT_CROSS, field = plan->d.out_mode == XRFTHIP_OUT_COMPLEX;
+    appendf(s, "  [fasth] the last pass of a three-axis %s: %d thr, %d columns of the half spectrum [%lld][%lld][%lld + 1] per workgroup%s, the radices from the plan "
                "(t: %lld = %s in LDS), lds=%zuB: window + transform along t + %s, ",
-            cross ? "cross" : "power", plan->h_thr, plan->h_G, (long long)d.ny, (long long)d.herm_ny, (long long)d.herm_nx / 2, cross ? " of each of the two fields" : "",
-            (long long)d.ny, rts.c_str(), plan->h_lds, cross ? "F0 conj(F1)" : "|F|^2");
+            cross ? "cross spectrum" : field ? "transform (the complex field)" : "power spectrum", plan->h_thr, plan->h_G, (long long)d.ny, (long long)d.herm_ny, (long long)d.herm_nx / 2,
+            cross ? " of each of the two fields" : "", (long long)d.ny, rts.c_str(), plan->h_lds,
+            cross ? "F0 conj(F1)" : !field ? "|F|^2" : plan->h_ph[0].p ? "F x the phase factors of each element's own indices" : "F");
     appendf(s, "every sample and its Hermitian twin stored as 16-byte pieces of 128-byte runs of the full [%lld][%lld][%lld] result, non-temporal\n",
             (long long)d.ny, (long long)d.herm_ny, (long long)d.herm_nx);
 }
@@ -614,7 +632,7 @@ static bool fastgy_uses_bluestein(const xrfthip_plan* P) { return P->gy_blue_m >
 #ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
 const FamilyOps kOpsFastG = {Family::FastG, run_fastg, describe_fastg, info_fastg, finalize_fastg, layout_one_pass, fastg_build_iso, nullptr, true, fastg_strided_if, true};  // (any bin map: per-bin position lists)
 const FamilyOps kOpsFastGY = {Family::FastGY, run_fastgy, describe_fastgy, info_fastgy, fast_phase_tables, layout_one_pass, nullptr, fastgy_uses_bluestein, false, nullptr, true};
-const FamilyOps kOpsFastH = {Family::FastH, run_fasth, describe_fasth, info_fasth, nullptr, layout_one_pass};  // (no phase table, no other family to hand the plan to)
+const FamilyOps kOpsFastH = {Family::FastH, run_fasth, describe_fasth, info_fasth, fasth_phase_tables, layout_one_pass};  // (phase tables of the field form only; no other family to hand the plan to)
 #endif
 
 template int fastn_rader_tables<float>(xrfthip_plan*);
@@ -634,6 +652,7 @@ void set_attrs_fastg() {
     SETF((fastgy_kernel<float, 0, 1>)); SETF((fastgy_kernel<float, 1, 1>)); SETF((fastgy_kernel<double, 0, 1>)); SETF((fastgy_kernel<double, 1, 1>));
     SETF((fastgy_kernel<float, 0, 2>)); SETF((fastgy_kernel<float, 1, 2>)); SETF((fastgy_kernel<double, 0, 2>)); SETF((fastgy_kernel<double, 1, 2>));
     SETF((fastgy_kernel<float, 0, 3>)); SETF((fastgy_kernel<float, 1, 3>)); SETF((fastgy_kernel<double, 0, 3>)); SETF((fastgy_kernel<double, 1, 3>));
-    SETF((fasth_kernel<float, false>)); SETF((fasth_kernel<float, true>)); SETF((fasth_kernel<double, false>)); SETF((fasth_kernel<double, true>));
+    SETF((fasth_kernel<float, kFastHPower>)); SETF((fasth_kernel<float, kFastHCross>)); SETF((fasth_kernel<double, kFastHPower>)); SETF((fasth_kernel<double, kFastHCross>));
+    SETF((fasth_kernel<float, kFastHField>)); SETF((fasth_kernel<double, kFastHField>));
 #undef SETF
 }

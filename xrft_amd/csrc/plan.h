@@ -343,7 +343,7 @@ enum class Family {
     FastY1D,         // ... as the two steps of a four-step transform of one long real sequence
     FastM,           // the two y-first passes, table lengths (fastm.h)
     FastN,           // ... with the lengths as data (fastn.h; either pass may still be a table kernel)
-    FastH,           // xrfthip_desc.herm_ny / herm_nx, the last pass of a three-axis spectrum: half spectrum in, full power / cross result out (fasth.h)
+    FastH,           // xrfthip_desc.herm_ny / herm_nx, the last pass of a three-axis spectrum / transform: half spectrum in, full power / cross / field result out (fasth.h)
 };
 constexpr int kFamilyCount = (int)Family::FastH + 1;  // (FastH is the last value: a value added behind it moves this line, and the table of rows with it)
 constexpr int kDeclined = 1;  // a try_* that does not take the descriptor (XRFTHIP_OK: taken, its tables built; < 0: an error)
@@ -423,6 +423,8 @@ struct xrfthip_plan {
     // radices, twiddles and digit reversal of nt: g_ry, g_twy, g_revy, g_hrevy
     int h_G = 0, h_thr = 0;
     size_t h_lds = 0;
+    std::vector<double> h_host_ph[3];  // XRFTHIP_HERM_FIELD: the output phase along t, herm_ny, herm_nx as handed to xrfthip_plan_set_phase (empty = none) ...
+    DevBuf h_ph[3];                    // ... and in the plan's precision on the device: all three (ones for an axis without a table) or none
     // FastS: ONE pass for a small real float32 slab that fits the registers of a CU: 256 x 256 power spectra (fasts.h)
     DevBuf tw_sy, tw_sx, s_tfirst;
     long long tune_sstagger = 0;  // XRFTHIP_FASTS_STAGGER: classes << 8 | steps of 3.4 us between the classes of a resident set of slab workgroups
@@ -568,6 +570,7 @@ inline bool fastm_pipeline(const xrfthip_plan* P) { return family_ops(P->family)
 inline bool two_pass_y(const xrfthip_plan* P) { return family_ops(P->family).two_pass_y; }
 inline bool inner_layout(const xrfthip_plan* P) { return family_ops(P->family).inner_layout; }
 inline bool dbl_phase_tables(const xrfthip_plan* P) { return P->dbl && family_ops(P->family).dbl_tables; }
+inline bool herm_field_plan(const xrfthip_plan* P) { return P && P->d.herm_ny > 0 && (P->d.flags & XRFTHIP_HERM_FIELD); }  // (... whose last pass writes the complex field)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's
 // input take them: pass 1 of the two-pass families, the load of the one-pass families.  The intermediate and the output are dense.

@@ -890,11 +890,13 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if ((d.flags & (XRFTHIP_FLIP0_Y | XRFTHIP_FLIP0_X)) && d.out_mode != XRFTHIP_OUT_CROSS && d.out_mode != XRFTHIP_OUT_PHASE) return XRFTHIP_BAD_ARG;
     if ((d.flags & XRFTHIP_FLIP0_Y) && d.ndim == 1) return XRFTHIP_BAD_ARG;
     // herm_ny / herm_nx: the columns of an AXIS_Y plan are the half spectrum of a real herm_ny x herm_nx grid (the last pass of a three-axis spectrum, fasth.h)
-    const bool herm = d.herm_ny != 0 || d.herm_nx != 0;
+    const bool herm = d.herm_ny != 0 || d.herm_nx != 0, field = (d.flags & XRFTHIP_HERM_FIELD) != 0;  // (field: the last pass writes F itself)
+    if (field && !herm) return XRFTHIP_BAD_ARG;
     if (herm) {
         if (d.herm_ny < 1 || d.herm_nx < 1 || d.herm_nx > (1LL << 30) || d.herm_ny > (1LL << 30)) return XRFTHIP_BAD_ARG;
-        if (!(d.flags & XRFTHIP_AXIS_Y) || (d.flags & ~(XRFTHIP_AXIS_Y | XRFTHIP_SHIFT_Y | XRFTHIP_ISHIFT_Y | XRFTHIP_SHIFT_X))) return XRFTHIP_BAD_ARG;
-        if (d.ndim != 2 || !cplx_in || (d.out_mode != XRFTHIP_OUT_POWER && d.out_mode != XRFTHIP_OUT_CROSS) || d.detrend) return XRFTHIP_BAD_ARG;
+        if (!(d.flags & XRFTHIP_AXIS_Y) || (d.flags & ~(XRFTHIP_AXIS_Y | XRFTHIP_SHIFT_Y | XRFTHIP_ISHIFT_Y | XRFTHIP_SHIFT_X | XRFTHIP_HERM_FIELD))) return XRFTHIP_BAD_ARG;
+        const bool mode_ok = field ? d.out_mode == XRFTHIP_OUT_COMPLEX : (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_CROSS);
+        if (d.ndim != 2 || !cplx_in || !mode_ok || d.detrend) return XRFTHIP_BAD_ARG;
         if (d.nx != d.herm_ny * (d.herm_nx / 2 + 1) || d.inner > 1 || d.mid > 1 || d.in_stride_y || d.in_stride_batch) return XRFTHIP_BAD_ARG;
     }
     if ((d.flags & XRFTHIP_AXIS_Y) && (d.ndim != 2 || (d.flags & XRFTHIP_FLIP0_X) || (d.flags & ((herm ? 0u : XRFTHIP_SHIFT_X) | XRFTHIP_ISHIFT_X | XRFTHIP_FLIP_X |
@@ -985,6 +987,13 @@ int xrfthip_plan_set_window(xrfthip_plan* plan, int axis, const double* h_window
 }
 
 int xrfthip_plan_set_phase(xrfthip_plan* plan, int axis, const double* h_phase, int64_t n) {
+    if (herm_field_plan(plan)) {  // the three output-phase tables of the field form: t, herm_ny, herm_nx (fasth.h carries the twins' own factors)
+        if (axis < 0 || axis > 2) return XRFTHIP_BAD_ARG;
+        const int64_t want3 = axis == 0 ? plan->d.ny : axis == 1 ? plan->d.herm_ny : plan->d.herm_nx;
+        if (h_phase && n != want3) return XRFTHIP_BAD_ARG;
+        plan->h_host_ph[axis].assign(h_phase ? h_phase : nullptr, h_phase ? h_phase + 2 * n : nullptr);
+        return finalize_plan(plan);
+    }
     if (!plan || axis < 0 || axis > 1 || herm_plan(plan)) return XRFTHIP_BAD_ARG;  // (herm: the twin of a sample at a Nyquist index does not carry the conjugate factor)
     // an input phase of a c2r transform covers the stored half of the x axis only
     const int64_t want = axis == 0 ? plan->d.ny : ((plan->d.flags & XRFTHIP_C2R_X) ? plan->d.nx / 2 + 1 : plan->d.nx);

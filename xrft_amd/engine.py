@@ -40,7 +40,7 @@ class SpectralPlan:
 
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
-                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0):
+                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
@@ -57,7 +57,8 @@ class SpectralPlan:
         self.mid = max(int(mid), 1)      # > 1: (batch, ny, mid, nx, inner): independent elements between the two transform axes
         # input strides in elements (0 = dense): the plan reads a box of a larger array where it lies (xrfthip_desc.in_stride_y / in_stride_batch)
         self.in_stride_y, self.in_stride_batch = int(in_stride_y), int(in_stride_batch)
-        # the last pass of a three-axis spectrum (xrfthip_desc.herm_ny / herm_nx): (batch, nt, herm_ny, herm_nx/2 + 1) complex in, the full (batch, nt, herm_ny, herm_nx) out
+        # the last pass of a three-axis spectrum (xrfthip_desc.herm_ny / herm_nx): (batch, nt, herm_ny, herm_nx/2 + 1) complex in, the full (batch, nt, herm_ny, herm_nx) out;
+        # with HERM_FIELD the complex transform itself (out_mode COMPLEX), whose output-phase tables are phase_y (t), phase_x (herm_ny) and phase_hx (herm_nx, the full axis)
         self.herm_ny, self.herm_nx = int(herm_ny), int(herm_nx)
         if self.herm_ny or self.herm_nx:
             self.nx_out = self.herm_ny * self.herm_nx
@@ -69,7 +70,7 @@ class SpectralPlan:
             if w is not None:
                 w = np.ascontiguousarray(w, dtype=np.float64)
                 _lib.check(self._dll.xrfthip_plan_set_window(self._h, axis, w.ctypes.data_as(C.c_void_p), w.size))
-        for axis, p in ((0, phase_y), (1, phase_x)):
+        for axis, p in ((0, phase_y), (1, phase_x), (2, phase_hx)):
             if p is not None:
                 p = np.ascontiguousarray(p, dtype=np.complex128)
                 _lib.check(self._dll.xrfthip_plan_set_phase(self._h, axis, p.ctypes.data_as(C.c_void_p), p.size))
