@@ -205,6 +205,25 @@ typedef struct xrfthip_desc {
      * bytes.  Without the flag every answer a herm descriptor gets is what it was: out_mode COMPLEX and xrfthip_plan_set_phase stay XRFTHIP_BAD_ARG. */
     int64_t herm_ny;
     int64_t herm_nx;
+    /* The mean over the batch inside the last pass: what the reference's users do with a batch of spectra (xrft.power_spectrum(..., chunks_to_segments=True).mean("x_segment"),
+     * ps.mean(["time", "y_segment", "x_segment"]): the Parseval, chunk and MITgcm notebooks) without the spectra of the single slabs ever reaching memory.
+     *   mean_batch = M > 1   every M consecutive slabs b = o * M + m give ONE output: d_out is [batch / M][ny][nx], real (POWER) or complex (CROSS), its value
+     *                        (1 / M) sum_m of what the plan without the field writes for slab o * M + m; shifts, detrend, windows, `scale` and the phase tables of a
+     *                        cross spectrum behave as on that plan.  0 or 1 = off; 1 is the plain plan itself, bit for bit (same family, same launches).
+     * XRFTHIP_BAD_ARG: a negative M, batch % M != 0, out_mode COMPLEX | PHASE, XRFTHIP_ISO.  XRFTHIP_UNSUPPORTED_LENGTH means "the caller composes" (the plain plan, then
+     * xrfthip_reduce_axis with scale = 1 / M): every kernel family without a mean form -- all but the two-pass float32 slabs (XRFTHIP_K_FASTY on 2-D plans; float16 /
+     * bfloat16 and strided input included: the column pass is the plain plan's) and the one-pass float32 slabs of 64 | 128 points per axis (XRFTHIP_K_FASTS, dense
+     * float32 input, POWER; a 256 x 256 mean plan is served by FASTY) -- hence also XRFTHIP_HALF_X / REALDIM_X2, XRFTHIP_AXIS_Y, inner / mid and herm_*; a later
+     * xrfthip_plan_set_* call that would move the plan to such a family answers the same.  Of these classes a plan takes, by default, those whose mean form measured
+     * not slower than the composition it replaces (profiles/r15_batch_mean.txt: every FASTY class; FASTS slabs of 128 rows); FASTS slabs of 64 rows answer
+     * XRFTHIP_UNSUPPORTED_LENGTH as well unless XRFTHIP_MEAN_ALL=1 is in the environment when the plan is created (docs/TUNING.md).
+     * Sums: no floating-point atomics; the order of every addition is fixed by the plan (M, the groups of slabs, the runs per output that xrfthip_plan_describe prints),
+     * so repeated calls return identical bits; at most 16 float32 terms are added in a row before the sum continues in float64 (complex128); a non-finite value in one
+     * slab makes exactly its own output non-finite.  The partial sums live in the workspace (xrfthip_workspace_bytes includes them: P float64 half spectra per output).
+     * xrfthip_plan_pass1_bytes keeps working on a mean plan (the column pass is unchanged).
+     * Descriptors with the struct_size of the five earlier versions are accepted (0).  As with the strides and herm_*, the status of xrfthip_plan_create tells the
+     * capability: an older library answers XRFTHIP_BAD_ARG to the larger struct_size. */
+    int64_t mean_batch;
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;

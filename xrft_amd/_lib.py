@@ -62,6 +62,7 @@ class Desc(C.Structure):
         ("in_stride_batch", C.c_int64),  # elements between its slabs (0 = ny * nx); trailing-axes layout only, strides in multiples of 16 bytes
         ("herm_ny", C.c_int64),  # > 0 (both): the columns of an AXIS_Y plan are the half spectrum of a real herm_ny x herm_nx grid -- the last pass of a
         ("herm_nx", C.c_int64),  # three-axis power / cross spectrum or (HERM_FIELD) transform: [batch][nt][herm_ny][herm_nx/2 + 1] complex in, the full [batch][nt][herm_ny][herm_nx] result out
+        ("mean_batch", C.c_int64),  # M > 1: the mean over every M consecutive slabs inside the last pass, POWER | CROSS: [batch / M][ny][nx] out (0 | 1: off)
     ]
 
 

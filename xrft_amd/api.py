@@ -34,7 +34,7 @@ from . import _lib, engine
 from .labeled import Coordinate, DataArray, from_any, to_like
 
 __all__ = ["clear_plan_cache", "fft", "ifft", "dft", "idft", "detrend", "power_spectrum", "cross_spectrum", "cross_phase", "isotropize",
-           "isotropic_power_spectrum", "isotropic_cross_spectrum", "fit_loglog"]
+           "isotropic_power_spectrum", "isotropic_cross_spectrum", "fit_loglog", "mean_power_spectrum", "mean_cross_spectrum"]
 
 _WINDOW_NAMES = [  # xrft.py:48-72
     "hann", "hamming", "kaiser", "tukey", "parzen", "taylor", "boxcar", "barthann", "bartlett", "blackman",
@@ -299,6 +299,7 @@ def clear_plan_cache():
         _plan_cache.clear()
         _STRIDED_REFUSED.clear()
         _HALF_REFUSED.clear()
+        _MEAN_REFUSED.clear()
         _BLUE_TABLES.clear()
         _TWO_STAGE.clear()
     engine.clear_workspaces()
@@ -501,6 +502,7 @@ def _arrange(c, da):
     return t, other
 
 
+_MEAN_REFUSED = OrderedDict()     # plan keys the library answered UNSUPPORTED_LENGTH to with mean_batch: those calls compose (the plain plan, then .mean), without asking again
 _STRIDED_REFUSED = OrderedDict()  # plan keys the library answered UNSUPPORTED_LENGTH to with input strides: those calls copy, without asking again
 _HALF_REFUSED = OrderedDict()     # ... and to with float16 / bfloat16 input: those calls widen the field once (engine.convert) and take the float32 plan
 
@@ -690,7 +692,13 @@ def _own_tensor(da, t):
     return None
 
 
-def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
+class _MeanDeclined(Exception):
+    """No plan takes this call with mean_batch (xrfthip_desc.mean_batch: XRFTHIP_UNSUPPORTED_LENGTH): the caller composes the plain call and .mean()."""
+
+
+def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0, mean_batch=0):
+    if mean_batch:  # the mean over every ``mean_batch`` consecutive slabs of the arranged (batch, ny, nx) array inside the last pass, or _MeanDeclined
+        return _execute_trailing(c, da, mode, scale, da2, c2, iso, extra_flags, mean_batch)
     k = _inplace_axis(c, da, iso) if (extra_flags & ~_lib.REALDIM_X2) == 0 else None
     if k is not None:
         out = _execute_axis_y(c, da, mode, scale, k, da2, c2, extra_flags)
@@ -711,7 +719,14 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
         out = _execute_inner(c, da, _lib.OUT_CROSS, scale, 0, da2, c2)
         if out is not None:
             return engine.angle(out), None, None
+    return _execute_trailing(c, da, mode, scale, da2, c2, iso, extra_flags, 0)
+
+
+def _execute_trailing(c, da, mode, scale, da2, c2, iso, extra_flags, mean_batch):
+    """The plan over the trailing axes of the arranged array (*other, [ny,] nx)."""
     t, other, strides = _arrange_view(c, da, keep_half=True)  # (a qualifying view of a larger array stays where it lies: no contiguous copy)
+    if mean_batch and t.dtype not in (torch.float32,) + _TORCH_HALF:
+        raise _MeanDeclined()
     ndim = len(c.dim)
     nx = da.sizes[c.xdim]
     ny = da.sizes[c.ydim] if c.ydim is not None else 1
@@ -738,6 +753,11 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
     if iso is not None:
         kw.update(binmap=iso["binmap"], nbins=iso["nbins"])
         bkey = iso.get("binmap_key")
+    if mean_batch:
+        kw["mean_batch"] = int(mean_batch)
+        with _plan_lock:
+            if _plan_key(bkey, dict(kw, dtype=torch.float32)) in _MEAN_REFUSED:
+                raise _MeanDeclined()
     if t.dtype in _TORCH_HALF:
         # the plan that reads the 2-byte samples where they lie: the float32 plan of this call with a half loader, or UNSUPPORTED_LENGTH (a family without one, a
         # field that is not 16-byte aligned): then the field is widened once and the float32 plan runs -- the same bits either way
@@ -782,6 +802,12 @@ def _execute(c, da, mode, scale, da2=None, c2=None, iso=None, extra_flags=0):
     except _lib.XrftHipError as e:
         if e.status != _lib.UNSUPPORTED_LENGTH:
             raise
+        if mean_batch:
+            with _plan_lock:
+                _MEAN_REFUSED[_plan_key(bkey, kw)] = True
+                while len(_MEAN_REFUSED) > 64:
+                    _MEAN_REFUSED.popitem(last=False)
+            raise _MeanDeclined() from e
         # numpy.fft takes any length; here a prime factor above 128 goes through Bluestein inside one LDS tile, which bounds
         # the length (2 n - 1 rounded up to 2^a 3^b 5^c complex samples must fit 160 KB)
         if ndim == 1 and iso is None and t2 is None and mode in (_lib.OUT_COMPLEX, _lib.OUT_POWER) and not (flags & (_lib.INVERSE | _lib.C2R_X | _lib.PHASE_IN)):
@@ -1762,6 +1788,105 @@ def cross_spectrum(da1, da2, dim=None, real_dim=None, scaling="density", window_
         d2w, wide2 = _wide(da2)  # (narrowed back only when BOTH were widened: float32 x float64 stays the promoted complex128, whatever the order)
         return to_like(_narrow(_spectrum_nd(d1w, d2w, _two_dims(da1, dim, real_dim, kwargs.get("real")), real_dim, scaling, window_correction, true_phase,
                                             dict(kwargs), one_at_a_time=True), wide1 and wide2), src)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Averaged spectra: power_spectrum(...).mean(mean_dim) / cross_spectrum(...).mean(mean_dim) with the mean taken inside the last pass of the plan
+# (xrfthip_desc.mean_batch): what the reference's users do with a batch of spectra (its Parseval, chunk and MITgcm notebooks end every spectral example with a
+# .mean over time steps or over the <dim>_segment dims of chunks_to_segments=True) without the spectra of the single slabs ever reaching memory.
+# ------------------------------------------------------------------------------------------------------
+def _check_mean_dims(names, dims):
+    for d in names:
+        if d not in dims:
+            raise ValueError(f"mean_dim {d!r} is not a non-transform dimension of the result (those are {list(dims)})")
+
+
+def _mean_fused(c, c2, mode, scale, flags, names, other):
+    """The labelled mean from ONE plan with mean_batch, or None where the call composes: the plan declines it (another kernel family, float64), real_dim, one
+    transform axis, mean dims that are not the innermost batch dims of the arranged (batch, ny, nx) array, a kept coordinate that spans a transform dim (the
+    composition's validating constructor answers that)."""
+    cda = c.da
+    k = len(set(names))
+    m = math.prod(cda.sizes[d] for d in set(names))
+    if len(c.dim) != 2 or flags or c.real_dim is not None or set(other[len(other) - k:]) != set(names) or m <= 1 or math.prod(cda.shape) == 0:
+        return None
+    if any(d in c.dim for n, v in cda.coords.items() if n not in c.dim for d in v.dims):
+        return None
+    try:
+        out, _, _ = _execute(c, cda, mode, scale, da2=None if c2 is None else c2.da, c2=c2, mean_batch=m)
+    except _MeanDeclined:
+        return None
+    kept = other[:len(other) - k]
+    extra = None
+    if c2 is not None and c.true_phase:  # (as _cross_result)
+        extra = {c.swap[d]: {"direct_lag": lag} for d, lag in zip(c.dim, c.lag_x)}
+    # labelled as _label_output does, without the averaged dims and the coordinates that span them (DataArray.mean drops those)
+    tdims = [c.ydim, c.xdim]
+    final = [c.swap.get(d, d) for d in c.rawdims if d in kept or d in tdims]
+    cur = kept + [c.swap[d] for d in tdims]
+    out = out.reshape([cda.sizes[d] for d in kept] + list(out.shape[-2:]))
+    if cur != final:
+        out = out.permute([cur.index(d) for d in final])
+    coords = {n: v._clone(n) for n, v in cda.coords.items() if n not in c.dim and not (set(v.dims) & set(names))}
+    for name, cv in c.new_coords.items():
+        attrs = dict(cv.attrs)
+        if extra and name in extra:
+            attrs.update(extra[name])
+        coords[name] = Coordinate(cv.dims, cv.values, attrs, name)
+    return DataArray._trusted(out, final, coords)
+
+
+def _mean_spectrum(da, da2, names, dim, real_dim, scaling, window_correction, true_phase, kwargs):
+    """The labelled mean of a one- or two-axis spectrum from ONE host analysis of the call -- fused where a plan takes it, else the plain call's execution and
+    .mean() -- or None: more than two transform axes, the deprecated ``real`` flag, lengths only the one-axis-at-a-time composition serves (the caller goes through
+    the public function)."""
+    if "real" in kwargs or _nd_dims(da, dim, real_dim, None) is not None:
+        return None
+    c, c2, mode, scale, flags = _spectrum(da, da2, dim, real_dim, scaling, window_correction, true_phase, dict(kwargs))
+    other = [d for d in c.da.dims if d not in c.dim]
+    _check_mean_dims(names, other)
+    fused = _mean_fused(c, c2, mode, scale, flags, names, other)
+    if fused is not None:
+        return fused
+    try:
+        if c2 is None:
+            out, _, oth = _execute(c, c.da, mode, scale, extra_flags=flags)
+            full = _label_output(c, c.da, out, oth)
+        else:
+            full = _cross_result(c, c2, mode, scale, flags)
+    except _UnsupportedLength:
+        return None
+    return full.mean(names)
+
+
+def mean_power_spectrum(da, mean_dim, dim=None, real_dim=None, scaling="density", window_correction=False, **kwargs):
+    """``power_spectrum(da, dim, ...).mean(mean_dim)`` -- same dims, coordinates, attrs and name -- with the mean taken inside the last pass where a plan does that
+    (float32 / float16 / bfloat16 fields, two transform axes; ``mean_dim`` all the other dims or the innermost of them; the shape classes whose mean form measured
+    faster than the composition, docs/TUNING.md XRFTHIP_MEAN_ALL): the result, and what the call allocates, shrink by the number of spectra averaged.  ``mean_dim``: a
+    name or a list of names of non-transform dims of the result, the ``<dim>_segment`` dims of ``chunks_to_segments=True`` included.  Every other call runs the plain
+    plan and ``.mean``."""
+    src = da
+    da = from_any(da)
+    names = [mean_dim] if isinstance(mean_dim, str) else list(mean_dim)
+    res = _mean_spectrum(da, None, names, dim, real_dim, scaling, window_correction, False, kwargs)
+    if res is None:
+        ps = power_spectrum(da, dim=dim, real_dim=real_dim, scaling=scaling, window_correction=window_correction, **kwargs)
+        _check_mean_dims(names, ps.dims)
+        res = ps.mean(names)
+    return to_like(res, src)
+
+
+def mean_cross_spectrum(da1, da2, mean_dim, dim=None, real_dim=None, scaling="density", window_correction=False, true_phase=True, **kwargs):
+    """``cross_spectrum(da1, da2, dim, ...).mean(mean_dim)``, the mean taken inside the last pass where a plan does that (see ``mean_power_spectrum``)."""
+    src = da1
+    da1, da2 = from_any(da1), from_any(da2)
+    names = [mean_dim] if isinstance(mean_dim, str) else list(mean_dim)
+    res = _mean_spectrum(da1, da2, names, dim, real_dim, scaling, window_correction, true_phase, kwargs)
+    if res is None:
+        cs = cross_spectrum(da1, da2, dim=dim, real_dim=real_dim, scaling=scaling, window_correction=window_correction, true_phase=true_phase, **kwargs)
+        _check_mean_dims(names, cs.dims)
+        res = cs.mean(names)
+    return to_like(res, src)
 
 
 def _cross_result(c, c2, mode, scale, flags):

@@ -52,6 +52,9 @@ struct FastS {
     long long in_slab;
     int in_pitch;
     int in_bf16;  // fasts_power_kernel<.., H16>: `in` holds 2-byte samples, bfloat16 (1) or float16 (0) (half_in.h); the float32 kernels never read it
+    // fasts_power_kernel<.., MEAN> (xrfthip_desc.mean_batch, fasts_mean.h): workgroup o mean_p + q walks run q of the mean_m slabs of output o; the other kernels never read the three
+    double* mean_part;  // [nslabs / mean_m][mean_p][NY/2 + 1][NX] float64 partial sums
+    int mean_m, mean_p;
 };
 
 constexpr size_t fasts_max(size_t a, size_t b) { return a > b ? a : b; }
@@ -136,16 +139,23 @@ template <int R> __device__ __forceinline__ void fasts_split(cf* b, int c) {
     }
 }
 
+}  // namespace xrft
+#include "fasts_mean.h"
+namespace xrft {
+
 // ISO: 0 the power spectrum; 1 the spectrum and its radial sums; 2 the radial sums only (XRFTHIP_NO_SPECTRUM_OUT).  MODE 1: power spectrum;
 // 0: the complex spectrum (xrft.fft / dft; ISO = 0)
 // STR: the rows of the input are p.in_pitch elements apart, its slabs p.in_slab (multiples of 4, the base 16-byte aligned: the 8-byte loads stay aligned and inside
 // their rows); a template parameter, so that the dense kernels keep their code
 // H16: the input is float16 / bfloat16 (dense): the same pair of columns per lane and row as ONE 4-byte load -- a wave reads 256 contiguous bytes per instruction --
 // widened in registers (half_in.h); everything behind the loads is the float32 kernel
-template <int RY, int RX, int ISO = 0, int MODE = 1, bool STR = false, bool H16 = false>
-__global__ void __launch_bounds__((SGeom<RY, RX>::T), (SGeom<RY, RX>::WPS)) fasts_power_kernel(FastS p) {
+// MEAN: the mean over p.mean_m consecutive slabs (fasts_mean.h): the workgroup walks one run of ONE output's slabs, nothing is emitted per slab, and the 34 sums that
+// cross the loop's back edge want the registers of two waves per SIMD (64 and 128 points per axis: at most 256 threads)
+template <int RY, int RX, int ISO = 0, int MODE = 1, bool STR = false, bool H16 = false, bool MEAN = false>
+__global__ void __launch_bounds__((SGeom<RY, RX>::T), (MEAN ? 2 : SGeom<RY, RX>::WPS)) fasts_power_kernel(FastS p) {
     static_assert(MODE == 1 || ISO == 0, "radial sums are of power spectra");
     static_assert(!(STR && H16), "half input is read dense");
+    static_assert(!MEAN || (MODE == 1 && ISO == 0 && RY <= 4 && RX <= 4), "the mean form: power spectra of 64 | 128 points per axis");
     typedef SGeom<RY, RX> G;
     constexpr int NY = G::NY, NX = G::NX, T = G::T, NXP = G::NXP, NROW = G::NROW, KGY = G::KGY, KGX = G::KGX;
     constexpr int P1 = G::P1, PX = G::PX, P3 = G::P3, PF = G::PF, HY = RY / 2, HX = RX / 2;
@@ -157,7 +167,7 @@ __global__ void __launch_bounds__((SGeom<RY, RX>::T), (SGeom<RY, RX>::WPS)) fast
     // a resident set walking the slabs (gridDim.x < nslabs; the default for long batches of 256 x 256 slabs, ONE workgroup per CU) has the 256 KB of loads
     // in flight beside the 256 KB of stores, and no register value crosses the loop's back edge.  (The complex form stages its result in halves and
     // emits it in place.)
-    constexpr bool PRE = MODE == 1;
+    constexpr bool PRE = MODE == 1 && !MEAN;
     // ---- the staged rows of slab `sl` leave: radial sums, then every output row whole
     auto emit = [&](long long sl) {
         int tid = threadIdx.x;
@@ -211,8 +221,14 @@ __global__ void __launch_bounds__((SGeom<RY, RX>::T), (SGeom<RY, RX>::WPS)) fast
     fastr_stagger(p.stagger);
     bool staged = false;
     long long prev = 0;
-    for (long long slab = blockIdx.x;; slab += gridDim.x) {
-        const bool have = slab < p.nslabs;
+    long long slab0 = blockIdx.x, slab_step = gridDim.x, slab_end = p.nslabs;
+    FastSMeanState<MEAN> ms;  // (empty unless MEAN: the sums that cross the back edge and the run of slabs, fasts_mean.h)
+    if constexpr (MEAN) {
+        ms.init(p, (long long)blockIdx.x);
+        slab0 = ms.lo; slab_step = 1; slab_end = ms.hi;
+    }
+    for (long long slab = slab0;; slab += slab_step) {
+        const bool have = slab < slab_end;
         int tid = threadIdx.x;
         XRFT_OPAQUE(tid);  // (nothing derived from the thread index is hoisted out of the slab loop and spilled: fastr.h)
         const int jp = tid % NXP, i0 = tid / NXP;  // packed column, first row
@@ -453,6 +469,22 @@ __global__ void __launch_bounds__((SGeom<RY, RX>::T), (SGeom<RY, RX>::WPS)) fast
                     }
         }
         __syncthreads();
+        if constexpr (MEAN) {
+            fasts_mean_accumulate<RY, RX>(Lf, ms.acc, ms.accx, row, cx);
+            if (++ms.chain < kMeanChain && slab + 1 < ms.hi) continue;
+            // ---- the chain ends: the sums leave through the staged rows (every thread overwrites its own samples), added (float64) to this workgroup's partial --
+            // written, the first time
+            fasts_mean_stage<RY, RX>(ms.acc, ms.accx, Lf, row, cx);
+            __syncthreads();
+            double* __restrict__ dst = p.mean_part + (size_t)blockIdx.x * (size_t)((NROW + 1) * NX);
+            for (int e = tid; e < (NROW + 1) * NX; e += T) {
+                const double v = (double)Lf[(e / NX) * PF + e % NX];
+                dst[e] = ms.first ? v : dst[e] + v;
+            }
+            ms.first = false;
+            ms.clear();
+            continue;  // (the next slab's first exchange starts with a barrier)
+        }
         staged = true;  // (MODE 1: emitted at the top of the next trip)
         prev = slab;
     }

@@ -405,6 +405,23 @@ static void fasty_launch_rows(const xrfthip_plan* P, const FastY& p, long long g
     }
 }
 
+// pass 2 of a mean plan (fasty_mean.h) for the group [g0, g0 + gc): (units per slab) x (runs per output) x (the outputs the group reaches) workgroups
+static void fasty_launch_rows_mean(const xrfthip_plan* P, const FastY& p, long long g0, long long gc, double* part, hipStream_t st) {
+    const xrfthip_desc& d = P->d;
+    const YGeomRt R = yrows_geom(P->ynx);
+    const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
+    const int rpu = two ? R.gxy : R.rk;
+    const long long M = d.mean_batch, nout = (g0 + gc - 1) / M - g0 / M + 1;
+    YMean m{part, g0, (int)M, P->mean_P};
+    xrfthip_plan::ProfRec* rec = prof_begin(P, "fasty_rows_mean", st);
+    const dim3 grid((unsigned)((long long)(P->y_nrow_pad / rpu) * P->mean_P * nout)), blk((unsigned)R.thr);
+#define YM_(NN) do { if (two) { auto k = &fasty_rows_mean_kernel<NN, 2>; XRFT_LAUNCH(k, grid, blk, R.lds, st, p, m); } \
+                     else { auto k = &fasty_rows_mean_kernel<NN, 1>; XRFT_LAUNCH(k, grid, blk, R.lds, st, p, m); } } while (0)
+    if (P->ynx == 4096) YM_(4096); else if (P->ynx == 2048) YM_(2048); else if (P->ynx == 1024) YM_(1024); else if (P->ynx == 512) YM_(512); else YM_(256);
+#undef YM_
+    prof_end(rec, st);
+}
+
 // parameter block of one group of slabs [g0, g0 + gc): the intermediate and the fit tables sit in ring slot `slot` (of slot_slabs slabs each)
 static FastY fasty_params(const xrfthip_plan* P, const float* in, void* out, double* iso, char* ws, long long g0, long long gc, int slot, long long slot_slabs) {
     // (slot 0 = field 0 / the only field, slot 1 = field 1 of a cross spectrum: its own intermediate and fit tables)
@@ -479,6 +496,7 @@ int fasty_tables(xrfthip_plan* P) {
 }
 int try_fasty(xrfthip_plan* P) {
     if (!fasty_fits(P)) return kDeclined;
+    // (a mean plan, xrfthip_desc.mean_batch: every class of fasty_mean.h measured faster than the composition it replaces, profiles/r15_batch_mean.txt)
     P->family = P->chosen = Family::FastY;
     return fasty_tables(P);
 }
@@ -586,6 +604,12 @@ static int run_fasty(const xrfthip_plan* P, const ExecArgs& a) {
     };
     // ... and with every field there, the workspace is the plan's without the fields' shares: what lies behind them moves up
     const bool compact = a.p1_mode[0] && (!two || a.p1_mode[1]);
+    // a mean plan (xrfthip_desc.mean_batch): the row pass adds into the outputs' partial sums, zero before the first group; one finishing pass writes d_out
+    double* mpart = nullptr;
+    if (mean_plan(P)) {
+        mpart = reinterpret_cast<double*>(ws + (P->off_mean - (compact ? (size_t)(two ? 2 : 1) * fasty_pass1_bytes(P) : 0)));
+        HIP_TRY(hipMemsetAsync(mpart, 0, P->ws_bytes - P->off_mean, st));
+    }
     for (long long g0 = 0; g0 < d.batch; g0 += P->G) {
         const long long gc = std::min<long long>(P->G, d.batch - g0);
         FastY p = fasty_params(P, in, out, iso, ws, g0, gc, 0, P->G);
@@ -603,10 +627,11 @@ static int run_fasty(const xrfthip_plan* P, const ExecArgs& a) {
             p.w2b = p1.w2;
             p.corr_b = p1.corr;
         }
-        fasty_launch_rows(P, p, gc, st, true);
+        if (mpart) fasty_launch_rows_mean(P, p, g0, gc, mpart, st);
+        else fasty_launch_rows(P, p, gc, st, true);
         HIP_TRY(hipGetLastError());
     }
-    return XRFTHIP_OK;
+    return mpart ? run_mean_finish(P, mpart, out, st) : XRFTHIP_OK;
 }
 
 // the two-pass pipeline on complex float32 slabs (fasty_c2c.h): columns -> rows, group by group
@@ -749,6 +774,7 @@ static void describe_fasty(const xrfthip_plan* plan, std::string& s, const char*
     appendf(s, "  [fasty] cols: %d thr, %d x 2 packed column pairs (FFT%lld r16x16x%lld, column-local detrend fused), %d columns/unit, lds=%zuB -> W2[slab][%d/%d][nx/%d][2][%d][%d] -> rows: %d thr, %d rows/unit (FFT%lld r16x16x%lld), lds=%zuB, |F|^2 + fftshift + mirror rows%s\n",
             C.thr, C.gxy, (long long)plan->d.ny, (long long)plan->d.ny / 256, C.cw, C.lds, plan->y_nrow_pad, C.rk, C.cw, C.rk, 2 * C.gxy,
             R.thr, R.rk, (long long)plan->d.nx, (long long)plan->d.nx / 256, R.lds, in_note);
+    if (mean_plan(plan)) appendf(s, "  [fasty mean] the row pass is fasty_rows_mean_kernel: a workgroup walks a run of ONE output's slabs inside the group, |F|^2 (F0 conj F1) summed in 32 registers\n");
     if ((plan->d.flags & XRFTHIP_ISO) && plan->ytcodes.p)
         appendf(s, "  [fasty radial sums] fused into the row pass (runs of equal bins from the staged rows, int64 fixed-point tables), bin codes: %s\n",
                 plan->ytfirst_on ? "radial map: per-bin gather, no atomics" : plan->ytcodes_compact ? "compact (radial map: first bin + step mask per 16 samples)" : "full (4 bytes per sample)");

@@ -53,6 +53,14 @@ int try_fasts(xrfthip_plan* P) {
     const uint32_t oks = XRFTHIP_SHIFT_Y | XRFTHIP_SHIFT_X | (d.out_mode == XRFTHIP_OUT_POWER ? (XRFTHIP_ISO | XRFTHIP_NO_SPECTRUM_OUT) : (XRFTHIP_ISHIFT_Y | XRFTHIP_ISHIFT_X));
     if (!(d.ndim == 2 && d.dtype == XRFTHIP_F32 && small_len(d.ny) && small_len(d.nx) && (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_COMPLEX) &&
           !(d.flags & ~oks) && env_ll("XRFTHIP_FASTS", 1) != 0)) return kDeclined;
+    // a mean plan (xrfthip_desc.mean_batch, fasts_mean.h): power spectra of 64 | 128 points per axis, dense float32 input.  A 1024-thread workgroup has 128 registers per
+    // thread, all in use: 256 x 256 goes to FastY's mean form, and so does nothing else of this family
+    if (mean_plan(P) && (d.ny == 256 || d.nx == 256 || d.out_mode != XRFTHIP_OUT_POWER || in_strided(P) || in_half(P))) return kDeclined;
+    // ... and by default only the classes that measured faster than the composition they replace (profiles/r15_batch_mean.txt): 128 rows -- (16384, 128, 128) 5.3 against
+    // 7.1 ms, (32768, 128, 64) 9.5 against 14.1.  With 64 rows -- (65536, 64, 64) 36.2 against 27.5, (32768, 64, 128) 18.6 against 14.1 -- the mean form lost, measured at
+    // the 16 workgroups per output that mean_layout's cap of ny / 4 runs leaves a one-output launch: a verdict on that launch shape (XRFTHIP_MEAN_RUNS), not on the
+    // kernel.  XRFTHIP_MEAN_ALL=1: every class the mean kernel takes
+    if (mean_plan(P) && d.ny != 128 && env_ll("XRFTHIP_MEAN_ALL", 0) == 0) return kDeclined;
     P->family = P->chosen = Family::FastS;
     P->tune_sgrid = env_ll("XRFTHIP_FASTS_GRID", -1);
     P->tune_sstagger = env_ll("XRFTHIP_FASTS_STAGGER", (3 << 8) | 2);  // (three classes 6.8 us apart: (4096, 256, 256) linear + Hann 310 -> 320 (the walk) -> 328 GFFT/s, profiles/r06_fasts_prefetch.txt)
@@ -61,6 +69,12 @@ int try_fasts(xrfthip_plan* P) {
     if (!rc) rc = plan_ones(P, 256);
     if (!rc && fasty_fits(P)) rc = fasty_tables(P);
     return rc;
+}
+
+// FastS's workspace: none, but a mean plan's partial sums (one workgroup per run of an output: the whole batch is one launch)
+static void layout_fasts(xrfthip_plan* P) {
+    layout_one_pass(P);
+    if (mean_plan(P)) P->ws_bytes = mean_layout(P, 0, 1, P->d.batch);
 }
 
 static int run_fasts(const xrfthip_plan* P, const ExecArgs& a) {
@@ -80,6 +94,19 @@ static int run_fasts(const xrfthip_plan* P, const ExecArgs& a) {
     p.shift_x = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0;
     p.scale = (float)d.scale;
     const SGeomRt G = sgeom(d.ny, d.nx);
+    if (mean_plan(P)) {  // fasts_power_kernel<.., MEAN>: workgroup o P + q walks run q of output o; then the finishing pass writes d_out
+        p.mean_part = reinterpret_cast<double*>(a.ws + P->off_mean); p.mean_m = (int)d.mean_batch; p.mean_p = P->mean_P;
+        const long long nwg = d.batch / d.mean_batch * P->mean_P;
+        if (nwg > 0x7fffffffLL) return XRFTHIP_BAD_ARG;
+        const dim3 mgrid((unsigned)nwg), mblk((unsigned)G.thr);
+        xrfthip_plan::ProfRec* mrec = prof_begin(P, "fasts_slab_mean", st);
+#define SM_(A, B) if (d.ny == 32 * A && d.nx == 32 * B) { auto k = &fasts_power_kernel<A, B, 0, 1, false, false, true>; XRFT_LAUNCH(k, mgrid, mblk, G.lds, st, p); }
+        SM_(2, 2) SM_(2, 4) SM_(4, 2) SM_(4, 4)
+#undef SM_
+        prof_end(mrec, st);
+        HIP_TRY(hipGetLastError());
+        return run_mean_finish(P, p.mean_part, a.out, st);
+    }
     // one workgroup per slab by default: measured against the resident set (kCUs x per_cu workgroups walking the slabs), (16384, 128, 128)
     // linear + Hann 531 vs 425 GFFT/s, (65536, 64, 64) 577 vs 497, 256 x 256 even (profiles/r04_fasts.txt)
     // ... except a 256 x 256 power spectrum (ONE 1024-thread workgroup per CU): a resident set that asks for its next slab while the staged rows of the
@@ -304,7 +331,7 @@ static void info_fasts(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTH
 static void info_fastr(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTR; *n = 1; }
 // (the entries in the order of struct FamilyOps: family, run, describe, kernel_info, finalize, layout, binmap, uses_bluestein, reads_strided)
 #ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
-const FamilyOps kOpsFastS = {Family::FastS, run_fasts, describe_fasts, info_fasts, fast_phase_tables, layout_one_pass, fasts_build_tfirst, nullptr, true};
+const FamilyOps kOpsFastS = {Family::FastS, run_fasts, describe_fasts, info_fasts, fast_phase_tables, layout_fasts, fasts_build_tfirst, nullptr, true};
 const FamilyOps kOpsFastR = {Family::FastR, run_fastr, describe_fastr, info_fastr, fast_phase_tables, layout_one_pass, nullptr, nullptr, true};
 const FamilyOps kOpsFastRComplex = {Family::FastRComplex, run_fastr, describe_fastr_complex, info_fastr, fast_phase_tables, layout_one_pass};
 const FamilyOps kOpsFastRRows = {Family::FastRRows, run_fastr, describe_fastr_rows, info_fastr, fast_phase_tables, layout_one_pass};

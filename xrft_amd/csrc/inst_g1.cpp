@@ -3,6 +3,7 @@
 #include "fasty.h"
 #include "fasty_iso.h"
 #include "fasty_c2c.h"
+#include "fasty_mean.h"
 #include "fastm.h"
 namespace xrft {
 #define XRFT_KW template __global__

@@ -57,6 +57,7 @@
 #include "fastn.h"
 #include "fastr.h"
 #include "fasts.h"
+#include "fasty_mean.h"
 #include "tile_fft.h"
 #include "fastg.h"
 #include "fasth.h"
@@ -468,6 +469,12 @@ struct xrfthip_plan {
     xrfthip_plan* sub_x = nullptr;
     xrfthip_plan* sub_y = nullptr;
     size_t off_sub = 0, off_det = 0, off_mid = 0, off_dws = 0;
+    // xrfthip_desc.mean_batch > 1 (fasty_mean.h, fasts_mean.h): mean_P runs per output (and group of slabs), each with a float64 partial of its own at off_mean --
+    // [batch / M][mean_P][ny/2 + 1][nx] (x2 complex) -- summed in order by mean_finish_kernel
+    int mean_P = 1;
+    long long mean_run = 0;        // the longest run of slabs one workgroup walks (describe)
+    long long tune_mean_runs = 0;  // XRFTHIP_MEAN_RUNS: runs per output, 0 = chosen by mean_layout
+    size_t off_mean = 0;
     ~xrfthip_plan() { for (auto* b : extra) delete b; prof_clear(); delete sub_x; delete sub_y; }
 };
 
@@ -571,6 +578,12 @@ inline bool two_pass_y(const xrfthip_plan* P) { return family_ops(P->family).two
 inline bool inner_layout(const xrfthip_plan* P) { return family_ops(P->family).inner_layout; }
 inline bool dbl_phase_tables(const xrfthip_plan* P) { return P->dbl && family_ops(P->family).dbl_tables; }
 inline bool herm_field_plan(const xrfthip_plan* P) { return P && P->d.herm_ny > 0 && (P->d.flags & XRFTHIP_HERM_FIELD); }  // (... whose last pass writes the complex field)
+// The mean over the batch inside the last pass (xrfthip_desc.mean_batch, normalised by xrfthip_plan_create: 0 = off, else M > 1): the families with a mean form are
+// FastY's two-pass slabs and FastS below 256 points per axis with dense float32 input; every other family answers XRFTHIP_UNSUPPORTED_LENGTH (the caller composes).
+inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1; }
+inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || P->family == Family::FastS; }
+size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs);  // (xrft_hip.cpp: mean_P and the partials behind `off`; returns the new end)
+int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStream_t st);  // (... and the finishing kernel, after the last group)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's
 // input take them: pass 1 of the two-pass families, the load of the one-pass families.  The intermediate and the output are dense.

@@ -637,7 +637,40 @@ void layout_passes(xrfthip_plan* P) {
         P->off_isopart = off;
         off = al(off + (size_t)G * P->iso_chunks * std::max(P->nbins, 1) * (two ? 2 : 1) * sizeof(double));
     }
+    if (mean_plan(P) && P->family == Family::FastY) off = mean_layout(P, off, (long long)P->y_nrow_pad / (nf == 2 ? fasty_rows_gx(P) : 2 * fasty_rows_gx(P)), G);
     P->ws_bytes = off;
+}
+
+// A mean plan's runs per output and its partial sums (fasty_mean.h): P->mean_P is chosen only so that the launch fills the card -- `units` workgroups per slab,
+// `slabs` slabs per launch, of which min(slabs, M) belong to one output -- and every run has a float64 (complex128) half spectrum of its own behind `off`.
+size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs) {
+    const xrfthip_desc& d = P->d;
+    const long long M = d.mean_batch, per_launch = std::max<long long>(1, slabs / M), cap = std::max<long long>(1, std::min(slabs, M));
+    // (... and at most ny / 4 runs: the partials stay within (P + 1) results, a float64 half spectrum being one result and two rows).  XRFTHIP_MEAN_RUNS pins P
+    // (1 .. min(slabs, M)) for measurements: long runs at 1, more workgroups than the rule gives above it
+    P->mean_P = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(cap, d.ny / 4), (4LL * kCUs) / std::max<long long>(1, units * per_launch)));
+    if (P->tune_mean_runs > 0) P->mean_P = (int)std::min<long long>(cap, P->tune_mean_runs);
+    P->mean_run = (cap + P->mean_P - 1) / P->mean_P;
+    P->off_mean = off;
+    const size_t bytes = (size_t)(d.batch / M) * (size_t)P->mean_P * (size_t)(d.ny / 2 + 1) * (size_t)d.nx * sizeof(double) * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1);
+    return (off + bytes + 255) & ~(size_t)255;
+}
+
+// ... and the pass that ends a mean plan's exec: the runs of every output summed in order, x 1 / M, every output row written once (mean_finish_kernel)
+int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStream_t st) {
+    const xrfthip_desc& d = P->d;
+    const long long nout = d.batch / d.mean_batch;
+    if (nout * d.ny > 0x7fffffffLL) return XRFTHIP_BAD_ARG;
+    xrfthip_plan::ProfRec* rec = prof_begin(P, "mean_finish", st);
+    const dim3 grid((unsigned)(nout * d.ny)), blk(256);
+    const int sy = (d.flags & XRFTHIP_SHIFT_Y) ? (int)(d.ny / 2) : 0, sx = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0;
+    const double inv_m = 1.0 / (double)d.mean_batch;
+    const cf *phy = reinterpret_cast<const cf*>(P->fph[0].p), *phx = reinterpret_cast<const cf*>(P->fph[1].p);
+    if (d.out_mode == XRFTHIP_OUT_CROSS) { auto k = &mean_finish_kernel<true>; XRFT_LAUNCH(k, grid, blk, 0, st, part, out, (int)d.ny, (int)d.nx, P->mean_P, inv_m, sy, sx, phy, phx, (P->fph_on && phy && phx) ? 1 : 0); }
+    else { auto k = &mean_finish_kernel<false>; XRFT_LAUNCH(k, grid, blk, 0, st, part, out, (int)d.ny, (int)d.nx, P->mean_P, inv_m, sy, sx, phy, phx, 0); }
+    prof_end(rec, st);
+    HIP_TRY(hipGetLastError());
+    return XRFTHIP_OK;
 }
 
 xrfthip_plan::ProfRec* prof_begin(const xrfthip_plan* P, const std::string& label, hipStream_t st) {
@@ -705,6 +738,8 @@ static int finalize_plan(xrfthip_plan* P) {
     if (in_strided(P) && !family_reads_strided(P)) return XRFTHIP_UNSUPPORTED_LENGTH;
     // ... and a half plan a family that reads 2-byte samples, or none (the caller widens): no other kernel may ever see the 2-byte buffer
     if (in_half(P) && !half_family(P)) return XRFTHIP_UNSUPPORTED_LENGTH;
+    // ... and a mean plan a family with a mean form, or none (the caller composes: the plain plan, then xrfthip_reduce_axis)
+    if (mean_plan(P) && !mean_family(P)) return XRFTHIP_UNSUPPORTED_LENGTH;
     if (const auto layout = family_ops(P->family).layout) layout(P);
     return XRFTHIP_OK;
 }
@@ -849,9 +884,9 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // (... and of the versions before `mid` and before the input strides: mid = 1, strides 0)
     // (... and of the version before herm_ny / herm_nx: 0, 0)
     constexpr uint32_t kOldDescSize = (uint32_t)offsetof(xrfthip_desc, inner), kOldDescSize2 = (uint32_t)offsetof(xrfthip_desc, mid), kOldDescSize3 = (uint32_t)offsetof(xrfthip_desc, in_stride_y),
-                       kOldDescSize4 = (uint32_t)offsetof(xrfthip_desc, herm_ny);
+                       kOldDescSize4 = (uint32_t)offsetof(xrfthip_desc, herm_ny), kOldDescSize5 = (uint32_t)offsetof(xrfthip_desc, mean_batch);  // (... and before mean_batch: 0)
     if (!plan || !desc || (desc->struct_size != sizeof(xrfthip_desc) && desc->struct_size != kOldDescSize && desc->struct_size != kOldDescSize2 && desc->struct_size != kOldDescSize3 &&
-                           desc->struct_size != kOldDescSize4)) return XRFTHIP_BAD_ARG;
+                           desc->struct_size != kOldDescSize4 && desc->struct_size != kOldDescSize5)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);
     dcopy.struct_size = sizeof(xrfthip_desc);
@@ -859,6 +894,8 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (dcopy.inner == 0) dcopy.inner = 1;
     if (dcopy.mid == 0) dcopy.mid = 1;
     if (dcopy.in_stride_y < 0 || dcopy.in_stride_batch < 0) return XRFTHIP_BAD_ARG;
+    if (dcopy.mean_batch < 0) return XRFTHIP_BAD_ARG;
+    if (dcopy.mean_batch == 1) dcopy.mean_batch = 0;  // (the plain plan itself)
     {   // strides that say what a dense array says are the dense plan (any family serves it)
         const int64_t row = (dcopy.flags & XRFTHIP_C2R_X) ? dcopy.nx / 2 + 1 : dcopy.nx;
         if (dcopy.in_stride_y > 0 && dcopy.in_stride_y < row) return XRFTHIP_BAD_ARG;
@@ -905,6 +942,11 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if ((d.flags & XRFTHIP_AXIS_Y) && (d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2)) &&
         (cplx_in || !(d.flags & XRFTHIP_HALF_X) || (d.flags & (XRFTHIP_SHIFT_Y | XRFTHIP_FLIP_Y | XRFTHIP_INVERSE)))) return XRFTHIP_BAD_ARG;
 
+    // mean_batch = M > 1: the mean over every M consecutive slabs inside the last pass (fasty_mean.h, fasts_mean.h); what has no mean form is "the caller composes"
+    if (d.mean_batch > 1) {
+        if (d.batch % d.mean_batch != 0 || (d.out_mode != XRFTHIP_OUT_POWER && d.out_mode != XRFTHIP_OUT_CROSS) || (d.flags & XRFTHIP_ISO)) return XRFTHIP_BAD_ARG;
+        if ((d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2 | XRFTHIP_AXIS_Y)) || d.inner > 1 || d.mid > 1 || herm) return XRFTHIP_UNSUPPORTED_LENGTH;
+    }
     const bool strided = d.in_stride_y != 0 || d.in_stride_batch != 0;
     if (strided && (d.inner > 1 || d.mid > 1 || (d.flags & XRFTHIP_AXIS_Y))) return XRFTHIP_BAD_ARG;  // (those layouts stay dense)
     if (strided) {  // "the caller copies": the in-slab index math is 32-bit (elements, and bytes as unsigned); every vector load stays one aligned instruction
@@ -925,6 +967,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     P->tune_fast_group = env_ll("XRFTHIP_FAST_GROUP", 0);
     P->tune_y = env_ll("XRFTHIP_YTUNE", kYTuneDefault);
     P->tune_isorows = env_ll("XRFTHIP_ISOROWS", 0);
+    P->tune_mean_runs = env_ll("XRFTHIP_MEAN_RUNS", 0);
     P->tune_group_bytes = env_ll("XRFTHIP_GROUP_BYTES", 512LL << 20);
     P->tune_cols_grid = env_ll("XRFTHIP_FAST_COLS_GRID", kCUs);
     P->tune_max_grid = env_ll("XRFTHIP_MAX_GRID", 8 * kCUs * 4);
@@ -1129,6 +1172,10 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
     if (in_half(plan)) appendf(in_note_, "; %s input read where it lies (2 bytes per sample), widened to float32 in registers", plan->in16 == 2 ? "bfloat16" : "float16");
     const char* in_note = in_note_.c_str();
     if (const auto describe = family_ops(plan->family).describe) describe(plan, s, in_note);
+    if (mean_plan(plan))
+        appendf(s, "  [mean over the batch] mean_batch=%lld: %lld outputs, each the mean of %lld consecutive slabs summed inside the last pass (at most %d float32 terms in a row, then "
+                   "float64), P=%d runs per output (run=%lld slabs at most per workgroup) with a float64 partial each (%zuB of the workspace), summed in order and written once by mean_finish; the spectra of the single slabs are never stored\n",
+                (long long)d.mean_batch, (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, kMeanChain, plan->mean_P, plan->mean_run, plan->ws_bytes - plan->off_mean);
     if (!inner_layout(plan)) {
         describe_passes(s, plan->passes_f0, "f0");
         describe_passes(s, plan->passes, "main");

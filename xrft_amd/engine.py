@@ -40,7 +40,7 @@ class SpectralPlan:
 
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
-                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None):
+                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
@@ -62,9 +62,12 @@ class SpectralPlan:
         self.herm_ny, self.herm_nx = int(herm_ny), int(herm_nx)
         if self.herm_ny or self.herm_nx:
             self.nx_out = self.herm_ny * self.herm_nx
+        # the mean over every ``mean_batch`` consecutive slabs inside the last pass (xrfthip_desc.mean_batch): batch // M outputs; 0 | 1 = the plain plan
+        self.mean_batch = int(mean_batch)
+        self.batch_out = self.batch // self.mean_batch if self.mean_batch > 1 else self.batch
         d = _lib.Desc(C.sizeof(_lib.Desc), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
                       int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
-                      self.herm_ny, self.herm_nx)
+                      self.herm_ny, self.herm_nx, self.mean_batch)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
         for axis, w in ((0, window_y), (1, window_x)):
             if w is not None:
@@ -165,14 +168,14 @@ class SpectralPlan:
                 raise ValueError("in1 does not match the plan")
         want_out = not (self.flags & _lib.NO_SPECTRUM_OUT)
         if want_out and out is None:
-            shape = (self.batch, self.ny_out, self.nx_out) + ((self.inner,) if self.inner > 1 else ())
+            shape = (self.batch_out, self.ny_out, self.nx_out) + ((self.inner,) if self.inner > 1 else ())
             if self.mid > 1:
                 shape = (self.batch, self.ny_out, self.mid, self.nx_out, self.inner)
             if self.herm_ny:
                 shape = (self.batch, self.ny, self.herm_ny, self.herm_nx)
             out = torch.empty(shape, dtype=self.out_dtype(), device=dev)
         elif want_out:  # a caller's buffer (graph capture, composed passes): held to the plan before the device sees its pointer
-            need = self.batch * self.ny_out * self.nx_out * self.inner * self.mid
+            need = self.batch_out * self.ny_out * self.nx_out * self.inner * self.mid
             if out.dtype != self.out_dtype() or not out.is_contiguous() or out.numel() != need or out.device != dev:
                 raise ValueError(f"out does not match the plan (dtype {self.out_dtype()}, contiguous, {need} elements on {dev})")
         iso_dtype = torch.complex128 if self.out_mode == _lib.OUT_CROSS else torch.float64
