@@ -340,6 +340,11 @@ MODES = [
     ("fasth-power-f32", herm_kw((8, 6, 10), C64, L.OUT_POWER, L.SHIFT_Y | L.SHIFT_X), {}, L.K_FASTH, "fasth"),
     ("fasth-cross-f64", herm_kw((12, 4, 6), C128, L.OUT_CROSS), {}, L.K_FASTH, "fasth"),
     ("fasth-power-odd", herm_kw((15, 5, 7), C64, L.OUT_POWER), {}, L.K_FASTH, "fasth"),  # (odd Hermitian axes, no Nyquist column; 15 = 5 x 3: two radices)
+    # the per-column line fit of AXIS_Y plans with a detrend (column_fit_kernel, csrc/aux_kernels.h): both y-only families, and 3 rows x 65 columns (64 columns x 4 row
+    # parts per workgroup: the fourth row part has no row, the second column block one column)
+    ("fastmy-linear", dict(ny=100, nx=200, dtype=F64, flags=L.AXIS_Y, detrend=L.DETREND_LINEAR), {}, L.K_FASTM_Y, "fastm y-only"),
+    ("fastgy-linear", dict(ny=103, nx=206, dtype=F64, flags=L.AXIS_Y, detrend=L.DETREND_LINEAR), {}, L.K_FASTG_Y, "fastg y-only"),
+    ("column-fit-3x65", dict(ny=3, nx=65, dtype=F64, flags=L.AXIS_Y, detrend=L.DETREND_LINEAR), {}, L.K_GENERIC, "main"),  # (three rows: the generic passes; the fit is the same kernel)
 ]
 
 # xrfthip Family (csrc/plan.h) -> the (kernel kind, describe tag) forms it shows; every Family has a ladder case (test_every_family_is_executed)

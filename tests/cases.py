@@ -1325,7 +1325,24 @@ def run_reduce_axis_cases():
             assert torch.equal(got, engine.reduce_axis(t, ax, 1.0 / v.shape[ax]))
             ref = v.astype("complex128" if dt.startswith("complex") else "float64").mean(axis=ax)
             npt.assert_allclose(got.cpu().numpy(), ref, rtol=3e-6 if dt in ("float32", "complex64") else 1e-13, atol=1e-6 if dt in ("float32", "complex64") else 1e-14)
-    da = xa.DataArray(torch.from_numpy(rng.standard_normal((6, 9))).to(dev), ("time", "freq_r"), {"time": np.arange(6), "freq_r": np.arange(9) * 0.1})
+    # the same bound at the edges of the launch: nothing behind the axis (inner = 1), an axis of one term (n = 1: a copy times the scale), both with two components per
+    # sample, and more results than the capped grid of 8 x 256 x 8 workgroups x 256 threads has threads (the grid-stride loop wraps, with a ragged last trip)
+    grid_threads = 8 * 256 * 8 * 256
+    for dt, shape, ax in (("complex64", (5, 7, 1), 1), ("complex64", (35, 7), 1), ("complex64", (5, 1, 33), 1), ("float64", (6, 1), 1), ("complex128", (1, 3), 0),
+                          ("float32", (2, 2, grid_threads // 2 + 3), 1)):
+        v = rng.standard_normal(shape)
+        if dt.startswith("complex"):
+            v = v + 1j * rng.standard_normal(shape)
+        v = v.astype(dt)
+        if len(shape) == 3 and shape[2] > 33:
+            assert v.size // shape[ax] > grid_threads and (v.size // shape[ax]) % 256 != 0
+        t = torch.from_numpy(v).to(dev)
+        got = engine.reduce_axis(t, ax, 1.0 / 3.0)
+        assert torch.equal(got, engine.reduce_axis(t, ax, 1.0 / 3.0))
+        ref = v.astype("complex128" if dt.startswith("complex") else "float64").sum(axis=ax) / 3.0
+        assert got.shape == ref.shape
+        npt.assert_allclose(got.cpu().numpy(), ref, rtol=3e-6 if dt in ("float32", "complex64") else 1e-13, atol=1e-6 if dt in ("float32", "complex64") else 1e-14)
+    da =xa.DataArray(torch.from_numpy(rng.standard_normal((6, 9))).to(dev), ("time", "freq_r"), {"time": np.arange(6), "freq_r": np.arange(9) * 0.1})
     m = da.mean("time")
     assert m.dims == ("freq_r",) and np.array_equal(m["freq_r"].values, np.arange(9) * 0.1)
     npt.assert_allclose(m.values, da.values.mean(axis=0), rtol=1e-13)

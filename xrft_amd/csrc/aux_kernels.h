@@ -222,8 +222,15 @@ static __global__ void finalize_coef3_kernel(const double* part, double* coef, l
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int ch = 0; ch < nchunk; ++ch)
-        for (int k = 0; k < 8; ++k) acc[k] += part[(b * nchunk + ch) * 8 + k];
+    // the chunks in runs of 64, then the runs' sums, both in order: two chains of at most 64 terms (one chain of the 4096 chunks of a 65 x 64 x 3 float64 block left
+    // 20 u max |x| of error in its mean; up to 64 chunks the bits are those of the single chain)
+    for (int c0 = 0; c0 < nchunk; c0 += 64) {
+        double run[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const int c1 = c0 + 64 < nchunk ? c0 + 64 : nchunk;
+        for (int ch = c0; ch < c1; ++ch)
+            for (int k = 0; k < 8; ++k) run[k] += part[(b * nchunk + ch) * 8 + k];
+        for (int k = 0; k < 8; ++k) acc[k] += run[k];
+    }
     const double n = (double)n0 * (double)n1 * (double)n2;
     const double bar[3] = {0.5 * (double)(n0 - 1), 0.5 * (double)(n1 - 1), 0.5 * (double)(n2 - 1)};
     const double len[3] = {(double)n0, (double)n1, (double)n2};
