@@ -81,7 +81,8 @@ typedef enum xrfthip_out_mode {
     XRFTHIP_OUT_COMPLEX = 0, /* F                    -> complex (c64 | c128)          xrft.fft            */
     XRFTHIP_OUT_POWER = 1,   /* |F|^2 * scale        -> real    (f32 | f64)           xrft.power_spectrum */
     XRFTHIP_OUT_CROSS = 2,   /* F0 conj(F1) * scale  -> complex                       xrft.cross_spectrum */
-    XRFTHIP_OUT_PHASE = 3    /* arg(F0 conj(F1))     -> real, in [-pi, pi]            xrft.cross_phase (xrft.py:838-874) */
+    XRFTHIP_OUT_PHASE = 3,   /* arg(F0 conj(F1))     -> real, in [-pi, pi]            xrft.cross_phase (xrft.py:838-874) */
+    XRFTHIP_OUT_COHERENCE = 4 /* |<F0 conj F1>|^2 / (<|F0|^2> <|F1|^2>) -> real (f32), <.> the mean over mean_batch slabs: mean plans only (xrfthip_desc.mean_batch) */
 } xrfthip_out_mode;
 
 typedef enum xrfthip_detrend_kind {
@@ -224,6 +225,23 @@ typedef struct xrfthip_desc {
      * Descriptors with the struct_size of the five earlier versions are accepted (0).  As with the strides and herm_*, the status of xrfthip_plan_create tells the
      * capability: an older library answers XRFTHIP_BAD_ARG to the larger struct_size. */
     int64_t mean_batch;
+    /* The magnitude-squared coherence of two fields, out_mode = XRFTHIP_OUT_COHERENCE: what a batch of cross spectra is averaged for, the other half of the pair that
+     * XRFTHIP_OUT_PHASE begins.  Valid only with mean_batch = M > 1 (no new field: the mode is a value of out_mode, and the status of xrfthip_plan_create tells the
+     * capability -- an older library answers XRFTHIP_BAD_ARG to out_mode 4).  Two real input fields (d_in0, d_in1, as CROSS; xrfthip_exec without d_in1 answers as
+     * CROSS does); d_out is real float32 [batch / M][ny][nx],
+     *   gamma^2 = |sum_m F0 conj(F1)|^2 / (sum_m |F0|^2  sum_m |F1|^2)   over the M slabs of an output,
+     * from ONE row pass that reads each field's intermediate once and keeps four sums per sample (re C, im C, A, B) where CROSS keeps two; the composition it replaces
+     * is three mean plans (CROSS, POWER of each field) and xrfthip_coherence.  Shifts, detrend and windows behave as on the CROSS mean plan; `scale` is applied inside
+     * the sums (|scale| in A and B) to keep them in range and cancels in the result, as does 1 / M; phase tables are accepted and have no effect (a factor of modulus
+     * one common to the M slabs leaves |<.>|^2 unchanged).  No clamp: a value may exceed 1 by rounding, and a zero denominator gives what IEEE division gives.
+     * XRFTHIP_BAD_ARG: mean_batch <= 1 (of one spectrum the coherence is 1 everywhere; M = 1 is normalised to 0 and has no plain plan to stand for), batch % M != 0,
+     * XRFTHIP_ISO, and every descriptor to which CROSS answers XRFTHIP_BAD_ARG (XRFTHIP_INVERSE, an unknown detrend, ...).  XRFTHIP_UNSUPPORTED_LENGTH ("the caller
+     * composes"): every plan whose family is not the two-pass float32 slabs (XRFTHIP_K_FASTY on a 2-D plan) -- float64, complex fields, slabs of 64 | 128 points on an axis (the
+     * one-pass kernel has no two-field form), XRFTHIP_HALF_X / REALDIM_X2, XRFTHIP_AXIS_Y, inner / mid, herm_* -- and a later xrfthip_plan_set_* call that would move
+     * the plan to another family answers the same.  float16 / bfloat16 and strided input are taken as the CROSS mean plan takes them (the column pass is the plain
+     * plan's).  Sums as above: no atomics, a fixed order, at most 16 float32 terms in a row, then float64; the partial is 4 float64 per sample and run
+     * ([output][P][ny/2 + 1][nx][re C, im C, A, B], in xrfthip_workspace_bytes); a non-finite value in one slab makes exactly its own output non-finite.
+     * xrfthip_plan_describe prints the [mean over the batch] line and the word "coherence".  XRFTHIP_MEAN_ALL and XRFTHIP_MEAN_RUNS apply as they do to CROSS. */
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;
@@ -371,7 +389,12 @@ int xrfthip_spectrum_tail(int32_t dtype, int64_t n, const void* d_a, const void*
  * spectrum, for xrft.cross_phase (xrft.py:838-874) on calls whose cross spectrum is composed of several plans. */
 int xrfthip_angle(int32_t dtype, int64_t n, const void* d_a, void* d_out, void* stream);
 
-/* The same over [outer][na][inner] with the real-dim factor [1, 2, ..., 2, (1 if last_is_one)] along axis `na` (xrft.py:673-682):
+/* d_out[e] = |d_cross[e]|^2 / (d_p0[e] * d_p1[e]): the magnitude-squared coherence from an averaged cross spectrum and the two averaged power spectra -- the tail
+ * of the composed route where no XRFTHIP_OUT_COHERENCE plan takes the call.  dtype = XRFTHIP_C64 | XRFTHIP_C128 of d_cross; d_p0, d_p1 and d_out are real of the
+ * matching precision.  Evaluated in float64 and rounded once; no clamp; a zero denominator gives what IEEE division gives (NaN for 0 / 0, else inf). */
+int xrfthip_coherence(int32_t dtype, int64_t n, const void* d_cross, const void* d_p0, const void* d_p1, void* d_out, void* stream);
+
+/* The same as xrfthip_spectrum_tail over [outer][na][inner] with the real-dim factor [1, 2, ..., 2, (1 if last_is_one)] along axis `na` (xrft.py:673-682):
  * the kept half of a real transform counts twice, except k = 0 and, for an even length, the Nyquist sample. */
 int xrfthip_spectrum_tail_axis(int32_t dtype, int64_t outer, int64_t na, int64_t inner, int32_t last_is_one, const void* d_a, const void* d_b,
                                void* d_out, double scale, void* stream);

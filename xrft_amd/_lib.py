@@ -15,6 +15,7 @@ LIB_NAME = "libxrft_hip.so"
 F32, F64, C64, C128 = 0, 1, 2, 3
 F16, BF16 = 4, 5  # real half-precision input of a plan / of xrfthip_convert: read at 2 bytes per sample, computed in float32
 OUT_COMPLEX, OUT_POWER, OUT_CROSS, OUT_PHASE = 0, 1, 2, 3
+OUT_COHERENCE = 4  # mean plans only (Desc.mean_batch > 1): |<F0 conj F1>|^2 / (<|F0|^2> <|F1|^2>), real
 DETREND_NONE, DETREND_CONSTANT, DETREND_LINEAR = 0, 1, 2
 HALF_X, SHIFT_Y, SHIFT_X, ISHIFT_Y, ISHIFT_X, FLIP_Y, FLIP_X = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
 REALDIM_X2, ISO, NO_SPECTRUM_OUT = 0x80, 0x100, 0x200
@@ -35,7 +36,7 @@ EXPORTS = [
     "xrfthip_detrend", "xrfthip_detrend3", "xrfthip_spectrum_tail", "xrfthip_spectrum_tail_axis", "xrfthip_gather_axis", "xrfthip_isotropize",
     "xrfthip_isotropize_workspace_bytes", "xrfthip_table_mul", "xrfthip_reduce_axis", "xrfthip_detrend_inner_workspace_bytes", "xrfthip_detrend_inner", "xrfthip_angle",
     "xrfthip_plan_uses_bluestein", "xrfthip_convert", "xrfthip_plan_kernel_info", "xrfthip_selftest_floor",
-    "xrfthip_plan_pass1_bytes", "xrfthip_plan_pass1_signature", "xrfthip_exec_ex",
+    "xrfthip_plan_pass1_bytes", "xrfthip_plan_pass1_signature", "xrfthip_exec_ex", "xrfthip_coherence",
 ]
 PASS1_PRIVATE, PASS1_PRODUCE, PASS1_CONSUME = 0, 1, 2  # xrfthip_exec_args.field[].pass1_mode
 
@@ -104,6 +105,7 @@ def _bind(dll):
     dll.xrfthip_table_mul.argtypes = [i32, i64, i64, i64, vp, vp, vp, vp]
     dll.xrfthip_reduce_axis.argtypes = [i32, i64, i64, i64, vp, vp, C.c_double, vp]
     dll.xrfthip_angle.argtypes = [i32, i64, vp, vp, vp]
+    dll.xrfthip_coherence.argtypes = [i32, i64, vp, vp, vp, vp, vp]
     dll.xrfthip_plan_uses_bluestein.argtypes = [vp]
     dll.xrfthip_plan_kernel_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     dll.xrfthip_convert.argtypes = [i32, i32, i64, vp, vp, vp]

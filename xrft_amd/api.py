@@ -1889,6 +1889,48 @@ def mean_cross_spectrum(da1, da2, mean_dim, dim=None, real_dim=None, scaling="de
     return to_like(res, src)
 
 
+def coherence(da1, da2, mean_dim, dim=None, real_dim=None, scaling="density", window_correction=False, true_phase=True, **kwargs):
+    """Magnitude-squared coherence ``|<F1 conj F2>|^2 / (<|F1|^2> <|F2|^2>)``, ``<.>`` the mean over ``mean_dim`` (time steps, or the ``<dim>_segment`` dims of
+    ``chunks_to_segments=True``): what a batch of cross spectra is averaged for, the other half of the pair ``cross_phase`` begins.  The arguments are those of
+    ``mean_cross_spectrum`` and so are dims, coordinates and coordinate attrs of the result; the value does not depend on ``scaling``, ``window_correction`` or
+    ``true_phase`` (they cancel), which are accepted so that the call mirrors the cross call.  Real data: float32, or float64 for float64 input; no clamp (a value
+    may exceed 1 by rounding).  Where a plan takes the call (the conditions of ``mean_cross_spectrum``'s fused route, two-pass float32 slabs) ONE row pass sums the
+    cross spectrum and both powers (XRFTHIP_OUT_COHERENCE) and one real result is written; every other call composes ``mean_cross_spectrum`` and
+    ``mean_power_spectrum`` of each field and divides in the library (xrfthip_coherence).  Fewer than two spectra averaged: ValueError (the coherence of one
+    spectrum is 1 everywhere)."""
+    src = da1
+    da1, da2 = from_any(da1), from_any(da2)
+    names = [mean_dim] if isinstance(mean_dim, str) else list(mean_dim)
+    kw = dict(dim=dim, real_dim=real_dim, scaling=scaling, window_correction=window_correction)
+
+    def count(sizes):
+        if math.prod(sizes[d] for d in set(names)) < 2:
+            raise ValueError(f"coherence needs at least two spectra to average: mean_dim {names} holds {math.prod(sizes[d] for d in set(names))} (of one spectrum it is 1 everywhere)")
+
+    res = None
+    if "real" in kwargs or _nd_dims(da1, dim, real_dim, None) is not None:  # (no one-analysis route: the public functions, as mean_cross_spectrum does there)
+        full = from_any(cross_spectrum(da1, da2, true_phase=true_phase, **kw, **kwargs))
+        _check_mean_dims(names, full.dims)
+        count(full.sizes)
+        cs = full.mean(names)
+        p1, p2 = (from_any(power_spectrum(d, **kw, **kwargs)).mean(names) for d in (da1, da2))
+    else:
+        c, c2, _, scale, flags = _spectrum(da1, da2, dim, real_dim, scaling, window_correction, true_phase, dict(kwargs))
+        other = [d for d in c.da.dims if d not in c.dim]
+        _check_mean_dims(names, other)
+        count(c.da.sizes)
+        res = _mean_fused(c, c2, _lib.OUT_COHERENCE, scale, flags, names, other)
+        if res is None:
+            cs = from_any(mean_cross_spectrum(da1, da2, names, true_phase=true_phase, **kw, **kwargs))
+            p1, p2 = (from_any(mean_power_spectrum(d, names, **kw, **kwargs)) for d in (da1, da2))
+    if res is None:
+        cross = _to_device(cs.data)
+        real_dt = torch.float32 if cross.dtype == torch.complex64 else torch.float64
+        res = DataArray(engine.coherence(cross, _to_device(p1.data).to(real_dt), _to_device(p2.data).to(real_dt)), cs.dims, cs.coords, None, None)
+    res.name = "{}_{}_coherence".format(da1.name, da2.name) if da1.name and da2.name else None
+    return to_like(res, src)
+
+
 def _cross_result(c, c2, mode, scale, flags):
     out, _, other = _execute(c, c.da, mode, scale, da2=c2.da, c2=c2, extra_flags=flags)
     extra = None

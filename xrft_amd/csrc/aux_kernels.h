@@ -473,6 +473,28 @@ __global__ void __launch_bounds__(256) angle_kernel(const C2<T>* __restrict__ a,
         out[e] = (T)atan2((double)a[e].im, (double)a[e].re);
 }
 
+// out[e] = |c[e]|^2 / (p0[e] p1[e]): the magnitude-squared coherence from an averaged cross spectrum and the two averaged power spectra (xrfthip_coherence).
+// Evaluated in float64 and rounded once: numerator and denominator are kept as a value and its rounding error (fma), and the quotient gets one correction step, so
+// the complex128 form is within a rounding of the exact value as the complex64 form is.  A non-finite correction (a zero or non-finite denominator) is dropped:
+// the result is then what IEEE division of the rounded terms gives.
+template <typename T>
+__global__ void __launch_bounds__(256) coherence_kernel(const C2<T>* __restrict__ c, const T* __restrict__ p0, const T* __restrict__ p1, T* __restrict__ out, long long n) {
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+        const double re = (double)c[e].re, im = (double)c[e].im, a = (double)p0[e], b = (double)p1[e];
+        // (the rounded products are kept apart from the additions that follow: contracted into an fma, rr + ii would no longer be the sum whose error num_lo holds)
+        double rr = re * re, ii = im * im, den = a * b;
+        XRFT_OPAQUE(rr);
+        XRFT_OPAQUE(ii);
+        XRFT_OPAQUE(den);
+        const double rr_lo = fma(re, re, -rr), ii_lo = fma(im, im, -ii), den_lo = fma(a, b, -den);
+        const double num = rr + ii, bv = num - rr, num_lo = ((rr - (num - bv)) + (ii - bv)) + (rr_lo + ii_lo);
+        double q = num / den;
+        const double corr = (fma(-q, den, num) + num_lo - q * den_lo) / den;
+        if (corr - corr == 0.0) q += corr;  // (finite)
+        out[e] = (T)q;
+    }
+}
+
 // out[o][i] = scale * sum_k in[o][k][i] over [outer][n][inner] (complex data: inner counts real components), the terms added in
 // the order k = 0, 1, ... in float64: a mean / sum over a batch dimension whose result does not depend on how the launch was
 // scheduled (the reference's users average isotropic spectra over the batch: xrft/tests/test_xrft.py:1011-1013, `.mean("d0")`).

@@ -32,12 +32,16 @@ __device__ __forceinline__ float mean_add(float acc, float v) {
 }
 
 // MODE 1 power, 2 cross (fasty_rows_kernel's).  The loads, the residual-trend terms and the transforms are fasty_rows_kernel's; nothing of its store loops is here.
+// MODE 3 coherence (XRFTHIP_OUT_COHERENCE): the geometry, loads and transforms of MODE 2 and 64 sums per thread -- the 32 of the cross spectrum, by the same
+// statements, and 16 + 16 of |F0|^2 |scale| and |F1|^2 |scale|, by the statements of MODE 1 -- for the partial [..][nx][re C, im C, A, B] that
+// mean_finish_coherence_kernel turns into |C|^2 / (A B).  64 sums beside the two rows do not fit the 168 registers of three waves per SIMD: two waves, 256 registers.
 template <int NX, int MODE>
-__global__ void __launch_bounds__((YRows<NX>::THR), 3) fasty_rows_mean_kernel(FastY p, YMean m) {
-    static_assert(MODE == 1 || MODE == 2, "the mean of power and cross spectra");
+__global__ void __launch_bounds__((YRows<NX>::THR), (MODE == 3 ? 2 : 3)) fasty_rows_mean_kernel(FastY p, YMean m) {
+    static_assert(MODE == 1 || MODE == 2 || MODE == 3, "the mean of power and cross spectra, and the sums of a coherence");
     typedef P2<NX> G;
     typedef YRows<NX> R;
-    constexpr bool TWO = MODE == 2;
+    constexpr bool TWO = MODE >= 2, COH = MODE == 3;
+    constexpr int NACC = COH ? 64 : 32;
     constexpr int NT = G::NT, GX = R::GX, THR = R::THR, RPU = TWO ? GX : 2 * GX, GSTR = YLds<NX, GX>::GSTR;
     constexpr int RSP = R::RS, RSC = NX + NX / 16;
     XRFT_DYN_SMEM(smem_raw);
@@ -52,9 +56,9 @@ __global__ void __launch_bounds__((YRows<NX>::THR), 3) fasty_rows_mean_kernel(Fa
     const long long o = m.g0 / m.M + ol;
     const long long lo = max(m.g0, o * (long long)m.M), hi = min(m.g0 + (long long)p.nslab, (o + 1) * (long long)m.M), len = hi - lo;
     const long long s_lo = lo + (long long)pp * len / m.P, s_hi = lo + (long long)(pp + 1) * len / m.P;
-    float acc[32];
+    float acc[NACC];
 #pragma unroll
-    for (int e = 0; e < 32; ++e) acc[e] = 0.f;
+    for (int e = 0; e < NACC; ++e) acc[e] = 0.f;
     int chain = 0;
     for (long long s = s_lo; s < s_hi; ++s) {
         int tid = threadIdx.x;
@@ -114,6 +118,15 @@ __global__ void __launch_bounds__((YRows<NX>::THR), 3) fasty_rows_mean_kernel(Fa
                 acc[2 * e] = mean_add(acc[2 * e], v.re);
                 acc[2 * e + 1] = mean_add(acc[2 * e + 1], v.im);
             }
+            if (COH) {
+                const float sc = fabsf(p.scale);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const cf va = a[e], vb = b[e];
+                    acc[(COH ? 32 : 0) + e] = mean_add(acc[(COH ? 32 : 0) + e], (va.re * va.re + va.im * va.im) * sc);
+                    acc[(COH ? 48 : 0) + e] = mean_add(acc[(COH ? 48 : 0) + e], (vb.re * vb.re + vb.im * vb.im) * sc);
+                }
+            }
         } else {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
@@ -143,17 +156,34 @@ __global__ void __launch_bounds__((YRows<NX>::THR), 3) fasty_rows_mean_kernel(Fa
                 }
         }
         __syncthreads();
-        constexpr int CW = TWO ? 2 : 1;  // doubles per sample
-        double* __restrict__ dst = m.part + ((size_t)(o * m.P + pp) * (size_t)(nyh + 1) + (size_t)ky0) * (size_t)NX * CW;
+        constexpr int CW = TWO ? 2 : 1;  // doubles per sample and staging round
+        constexpr int PW = COH ? 4 : CW;  // doubles per sample of the partial
+        double* __restrict__ dst = m.part + ((size_t)(o * m.P + pp) * (size_t)(nyh + 1) + (size_t)ky0) * (size_t)NX * PW;
         for (int e = tid; e < RPU * NX * CW; e += THR) {
             const int rl = e / (NX * CW), c = e % (NX * CW);
             if (ky0 + rl > nyh) continue;  // (padding rows of the last unit)
             const float v = TWO ? stg[rl * 2 * RSC + 2 * nat16(c >> 1) + (c & 1)] : stg[rl * RSP + nat16(c)];
-            dst[(size_t)rl * NX * CW + c] += (double)v;
+            dst[(size_t)rl * NX * PW + (COH ? 4 * (c >> 1) + (c & 1) : c)] += (double)v;
         }
         __syncthreads();  // (the next slab's transforms overwrite the staged rows)
+        if (COH) {  // the second round through the same region (two values per sample do not fit beside each other): (A, B) staged as the pair (re C, im C) was
 #pragma unroll
-        for (int e = 0; e < 32; ++e) acc[e] = 0.f;
+            for (int bb = 0; bb < G::NB; ++bb)
+#pragma unroll
+                for (int k3 = 0; k3 < G::R3; ++k3) {
+                    const int e = bb * G::R3 + k3;
+                    lds[g * RSC + nat16(held_k<NX>(u, bb, k3))] = mk<float>(acc[(COH ? 32 : 0) + e], acc[(COH ? 48 : 0) + e]);
+                }
+            __syncthreads();
+            for (int e = tid; e < RPU * NX * 2; e += THR) {
+                const int rl = e / (NX * 2), c = e % (NX * 2);
+                if (ky0 + rl > nyh) continue;
+                dst[(size_t)rl * NX * 4 + 4 * (c >> 1) + 2 + (c & 1)] += (double)stg[rl * 2 * RSC + 2 * nat16(c >> 1) + (c & 1)];
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int e = 0; e < NACC; ++e) acc[e] = 0.f;
         chain = 0;
     }
 }
@@ -187,6 +217,32 @@ __global__ void __launch_bounds__(256) mean_finish_kernel(const double* __restri
         } else {
             reinterpret_cast<float*>(out)[oi] = (float)(sr * inv_m);
         }
+    }
+}
+
+// The coherence of a mean plan (XRFTHIP_OUT_COHERENCE): part is [output][P][ny/2 + 1][nx][re C, im C, A, B] -- the sums over the M slabs of F0 conj(F1) scale,
+// |F0|^2 |scale| and |F1|^2 |scale| -- and out[o][row][c] = |sum C|^2 / (sum A  sum B), the P partials of each of the four added in order, float64.  1 / M and the
+// scale cancel; the mirrored row holds the same number (|conj C| = |C|, and the true-phase factors have modulus one): rows rotated and mirrored as a power spectrum's.
+// No clamp: a value may exceed 1 by rounding, and a zero denominator gives what IEEE division gives.
+static __global__ void __launch_bounds__(256) mean_finish_coherence_kernel(const double* __restrict__ part, float* __restrict__ out, int ny, int nx, int P, int shift_y, int shift_x) {
+    const long long o = (long long)blockIdx.x / ny;
+    const int orow = (int)((long long)blockIdx.x % ny);
+    const int fy = (orow - shift_y) & (ny - 1);
+    const bool mir = fy > ny / 2;
+    const int r = mir ? ny - fy : fy, nrow = ny / 2 + 1;
+    const size_t pstr = (size_t)nrow * nx * 4;
+    const double* __restrict__ src = part + ((size_t)o * P * nrow + r) * (size_t)nx * 4;
+    for (int c = threadIdx.x; c < nx; c += 256) {
+        const int fx = (c - shift_x) & (nx - 1), kx = mir ? (nx - fx) & (nx - 1) : fx;
+        double sr = 0.0, si = 0.0, sa = 0.0, sb = 0.0;
+        for (int q = 0; q < P; ++q) {
+            const double* __restrict__ s4 = src + q * pstr + (size_t)kx * 4;
+            sr += s4[0];
+            si += s4[1];
+            sa += s4[2];
+            sb += s4[3];
+        }
+        out[((size_t)o * ny + orow) * (size_t)nx + c] = (float)((sr * sr + si * si) / (sa * sb));
     }
 }
 

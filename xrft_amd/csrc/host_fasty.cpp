@@ -415,7 +415,8 @@ static void fasty_launch_rows_mean(const xrfthip_plan* P, const FastY& p, long l
     YMean m{part, g0, (int)M, P->mean_P};
     xrfthip_plan::ProfRec* rec = prof_begin(P, "fasty_rows_mean", st);
     const dim3 grid((unsigned)((long long)(P->y_nrow_pad / rpu) * P->mean_P * nout)), blk((unsigned)R.thr);
-#define YM_(NN) do { if (two) { auto k = &fasty_rows_mean_kernel<NN, 2>; XRFT_LAUNCH(k, grid, blk, R.lds, st, p, m); } \
+#define YM_(NN) do { if (P->coherence) { auto k = &fasty_rows_mean_kernel<NN, 3>; XRFT_LAUNCH(k, grid, blk, R.lds, st, p, m); } \
+                     else if (two) { auto k = &fasty_rows_mean_kernel<NN, 2>; XRFT_LAUNCH(k, grid, blk, R.lds, st, p, m); } \
                      else { auto k = &fasty_rows_mean_kernel<NN, 1>; XRFT_LAUNCH(k, grid, blk, R.lds, st, p, m); } } while (0)
     if (P->ynx == 4096) YM_(4096); else if (P->ynx == 2048) YM_(2048); else if (P->ynx == 1024) YM_(1024); else if (P->ynx == 512) YM_(512); else YM_(256);
 #undef YM_
@@ -774,7 +775,8 @@ static void describe_fasty(const xrfthip_plan* plan, std::string& s, const char*
     appendf(s, "  [fasty] cols: %d thr, %d x 2 packed column pairs (FFT%lld r16x16x%lld, column-local detrend fused), %d columns/unit, lds=%zuB -> W2[slab][%d/%d][nx/%d][2][%d][%d] -> rows: %d thr, %d rows/unit (FFT%lld r16x16x%lld), lds=%zuB, |F|^2 + fftshift + mirror rows%s\n",
             C.thr, C.gxy, (long long)plan->d.ny, (long long)plan->d.ny / 256, C.cw, C.lds, plan->y_nrow_pad, C.rk, C.cw, C.rk, 2 * C.gxy,
             R.thr, R.rk, (long long)plan->d.nx, (long long)plan->d.nx / 256, R.lds, in_note);
-    if (mean_plan(plan)) appendf(s, "  [fasty mean] the row pass is fasty_rows_mean_kernel: a workgroup walks a run of ONE output's slabs inside the group, |F|^2 (F0 conj F1) summed in 32 registers\n");
+    if (mean_plan(plan)) appendf(s, "  [fasty mean] the row pass is fasty_rows_mean_kernel: a workgroup walks a run of ONE output's slabs inside the group, |F|^2 (F0 conj F1) summed in 32 registers%s\n",
+                                  plan->coherence ? "; coherence: |F0|^2 and |F1|^2 beside them, 64 registers, two waves per SIMD" : "");
     if ((plan->d.flags & XRFTHIP_ISO) && plan->ytcodes.p)
         appendf(s, "  [fasty radial sums] fused into the row pass (runs of equal bins from the staged rows, int64 fixed-point tables), bin codes: %s\n",
                 plan->ytfirst_on ? "radial map: per-bin gather, no atomics" : plan->ytcodes_compact ? "compact (radial map: first bin + step mask per 16 samples)" : "full (4 bytes per sample)");

@@ -35,7 +35,8 @@ XRFT_KI_Y2_(256) XRFT_KI_Y2_(512) XRFT_KI_Y2_(1024) XRFT_KI_Y2_(2048)
     XRFT_KW void fasty_isorows_kernel<NN, 1, true>(FastY); XRFT_KW void fasty_isorows_kernel<NN, 2, true>(FastY);
 XRFT_KI_YI_(1024) XRFT_KI_YI_(2048) XRFT_KI_YI_(4096)
 #undef XRFT_KI_YI_
-#define XRFT_KI_YM_(NN) XRFT_KW void fasty_rows_mean_kernel<NN, 1>(FastY, YMean); XRFT_KW void fasty_rows_mean_kernel<NN, 2>(FastY, YMean);  /* (fasty_mean.h: the mean over the batch) */
+#define XRFT_KI_YM_(NN) XRFT_KW void fasty_rows_mean_kernel<NN, 1>(FastY, YMean); XRFT_KW void fasty_rows_mean_kernel<NN, 2>(FastY, YMean); \
+    XRFT_KW void fasty_rows_mean_kernel<NN, 3>(FastY, YMean);  /* (fasty_mean.h: the mean over the batch; 3: the sums of a coherence) */
 XRFT_KI_YM_(256) XRFT_KI_YM_(512) XRFT_KI_YM_(1024) XRFT_KI_YM_(2048) XRFT_KI_YM_(4096)
 #undef XRFT_KI_YM_
 XRFT_KW void fasty_rows_kernel<256, 1, false, true, true>(FastY); XRFT_KW void fasty_rows_kernel<256, 0, false, true, true>(FastY);

@@ -475,6 +475,9 @@ struct xrfthip_plan {
     long long mean_run = 0;        // the longest run of slabs one workgroup walks (describe)
     long long tune_mean_runs = 0;  // XRFTHIP_MEAN_RUNS: runs per output, 0 = chosen by mean_layout
     size_t off_mean = 0;
+    // XRFTHIP_OUT_COHERENCE: the descriptor says OUT_CROSS from xrfthip_plan_create on -- every check, table, family and the column pass are the CROSS mean plan's -- and
+    // this remembers what the row pass sums (fasty_rows_mean_kernel<NX, 3>: re C, im C, A, B per sample) and what mean_finish writes (|C|^2 / (A B), real)
+    bool coherence = false;
     ~xrfthip_plan() { for (auto* b : extra) delete b; prof_clear(); delete sub_x; delete sub_y; }
 };
 
@@ -581,7 +584,7 @@ inline bool herm_field_plan(const xrfthip_plan* P) { return P && P->d.herm_ny > 
 // The mean over the batch inside the last pass (xrfthip_desc.mean_batch, normalised by xrfthip_plan_create: 0 = off, else M > 1): the families with a mean form are
 // FastY's two-pass slabs and FastS below 256 points per axis with dense float32 input; every other family answers XRFTHIP_UNSUPPORTED_LENGTH (the caller composes).
 inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1; }
-inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || P->family == Family::FastS; }
+inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || (P->family == Family::FastS && !P->coherence); }  // (FastS has no two-field form)
 size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs);  // (xrft_hip.cpp: mean_P and the partials behind `off`; returns the new end)
 int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStream_t st);  // (... and the finishing kernel, after the last group)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)

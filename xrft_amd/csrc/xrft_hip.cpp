@@ -652,7 +652,8 @@ size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs
     if (P->tune_mean_runs > 0) P->mean_P = (int)std::min<long long>(cap, P->tune_mean_runs);
     P->mean_run = (cap + P->mean_P - 1) / P->mean_P;
     P->off_mean = off;
-    const size_t bytes = (size_t)(d.batch / M) * (size_t)P->mean_P * (size_t)(d.ny / 2 + 1) * (size_t)d.nx * sizeof(double) * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1);
+    // (doubles per sample: a power 1, a cross spectrum 2, a coherence 4 -- re C, im C, A, B)
+    const size_t bytes = (size_t)(d.batch / M) * (size_t)P->mean_P * (size_t)(d.ny / 2 + 1) * (size_t)d.nx * sizeof(double) * (P->coherence ? 4 : d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1);
     return (off + bytes + 255) & ~(size_t)255;
 }
 
@@ -666,7 +667,8 @@ int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStr
     const int sy = (d.flags & XRFTHIP_SHIFT_Y) ? (int)(d.ny / 2) : 0, sx = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0;
     const double inv_m = 1.0 / (double)d.mean_batch;
     const cf *phy = reinterpret_cast<const cf*>(P->fph[0].p), *phx = reinterpret_cast<const cf*>(P->fph[1].p);
-    if (d.out_mode == XRFTHIP_OUT_CROSS) { auto k = &mean_finish_kernel<true>; XRFT_LAUNCH(k, grid, blk, 0, st, part, out, (int)d.ny, (int)d.nx, P->mean_P, inv_m, sy, sx, phy, phx, (P->fph_on && phy && phx) ? 1 : 0); }
+    if (P->coherence) { auto k = &mean_finish_coherence_kernel; XRFT_LAUNCH(k, grid, blk, 0, st, part, reinterpret_cast<float*>(out), (int)d.ny, (int)d.nx, P->mean_P, sy, sx); }  // (1 / M and the phase factors cancel)
+    else if (d.out_mode == XRFTHIP_OUT_CROSS) { auto k = &mean_finish_kernel<true>; XRFT_LAUNCH(k, grid, blk, 0, st, part, out, (int)d.ny, (int)d.nx, P->mean_P, inv_m, sy, sx, phy, phx, (P->fph_on && phy && phx) ? 1 : 0); }
     else { auto k = &mean_finish_kernel<false>; XRFT_LAUNCH(k, grid, blk, 0, st, part, out, (int)d.ny, (int)d.nx, P->mean_P, inv_m, sy, sx, phy, phx, 0); }
     prof_end(rec, st);
     HIP_TRY(hipGetLastError());
@@ -912,7 +914,15 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (d.batch < 0 || d.nx < 1 || d.ny < 1 || (d.ndim == 1 && d.ny != 1)) return XRFTHIP_BAD_ARG;
     if (d.nx > (1LL << 30) || d.ny > (1LL << 30) || d.nx * d.ny > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;  // per-element index math is 32-bit
     if (d.dtype < XRFTHIP_F32 || d.dtype > XRFTHIP_C128) return XRFTHIP_BAD_ARG;
-    if (d.out_mode < XRFTHIP_OUT_COMPLEX || d.out_mode > XRFTHIP_OUT_PHASE) return XRFTHIP_BAD_ARG;
+    if (dcopy.out_mode < XRFTHIP_OUT_COMPLEX || dcopy.out_mode > XRFTHIP_OUT_COHERENCE) return XRFTHIP_BAD_ARG;
+    // XRFTHIP_OUT_COHERENCE: |<F0 conj F1>|^2 / (<|F0|^2> <|F1|^2>) over every mean_batch slabs.  It exists only as a mean plan (of one spectrum it is 1 everywhere, and
+    // M = 1 was normalised to the plain plan above).  From here on the descriptor says XRFTHIP_OUT_CROSS -- every check, every table, the family, the workspace in front of
+    // the partial sums and the column pass are the CROSS mean plan's -- and `coherence` remembers what the row pass sums; it is served by FastY's two passes only (finalize_plan)
+    const bool coherence = dcopy.out_mode == XRFTHIP_OUT_COHERENCE;
+    if (coherence) {
+        if (dcopy.mean_batch <= 1) return XRFTHIP_BAD_ARG;
+        dcopy.out_mode = XRFTHIP_OUT_CROSS;
+    }
     if ((d.flags & (XRFTHIP_INVERSE | XRFTHIP_C2R_X | XRFTHIP_PHASE_IN)) && (d.dtype < XRFTHIP_C64 || d.out_mode != XRFTHIP_OUT_COMPLEX || d.detrend)) return XRFTHIP_BAD_ARG;
     if ((d.flags & XRFTHIP_C2R_X) && (!(d.flags & XRFTHIP_INVERSE) || (d.nx & 1) || (d.flags & (XRFTHIP_ISHIFT_X | XRFTHIP_FLIP_X)))) return XRFTHIP_BAD_ARG;
     if (d.detrend < XRFTHIP_DETREND_NONE || d.detrend > XRFTHIP_DETREND_LINEAR) return XRFTHIP_BAD_ARG;
@@ -973,6 +983,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     P->tune_max_grid = env_ll("XRFTHIP_MAX_GRID", 8 * kCUs * 4);
     P->cplx_in = cplx_in;
     P->in16 = in16;
+    P->coherence = coherence;
     P->dbl = d.dtype == XRFTHIP_F64 || d.dtype == XRFTHIP_C128;
     P->rsize = P->dbl ? 8 : 4;
     P->csize = 2 * P->rsize;
@@ -1164,7 +1175,7 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
     const xrfthip_desc& d = plan->d;
     if (!inner_layout(plan))  // (FusedInner / Composite: a header of their own)
         appendf(s, "xrfthip plan: ndim=%d batch=%lld ny=%lld nx=%lld dtype=%d mode=%d detrend=%d flags=0x%x width=%lld nx_out=%lld mirror=%d group=%d ws=%zuB\n",
-                d.ndim, (long long)d.batch, (long long)d.ny, (long long)d.nx, d.dtype, d.out_mode, d.detrend, d.flags,
+                d.ndim, (long long)d.batch, (long long)d.ny, (long long)d.nx, d.dtype, plan->coherence ? (int)XRFTHIP_OUT_COHERENCE : (int)d.out_mode, d.detrend, d.flags,
                 plan->width, plan->nx_out, (int)plan->mirror, plan->G, plan->ws_bytes);
     // a strided plan: said on the line of the pass that reads the caller's input, by every family that family_reads_strided() names (empty on a dense plan)
     std::string in_note_;
@@ -1176,6 +1187,9 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
         appendf(s, "  [mean over the batch] mean_batch=%lld: %lld outputs, each the mean of %lld consecutive slabs summed inside the last pass (at most %d float32 terms in a row, then "
                    "float64), P=%d runs per output (run=%lld slabs at most per workgroup) with a float64 partial each (%zuB of the workspace), summed in order and written once by mean_finish; the spectra of the single slabs are never stored\n",
                 (long long)d.mean_batch, (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, kMeanChain, plan->mean_P, plan->mean_run, plan->ws_bytes - plan->off_mean);
+    if (mean_plan(plan) && plan->coherence)
+        appendf(s, "  [coherence] the partial holds re C, im C, A, B per sample (C = sum F0 conj F1, A = sum |F0|^2, B = sum |F1|^2); mean_finish writes |C|^2 / (A B), real, "
+                   "no clamp; scale, 1 / M and the phase tables cancel\n");
     if (!inner_layout(plan)) {
         describe_passes(s, plan->passes_f0, "f0");
         describe_passes(s, plan->passes, "main");

@@ -116,7 +116,7 @@ class SpectralPlan:
         if self._pass1 is None:
             nb = int(self._dll.xrfthip_plan_pass1_bytes(self._h))
             sigs = []
-            for f in range((2 if self.out_mode in (_lib.OUT_CROSS, _lib.OUT_PHASE) else 1) if nb else 0):
+            for f in range((2 if self.out_mode in (_lib.OUT_CROSS, _lib.OUT_PHASE, _lib.OUT_COHERENCE) else 1) if nb else 0):
                 sig = C.c_uint64(0)
                 _lib.check(self._dll.xrfthip_plan_pass1_signature(self._h, f, C.byref(sig)))
                 sigs.append(int(sig.value))
@@ -139,7 +139,7 @@ class SpectralPlan:
         return out
 
     def out_dtype(self):
-        real = self.out_mode in (_lib.OUT_POWER, _lib.OUT_PHASE) or (self.flags & _lib.C2R_X)
+        real = self.out_mode in (_lib.OUT_POWER, _lib.OUT_PHASE, _lib.OUT_COHERENCE) or (self.flags & _lib.C2R_X)
         return _REAL_OF[self.dtype] if real else _CPLX_OF[self.dtype]
 
     def _layout_ok(self, t):
@@ -163,7 +163,7 @@ class SpectralPlan:
         nx_in = self.nx // 2 + 1 if (self.flags & _lib.C2R_X) else self.nx
         if in0.dtype != self.dtype or not self._layout_ok(in0) or in0.numel() != self.batch * self.ny * nx_in * self.inner * self.mid:
             raise ValueError("in0 does not match the plan (dtype / contiguity / size)")
-        if self.out_mode in (_lib.OUT_CROSS, _lib.OUT_PHASE):
+        if self.out_mode in (_lib.OUT_CROSS, _lib.OUT_PHASE, _lib.OUT_COHERENCE):
             if in1 is None or in1.dtype != self.dtype or not self._layout_ok(in1) or in1.numel() != in0.numel():
                 raise ValueError("in1 does not match the plan")
         want_out = not (self.flags & _lib.NO_SPECTRUM_OUT)
@@ -497,6 +497,21 @@ def angle(a):
     a = a.contiguous()
     out = torch.empty(a.shape, dtype=torch.float32 if a.dtype == torch.complex64 else torch.float64, device=a.device)
     _lib.check(dll.xrfthip_angle(_DTYPES[a.dtype], a.numel(), _ptr(a), _ptr(out), _stream_handle(a)))
+    return out
+
+
+def coherence(cross, p0, p1):
+    """|cross|^2 / (p0 p1) of an averaged cross spectrum (complex) and the two averaged power spectra (real, the matching precision): the magnitude-squared
+    coherence where it is composed of three mean spectra.  No clamp; a zero denominator gives what IEEE division gives."""
+    dll = _lib.load()
+    if not cross.is_complex():
+        raise ValueError("coherence needs a complex cross spectrum")
+    real_dt = torch.float32 if cross.dtype == torch.complex64 else torch.float64
+    if p0.shape != cross.shape or p1.shape != cross.shape or p0.dtype != real_dt or p1.dtype != real_dt or p0.device != cross.device or p1.device != cross.device:
+        raise ValueError(f"coherence needs two {real_dt} power spectra of the cross spectrum's shape on its device")
+    cross, p0, p1 = cross.contiguous(), p0.contiguous(), p1.contiguous()
+    out = torch.empty(cross.shape, dtype=real_dt, device=cross.device)
+    _lib.check(dll.xrfthip_coherence(_DTYPES[cross.dtype], cross.numel(), _ptr(cross), _ptr(p0), _ptr(p1), _ptr(out), _stream_handle(cross)))
     return out
 
 
