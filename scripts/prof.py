@@ -2,7 +2,6 @@
 """scripts/prof.py -- ONE parametrised per-kernel profiler for the GPU box (replaces the prof_*.py family of rounds 2-5).
 
     python scripts/prof.py call  <fn> <nt,ny,nx[,dtype]> [key=value ...] [--lib path.so] [--env K=V ...] [--reps N]
-    python scripts/prof.py iso          old vs new radial-sum row kernel (XRFTHIP_ISOROWS = 0 | 1), and its phase clocks (= 2)
     python scripts/prof.py headline [--lib path.so]   the headline call, wall + per-kernel us per slab (A/B of two builds on one box)
     python scripts/prof.py c2           dft / power_spectrum of (1024, 65536) float32 rows, per kernel
 
@@ -133,66 +132,6 @@ def cmd_call(a):
     print("   " + plan.describe().strip().replace("\n", "\n   "))
 
 
-def cmd_iso(a):
-    """profiles/r06_tune_iso.txt: fasty_rows_kernel<.., ISO> (XRFTHIP_ISOROWS=0) against fasty_isorows_kernel (1), then the phase clocks (2)."""
-    setup(a.lib, a.env)
-    import numpy as np
-    import torch
-
-    import xrft_amd as xrft
-    from xrft_amd import api
-
-    for name, n, nt, two, det in (("isotropic_power_spectrum 4096^2", 4096, 32, False, None), ("isotropic_power_spectrum 4096^2 linear", 4096, 32, False, "linear"),
-                                  ("isotropic_power_spectrum 2048^2", 2048, 64, False, None), ("isotropic_cross_spectrum 2048^2", 2048, 64, True, None),
-                                  ("isotropic_cross_spectrum 2048^2 linear", 2048, 64, True, "linear"), ("isotropic_power_spectrum 1024^2", 1024, 256, False, None)):
-        d1, d2 = make((nt, n, n), "float32", two)
-        fn = (lambda: xrft.isotropic_cross_spectrum(d1, d2, dim=["y", "x"], window="hann", detrend=det)) if two else \
-             (lambda: xrft.isotropic_power_spectrum(d1, dim=["y", "x"], window="hann", detrend=det))
-        print(f"== {name}, {nt} slabs; us per slab", flush=True)
-        res = {}
-        for mode, label in (("0", "fasty_rows_kernel<ISO> (round 5)"), ("1", "fasty_isorows_kernel (persistent, prefetch)")):
-            os.environ["XRFTHIP_ISOROWS"] = mode
-            api.clear_plan_cache()
-            wall, kern, _plan = timed(fn, nt, a.reps)
-            line(label, wall, kern, n * n)
-            res[mode] = np.asarray(fn().values)
-        print(f"  results bit-identical between the two kernels: {np.array_equal(res['0'], res['1'])}; repeats of the new one bit-identical: "
-              f"{np.array_equal(res['1'], np.asarray(fn().values))}", flush=True)
-        os.environ["XRFTHIP_ISOROWS"] = "2"  # the profiling build of the kernel prints its phase clocks on stderr after every launch
-        api.clear_plan_cache()
-        sys.stderr.flush()
-        fn(); torch.cuda.synchronize()
-        fn(); torch.cuda.synchronize()
-        os.environ["XRFTHIP_ISOROWS"] = "1"
-        api.clear_plan_cache()
-        del d1, d2
-        torch.cuda.empty_cache()
-
-
-def cmd_isoq(a):
-    """the new row kernel only (XRFTHIP_ISOROWS=1), then its phase clocks (=2), under whatever XRFTHIP_YTUNE the caller set: tuning sweeps"""
-    setup(a.lib, a.env)
-    import torch
-
-    import xrft_amd as xrft
-    from xrft_amd import api
-
-    for name, n, nt, two in (("iso PS 4096^2", 4096, 32, False), ("iso PS 2048^2", 2048, 64, False), ("iso CS 2048^2", 2048, 64, True)):
-        d1, d2 = make((nt, n, n), "float32", two)
-        fn = (lambda: xrft.isotropic_cross_spectrum(d1, d2, dim=["y", "x"], window="hann")) if two else (lambda: xrft.isotropic_power_spectrum(d1, dim=["y", "x"], window="hann"))
-        os.environ["XRFTHIP_ISOROWS"] = "1"
-        api.clear_plan_cache()
-        wall, kern, _plan = timed(fn, nt, a.reps)
-        line(name, wall, kern, n * n)
-        os.environ["XRFTHIP_ISOROWS"] = "2"
-        api.clear_plan_cache()
-        fn(); torch.cuda.synchronize()
-        os.environ["XRFTHIP_ISOROWS"] = "1"
-        api.clear_plan_cache()
-        del d1, d2
-        torch.cuda.empty_cache()
-
-
 def cmd_headline(a):
     setup(a.lib, a.env)
     import numpy as np
@@ -228,7 +167,7 @@ def cmd_c2(a):
 def main():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("call", "iso", "isoq", "headline", "c2"):
+    for name in ("call", "headline", "c2"):
         sp = sub.add_parser(name)
         sp.add_argument("--lib", default=None)
         sp.add_argument("--env", action="append", default=[])
@@ -240,7 +179,7 @@ def main():
         if name == "headline":
             sp.add_argument("--nt", type=int, default=64)
     a = ap.parse_args()
-    {"call": cmd_call, "iso": cmd_iso, "isoq": cmd_isoq, "headline": cmd_headline, "c2": cmd_c2}[a.cmd](a)
+    {"call": cmd_call, "headline": cmd_headline, "c2": cmd_c2}[a.cmd](a)
 
 
 if __name__ == "__main__":

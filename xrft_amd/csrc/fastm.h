@@ -109,16 +109,12 @@ template <typename T, int N, int GOV = 0> struct MGeom {
     static constexpr int STR = ((N + N / PQ + 3) / 8) * 8 + 4;  // the smallest s >= N + N / PQ with s = 4 (mod 8)
     static constexpr size_t CS = 2 * sizeof(T);
     // sequences per workgroup: as many (a power of two) as keep three workgroups on a CU
-#ifndef XRFT_M_LDSCAP
-#define XRFT_M_LDSCAP (N >= 1800 ? 78 * 1024 : 52 * 1024)  /* three workgroups per CU; two for the long sequences (a pair of 2000-point complex128 sequences is 70 KB) */
-#endif
-    // (at most 4: 8 columns per workgroup divide every length of the table; and at most XRFT_M_MAXTHR threads: one butterfly per thread and pass.
+    static constexpr size_t LDSCAP = N >= 1800 ? 78 * 1024 : 52 * 1024;  // three workgroups per CU; two for the long sequences (a pair of 2000-point complex128 sequences is 70 KB)
+    // (at most 4: 8 columns per workgroup divide every length of the table; and at most MAXTHR threads: one butterfly per thread and pass.
     // 640 until the lengths 1800 ... 2160 joined: four float32 sequences of them fit the LDS, and 16-byte row segments -- two sequences --
     // load at half the rate of 32-byte ones: (64, 2000, 2000) float32 pass 1 12.5 us per slab for 6 us of bytes)
-#ifndef XRFT_M_MAXTHR
-#define XRFT_M_MAXTHR 640
-#endif
-    static constexpr int G0 = ((size_t)4 * STR * CS <= XRFT_M_LDSCAP && 4 * BMAX <= XRFT_M_MAXTHR) ? 4 : (size_t)2 * STR * CS <= XRFT_M_LDSCAP ? 2 : 1;
+    static constexpr int MAXTHR = 640;
+    static constexpr int G0 = ((size_t)4 * STR * CS <= LDSCAP && 4 * BMAX <= MAXTHR) ? 4 : (size_t)2 * STR * CS <= LDSCAP ? 2 : 1;
     static constexpr int G = GOV > 0 ? GOV : G0;
     static constexpr int THR = ((G * BMAX + 63) / 64) * 64;
     static constexpr size_t LDS_ROWS = ((size_t)G * STR + M0) * CS;                                    // sequences + pass-1 twiddles
@@ -128,10 +124,8 @@ template <typename T, int N, int GOV = 0> struct MGeom {
     // pass 2, one field: sequences (= rows) per workgroup, its threads, LDS and launch bound.  Half of pass 1's (but whole lines of
     // W2: >= 2 rows): its reads and writes are contiguous whatever the count, and six small workgroups per CU interleave their
     // load / transform / store phases better than three (C5 row pass 4.22 -> 3.74 us per slab)
-#ifndef XRFT_M_ROWS_SHIFT
-#define XRFT_M_ROWS_SHIFT 1
-#endif
-    static constexpr int GR1 = (G >> XRFT_M_ROWS_SHIFT) < 2 ? (G < 2 ? G : 2) : (G >> XRFT_M_ROWS_SHIFT);
+    static constexpr int ROWS_SHIFT = 1;
+    static constexpr int GR1 = (G >> ROWS_SHIFT) < 2 ? (G < 2 ? G : 2) : (G >> ROWS_SHIFT);
     template <int GG> struct Rows {
         static constexpr int THR = ((GG * BMAX + 63) / 64) * 64;
         static constexpr size_t LDS = ((size_t)GG * STR + M0) * CS;
@@ -183,13 +177,8 @@ struct FastM {
     int in_pitch;
 };
 
-// profiling builds (scripts/build_ablate_m.sh, -DXRFT_MDBG=bits; 0 in the product): 1 = the intermediate is written with plain
-// stores, 2 = the result too, 4 = no transforms (passes skipped), 8 = no stores, 16 = no loads of the sequences
-#ifndef XRFT_MDBG
-#define XRFT_MDBG 0
-#endif
-
 // 16-byte store that bypasses the caches' retention (the next reader is another kernel, a whole group of slabs later)
+// (PLAIN: an ordinary store instead, for fastn_irows_kernel, whose pieces of a 128-byte line meet in the L2)
 template <typename T, bool PLAIN = false> __device__ __forceinline__ void mr_store16_nt(void* dst, const void* src16) {
 #ifdef XRFT_EMULATE
     memcpy(dst, src16, 16);
@@ -201,12 +190,11 @@ template <typename T, bool PLAIN = false> __device__ __forceinline__ void mr_sto
 }
 
 // one complex value (16 bytes float64, 8 bytes float32), non-temporal
-template <typename T, bool PLAIN = false> __device__ __forceinline__ void mr_store_ct_nt(void* dst, const C2<T>& v) {
-    if (sizeof(T) == 8) { mr_store16_nt<T, PLAIN>(dst, &v); return; }
+template <typename T> __device__ __forceinline__ void mr_store_ct_nt(void* dst, const C2<T>& v) {
+    if (sizeof(T) == 8) { mr_store16_nt<T>(dst, &v); return; }
 #ifdef XRFT_EMULATE
     memcpy(dst, &v, sizeof(v));
 #else
-    if (PLAIN) { *reinterpret_cast<C2<T>*>(dst) = v; return; }
     typedef float v2f __attribute__((ext_vector_type(2)));
     __builtin_nontemporal_store(*reinterpret_cast<const v2f*>(&v), reinterpret_cast<v2f*>(dst));
 #endif
@@ -379,7 +367,7 @@ __global__ void __launch_bounds__((MGeom<T, NY, GOV>::THR), (MGeom<T, NY, GOV>::
     for (int q = 0; q < R0; ++q) {
         a[q] = mk<T>((T)0, (T)0); wyv[q] = (T)0;
         if (on) {
-            if (!(XRFT_MDBG & 16)) a[q] = *reinterpret_cast<const CT*>(src + (off0 + rstep * (unsigned)q));
+            a[q] = *reinterpret_cast<const CT*>(src + (off0 + rstep * (unsigned)q));
             wyv[q] = wy[j + q * M0];
         }
     }
@@ -429,13 +417,8 @@ __global__ void __launch_bounds__((MGeom<T, NY, GOV>::THR), (MGeom<T, NY, GOV>::
         }
         a[q] = mk<T>(a[q].re * (wyv[q] * wx.re), a[q].im * (wyv[q] * wx.im));
     }
-    if (XRFT_MDBG & 4) {
-        if (on) for (int q = 0; q < R0; ++q) lds[g * STR + M::pn(j + q * M0)] = a[q];
-        __syncthreads();
-    } else {
-        if (on) mr_pass0<T, NY>(a, lds + g * STR, j, w0);
-        mr_fft_tail<T, NY, G, THR>(lds, tid, tw1);
-    }
+    if (on) mr_pass0<T, NY>(a, lds + g * STR, j, w0);
+    mr_fft_tail<T, NY, G, THR>(lds, tid, tw1);
     if (DET && tid < 4 * G) {  // (sum d, sum (i - ibar) d, 0, 0) per column
         const int c = tid / G, gg = tid % G;  // c: 0, 1 = sum d of columns 2gg, 2gg+1; 2, 3 = the first moments
         double acc = 0.0;
@@ -460,7 +443,7 @@ __global__ void __launch_bounds__((MGeom<T, NY, GOV>::THR), (MGeom<T, NY, GOV>::
             const CT zk = z[M::pn(k)], zc = cconj(z[M::pn(k == 0 ? 0 : NY - k)]);
             const CT o = (col & 1) ? cscale(mul_mi(zk - zc), (T)0.5) : cscale(zk + zc, (T)0.5);
             const unsigned off = ((((unsigned)(k >> p.l_rk) * (unsigned)nxb + (unsigned)xb) << p.l_rk) + (unsigned)(k & (rk - 1))) * (unsigned)CW + (unsigned)col;
-            if (!(XRFT_MDBG & 8) || o.re == (T)1.2345) mr_store_ct_nt<T, (XRFT_MDBG & 1) != 0>(w2s + (size_t)off * sizeof(CT), o);
+            mr_store_ct_nt<T>(w2s + (size_t)off * sizeof(CT), o);
         }
     }
 }
@@ -825,7 +808,7 @@ __global__ void __launch_bounds__((MGeom<T, NX>::template Rows<MRowsG<T, NX, MOD
         if (live) {
             const int x = j + q * M0;
             // element (ky, x) of the block [x / CW][ky % RK][x % CW]
-            if (!(XRFT_MDBG & 16)) a[q] = blk[((((x >> p.l_cw) << p.l_rk) + (ky & (rk - 1))) << p.l_cw) + (x & cwm)];
+            a[q] = blk[((((x >> p.l_cw) << p.l_rk) + (ky & (rk - 1))) << p.l_cw) + (x & cwm)];
             if (addback) c[q] = cr[x];
         }
     }
@@ -836,13 +819,8 @@ __global__ void __launch_bounds__((MGeom<T, NX>::template Rows<MRowsG<T, NX, MOD
             a[q].im = fma(c[q].re, h0.im, fma(c[q].im, h1.im, a[q].im));
         }
     }
-    if (XRFT_MDBG & 4) {
-        if (on) for (int q = 0; q < R0; ++q) lds[t * STR + M::pn(j + q * M0)] = a[q];
-        __syncthreads();
-    } else {
-        if (on) mr_pass0<T, NX>(a, lds + t * STR, j, w0);
-        mr_fft_tail<T, NX, G, THR>(lds, tid, tw1);
-    }
+    if (on) mr_pass0<T, NX>(a, lds + t * STR, j, w0);
+    mr_fft_tail<T, NX, G, THR>(lds, tid, tw1);
     const int sx = p.shift_x, sy = p.shift_y;
     const T sc = (T)p.scale;
     if (ISO) {
@@ -1028,7 +1006,7 @@ __global__ void __launch_bounds__((MGeom<T, NX>::template Rows<MRowsG<T, NX, MOD
                 else reinterpret_cast<CT*>(o)[i] = va;
             }
         }
-        if (!(XRFT_MDBG & 8) || reinterpret_cast<T*>(o)[0] == (T)1.2345) mr_store16_nt<T, (XRFT_MDBG & 2) != 0>(outs + (size_t)orow * NX + c, o);
+        mr_store16_nt<T>(outs + (size_t)orow * NX + c, o);
     }
 }
 

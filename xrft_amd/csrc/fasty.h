@@ -37,68 +37,6 @@ __device__ __forceinline__ void xrft_store_nt(float* dst, F4 v) {
 #endif
 }
 
-// FastY::tune (XRFTHIP_YTUNE, read once at plan creation): cache policies of the four streams and a start stagger, kept as knobs
-// because the right setting is a property of the memory system, measured (scripts/tune_yf.py -> profiles/r03_tune_yf.txt):
-//   bits 0-1  pass 1, stores of the intermediate: 0 non-temporal, 1 plain, 2 write-through (sc1)
-//   bit  2    pass 1, loads of the input non-temporal
-//   bit  3    pass 2, loads of the intermediate non-temporal
-//   bit  4    pass 2, stores of the result plain instead of non-temporal
-//   bit  21   pass 1: the workgroups that share the input's 128-byte lines (consecutive column blocks of one XCD) meet on a counter
-//             before they load, with a time-out (round 4: does the 1.45x input over-fetch go away when the sharers load together?)
-//   bits 8-15 the second workgroup of every CU (blocks 256..511 of a launch) starts n x 3.4 us late: the two residents of a CU
-//             then run their load / transform / store phases out of step for the whole launch
-// The product build compiles the default in (a run-time policy in the store loops costs the column kernel a spilled register);
-// scripts/build_tune_yf.sh builds a second library with -DXRFT_YTUNE_RT whose kernels read FastY::tune, for scripts/tune_yf.py.
-constexpr long long kYTuneDefault = 0;
-#ifdef XRFT_YTUNE_RT
-#define XRFT_YTUNE(p) ((p).tune)
-#else
-#define XRFT_YTUNE(p) ((int)kYTuneDefault)
-#endif
-
-// 16-byte store at base + off with a run-time cache policy: 0 non-temporal, 1 plain, 2 write-through to memory (sc1; `base` must be
-// wave-uniform: it becomes the buffer descriptor -- a per-lane base is a 64-iteration waterfall loop, 154 us per slab)
-__device__ __forceinline__ void xrft_store_pol(char* base, unsigned off, F4 v, int pol) {
-#ifdef XRFT_EMULATE
-    *reinterpret_cast<F4*>(base + off) = v;
-#else
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    const v4f t = {v.x, v.y, v.z, v.w};
-    if (pol == 0) __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(base + off));
-    else if (pol == 1) *reinterpret_cast<v4f*>(base + off) = t;
-    else __builtin_amdgcn_raw_buffer_store_b128(t, __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000), (int)off, 0, 16);
-#endif
-}
-__device__ __forceinline__ F4 xrft_load_pol(const char* src, bool nt) {
-#ifdef XRFT_EMULATE
-    return *reinterpret_cast<const F4*>(src);
-#else
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    if (!nt) return *reinterpret_cast<const F4*>(src);
-    const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src));
-    F4 r; r.x = t.x; r.y = t.y; r.z = t.z; r.w = t.w;
-    return r;
-#endif
-}
-__device__ __forceinline__ cf xrft_load8_pol(const char* src, bool nt) {
-#ifdef XRFT_EMULATE
-    return *reinterpret_cast<const cf*>(src);
-#else
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    if (!nt) return *reinterpret_cast<const cf*>(src);
-    const v2f t = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(src));
-    return mk<float>(t.x, t.y);
-#endif
-}
-// start stagger (FastY::tune bits 8-15): blocks 256..511 = the second resident of every CU at launch start
-__device__ __forceinline__ void xrft_stagger(int tune) {
-#ifndef XRFT_EMULATE
-    const int n = (tune >> 8) & 0xff;
-    if (n && blockIdx.x >= 256u && blockIdx.x < 512u)
-        for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
-}
-
 struct FastY {
     const float* in;         // [slab][ny][nx] float32
     cf* w2;                  // intermediate, see above
@@ -135,26 +73,14 @@ struct FastY {
     int nslab;
     int shift_y, shift_x;    // 0 or n/2
     float scale;
-    int tune;                // see kYTuneDefault
-    long long* tim;          // fasty_isorows_kernel<.., TIM>: [workgroup][8] shader-clock sums of its phases (profiling build only; null otherwise)
-    unsigned* rdv;           // tune bit 21: one arrival counter per (slab, group of the column blocks that share the input's 128-byte lines), zeroed per launch
-    long long in_slab;       // fasty_cols_kernel<.., STR>: elements between the slabs of `in` and between its rows (xrfthip_desc.in_stride_batch / in_stride_y):
+    long long in_slab;      // fasty_cols_kernel<.., STR>: elements between the slabs of `in` and between its rows (xrfthip_desc.in_stride_batch / in_stride_y):
     int in_pitch;            // a box of a larger field read where it lies; the dense kernels never read the two
     int in_bf16;             // fasty_cols_kernel<.., H16>: `in` holds 2-byte samples, bfloat16 (1) or float16 (0) (half_in.h); the float32 kernels never read it
 };
 
-// phase-ablation bits for profiling builds (scripts/gpu_ablate_yf.sh compiles variants with -DXRFT_YDBG=bits); 0 in the product
-#ifndef XRFT_YDBG
-#define XRFT_YDBG 0
-#endif
-
 // geometry of pass 1 for NY-point columns
 template <int NY> struct YCols {
-#ifdef XRFT_YCOLS_WIDE  // (round-6 experiment, scripts/prof.py cols-wide: a 1024-thread workgroup owns 16 columns of a 4096-point slab -- 64-byte row segments, two sharers per input line instead of four)
-    static constexpr int THR = NY >= 4096 ? 1024 : NY >= 2048 ? 512 : 256;
-#else
     static constexpr int THR = NY >= 2048 ? 512 : 256;
-#endif
     static constexpr int NT = NY / 16;
     static constexpr int GY = THR / NT;              // lockstep transform pairs per workgroup: 2, 4, 4, 8, 16
     static constexpr int CW = 4 * GY;                // real columns per workgroup
@@ -176,9 +102,9 @@ template <int N, int GX> struct YLds {
 // that one transform is parked in LDS whenever the other is inside a butterfly (a butterfly needs 32 temporaries on top
 // of its 32 data registers: with both transforms live the kernel would not fit 128 VGPRs).  In / out conventions per
 // transform as fft_p2_group.
-// (fft_p2_pair_w: the first-stage twiddle W_N^u handed in -- a persistent workgroup loads it once)
-template <int N> __device__ __forceinline__ void fft_p2_pair_w(cf* a, cf* b, int u, cf* lds, const cf w1, const cf* tw2) {
+template <int N> __device__ __forceinline__ void fft_p2_pair(cf* a, cf* b, int u, cf* lds, const cf* __restrict__ tw, const cf* tw2) {
     typedef P2<N> G;
+    const cf w1 = tw[u];  // W_N^u
     const int k1 = u / G::R3, v = u % G::R3;
     dft16(a);
     twiddle16(a, w1);
@@ -233,10 +159,6 @@ template <int N> __device__ __forceinline__ void fft_p2_pair_w(cf* a, cf* b, int
     __syncthreads();
 }
 
-template <int N> __device__ __forceinline__ void fft_p2_pair(cf* a, cf* b, int u, cf* lds, const cf* __restrict__ tw, const cf* tw2) {
-    fft_p2_pair_w<N>(a, b, u, lds, tw[u], tw2);  // W_N^u
-}
-
 // slot of frequency k held as element (bb, k3) by thread u after fft_p2_group / fft_p2_pair
 template <int N> __device__ __forceinline__ int held_k(int u, int bb, int k3) {
     const int pr = u + P2<N>::NT * bb;
@@ -267,7 +189,6 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
     const int tid = threadIdx.x, g = tid % GY, u = tid / GY;
     cf* mine = lds + g * GSTR;
     cf* tw2 = lds + GY * GSTR;
-    xrft_stagger(XRFT_YTUNE(p));
     fill_tw2<NY>(tw2, p.tw_y, tid, THR);
     // unit = (slab, column block).  Blocks b, b+8, b+16, ... run on one XCD (round-robin dispatch): give each XCD a
     // contiguous range of column blocks, so that the workgroups sharing a 128-byte line of the input share an L2.
@@ -276,34 +197,10 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
     if ((nxb & 7) == 0) {
         const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3, per = nxb >> 3;
         slab = j / per;
-        int jj = j % per;
-        // (tuning build: where the four sharers of a line go.  Workgroups k and k + 32 of an XCD land on one CU in the first round of
-        // a launch -- scripts/ubench/cuid.hip -- so sharers 16 or 32 apart share an L1 while they stay in step)
-        const int mp = (XRFT_YTUNE(p) >> 19) & 3;
-        if (mp == 1 && (per & 3) == 0) jj = (jj % (per >> 2)) * 4 + jj / (per >> 2);
-        else if (mp == 2 && per == 64) jj = ((jj & 31) >> 1) * 4 + (jj & 1) * 2 + (jj >> 5);
-        xb = xcd * per + jj;
+        xb = xcd * per + j % per;
     } else {
         slab = blockIdx.x / nxb;
         xb = blockIdx.x % nxb;
-    }
-    if ((XRFT_YTUNE(p) >> 21) & 1) {
-#ifndef XRFT_EMULATE
-        // rendezvous of the sharers of a line group: 128 / (4 CW) column blocks, consecutive on one XCD (dispatched in order: at most
-        // one group is partially resident, so the wait cannot deadlock; the time-out is a belt)
-        constexpr int SH = 128 / (4 * Y::CW) > 1 ? 128 / (4 * Y::CW) : 1;
-        if (SH > 1) {
-            if (tid == 0) {
-                unsigned* ctr = p.rdv + (size_t)slab * (nxb / SH) + xb / SH;
-                __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                for (int it = 0; it < 4000; ++it) {
-                    if (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)SH) break;
-                    __builtin_amdgcn_s_sleep(2);
-                }
-            }
-            __syncthreads();
-        }
-#endif
     }
     const int x0 = xb * Y::CW + 4 * g;
     // uniform 64-bit base + one 32-bit per-lane byte offset (a slab is < 4 GB): scalar-base loads, no 64-bit address per row
@@ -348,8 +245,10 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
         }
     }
     F4 raw[16];
+    // plain loads: four workgroups share each 128-byte line of the input and must find it in L2 (non-temporal loads: column pass
+    // 47 against 30 us per 4096^2 slab, profiles/r03_tune_yf.txt)
 #pragma unroll
-    for (int q = 0; q < 16; ++q) raw[q] = H16 ? xrft_load4_h16(src + (off0 + rstep * (unsigned)q), p.in_bf16) : xrft_load_pol(src + (off0 + rstep * (unsigned)q), (XRFT_YTUNE(p) & 4) != 0);
+    for (int q = 0; q < 16; ++q) raw[q] = H16 ? xrft_load4_h16(src + (off0 + rstep * (unsigned)q), p.in_bf16) : *reinterpret_cast<const F4*>(src + (off0 + rstep * (unsigned)q));
     if (DET) {
         auto med3 = [](float x, float y, float z) { return fmaxf(fminf(x, y), fminf(fmaxf(x, y), z)); };
         const float mt[4] = {med3(rt[0].x, rt[1].x, rt[2].x), med3(rt[0].y, rt[1].y, rt[2].y), med3(rt[0].z, rt[1].z, rt[2].z), med3(rt[0].w, rt[1].w, rt[2].w)};
@@ -434,7 +333,7 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
             for (int c = 0; c < 8; ++c) part[((tid >> 6) * GY + g) * 8 + c] = (double)v[c];
         }
     }
-    if (!(XRFT_YDBG & 32)) fft_p2_pair<NY>(a, b, u, mine, p.tw_y, tw2);
+    fft_p2_pair<NY>(a, b, u, mine, p.tw_y, tw2);
     // (the lane indices are re-derived from an opaque copy of the thread index: carried from the top of the kernel through the
     // transforms they were spilled -- 3 dwords per lane = 3 MB of scratch traffic per 4096^2 slab each way)
     int tid2 = threadIdx.x;
@@ -469,8 +368,10 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
                 const unsigned off = ((((unsigned)(k / Y::RK) * (unsigned)nxb + (unsigned)xb) * 2u + set) * Y::LBS) + (k % Y::RK) * (2 * GY) + 2 * g2;
                 F4 o; o.x = ra.re; o.y = ra.im; o.z = rb.re; o.w = rb.im;
                 // non-temporal: the next reader is another kernel, a whole group of slabs later; kept out of L2 the lines leave
-                // it to the input, whose 128-byte lines are shared by four workgroups (PMC: 1.34x over-fetch with plain stores)
-                if (!(XRFT_YDBG & 64) || o.x == 1.2345f) xrft_store_pol(w2s, off * 8u, o, XRFT_YTUNE(p) & 3);
+                // it to the input, whose 128-byte lines are shared by four workgroups (PMC: 1.34x over-fetch with plain stores; plain
+                // and write-through stores measured level in time, profiles/r03_tune_yf.txt).  `w2s` is wave-uniform, the per-lane
+                // part a 32-bit offset (a per-lane 64-bit base in a buffer store was a 64-iteration waterfall loop, 154 us per slab).
+                xrft_store_nt(reinterpret_cast<float*>(w2s + off * 8u), o);
             }
         }
         if (set == 0) __syncthreads();
@@ -550,12 +451,12 @@ template <int NRW> __device__ __forceinline__ double quad_rows_sum(double v) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The per-bin gather of the radial sums (xrft.py:895-906) from rows staged in LDS, shared by fasty_rows_kernel<.., ISO> and
-// fasty_isorows_kernel (fasty_iso.h).  Step (1) of those kernels left the sum of every run of equal bins of a 16-sample segment on
+// The per-bin gather of the radial sums (xrft.py:895-906) from rows staged in LDS, for fasty_rows_kernel<.., ISO>.
+// Step (1) of that kernel left the sum of every run of equal bins of a 16-sample segment on
 // the run's last sample; here the owner of a (bin, row) walks the bin's two kx ranges of that row, one staged value per segment it
 // touches, and adds them in float64 in a fixed order (+kx side by rising segment, then the -kx side); the NRW rows of a bin are
-// adjacent lanes of a quad and meet in lane order.  The phase is a chain of LDS latencies, not of work (measured with the profiling
-// build of fasty_isorows_kernel: 7900 shader cycles per unit of four 4096-sample rows with a branch and a wait per read, 5600 so):
+// adjacent lanes of a quad and meet in lane order.  The phase is a chain of LDS latencies, not of work (measured with phase
+// clocks, profiles/r06_tune_iso.txt: 7900 shader cycles per unit of four 4096-sample rows with a branch and a wait per read, 5600 so):
 // the first two segments of either side of KB sweeps are read up front with UNCONDITIONAL, masked reads (a bin narrower than 16
 // samples touches no more), the few lanes whose bin hugs |k| = ky walk on four reads per trip, and the rows of a bin are added by DPP
 // quad permutes instead of trips through the LDS crossbar.
@@ -593,7 +494,7 @@ __device__ __forceinline__ void radial_walk(const float* rowp, int seg0, int lim
 
 template <int NX, int NRW, int CPS, int BPI, int KB>
 __device__ __forceinline__ void radial_gather_batch(const float* rowp, int row, bool live, bool twin, int blo, int bhi, int k0, int kn, const unsigned* rg,
-                                                int blane, double* __restrict__ part, bool store) {
+                                                int blane, double* __restrict__ part) {
     constexpr bool TWO = CPS == 2;
     constexpr int HW = TWO ? 2 : 1;
     auto walk = [&](int seg0, int lim, double& sre, double& sim) { radial_walk<NX, CPS>(rowp, seg0, lim, sre, sim); };
@@ -650,7 +551,7 @@ __device__ __forceinline__ void radial_gather_batch(const float* rowp, int row, 
         if (twin) { sre *= 2.0; sim = 0.0; }  // V + conj V (a power spectrum's two samples are equal)
         sre = quad_rows_sum<NRW>(sre);  // rows 0 .. NRW - 1 in a fixed tree order: (r0 + r1) + (r2 + r3)
         if (TWO) sim = quad_rows_sum<NRW>(sim);
-        if (row == 0 && bn < bhi && store) {
+        if (row == 0 && bn < bhi) {
             part[bn * HW] = sre;
             if (TWO) part[2 * bn + (TWO ? 1 : 0)] = sim;
         }
@@ -686,7 +587,6 @@ __global__ void __launch_bounds__((YRows<NX, FS>::THR), ((ISO && YRows<NX, FS>::
     cf* mine = lds + g * GSTR;
     cf* tw2 = lds + GX * GSTR;
     // (the radial-sum tables alias the transforms' LDS: a separate 12-20 KB would cost the second workgroup per CU)
-    xrft_stagger(XRFT_YTUNE(p));
     fill_tw2<NX>(tw2, p.tw_x, tid, THR);
     const int nyh = p.ny >> 1;
     // FS: rows 0 .. ny/2 - 1 fill whole units; the Nyquist rows (k1 = ny/2) of GX consecutive slabs share one extra unit (transform A
@@ -702,7 +602,7 @@ __global__ void __launch_bounds__((YRows<NX, FS>::THR), ((ISO && YRows<NX, FS>::
     const char* __restrict__ w2s = reinterpret_cast<const char*>(p.w2 + (size_t)slab * p.nrow_pad * NX);
     const char* __restrict__ w2t = TWO ? reinterpret_cast<const char*>(p.w2b + (size_t)slab * p.nrow_pad * NX) : w2s;
     const char* __restrict__ crb = reinterpret_cast<const char*>(p.corr + (size_t)slab * NX * 2);
-    const bool addback = p.detrend && !(XRFT_YDBG & 1);
+    const bool addback = p.detrend != 0;
     cf cr[16];
     if (addback) {
 #pragma unroll
@@ -710,13 +610,13 @@ __global__ void __launch_bounds__((YRows<NX, FS>::THR), ((ISO && YRows<NX, FS>::
     }
     const unsigned offA = w2_offset(p, kyA, u) * 8u, offB = w2_offset(p, kyB, u) * 8u;
     cf a[16], b[16];
-    const bool ntw = (XRFT_YTUNE(p) & 8) != 0;
+    // (plain loads of the intermediate: non-temporal ones measured level, profiles/r03_tune_yf.txt)
     if (NT >= (1 << p.l_cw)) {  // x = u + NT q advances by whole column blocks: constant stride
         const unsigned qstr = (unsigned)(((NT >> p.l_cw) * 2) << (p.l_rk + p.l_2gy)) * 8u;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            a[q] = xrft_load8_pol(w2s + (offA + qstr * (unsigned)q), ntw);
-            b[q] = xrft_load8_pol(w2t + (offB + qstr * (unsigned)q), ntw);
+            a[q] = *reinterpret_cast<const cf*>(w2s + (offA + qstr * (unsigned)q));
+            b[q] = *reinterpret_cast<const cf*>(w2t + (offB + qstr * (unsigned)q));
         }
     } else {
 #pragma unroll
@@ -769,7 +669,7 @@ __global__ void __launch_bounds__((YRows<NX, FS>::THR), ((ISO && YRows<NX, FS>::
 #pragma unroll
         for (int q = 0; q < 16; ++q) { a[q] = cmul(a[q], ba); b[q] = cmul(b[q], bb_); }
     }
-    if (!(XRFT_YDBG & 4)) fft_p2_pair<NX>(a, b, u, mine, p.tw_x, tw2);
+    fft_p2_pair<NX>(a, b, u, mine, p.tw_x, tw2);
     if (TWO) {  // F0 conj(F1) * scale, in place of transform A (xrft.py:825)
 #pragma unroll
         for (int e = 0; e < 16; ++e) a[e] = cscale(cmulc(a[e], b[e]), p.scale);
@@ -811,7 +711,7 @@ __global__ void __launch_bounds__((YRows<NX, FS>::THR), ((ISO && YRows<NX, FS>::
             const int orow = mir ? ((p.ny - ky) + p.shift_y) & my : (ky + p.shift_y) & my;
             // non-temporal: the result is not read again, and keeping it out of the caches leaves the Infinity Cache to the
             // intermediate (scripts/ubench/yfirst.hip: 45.8 vs 50.9 us per slab for the two passes at 2 slabs per group)
-            if (!(XRFT_YDBG & 8) || v.x == 1.2345f) xrft_store_pol(reinterpret_cast<char*>(outs), (unsigned)(((size_t)orow * NX + c) * 4u), v, (XRFT_YTUNE(p) >> 4) & 1 ? 1 : 0);
+            xrft_store_nt(reinterpret_cast<float*>(reinterpret_cast<char*>(outs) + (unsigned)(((size_t)orow * NX + c) * 4u)), v);
         }
     };
     // complex rows staged at cbase[rl * RSC + nat16(kx)] (natural order) = the unit's rows r0 .. r0 + nrows - 1 (not the four-step form)
@@ -962,7 +862,7 @@ __global__ void __launch_bounds__((YRows<NX, FS>::THR), ((ISO && YRows<NX, FS>::
                     rg[k] = rn[k];
                     rn[k] = range_of(blo + (k0 + KB + k) * BPI + blane);  // (the next batch's ranges are in flight behind this batch's sums)
                 }
-                radial_gather_batch<NX, NRW, CPS, BPI, KB>(rowp, row, live, twin, blo, bhi, k0, min(nsw - k0, KB), rg, blane, part, true);
+                radial_gather_batch<NX, NRW, CPS, BPI, KB>(rowp, row, live, twin, blo, bhi, k0, min(nsw - k0, KB), rg, blane, part);
             }
             return;
         }
@@ -1008,10 +908,7 @@ __global__ void __launch_bounds__((YRows<NX, FS>::THR), ((ISO && YRows<NX, FS>::
             // this thread's run of L samples of row ky0 + rd NR + rl: bin codes in natural order, (bin + 1) | (mirror bin + 1) << 16
             unsigned codes[L];
             const int kyr = ky0 + rd * NR + rl;
-            if (XRFT_YTUNE(p) & (1 << 16)) {  // (ablation, tuning build: no bin-code loads)
-#pragma unroll
-                for (int i = 0; i < L; ++i) codes[i] = (unsigned)(1 + ((kx0 + i) >> 2)) * 0x10001u;
-            } else if (p.tcodes_compact) {
+            if (p.tcodes_compact) {
                 // A radial bin map is monotone along a half row and moves by at most one bin per sample: 16 samples = the first
                 // one's bin and a mask of the steps (built and verified on the host, fasty_build_tcodes).  4 bytes per 16 samples
                 // instead of 64: the full table (33.6 MB at 4096^2, read once per slab -- loads do not stay in the Infinity Cache --
@@ -1040,27 +937,24 @@ __global__ void __launch_bounds__((YRows<NX, FS>::THR), ((ISO && YRows<NX, FS>::
             // run's last sample, and records its magnitude in the bins it goes to (one atomicMax per run and bin)
             const float* src = sreg + rl * RSI + (MODE == 1 ? 1 : 2) * nat16(kx0);
             float rsr[L], rsi[MODE == 2 ? L : 1];
-            if (!(XRFT_YTUNE(p) & (1 << 17))) {
-                float sr = 0.f, si = 0.f;
+            float sr = 0.f, si = 0.f;
 #pragma unroll
-                for (int i = 0; i < L; ++i) {
-                    if (MODE == 1) sr += src[i];
-                    else { sr += src[2 * i]; si += src[2 * i + 1]; }
-                    rsr[i] = sr;
-                    if (MODE == 2) rsi[i] = si;
-                    const bool last = i == L - 1 || codes[i + 1] != codes[i];
-                    if (last) {
-                        const unsigned cd = codes[i] & 0xffffu, cm = codes[i] >> 16, m = __float_as_uint(fabsf(sr) + fabsf(si));
-                        if (cd) atomicMax(&bmax[cd - 1], m);
-                        if (cm && cm != cd) atomicMax(&bmax[cm - 1], m);
-                        sr = 0.f; si = 0.f;
-                    }
+            for (int i = 0; i < L; ++i) {
+                if (MODE == 1) sr += src[i];
+                else { sr += src[2 * i]; si += src[2 * i + 1]; }
+                rsr[i] = sr;
+                if (MODE == 2) rsi[i] = si;
+                const bool last = i == L - 1 || codes[i + 1] != codes[i];
+                if (last) {
+                    const unsigned cd = codes[i] & 0xffffu, cm = codes[i] >> 16, m = __float_as_uint(fabsf(sr) + fabsf(si));
+                    if (cd) atomicMax(&bmax[cd - 1], m);
+                    if (cm && cm != cd) atomicMax(&bmax[cm - 1], m);
+                    sr = 0.f; si = 0.f;
                 }
             }
             __syncthreads();
             // sweep 2: every run sum converted to int64 fixed point 40 bits below its bin's largest and added with an INTEGER atomic
             // (exact: the order in which lanes arrive does not matter)
-            if (!(XRFT_YTUNE(p) & (1 << 17)))
 #pragma unroll
             for (int i = 0; i < L; ++i) {
                 const bool last = i == L - 1 || codes[i + 1] != codes[i];
@@ -1082,7 +976,6 @@ __global__ void __launch_bounds__((YRows<NX, FS>::THR), ((ISO && YRows<NX, FS>::
             __syncthreads();
             // this round's sums, back in floating point, into the workgroup's row of the partial table (the same thread adds round 2
             // to what it wrote in round 1: a fixed order).  A bin with an inf / nan member is +inf (power) or nan, as IEEE sums are.
-            if (!(XRFT_YTUNE(p) & (1 << 18)))
             for (int i = tid; i < p.nbins * HW; i += THR) {
                 const unsigned bm = bmax[i / HW];
                 double v = ldexp((double)(long long)acc[i], (int)(bm >> 23) - 127 - 40);

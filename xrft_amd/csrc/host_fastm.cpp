@@ -506,13 +506,8 @@ static void fastm_launch_cols(const xrfthip_plan* P, const FastM& p, long long g
     xrfthip_plan::ProfRec* rec = prof_begin(P, rt ? "fastn_cols" : "fastm_cols", st);
     if (rt) fastn_launch_cols(P, p, st);
     const dim3 grid((unsigned)(8 * ((p.nunits + 7) / 8))), blk((unsigned)C.thr);
-#ifdef XRFT_M_BIGLDS  /* profiling builds with more than 64 KB of LDS per workgroup */
-#define MBIG_(k, n) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(n))
-#else
-#define MBIG_(k, n) ((void)0)
-#endif
-#define MCG_(TT, NN, GG, SS) do { if (d.detrend) { auto k = &fastm_cols_kernel<TT, NN, true, GG, SS>; MBIG_(k, C.lds_cols); XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } \
-                                  else { auto k = &fastm_cols_kernel<TT, NN, false, GG, SS>; MBIG_(k, C.lds_cols); XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } } while (0)
+#define MCG_(TT, NN, GG, SS) do { if (d.detrend) { auto k = &fastm_cols_kernel<TT, NN, true, GG, SS>; XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } \
+                                  else { auto k = &fastm_cols_kernel<TT, NN, false, GG, SS>; XRFT_LAUNCH(k, grid, blk, C.lds_cols, st, p); } } while (0)
 #define MC_(TT, NN) do { if (str) MCG_(TT, NN, 0, true); else MCG_(TT, NN, 0, false); } while (0)  /* (str: a box of a larger field, read where it lies) */
 #define XD_(NN) if (P->yny == NN) MC_(double, NN);
 #define XF_(NN) if (P->yny == NN) MC_(float, NN);
@@ -554,7 +549,7 @@ static void fastm_launch_rows(const xrfthip_plan* P, const FastM& p, long long g
     const size_t lds_rows = full ? R.lds_rows : R.lds_r1;
     const size_t lds_iso = p.tfirst ? lds_rows : lds_rows + (size_t)P->nbins * (d.out_mode == XRFTHIP_OUT_CROSS ? 20 : 12) * (size_t)p.iso_ncopy;  // (the gather needs no tables)
 #define MR_(TT, NN) do { \
-        if (d.out_mode == XRFTHIP_OUT_POWER) { if (fused) { auto k = &fastm_rows_kernel<TT, NN, 1, true>; XRFT_LAUNCH(k, grid, blk, lds_iso, st, p); } else { auto k = &fastm_rows_kernel<TT, NN, 1>; MBIG_(k, lds_rows); XRFT_LAUNCH(k, grid, blk, lds_rows, st, p); } } \
+        if (d.out_mode == XRFTHIP_OUT_POWER) { if (fused) { auto k = &fastm_rows_kernel<TT, NN, 1, true>; XRFT_LAUNCH(k, grid, blk, lds_iso, st, p); } else { auto k = &fastm_rows_kernel<TT, NN, 1>; XRFT_LAUNCH(k, grid, blk, lds_rows, st, p); } } \
         else if (d.out_mode == XRFTHIP_OUT_CROSS) { if (fused) { auto k = &fastm_rows_kernel<TT, NN, 2, true>; XRFT_LAUNCH(k, grid, blk, lds_iso, st, p); } else { auto k = &fastm_rows_kernel<TT, NN, 2>; XRFT_LAUNCH(k, grid, blk, R.lds_rows, st, p); } } \
         else if (d.out_mode == XRFTHIP_OUT_PHASE) { auto k = &fastm_rows_kernel<TT, NN, 3>; XRFT_LAUNCH(k, grid, blk, R.lds_rows, st, p); } \
         else { auto k = &fastm_rows_kernel<TT, NN, 0>; XRFT_LAUNCH(k, grid, blk, lds_rows, st, p); } } while (0)

@@ -52,18 +52,23 @@ template <int NX, bool FS = false> static YGeomRt yrows_geom_t() {
     typedef YRows<NX, FS> R;
     return {R::THR, R::GX, 0, R::RPU, 0, (size_t)(R::GX * YLds<NX, R::GX>::GSTR + 16 * P2<NX>::R3) * sizeof(cf)};
 }
+// n, one of the five lengths of fasty.h (anything else counts as 256), as a compile-time constant: f(std::integral_constant<int, N>())
+template <class F> static auto with_ylen(long long n, F&& f) {
+    switch (n) {
+        case 4096: return f(std::integral_constant<int, 4096>());
+        case 2048: return f(std::integral_constant<int, 2048>());
+        case 1024: return f(std::integral_constant<int, 1024>());
+        case 512: return f(std::integral_constant<int, 512>());
+        default: return f(std::integral_constant<int, 256>());
+    }
+}
 static int ycols_gstr(long long ny) {  // complex elements of LDS per packed column pair of pass 1 (YLds<NY, GY>::GSTR)
-    switch (ny) { case 4096: return YLds<4096, YCols<4096>::GY>::GSTR; case 2048: return YLds<2048, YCols<2048>::GY>::GSTR; case 1024: return YLds<1024, YCols<1024>::GY>::GSTR;
-                  case 512: return YLds<512, YCols<512>::GY>::GSTR; default: return YLds<256, YCols<256>::GY>::GSTR; }
+    return with_ylen(ny, [](auto n) { constexpr int N = decltype(n)::value; return (int)YLds<N, YCols<N>::GY>::GSTR; });
 }
-YGeomRt ycols_geom(long long ny) {
-    switch (ny) { case 4096: return ycols_geom_t<4096>(); case 2048: return ycols_geom_t<2048>(); case 1024: return ycols_geom_t<1024>();
-                  case 512: return ycols_geom_t<512>(); default: return ycols_geom_t<256>(); }
-}
+YGeomRt ycols_geom(long long ny) { return with_ylen(ny, [](auto n) { return ycols_geom_t<decltype(n)::value>(); }); }
 YGeomRt yrows_geom(long long nx, bool fs) {  // .rk = rows per workgroup; fs: the four-step 1-D form (256-point rows)
     if (fs) return yrows_geom_t<256, true>();
-    switch (nx) { case 4096: return yrows_geom_t<4096>(); case 2048: return yrows_geom_t<2048>(); case 1024: return yrows_geom_t<1024>();
-                  case 512: return yrows_geom_t<512>(); default: return yrows_geom_t<256>(); }
+    return with_ylen(nx, [](auto n) { return yrows_geom_t<decltype(n)::value>(); });
 }
 long long fasty_rows_gx(const xrfthip_plan* P) { return yrows_geom(P->ynx, P->family == Family::FastY1D).gxy; }
 
@@ -270,28 +275,11 @@ static int fasty_build_tcodes(xrfthip_plan* P, const int32_t* bm) {
     return P->ytcodes.upload(t.data(), t.size() * sizeof(uint32_t));
 }
 // the radial-sum tables of one round share the transforms' LDS with the staged half of the workgroup's rows: they must fit the other half
-static bool fasty_iso_tables_fit(const xrfthip_plan* P, int nbins) {
+static bool fasty_radial_tables_fit(const xrfthip_plan* P, int nbins) {
     const YGeomRt R = yrows_geom(P->ynx);
     const size_t half = (size_t)R.gxy * (size_t)(P->ynx + P->ynx / 16) * 4;  // GX rows of floats = GX / 2 rows of complex
     const size_t hw = P->d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1;
     return nbins <= 65534 && (size_t)nbins * (8 * hw + 4) <= half;
-}
-
-// Workgroups of `kernel` the whole device holds at once (a persistent launch's grid): the occupancy calculator's count per CU times the CUs,
-// asked once per kernel.
-static long long resident_workgroups(const void* kernel, int threads, size_t lds) {
-    static std::mutex mu;
-    static std::map<const void*, long long> memo;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = memo.find(kernel);
-    if (it != memo.end()) return it->second;
-    int per_cu = 0, cus = 0, dev = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    const long long n = (long long)per_cu * cus;
-    memo[kernel] = n;
-    return n;
 }
 
 static void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long gc, hipStream_t st, bool prof) {
@@ -299,32 +287,22 @@ static void fasty_launch_cols(const xrfthip_plan* P, const FastY& p, long long g
     const YGeomRt C = ycols_geom(P->yny);
     xrfthip_plan::ProfRec* rec = prof ? prof_begin(P, "fasty_cols", st) : nullptr;
     const dim3 grid((unsigned)(gc * (P->ynx / C.cw))), blk((unsigned)C.thr);
-#define YC_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
-                     else { auto k = &fasty_cols_kernel<NN, false>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
-#define YCW_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
-                      else { auto k = &fasty_cols_kernel<NN, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
-#define YCS_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
-                      else { auto k = &fasty_cols_kernel<NN, false, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
-#define YCH_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true, false, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
-                      else { auto k = &fasty_cols_kernel<NN, false, false, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
-#define YCHW_(NN) do { if (d.detrend) { auto k = &fasty_cols_kernel<NN, true, true, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } \
-                       else { auto k = &fasty_cols_kernel<NN, false, true, false, true>; XRFT_LAUNCH(k, grid, blk, C.lds, st, p); } } while (0)
-    if (in_half(P)) {  // float16 / bfloat16 input, dense (half_in.h): the 2-byte loaders of the same two forms
-        if (P->fast1d_win) { if (P->yny == 4096) YCHW_(4096); else if (P->yny == 2048) YCHW_(2048); else if (P->yny == 1024) YCHW_(1024); else if (P->yny == 512) YCHW_(512); else YCHW_(256); }
-        else if (P->yny == 4096) YCH_(4096); else if (P->yny == 2048) YCH_(2048); else if (P->yny == 1024) YCH_(1024); else if (P->yny == 512) YCH_(512); else YCH_(256);
-    }
-    else if (in_strided(P)) {  // a box of a larger field, read where it lies (FastY only: xrfthip_plan_create)
-        if (P->yny == 4096) YCS_(4096); else if (P->yny == 2048) YCS_(2048); else if (P->yny == 1024) YCS_(1024); else if (P->yny == 512) YCS_(512); else YCS_(256);
-    }
-    else if (P->fast1d_win) {  // four-step 1-D with a window: the slab-shaped window table
-        if (P->yny == 4096) YCW_(4096); else if (P->yny == 2048) YCW_(2048); else if (P->yny == 1024) YCW_(1024); else if (P->yny == 512) YCW_(512); else YCW_(256);
-    }
-    else if (P->yny == 4096) YC_(4096); else if (P->yny == 2048) YC_(2048); else if (P->yny == 1024) YC_(1024); else if (P->yny == 512) YC_(512); else YC_(256);
-#undef YC_
-#undef YCW_
-#undef YCS_
-#undef YCH_
-#undef YCHW_
+    auto launch = [&](auto kern) { XRFT_LAUNCH(kern, grid, blk, C.lds, st, p); };
+    with_ylen(P->yny, [&](auto n) {
+        constexpr int NN = decltype(n)::value;
+        const bool det = d.detrend != 0;
+        if (in_half(P)) {  // float16 / bfloat16 input, dense (half_in.h): the 2-byte loaders of the same two forms
+            if (P->fast1d_win) { if (det) launch(&fasty_cols_kernel<NN, true, true, false, true>); else launch(&fasty_cols_kernel<NN, false, true, false, true>); }
+            else if (det) launch(&fasty_cols_kernel<NN, true, false, false, true>); else launch(&fasty_cols_kernel<NN, false, false, false, true>);
+        }
+        else if (in_strided(P)) {  // a box of a larger field, read where it lies (FastY only: xrfthip_plan_create)
+            if (det) launch(&fasty_cols_kernel<NN, true, false, true>); else launch(&fasty_cols_kernel<NN, false, false, true>);
+        }
+        else if (P->fast1d_win) {  // four-step 1-D with a window: the slab-shaped window table
+            if (det) launch(&fasty_cols_kernel<NN, true, true>); else launch(&fasty_cols_kernel<NN, false, true>);
+        }
+        else if (det) launch(&fasty_cols_kernel<NN, true>); else launch(&fasty_cols_kernel<NN, false>);
+    });
     prof_end(rec, st);
     if (d.detrend) {  // plane (2-D) or line through the whole sequence (four-step 1-D) from the per-column sums -> what pass 2 has to add back
         rec = prof ? prof_begin(P, "fasty_fit", st) : nullptr;
@@ -345,57 +323,19 @@ static void fasty_launch_rows(const xrfthip_plan* P, const FastY& p, long long g
     const dim3 grid((unsigned)(P->family == Family::FastY1D ? gc * ((P->yny / 2) / rpu) + (gc + R.gxy - 1) / R.gxy : gc * (P->y_nrow_pad / rpu))), blk((unsigned)R.thr);
     const int hw = d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1;
     const size_t lds = R.lds;  // (the radial-sum tables alias the transforms' LDS)
-    // nothing but the radial sums of a radial map leaves the pass: the persistent kernel of fasty_iso.h (as many workgroups as the chip holds)
-    // (measured, profiles/r06_tune_iso.txt: with the pipelined gather in BOTH kernels the workgroup-per-unit kernel is level or ahead -- 19.1 against 19.5 us per 4096^2
-    // slab, 4.87 against 5.26 at 2048^2, 1.21 against 1.20 at 1024^2 -- so the persistent kernel is opt-in: XRFTHIP_ISOROWS=1; =2 its profiling build)
-    const bool iso_persistent = P->tune_isorows == 2 || P->tune_isorows == 1;
-    if (iso_on && p.out == nullptr && p.tfirst != nullptr && P->family != Family::FastY1D && iso_persistent && P->ynx >= 1024 &&
-        (d.out_mode == XRFTHIP_OUT_POWER || d.out_mode == XRFTHIP_OUT_CROSS)) {
-        const long long total = gc * (P->y_nrow_pad / rpu);
-        const bool tim = P->tune_isorows == 2;
-        FastY q = p;
-        void (*kern)(FastY) = nullptr;
-#define YI_(NN) kern = d.out_mode == XRFTHIP_OUT_POWER ? (tim ? &fasty_isorows_kernel<NN, 1, true> : &fasty_isorows_kernel<NN, 1, false>) \
-                                                       : (tim ? &fasty_isorows_kernel<NN, 2, true> : &fasty_isorows_kernel<NN, 2, false>)
-        if (P->ynx == 4096) YI_(4096); else if (P->ynx == 2048) YI_(2048); else YI_(1024);
-#undef YI_
-        const long long slots = resident_workgroups(reinterpret_cast<const void*>(kern), R.thr, lds);
-        const unsigned nblk = (unsigned)std::min<long long>(total, slots);
-        if (tim) {
-            std::vector<long long> z((size_t)nblk * 8, 0);
-            if (P->iso_tim.upload(z.data(), z.size() * sizeof(long long)) == XRFTHIP_OK) q.tim = reinterpret_cast<long long*>(P->iso_tim.p);
-        }
-        XRFT_LAUNCH(kern, dim3(nblk), blk, lds, st, q);
-        prof_end(rec, st);
-        if (tim && q.tim) {
-            (void)hipStreamSynchronize(st);
-            std::vector<long long> h((size_t)nblk * 8, 0);
-            (void)hipMemcpy(h.data(), q.tim, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
-            double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (unsigned b = 0; b < nblk; ++b) for (int i = 0; i < 8; ++i) acc[i] += (double)h[(size_t)b * 8 + i];
-            const double units = std::max(acc[7], 1.0);
-            std::fprintf(stderr, "[xrfthip isorows nx=%lld mode=%d] %u workgroups, %.0f units; shader-clock cycles per unit: wait+tables+addback %.0f | fft %.0f | stage+barrier %.0f | "
-                         "prefetch issue %.0f | segments %.0f | barrier %.0f | gather %.0f | total %.0f\n", (long long)P->ynx, (int)d.out_mode, nblk, units, acc[0] / units, acc[1] / units,
-                         acc[2] / units, acc[3] / units, acc[4] / units, acc[5] / units, acc[6] / units, (acc[0] + acc[1] + acc[2] + acc[3] + acc[4] + acc[5] + acc[6]) / units);
-        }
-    } else {
-#define YR_(NN) do { \
-        if (d.out_mode == XRFTHIP_OUT_POWER) { if (iso_on) { auto k = &fasty_rows_kernel<NN, 1, true>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } else { auto k = &fasty_rows_kernel<NN, 1, false>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } } \
-        else if (d.out_mode == XRFTHIP_OUT_CROSS) { if (iso_on) { auto k = &fasty_rows_kernel<NN, 2, true>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } else { auto k = &fasty_rows_kernel<NN, 2, false>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } } \
-        else if (d.out_mode == XRFTHIP_OUT_PHASE) { auto k = &fasty_rows_kernel<NN, 3, false>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } \
-        else { auto k = &fasty_rows_kernel<NN, 0, false>; XRFT_LAUNCH(k, grid, blk, lds, st, p); } } while (0)
+    auto launch = [&](auto kern) { XRFT_LAUNCH(kern, grid, blk, lds, st, p); };
     if (P->family == Family::FastY1D) {  // four-step 1-D: rows of 256 samples, transposed stores
-        if (P->fast1d_win) {
-            if (d.out_mode == XRFTHIP_OUT_POWER) { auto k = &fasty_rows_kernel<256, 1, false, true, true>; XRFT_LAUNCH(k, grid, blk, lds, st, p); }
-            else { auto k = &fasty_rows_kernel<256, 0, false, true, true>; XRFT_LAUNCH(k, grid, blk, lds, st, p); }
-        }
-        else if (d.out_mode == XRFTHIP_OUT_POWER) { auto k = &fasty_rows_kernel<256, 1, false, true>; XRFT_LAUNCH(k, grid, blk, lds, st, p); }
-        else { auto k = &fasty_rows_kernel<256, 0, false, true>; XRFT_LAUNCH(k, grid, blk, lds, st, p); }
+        if (P->fast1d_win) { if (d.out_mode == XRFTHIP_OUT_POWER) launch(&fasty_rows_kernel<256, 1, false, true, true>); else launch(&fasty_rows_kernel<256, 0, false, true, true>); }
+        else if (d.out_mode == XRFTHIP_OUT_POWER) launch(&fasty_rows_kernel<256, 1, false, true>); else launch(&fasty_rows_kernel<256, 0, false, true>);
     }
-    else if (P->ynx == 4096) YR_(4096); else if (P->ynx == 2048) YR_(2048); else if (P->ynx == 1024) YR_(1024); else if (P->ynx == 512) YR_(512); else YR_(256);
-#undef YR_
+    else with_ylen(P->ynx, [&](auto n) {
+        constexpr int NN = decltype(n)::value;
+        if (d.out_mode == XRFTHIP_OUT_POWER) { if (iso_on) launch(&fasty_rows_kernel<NN, 1, true>); else launch(&fasty_rows_kernel<NN, 1, false>); }
+        else if (d.out_mode == XRFTHIP_OUT_CROSS) { if (iso_on) launch(&fasty_rows_kernel<NN, 2, true>); else launch(&fasty_rows_kernel<NN, 2, false>); }
+        else if (d.out_mode == XRFTHIP_OUT_PHASE) launch(&fasty_rows_kernel<NN, 3, false>);
+        else launch(&fasty_rows_kernel<NN, 0, false>);
+    });
     prof_end(rec, st);
-    }
     if (iso_on) {  // the row workgroups' partial sums, added in order
         rec = prof ? prof_begin(P, "fasty_iso_reduce", st) : nullptr;
         const int nb = P->nbins * hw, upr = P->y_nrow_pad / rpu;
@@ -415,11 +355,11 @@ static void fasty_launch_rows_mean(const xrfthip_plan* P, const FastY& p, long l
     YMean m{part, g0, (int)M, P->mean_P};
     xrfthip_plan::ProfRec* rec = prof_begin(P, "fasty_rows_mean", st);
     const dim3 grid((unsigned)((long long)(P->y_nrow_pad / rpu) * P->mean_P * nout)), blk((unsigned)R.thr);
-#define YM_(NN) do { if (P->coherence) { auto k = &fasty_rows_mean_kernel<NN, 3>; XRFT_LAUNCH(k, grid, blk, R.lds, st, p, m); } \
-                     else if (two) { auto k = &fasty_rows_mean_kernel<NN, 2>; XRFT_LAUNCH(k, grid, blk, R.lds, st, p, m); } \
-                     else { auto k = &fasty_rows_mean_kernel<NN, 1>; XRFT_LAUNCH(k, grid, blk, R.lds, st, p, m); } } while (0)
-    if (P->ynx == 4096) YM_(4096); else if (P->ynx == 2048) YM_(2048); else if (P->ynx == 1024) YM_(1024); else if (P->ynx == 512) YM_(512); else YM_(256);
-#undef YM_
+    auto launch = [&](auto kern) { XRFT_LAUNCH(kern, grid, blk, R.lds, st, p, m); };
+    with_ylen(P->ynx, [&](auto n) {
+        constexpr int NN = decltype(n)::value;
+        if (P->coherence) launch(&fasty_rows_mean_kernel<NN, 3>); else if (two) launch(&fasty_rows_mean_kernel<NN, 2>); else launch(&fasty_rows_mean_kernel<NN, 1>);
+    });
     prof_end(rec, st);
 }
 
@@ -471,7 +411,6 @@ static FastY fasty_params(const xrfthip_plan* P, const float* in, void* out, dou
     if (P->family == Family::FastY1D) p.win_y = p.win_x = reinterpret_cast<const float*>(P->ones4096.p);  // (a window of the whole sequence: win2d)
     p.win2d = reinterpret_cast<const float*>(P->fast1d_win ? P->win2d.p : nullptr);
     p.scale = (float)d.scale;
-    p.tune = (int)P->tune_y;
     return p;
 }
 
@@ -554,9 +493,9 @@ int try_fastyc(xrfthip_plan* P) {
 
 // ---- the pass-1 block (xrfthip_exec_ex): what the column pass and the fit kernel leave for ONE field -- intermediate, per-column sums and lines, corrections --
 // as one piece of memory outside the workspace, so that a second plan over the same field can read it instead of running the two kernels again.
-// Only where the whole batch is one group of slabs (the block is the field's, not a ring slot's) and pass 1 keeps no state beside it (the rendezvous counters).
+// Only where the whole batch is one group of slabs (the block is the field's, not a ring slot's).
 size_t fasty_pass1_bytes(const xrfthip_plan* P) {
-    if (P->family != Family::FastY || P->d.batch < 1 || P->G < P->d.batch || ((P->tune_y >> 21) & 1)) return 0;
+    if (P->family != Family::FastY || P->d.batch < 1 || P->G < P->d.batch) return 0;
     if (((P->p1_w | P->p1_fit | P->p1_corr) & 255) || !P->p1_w) return 0;  // (the lengths of fasty.h leave whole 256-byte units: the workspace holds exactly these bytes per field)
     return P->p1_w + P->p1_fit + P->p1_corr;
 }
@@ -574,7 +513,7 @@ uint64_t fasty_pass1_signature(const xrfthip_plan* P, int field) {
     const xrfthip_desc& d = P->d;
     const YGeomRt C = ycols_geom(P->yny);
     Fnv f;
-    f.num(XRFTHIP_VERSION); f.num(XRFT_YDBG); f.num((long long)sizeof(cf));
+    f.num(XRFTHIP_VERSION); f.num((long long)sizeof(cf));
     // the kernel: fasty_cols_kernel<NY, DET, W2D = false, STR>, then fasty_fit_kernel with a detrend
     f.num(P->yny); f.num(d.detrend != 0); f.num(in_strided(P)); f.num(d.detrend);
     f.num(d.ny); f.num(d.nx); f.num(d.batch); f.num(P->G); f.num(P->y_nrow_pad); f.num(d.dtype); f.num(d.ndim);
@@ -587,7 +526,6 @@ uint64_t fasty_pass1_signature(const xrfthip_plan* P, int field) {
     f.num((d.flags & fy) != 0); f.num((d.flags & fx) != 0);
     // the tables pass 1 reads: the windows (the float32 tables are these values rounded; none = ones) -- win_x is the fit kernel's, too; W_ny^k follows from ny
     f.table(P->host_win_y); f.table(P->host_win_x);
-    f.num(P->tune_y);
     return f.h;
 }
 
@@ -616,10 +554,6 @@ static int run_fasty(const xrfthip_plan* P, const ExecArgs& a) {
         FastY p = fasty_params(P, in, out, iso, ws, g0, gc, 0, P->G);
         in_block(p, 0);
         if (compact) p.iso_part = reinterpret_cast<double*>(ws + (P->off_isopart - (size_t)(two ? 2 : 1) * fasty_pass1_bytes(P)));
-        if ((P->tune_y >> 21) & 1) {
-            p.rdv = reinterpret_cast<unsigned*>(ws + P->off_rdv);
-            HIP_TRY(hipMemsetAsync(p.rdv, 0, (size_t)gc * (size_t)std::max<long long>(P->ynx / 8, 1) * sizeof(unsigned), st));
-        }
         if (a.p1_mode[0] != XRFTHIP_PASS1_CONSUME) fasty_launch_cols(P, p, gc, st, true);
         if (two) {  // field 1 through the same column pass into its own intermediate; the row pass reads both
             FastY p1 = fasty_params(P, in1, out, iso, ws, g0, gc, 1, P->G);
@@ -686,17 +620,13 @@ static int run_fastyc(const xrfthip_plan* P, const ExecArgs& a) {
         p.scale = (float)d.scale;
         xrfthip_plan::ProfRec* rec = prof_begin(P, "fastyc_cols", st);
         const dim3 gridc((unsigned)(gc * nxb_full + (c2r ? gc : 0))), blkc((unsigned)C.thr);
-#define YCC_(NN) do { auto k = &fastyc_cols_kernel<NN>; XRFT_LAUNCH(k, gridc, blkc, lds_c, st, p); } while (0)
-        if (d.ny == 4096) YCC_(4096); else if (d.ny == 2048) YCC_(2048); else if (d.ny == 1024) YCC_(1024); else if (d.ny == 512) YCC_(512); else YCC_(256);
-#undef YCC_
+        with_ylen(d.ny, [&](auto n) { auto k = &fastyc_cols_kernel<decltype(n)::value>; XRFT_LAUNCH(k, gridc, blkc, lds_c, st, p); });
         prof_end(rec, st);
         rec = prof_begin(P, "fastyc_rows", st);
         const dim3 gridr((unsigned)(gc * (d.ny / R.rk))), blkr((unsigned)R.thr);
-#define YCR_(NN) do { auto k = &fastyc_rows_kernel<NN>; XRFT_LAUNCH(k, gridr, blkr, R.lds, st, p); } while (0)
 #define YC2_(NN) do { auto k = &fastyc_rows_c2r_kernel<NN, false>; XRFT_LAUNCH(k, gridr, blkr, R.lds, st, p); } while (0)
-        if (c2r) { if (nxt == 2048) YC2_(2048); else if (nxt == 1024) YC2_(1024); else if (nxt == 512) YC2_(512); else YC2_(256); }
-        else if (d.nx == 4096) YCR_(4096); else if (d.nx == 2048) YCR_(2048); else if (d.nx == 1024) YCR_(1024); else if (d.nx == 512) YCR_(512); else YCR_(256);
-#undef YCR_
+        if (c2r) { if (nxt == 2048) YC2_(2048); else if (nxt == 1024) YC2_(1024); else if (nxt == 512) YC2_(512); else YC2_(256); }  // (four lengths: nx / 2)
+        else with_ylen(d.nx, [&](auto n) { auto k = &fastyc_rows_kernel<decltype(n)::value>; XRFT_LAUNCH(k, gridr, blkr, R.lds, st, p); });
 #undef YC2_
         prof_end(rec, st);
         HIP_TRY(hipGetLastError());
@@ -764,7 +694,7 @@ static void layout_fastyc(xrfthip_plan* P) {
 }
 static int fasty_binmap(xrfthip_plan* P, const int32_t* bm) {
     const int rc = fasty_build_tcodes(P, bm);
-    if (!rc && !P->ytfirst_on && !fasty_iso_tables_fit(P, P->nbins)) settle_family(P, true);  // (any map: the atomic tables alias half of the transforms' LDS)
+    if (!rc && !P->ytfirst_on && !fasty_radial_tables_fit(P, P->nbins)) settle_family(P, true);  // (any map: the atomic tables alias half of the transforms' LDS)
     return rc;
 }
 static void describe_fasty(const xrfthip_plan* plan, std::string& s, const char* in_note) {
@@ -826,9 +756,6 @@ void set_attrs_fasty() {
     SETF((fastyc_rows_c2r_kernel<2048, false>)); SETF((fastyc_rows_c2r_kernel<1024, false>)); SETF((fastyc_rows_c2r_kernel<512, false>)); SETF((fastyc_rows_c2r_kernel<256, false>));
     SETF((fastyc_rows_c2r_kernel<2048, true>)); SETF((fastyc_rows_c2r_kernel<1024, true>)); SETF((fastyc_rows_c2r_kernel<512, true>)); SETF((fastyc_rows_c2r_kernel<256, true>));
 #undef SETC
-#define SETI(NN) SETF((fasty_isorows_kernel<NN, 1, false>)); SETF((fasty_isorows_kernel<NN, 2, false>)); SETF((fasty_isorows_kernel<NN, 1, true>)); SETF((fasty_isorows_kernel<NN, 2, true>))
-    SETI(4096); SETI(2048); SETI(1024);
-#undef SETI
     SETF((fasty_rows_kernel<256, 0, false, true>)); SETF((fasty_rows_kernel<256, 1, false, true>));
     SETF((fasty_rows_kernel<256, 0, false, true, true>)); SETF((fasty_rows_kernel<256, 1, false, true, true>));
 #undef SETF

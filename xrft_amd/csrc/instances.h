@@ -31,10 +31,6 @@ XRFT_KI_YC_(256) XRFT_KI_YC_(512) XRFT_KI_YC_(1024) XRFT_KI_YC_(2048) XRFT_KI_YC
 #define XRFT_KI_Y2_(NN) XRFT_KW void fastyc_rows_c2r_kernel<NN, false>(FastYC); XRFT_KW void fastyc_rows_c2r_kernel<NN, true>(FastYC);
 XRFT_KI_Y2_(256) XRFT_KI_Y2_(512) XRFT_KI_Y2_(1024) XRFT_KI_Y2_(2048)
 #undef XRFT_KI_Y2_
-#define XRFT_KI_YI_(NN) XRFT_KW void fasty_isorows_kernel<NN, 1, false>(FastY); XRFT_KW void fasty_isorows_kernel<NN, 2, false>(FastY); \
-    XRFT_KW void fasty_isorows_kernel<NN, 1, true>(FastY); XRFT_KW void fasty_isorows_kernel<NN, 2, true>(FastY);
-XRFT_KI_YI_(1024) XRFT_KI_YI_(2048) XRFT_KI_YI_(4096)
-#undef XRFT_KI_YI_
 #define XRFT_KI_YM_(NN) XRFT_KW void fasty_rows_mean_kernel<NN, 1>(FastY, YMean); XRFT_KW void fasty_rows_mean_kernel<NN, 2>(FastY, YMean); \
     XRFT_KW void fasty_rows_mean_kernel<NN, 3>(FastY, YMean);  /* (fasty_mean.h: the mean over the batch; 3: the sums of a coherence) */
 XRFT_KI_YM_(256) XRFT_KI_YM_(512) XRFT_KI_YM_(1024) XRFT_KI_YM_(2048) XRFT_KI_YM_(4096)

@@ -7,7 +7,7 @@
 //                    tile passes (tile_fft.h) and their workspace layout, the table of rows (family_ops), profiling, the C ABI of the plan:
 //                    finalize / set_binmap / kernel_info / describe / exec go through the plan's row
 //                    (Generic)
-//   host_fasty.cpp   the y-first float32 two-pass pipeline (fasty.h, fasty_iso.h) and its complex form (fasty_c2c.h): try_*, tables, launchers
+//   host_fasty.cpp   the y-first float32 two-pass pipeline (fasty.h, fasty_mean.h) and its complex form (fasty_c2c.h): try_*, tables, launchers
 //                    (FastY, FastY1D, FastYC, FastYCFourStep)
 //   host_fastm.cpp   the mixed-radix pipeline on the lat/lon lengths (fastm.h), its run-time-radix form (fastn.h), the one-axis table kernels
 //                    (FastM, FastN, FastMY, FastMX)
@@ -50,7 +50,6 @@
 #include "aux_kernels.h"
 #include "fastp2.h"
 #include "fasty.h"
-#include "fasty_iso.h"
 #include "fasty_c2c.h"
 #include "selftest.h"
 #include "fastm.h"
@@ -369,7 +368,7 @@ struct xrfthip_plan {
     std::vector<Pass> passes;     // main pipeline (field 1 for CROSS)
     std::vector<Pass> passes_f0;  // CROSS: field 0 -> raw F0 buffer
     // workspace layout (byte offsets)
-    size_t off_acc = 0, off_coef = 0, off_w = 0, off_w2 = 0, off_f0 = 0, off_pt = 0, off_rowfit = 0, off_corr = 0, off_isopart = 0, off_isotmp = 0, off_rdv = 0, ws_bytes = 0;
+    size_t off_acc = 0, off_coef = 0, off_w = 0, off_w2 = 0, off_f0 = 0, off_pt = 0, off_rowfit = 0, off_corr = 0, off_isopart = 0, off_isotmp = 0, ws_bytes = 0;
     // the two y-first passes: what pass 1 leaves for ONE field inside the workspace -- its share of the intermediate (off_w), of the per-column sums and lines (off_rowfit) and
     // of the corrections (off_corr).  A pass-1 block handed in from outside (xrfthip_exec_ex) holds the three, in this order (layout_passes; fasty_pass1_bytes)
     size_t p1_w = 0, p1_fit = 0, p1_corr = 0;
@@ -452,10 +451,6 @@ struct xrfthip_plan {
     bool fast1d_win = false;         // the four-step plan carries a window: slab-shaped window table, per-column window spectra
     // tuning knobs from the environment, read once when the plan is created (never in xrfthip_exec)
     long long tune_group = 0, tune_fast_group = 0, tune_group_bytes = 512LL << 20, tune_cols_grid = 256, tune_max_grid = 8192;
-    long long tune_y = 0;  // XRFTHIP_YTUNE: cache policies / start stagger of the y-first float32 kernels (FastY::tune), fixed at plan creation
-    long long tune_isorows = 0;  // XRFTHIP_ISOROWS: 1 the persistent radial-sum row kernel (fasty_iso.h) when nothing but the sums leaves pass 2; 0 (default) fasty_rows_kernel<.., ISO>;
-                                 // 2 its profiling build (per-phase shader-clock sums printed after every launch: scripts/prof.py iso-phases -- synchronises, never in the product)
-    mutable DevBuf iso_tim;      // ... whose counters live here
     // optional per-pass event timing (bench only; a plan with profiling on is not re-entrant)
     bool prof = false;
     struct ProfRec { std::string label; hipEvent_t a, b; };

@@ -621,8 +621,6 @@ void layout_passes(xrfthip_plan* P) {
         const size_t upr = (size_t)P->y_nrow_pad / (two ? gx : 2 * gx);
         off = al(off + (size_t)G * upr * P->nbins * (two ? 2 : 1) * sizeof(double));
     }
-    P->off_rdv = off;
-    if (fast && !fastm_pipeline(P) && ((P->tune_y >> 21) & 1)) off = al(off + (size_t)G * (size_t)std::max<long long>(P->ynx / 8, 1) * sizeof(unsigned));  // (tuning: rendezvous counters of pass 1)
     P->off_isotmp = off;
     if (fastm_iso_fused(P)) {  // fastm with the radial sums inside pass 2: one partial table per row workgroup
         const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
@@ -975,8 +973,6 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     P->d = d;
     P->tune_group = env_ll("XRFTHIP_GROUP", 0);
     P->tune_fast_group = env_ll("XRFTHIP_FAST_GROUP", 0);
-    P->tune_y = env_ll("XRFTHIP_YTUNE", kYTuneDefault);
-    P->tune_isorows = env_ll("XRFTHIP_ISOROWS", 0);
     P->tune_mean_runs = env_ll("XRFTHIP_MEAN_RUNS", 0);
     P->tune_group_bytes = env_ll("XRFTHIP_GROUP_BYTES", 512LL << 20);
     P->tune_cols_grid = env_ll("XRFTHIP_FAST_COLS_GRID", kCUs);
