@@ -242,6 +242,29 @@ typedef struct xrfthip_desc {
      * plan's).  Sums as above: no atomics, a fixed order, at most 16 float32 terms in a row, then float64; the partial is 4 float64 per sample and run
      * ([output][P][ny/2 + 1][nx][re C, im C, A, B], in xrfthip_workspace_bytes); a non-finite value in one slab makes exactly its own output non-finite.
      * xrfthip_plan_describe prints the [mean over the batch] line and the word "coherence".  XRFTHIP_MEAN_ALL and XRFTHIP_MEAN_RUNS apply as they do to CROSS. */
+    /* Welch spectra: the mean spectrum of the OVERLAPPING segments of a long series, each segment read where it lies and no segment's spectrum ever stored -- Welch's
+     * method (scipy.signal.welch / csd), the reference's power_spectrum(da, dim="time", chunks_to_segments=True, window="hann", detrend="linear").mean("time_segment")
+     * with an overlap.  One in_stride_batch cannot say "series pitch and segment hop", hence the field.
+     *   seg_hop = H >= 1   samples between the starts of consecutive segments.  Valid with ndim = 1, ny = 1, nx = L (the segment length), mean_batch = M >= 2 (the
+     *                      segments per series), batch = P * M (P series), dtype XRFTHIP_F32, out_mode POWER | CROSS.  Input sample j of segment s of series p is
+     *                      d_in0[p * in_stride_batch + s * H + j] (and d_in1 of a CROSS plan): in_stride_batch is HERE the series pitch, 0 = the dense span
+     *                      (M - 1) * H + L.  d_out is [P][nx_out], real (POWER) or complex (CROSS), its value (1 / M) sum_s of what the plain 1-D plan writes for
+     *                      segment s.  Any 1 <= H <= L: H = L is the reshape of chunks_to_segments, H = L / 2 Welch's usual half overlap.
+     *                      0 = off: everything is as without the field (a 1-D mean_batch plan answers XRFTHIP_UNSUPPORTED_LENGTH).
+     * Alignment: d_in0 / d_in1 4-byte aligned, whatever H and the pitch are (the kernel loads single samples); no byte outside [p * pitch, p * pitch + (M - 1) * H + L)
+     * of each series is touched.  Accepted: detrend NONE | CONSTANT | LINEAR per segment, as the 1-D plans define it; a window on axis 1; `scale`; XRFTHIP_SHIFT_X;
+     * XRFTHIP_HALF_X with or without XRFTHIP_REALDIM_X2 (the one-sided spectrum, nx_out = L / 2 + 1; not together with SHIFT_X); XRFTHIP_ISHIFT_X (a factor (-1)^k
+     * that cancels in both products: no effect); a phase table on axis 1 for CROSS (the net factor multiplies the mean, once).
+     * XRFTHIP_BAD_ARG: H < 0, H > L; seg_hop with ndim = 2, XRFTHIP_AXIS_Y, inner / mid, herm_*, XRFTHIP_ISO or in_stride_y; mean_batch < 2; batch % M != 0;
+     * out_mode COMPLEX | PHASE | COHERENCE; a pitch smaller than the span.  XRFTHIP_UNSUPPORTED_LENGTH ("the caller composes": the segments copied out, the plain
+     * 1-D plan, xrfthip_reduce_axis): L not a power of two in 64 .. 4096, float64 / complex / float16 / bfloat16 input, the FLIP flags.
+     * Sums: no floating-point atomics; the order of every addition is fixed by the plan, so repeated calls return identical bits; at most 16 float32 terms are added in
+     * a row before the sum continues in float64; a non-finite sample makes exactly its own series' output non-finite.  The runs per output (xrfthip_plan_describe;
+     * XRFTHIP_MEAN_RUNS pins them) let a few long series fill the card; their float64 partials live in the workspace (xrfthip_workspace_bytes includes them).
+     * Served by the Welch form of the rows family (xrfthip_plan_kernel_info: XRFTHIP_K_FASTW).  Descriptors with the struct_size of the six earlier versions are accepted (0).  As with mean_batch, the status of
+     * xrfthip_plan_create tells the capability: an older library answers XRFTHIP_BAD_ARG to the larger struct_size. */
+    int64_t seg_hop;
+    int64_t seg_reserved; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_hop: struct_size is that of the version before the two, or sizeof(xrfthip_desc) */
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;
@@ -295,7 +318,8 @@ typedef enum xrfthip_kernel_kind {
     XRFTHIP_K_FASTS = 9,      /* one pass over a small float32 slab in registers */
     XRFTHIP_K_FASTR = 10,     /* one pass over a long float32 row in registers */
     XRFTHIP_K_COMPOSITE = 11, /* xrfthip_desc.inner / .mid: two one-axis plans */
-    XRFTHIP_K_FASTH = 12      /* xrfthip_desc.herm_ny / herm_nx: the last pass of a three-axis spectrum, half spectrum in, full result out */
+    XRFTHIP_K_FASTH = 12,     /* xrfthip_desc.herm_ny / herm_nx: the last pass of a three-axis spectrum, half spectrum in, full result out */
+    XRFTHIP_K_FASTW = 13      /* xrfthip_desc.seg_hop: Welch spectra, overlapping segments of a series read in place and averaged in one pass */
 } xrfthip_kernel_kind;
 int xrfthip_plan_kernel_info(const xrfthip_plan* plan, int32_t* kind, int32_t* per_workgroup);
 

@@ -27,7 +27,7 @@ FLIP0_Y, FLIP0_X = 0x4000, 0x8000  # cross spectra: flip field 0 (FLIP_Y / FLIP_
 HALF_Y = 0x10000  # inner / mid layouts (ABI 0.1.6): real_dim along the FIRST of the two transform axes (ny / 2 + 1 rows out)
 HERM_FIELD = 0x20000  # herm_ny / herm_nx descriptors: the last pass writes the complex field F itself (out_mode COMPLEX), with three output-phase tables (axis 0, 1, 2)
 # xrfthip_kernel_kind (xrfthip_plan_kernel_info)
-K_GENERIC, K_FASTY, K_FASTM, K_FASTN, K_FASTM_Y, K_FASTM_X, K_FASTG_Y, K_FASTG_ROWS, K_FASTG, K_FASTS, K_FASTR, K_COMPOSITE, K_FASTH = range(13)
+K_GENERIC, K_FASTY, K_FASTM, K_FASTN, K_FASTM_Y, K_FASTM_X, K_FASTG_Y, K_FASTG_ROWS, K_FASTG, K_FASTS, K_FASTR, K_COMPOSITE, K_FASTH, K_FASTW = range(14)
 
 EXPORTS = [
     "xrfthip_version", "xrfthip_strerror", "xrfthip_last_hip_error", "xrfthip_plan_create",
@@ -67,6 +67,14 @@ class Desc(C.Structure):
     ]
 
 
+class DescSeg(C.Structure):
+    """xrfthip_desc as the library has it now: ``Desc`` (the version up to mean_batch, still accepted under its own struct_size) and the two words appended together."""
+    _fields_ = Desc._fields_ + [
+        ("seg_hop", C.c_int64),  # H >= 1: Welch spectra -- the M segments of nx samples of a series start H samples apart (in_stride_batch: the series pitch); 0: off
+        ("seg_reserved", C.c_int64),  # 0
+    ]
+
+
 class _ExecField(C.Structure):
     _fields_ = [("pass1_block", C.c_void_p), ("pass1_mode", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -84,7 +92,7 @@ def _bind(dll):
     dll.xrfthip_strerror.restype = C.c_char_p
     dll.xrfthip_strerror.argtypes = [C.c_int]
     dll.xrfthip_last_hip_error.restype = C.c_int
-    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), C.POINTER(Desc)]
+    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc or a DescSeg, by reference)
     dll.xrfthip_plan_destroy.argtypes = [vp]
     dll.xrfthip_plan_set_window.argtypes = [vp, C.c_int, vp, i64]
     dll.xrfthip_plan_set_phase.argtypes = [vp, C.c_int, vp, i64]

@@ -34,7 +34,8 @@ from . import _lib, engine
 from .labeled import Coordinate, DataArray, from_any, to_like
 
 __all__ = ["clear_plan_cache", "fft", "ifft", "dft", "idft", "detrend", "power_spectrum", "cross_spectrum", "cross_phase", "isotropize",
-           "isotropic_power_spectrum", "isotropic_cross_spectrum", "fit_loglog", "mean_power_spectrum", "mean_cross_spectrum"]
+           "isotropic_power_spectrum", "isotropic_cross_spectrum", "fit_loglog", "mean_power_spectrum", "mean_cross_spectrum", "welch_power_spectrum", "welch_cross_spectrum",
+           "welch_coherence"]
 
 _WINDOW_NAMES = [  # xrft.py:48-72
     "hann", "hamming", "kaiser", "tukey", "parzen", "taylor", "boxcar", "barthann", "bartlett", "blackman",
@@ -1927,6 +1928,173 @@ def coherence(da1, da2, mean_dim, dim=None, real_dim=None, scaling="density", wi
         cross = _to_device(cs.data)
         real_dt = torch.float32 if cross.dtype == torch.complex64 else torch.float64
         res = DataArray(engine.coherence(cross, _to_device(p1.data).to(real_dt), _to_device(p2.data).to(real_dt)), cs.dims, cs.coords, None, None)
+    res.name = "{}_{}_coherence".format(da1.name, da2.name) if da1.name and da2.name else None
+    return to_like(res, src)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Welch spectra: the mean spectrum of the overlapping segments of a long series (scipy.signal.welch / csd / coherence; the reference's
+# power_spectrum(da, dim="time", chunks_to_segments=True, window="hann", detrend="linear").mean("time_segment") with an overlap).  Fused where a plan takes the call
+# (xrfthip_desc.seg_hop: the segments read where they lie, no segment's spectrum stored), else composed: the segments unfolded, the public call, .mean.
+# ------------------------------------------------------------------------------------------------------
+def _welch_args(da, dim, nperseg, noverlap, least=1):
+    """(hop, number of segments) after the checks; trailing samples that do not fill a segment are dropped (as scipy.signal.welch does)."""
+    if not isinstance(dim, str):
+        raise ValueError(f"dim must be the name of ONE dimension (the axis the segments are cut from), not {dim!r}")
+    n = da.sizes[dim] if dim in da.dims else da.get_axis_num(dim)
+    nperseg = int(nperseg)
+    if nperseg < 1 or nperseg > n:
+        raise ValueError(f"nperseg = {nperseg} is not in 1 .. {n}, the length of {dim!r}")
+    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
+    if noverlap < 0 or noverlap >= nperseg:
+        raise ValueError(f"noverlap = {noverlap} must be in 0 .. nperseg - 1 = {nperseg - 1}")
+    hop = nperseg - noverlap
+    m = (n - nperseg) // hop + 1
+    if m < least:
+        raise ValueError(f"{m} segment(s) of {nperseg} samples fit {dim!r} ({n} samples, hop {hop}): at least {least} are needed")
+    return nperseg, hop, m
+
+
+def _welch_segments(da, dim, nperseg, hop):
+    """The labelled array of segments, a VIEW of the device data (tensor.unfold): ``dim`` becomes ``<dim>_segment`` where it lay and the samples of a segment are the
+    new last dim ``dim``, whose coordinate is the first ``nperseg`` values of the series' (every segment has the same spacing; the lag is the first segment's)."""
+    t = _to_device(da.data)
+    ax = da.get_axis_num(dim)
+    seg = t.unfold(ax, nperseg, hop)
+    dims = list(da.dims)
+    dims[ax] = dim + "_segment"
+    dims.append(dim)
+    coords = {}
+    for k, v in da.coords.items():
+        if k == dim:
+            coords[k] = Coordinate((dim,), np.asarray(v.values)[:nperseg], v.attrs, k)
+        elif dim not in v.dims:
+            coords[k] = v
+    return DataArray(seg, dims, coords, da.name, da.attrs)
+
+
+def _welch_series(da, dim):
+    """(series, samples) float32 device tensor with unit stride along the samples and one pitch between the series, and that pitch: the array itself where ``dim`` is
+    the trailing, contiguous axis; else arranged first (one transposed copy)."""
+    t = _to_device(da.data)
+    ax = da.get_axis_num(dim)
+    if ax != t.dim() - 1:
+        t = t.movedim(ax, -1)
+    if not (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+        t = t.contiguous().reshape(-1, t.shape[-1])
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def _welch_fused(c, c2, da, da2, dim, nperseg, hop, m, mode, scale, flags):
+    """The (series, nx_out) result of ONE plan with seg_hop, or None where the call composes: float64 / complex / half data, fewer than two segments, a length or a
+    flag the plan declines (XRFTHIP_UNSUPPORTED_LENGTH: lengths off the power-of-two table, a descending coordinate's flip), an empty array."""
+    if m < 2 or any(d is not None and _to_device(d.data).dtype != torch.float32 for d in (da, da2)) or math.prod(da.shape) == 0:
+        return None
+    fl, win, ph = _flags_tables(c, c.da, None if c2 is None else c2.lag_x, None if c2 is None else c2.reversed)
+    t, pitch = _welch_series(da, dim)
+    t2 = None
+    if da2 is not None:
+        t2, pitch2 = _welch_series(da2, dim)
+        if t2.shape != t.shape:
+            raise ValueError("The two datasets have different dimensions")
+        if pitch2 != pitch:
+            t, t2 = t.contiguous(), t2.contiguous()
+            pitch = t.shape[1]
+    kw = dict(ndim=1, batch=t.shape[0] * m, ny=1, nx=nperseg, dtype=torch.float32, out_mode=mode, detrend=c.detrend, flags=fl | flags, scale=float(scale),
+              window_x=win["x"], phase_x=None if mode == _lib.OUT_POWER else ph["x"], mean_batch=m, seg_hop=hop, in_stride_batch=int(pitch))
+    key = _plan_key(None, kw)
+    with _plan_lock:
+        if key in _MEAN_REFUSED:
+            return None
+    try:
+        plan = _get_plan(**kw)
+    except _lib.XrftHipError as e:
+        if e.status != _lib.UNSUPPORTED_LENGTH:
+            raise
+        with _plan_lock:
+            _MEAN_REFUSED[key] = True
+            while len(_MEAN_REFUSED) > 64:
+                _MEAN_REFUSED.popitem(last=False)
+        return None
+    out, _ = plan.execute(t, t2)
+    return out
+
+
+def _welch_spectrum(da, da2, dim, nperseg, noverlap, real_dim, scaling, window_correction, true_phase, kwargs, least=1):
+    da = from_any(da)
+    da2 = None if da2 is None else from_any(da2)
+    nperseg, hop, m = _welch_args(da, dim, nperseg, noverlap, least)
+    if da2 is not None and (tuple(da2.dims) != tuple(da.dims) or da2.shape != da.shape):
+        raise ValueError("The two datasets have different dimensions")
+    if real_dim is not None and real_dim != dim:
+        raise ValueError(f"real_dim must be {dim!r}, the one transform dimension, or None")
+    unknown = set(kwargs) - {"detrend", "window", "shift", "spacing_tol"}
+    if unknown:
+        raise TypeError(f"got an unexpected keyword argument {sorted(unknown)[0]!r}")
+    seg = _welch_segments(da, dim, nperseg, hop)
+    seg2 = None if da2 is None else _welch_segments(da2, dim, nperseg, hop)
+    sname = dim + "_segment"
+    # the labels, the scaling and the tables are those of ONE segment's spectrum
+    head = seg.isel(**{sname: 0})
+    head2 = None if seg2 is None else seg2.isel(**{sname: 0})
+    c, c2, mode, scale, flags = _spectrum(head, head2, [dim], real_dim, scaling, window_correction, true_phase, dict(kwargs))
+    if c.detrend == _lib.DETREND_LINEAR:  # (_refuse_nonfinite has seen the first segment: the refusal of the composed call covers every segment)
+        for d in (da, da2):
+            if d is None:
+                continue
+            lo, hi = torch.aminmax(_to_device(d.data).narrow(d.get_axis_num(dim), 0, (m - 1) * hop + nperseg))  # (a reduction: no array of flags; a NaN propagates into both)
+            if not bool(torch.isfinite(lo) & torch.isfinite(hi)):
+                raise ValueError("array must not contain infs or NaNs")
+    out = _welch_fused(c, c2, da, da2, dim, nperseg, hop, m, mode, scale, flags)
+    if out is not None:
+        extra = None
+        if c2 is not None and c.true_phase:  # (as _cross_result)
+            extra = {c.swap[d]: {"direct_lag": lag} for d, lag in zip(c.dim, c.lag_x)}
+        return _label_output(c, head, out, [d for d in head.dims if d != dim], extra)
+    kw = dict(dim=[dim], real_dim=real_dim, scaling=scaling, window_correction=window_correction, **kwargs)
+    full = power_spectrum(seg, **kw) if seg2 is None else cross_spectrum(seg, seg2, true_phase=true_phase, **kw)
+    return full.mean(sname)
+
+
+def welch_power_spectrum(da, dim, nperseg, noverlap=None, real_dim=None, scaling="density", window_correction=False, detrend=None, window=None, shift=True,
+                         spacing_tol=1e-3):
+    """Welch's estimate of the power spectrum along ``dim``: the series is cut into segments of ``nperseg`` samples that overlap by ``noverlap`` (default
+    ``nperseg // 2``; trailing samples that do not fill a segment are dropped, as scipy.signal.welch does), and the result is the mean over the segments of
+    ``power_spectrum`` of each -- detrend and window per segment.  Dims: the other dims in their order, then ``freq_<dim>``; coordinates and attrs are those of
+    ``power_spectrum`` of the first ``nperseg`` samples.  With ``window_correction=True`` and ``window="hann"`` the values are those of
+    ``scipy.signal.welch(..., return_onesided=False)`` after an fftshift (``real_dim=dim``: of ``return_onesided=True``).
+    float32 series whose ``nperseg`` is a power of two in 64 .. 4096 are read where they lie by ONE pass (xrfthip_desc.seg_hop: neither the copy of the segments nor
+    their spectra reach memory; a ``dim`` that is not the trailing axis costs one transposed copy first); every other call unfolds the segments, runs the plain
+    call and ``.mean``."""
+    src = da
+    kw = dict(detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol)
+    return to_like(_welch_spectrum(da, None, dim, nperseg, noverlap, real_dim, scaling, window_correction, False, kw), src)
+
+
+def welch_cross_spectrum(da1, da2, dim, nperseg, noverlap=None, real_dim=None, scaling="density", window_correction=False, detrend=None, window=None, shift=True,
+                         spacing_tol=1e-3, true_phase=True):
+    """Welch's estimate of the cross spectrum: the mean over the overlapping segments of ``cross_spectrum(seg1, seg2)``, ``F1 conj(F2)`` (see
+    ``welch_power_spectrum``).  scipy.signal.csd(x, y) forms ``conj(X) Y``: for coordinates that start at 0 (or ``true_phase=False``)
+    ``welch_cross_spectrum(x, y, ...)`` with ``window_correction=True`` is ``conj(scipy.signal.csd(x, y, return_onesided=False))`` after an fftshift, which is
+    ``csd(y, x)``."""
+    src = da1
+    kw = dict(detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol)
+    return to_like(_welch_spectrum(da1, da2, dim, nperseg, noverlap, real_dim, scaling, window_correction, true_phase, kw), src)
+
+
+def welch_coherence(da1, da2, dim, nperseg, noverlap=None, real_dim=None, scaling="density", window_correction=False, detrend=None, window=None, shift=True,
+                    spacing_tol=1e-3, true_phase=True):
+    """Magnitude-squared coherence ``|<F1 conj F2>|^2 / (<|F1|^2> <|F2|^2>)``, ``<.>`` the mean over the overlapping segments: scipy.signal.coherence.  The three
+    means are ``welch_cross_spectrum`` and ``welch_power_spectrum`` of each series; the division is the library's (xrfthip_coherence; no clamp).  Fewer than two
+    segments: ValueError (of one spectrum the coherence is 1 everywhere)."""
+    src = da1
+    da1, da2 = from_any(da1), from_any(da2)
+    kw = dict(detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol)
+    cs = from_any(_welch_spectrum(da1, da2, dim, nperseg, noverlap, real_dim, scaling, window_correction, true_phase, kw, least=2))
+    p1, p2 = (from_any(_welch_spectrum(d, None, dim, nperseg, noverlap, real_dim, scaling, window_correction, False, kw)) for d in (da1, da2))
+    cross = _to_device(cs.data)
+    real_dt = torch.float32 if cross.dtype == torch.complex64 else torch.float64
+    res = DataArray(engine.coherence(cross.contiguous(), _to_device(p1.data).to(real_dt).contiguous(), _to_device(p2.data).to(real_dt).contiguous()), cs.dims, cs.coords, None, None)
     res.name = "{}_{}_coherence".format(da1.name, da2.name) if da1.name and da2.name else None
     return to_like(res, src)
 

@@ -185,7 +185,9 @@ int try_fastr(xrfthip_plan* P) {
 }
 
 // one pass over 65536-sample float32 rows (fastr.h): a 1024-thread workgroup per row, or a resident set walking the rows
+static int run_fastw(const xrfthip_plan* P, const ExecArgs& a);
 static int run_fastr(const xrfthip_plan* P, const ExecArgs& a) {
+    if (P->family == Family::FastR && P->w_on) return run_fastw(P, a);  // (the Welch form)
     const xrfthip_desc& d = P->d;
     const void* in = a.in0; void* out = a.out; hipStream_t st = a.stream;
     const bool cin = P->family == Family::FastRComplex;
@@ -293,9 +295,94 @@ static int run_fastr(const xrfthip_plan* P, const ExecArgs& a) {
     return XRFTHIP_OK;
 }
 
+// FastR's Welch form (xrfthip_desc.seg_hop, fastw.h): the mean power / cross spectrum of the overlapping L-sample segments of each series, one pass over the series.
+// xrfthip_plan_create has checked the descriptor's shape (XRFTHIP_BAD_ARG); what is declined here is "the caller composes"
+int try_fastw(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    if (!welch_plan(P)) return kDeclined;
+    const bool len_ok = d.nx >= 64 && d.nx <= 4096 && (d.nx & (d.nx - 1)) == 0;
+    const uint32_t okw = XRFTHIP_SHIFT_X | XRFTHIP_ISHIFT_X | XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2;
+    if (!len_ok || d.dtype != XRFTHIP_F32 || in_half(P) || (d.flags & ~okw) || env_ll("XRFTHIP_FASTW", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
+    if (d.batch / d.mean_batch * 1024 > 0x7fffffffLL) return XRFTHIP_UNSUPPORTED_LENGTH;  // (one launch: outputs x runs workgroups)
+    P->family = P->chosen = Family::FastR;  // (the rows family: its Welch form)
+    P->w_on = true;
+    FftTables& t = P->tables[(int)d.nx];
+    const int rc = build_tables<float>(t, (int)d.nx);  // W_L^k, the radices of the in-place passes, and where they leave frequency k
+    if (rc) return rc;
+    for (int r : t.radix)
+        if (r != 2 && r != 4 && r != 8 && r != 16) return XRFTHIP_UNSUPPORTED_LENGTH;
+    return XRFTHIP_OK;
+}
+
+// FastW's workspace: the float64 partial of every run of every output (one launch, one workgroup per run); then the tile of a workgroup: as many pairs of segments
+// per round as the longest run has, a power of two, kWPoints points at most
+static void layout_fastw(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    layout_one_pass(P);
+    P->ws_bytes = mean_layout(P, 0, 1, d.batch);
+    const long long pairs = (P->mean_run + 1) / 2;
+    int G = 1;
+    while (G < pairs && G * d.nx < kWPoints) G *= 2;
+    P->w_G = G;
+    long long ss = d.nx + (d.nx >> 4) + 1;
+    if ((ss & 1) == 0) ++ss;  // (an odd stride: the sequences of a tile start on different banks)
+    P->w_stride = (int)ss;
+    const size_t tile = (((size_t)G * (size_t)ss + 1) & ~(size_t)1) * sizeof(cf);
+    P->w_lds = tile * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1) + (size_t)(2 * kWThreads + 4 * G) * sizeof(double);
+}
+
+static int run_fastw(const xrfthip_plan* P, const ExecArgs& a) {
+    const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
+    const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
+    const FftTables& t = P->tables.at((int)d.nx);
+    FastW p{};
+    p.in0 = (const float*)a.in0; p.in1 = (const float*)a.in1;
+    p.part = reinterpret_cast<double*>(a.ws + P->off_mean);
+    p.tw = (const cf*)t.tw.p; p.rev = (const unsigned*)t.rev.p;
+    p.win = (const float*)P->win[1].p;
+    p.pitch = P->w_pitch; p.hop = d.seg_hop;
+    p.L = (int)d.nx; p.M = (int)d.mean_batch; p.P = P->mean_P; p.G = P->w_G;
+    p.seq_stride = P->w_stride; p.pad_shift = 4;
+    p.nr = (int)t.radix.size();
+    for (int i = 0; i < p.nr; ++i) p.radix[i] = t.radix[i];
+    p.detrend = d.detrend;
+    p.scale = (float)d.scale;
+    const long long nout = d.batch / d.mean_batch, nwg = nout * P->mean_P;
+    if (nwg > 0x7fffffffLL) return XRFTHIP_BAD_ARG;
+    const dim3 grid((unsigned)nwg), blk((unsigned)kWThreads);
+    xrfthip_plan::ProfRec* rec = prof_begin(P, "fastw_segments", st);
+    if (two) { auto k = &fastw_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
+    else { auto k = &fastw_kernel<false>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
+    prof_end(rec, st);
+    HIP_TRY(hipGetLastError());
+    rec = prof_begin(P, "fastw_finish", st);
+    const int nxo = (int)P->nx_out, shift = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0, rd2 = (d.flags & XRFTHIP_REALDIM_X2) ? 1 : 0;
+    const double half_inv_m = 0.5 / (double)d.mean_batch;
+    const cf* ph = reinterpret_cast<const cf*>(P->fph[1].p);
+    const dim3 fgrid((unsigned)nout), fblk(256);
+    if (two) { auto k = &fastw_finish_kernel<true>; XRFT_LAUNCH(k, fgrid, fblk, 0, st, (const double*)p.part, a.out, p.L, nxo, p.P, half_inv_m, shift, rd2, ph, (P->fph_on && ph) ? 1 : 0); }
+    else { auto k = &fastw_finish_kernel<false>; XRFT_LAUNCH(k, fgrid, fblk, 0, st, (const double*)p.part, a.out, p.L, nxo, p.P, half_inv_m, shift, rd2, ph, 0); }
+    prof_end(rec, st);
+    HIP_TRY(hipGetLastError());
+    return XRFTHIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
-// the rows of FastS, FastR, FastRComplex and FastRRows (plan.h, FamilyOps)
+// the rows of FastS, FastR (with its Welch form), FastRComplex and FastRRows (plan.h, FamilyOps)
 // ---------------------------------------------------------------------------------------------------------------
+static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*) {
+    const xrfthip_desc& d = plan->d;
+    const FftTables& t = plan->tables.at((int)d.nx);
+    std::string rad;
+    for (int r : t.radix) appendf(rad, "%s%d", rad.empty() ? "" : "x", r);
+    appendf(s, "  [fastw] Welch spectra, one pass: %lld series of %lld segments of %lld samples, hop %lld (series pitch %lld), each segment read where it lies with 4-byte loads; "
+               "one %d-thread workgroup per run, %d segments per round packed in pairs (a + i b) as %d sequences of an LDS tile, detrend and window in the tile, radix "
+               "%s in place, |Z|^2 (Z conj Z') summed in %d float32 registers per thread, the pair symmetrised once by fastw_finish; lds=%zuB; "
+               "fastw_kernel: 115 VGPRs, no scratch, 4 waves per SIMD (two fields: 164 VGPRs, 3 waves); 4 algorithmic bytes per sample of the series through memory\n",
+            (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, (long long)d.nx, (long long)d.seg_hop, plan->w_pitch, kWThreads, 2 * plan->w_G, plan->w_G,
+            rad.c_str(), kWAcc * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1), plan->w_lds);
+}
 static void describe_fasts(const xrfthip_plan* plan, std::string& s, const char* in_note) {
     const SGeomRt G = sgeom(plan->d.ny, plan->d.nx);
     appendf(s, "  [fasts] one pass, one %d-thread workgroup per %lld x %lld slab (%d fit a CU): the packed columns' transform, their split and the rows' "
@@ -303,7 +390,9 @@ static void describe_fasts(const xrfthip_plan* plan, std::string& s, const char*
                "rows staged in LDS and written whole with the fftshift and the Hermitian mirror, lds=%zuB; 8 algorithmic bytes per sample through memory%s\n",
             G.thr, (long long)plan->d.ny, (long long)plan->d.nx, G.per_cu, (long long)plan->d.ny / 32, (long long)plan->d.nx / 32, G.lds, in_note);
 }
+static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*);
 static void describe_fastr(const xrfthip_plan* plan, std::string& s, const char* in_note) {
+    if (plan->w_on) { describe_fastw(plan, s, in_note); return; }
     const long long nxr = plan->d.nx;
     appendf(s, "  [fastr] one pass, one %lld-thread workgroup per %lld-sample row (grid %lld): the packed %lld-point complex transform in registers (32 per thread, "
                "r32x%dx%d, LDS exchanges%s), real split through the LDS, lds=%zuB; per-row detrend + window + full (or half) spectrum; "
@@ -328,11 +417,15 @@ static void describe_fastr_rows(const xrfthip_plan* plan, std::string& s, const 
                "16 algorithmic bytes per point through memory\n", R.thr, R.rk, (long long)plan->d.nx, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse" : "forward");
 }
 static void info_fasts(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTS; *n = 1; }
-static void info_fastr(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTR; *n = 1; }
+static void info_fastr(const xrfthip_plan* plan, int32_t* k, int32_t* n) {
+    if (plan->family == Family::FastR && plan->w_on) { *k = XRFTHIP_K_FASTW; *n = 2 * plan->w_G; return; }  // (the Welch form: segments per round)
+    *k = XRFTHIP_K_FASTR; *n = 1;
+}
+static void layout_fastr(xrfthip_plan* P) { if (P->w_on) layout_fastw(P); else layout_one_pass(P); }
 // (the entries in the order of struct FamilyOps: family, run, describe, kernel_info, finalize, layout, binmap, uses_bluestein, reads_strided)
 #ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
 const FamilyOps kOpsFastS = {Family::FastS, run_fasts, describe_fasts, info_fasts, fast_phase_tables, layout_fasts, fasts_build_tfirst, nullptr, true};
-const FamilyOps kOpsFastR = {Family::FastR, run_fastr, describe_fastr, info_fastr, fast_phase_tables, layout_one_pass, nullptr, nullptr, true};
+const FamilyOps kOpsFastR = {Family::FastR, run_fastr, describe_fastr, info_fastr, fast_phase_tables, layout_fastr, nullptr, nullptr, true};
 const FamilyOps kOpsFastRComplex = {Family::FastRComplex, run_fastr, describe_fastr_complex, info_fastr, fast_phase_tables, layout_one_pass};
 const FamilyOps kOpsFastRRows = {Family::FastRRows, run_fastr, describe_fastr_rows, info_fastr, fast_phase_tables, layout_one_pass};
 #endif
@@ -342,6 +435,7 @@ const FamilyOps kOpsFastRRows = {Family::FastRRows, run_fastr, describe_fastr_ro
 void set_attrs_rows() {
     const int m = (int)kLdsMax;
 #define SETF(K) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, m)
+    SETF((fastw_kernel<false>)); SETF((fastw_kernel<true>));  // (two tiles of 4096 points and their padding)
     SETF((fasts_power_kernel<8, 8, 0, 0>)); SETF((fasts_power_kernel<8, 4, 0, 0>)); SETF((fasts_power_kernel<4, 8, 0, 0>));
     SETF((fasts_power_kernel<8, 8, 0>)); SETF((fasts_power_kernel<8, 8, 1>)); SETF((fasts_power_kernel<8, 8, 2>));  // (above 64 KB of dynamic LDS)
     SETF((fasts_power_kernel<8, 4, 0>)); SETF((fasts_power_kernel<8, 4, 1>)); SETF((fasts_power_kernel<8, 4, 2>));

@@ -15,7 +15,8 @@
 //                    the last pass of a three-axis spectrum (fasth.h)
 //                    (FastG, FastGY, FastH)
 //   host_rows.cpp    the register-resident one-pass kernels: small float32 slabs (fasts.h), long rows and complex rows (fastr.h)
-//                    (FastS, FastR, FastRComplex, FastRRows)
+//                    and Welch spectra, overlapping segments of a series averaged in one pass (fastw.h)
+//                    (FastS, FastR and its Welch form, FastRComplex, FastRRows)
 //   host_inner.cpp   two transform axes that are not the trailing pair (xrfthip_desc.inner / .mid): the fused passes and the composite plan
 //                    (FusedInner, Composite)
 //   ops.cpp          the stand-alone operations of the ABI (detrend, spectrum tail, gather, convert, reduce, isotropize, ...)
@@ -60,6 +61,7 @@
 #include "tile_fft.h"
 #include "fastg.h"
 #include "fasth.h"
+#include "fastw.h"
 #ifdef XRFT_SPLIT_TUS  /* the library built from several translation units: the fasty / fastm kernels are instantiated in inst_g*.cpp */
 namespace xrft {
 #define XRFT_KW extern template __global__
@@ -334,7 +336,7 @@ enum class Family {
     FastGY,          // one pass along one axis that is not the contiguous one, or along rows with one Rader prime (gy_rows) (fastg.h)
     FastMX,          // short rows, table lengths (fastm.h, fastm_xonly_kernel)
     FastMY,          // one axis that is not the contiguous one, table lengths (fastm.h, fastm_yonly_kernel)
-    FastR,           // one pass over a long real float32 row in registers (fastr.h)
+    FastR,           // one pass over a long real float32 row in registers (fastr.h); its Welch form (xrfthip_plan::w_on: xrfthip_desc.seg_hop, fastw.h) walks the overlapping segments of a series
     FastRComplex,    // ... complex rows of 2048 .. 16384 points (fastc_kernel)
     FastRRows,       // complex rows of 256 .. 4096 points: the row pass of fasty_c2c.h on the input's own rows
     FastYC,          // the two passes of fasty_c2c.h over complex float32 slabs
@@ -473,6 +475,12 @@ struct xrfthip_plan {
     // XRFTHIP_OUT_COHERENCE: the descriptor says OUT_CROSS from xrfthip_plan_create on -- every check, table, family and the column pass are the CROSS mean plan's -- and
     // this remembers what the row pass sums (fasty_rows_mean_kernel<NX, 3>: re C, im C, A, B per sample) and what mean_finish writes (|C|^2 / (A B), real)
     bool coherence = false;
+    // FastR's Welch form (xrfthip_desc.seg_hop): samples between series (the descriptor's in_stride_batch, or the dense span; d.in_stride_batch is 0 from xrfthip_plan_create on),
+    // the pairs of segments one workgroup transforms per round and its tile
+    long long w_pitch = 0;
+    bool w_on = false;  // the plan is FastR's Welch form (try_fastw took it): launcher, describe text, kernel kind (XRFTHIP_K_FASTW) and layout are that form's
+    int w_G = 1, w_stride = 0;
+    size_t w_lds = 0;
     ~xrfthip_plan() { for (auto* b : extra) delete b; prof_clear(); delete sub_x; delete sub_y; }
 };
 
@@ -553,6 +561,7 @@ void set_attrs_fastg();
 void set_attrs_rows();
 
 // the families' try_* (xrfthip_plan_create calls them in this order; the first that does not return kDeclined decides)
+int try_fastw(xrfthip_plan* P);
 int try_fasth(xrfthip_plan* P);
 int try_fasts(xrfthip_plan* P);
 int try_fastyc(xrfthip_plan* P);
@@ -579,9 +588,10 @@ inline bool herm_field_plan(const xrfthip_plan* P) { return P && P->d.herm_ny > 
 // The mean over the batch inside the last pass (xrfthip_desc.mean_batch, normalised by xrfthip_plan_create: 0 = off, else M > 1): the families with a mean form are
 // FastY's two-pass slabs and FastS below 256 points per axis with dense float32 input; every other family answers XRFTHIP_UNSUPPORTED_LENGTH (the caller composes).
 inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1; }
-inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || (P->family == Family::FastS && !P->coherence); }  // (FastS has no two-field form)
+inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || (P->family == Family::FastS && !P->coherence) || (P->family == Family::FastR && P->w_on); }  // (FastS has no two-field form)
 size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs);  // (xrft_hip.cpp: mean_P and the partials behind `off`; returns the new end)
 int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStream_t st);  // (... and the finishing kernel, after the last group)
+inline bool welch_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0; }  // (the descriptor asks for the mean over overlapping segments: served by FastR's Welch form or not at all)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's
 // input take them: pass 1 of the two-pass families, the load of the one-pass families.  The intermediate and the output are dense.

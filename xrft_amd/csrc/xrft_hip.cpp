@@ -646,7 +646,9 @@ size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs
     const long long M = d.mean_batch, per_launch = std::max<long long>(1, slabs / M), cap = std::max<long long>(1, std::min(slabs, M));
     // (... and at most ny / 4 runs: the partials stay within (P + 1) results, a float64 half spectrum being one result and two rows).  XRFTHIP_MEAN_RUNS pins P
     // (1 .. min(slabs, M)) for measurements: long runs at 1, more workgroups than the rule gives above it
-    P->mean_P = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(cap, d.ny / 4), (4LL * kCUs) / std::max<long long>(1, units * per_launch)));
+    // (a Welch plan, ny = 1: at most M / 2 runs -- a run holds a pair of segments at least; its partial is one spectrum of L values)
+    const long long most = welch_plan(P) ? std::max<long long>(1, M / 2) : d.ny / 4;
+    P->mean_P = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(cap, most), (4LL * kCUs) / std::max<long long>(1, units * per_launch)));
     if (P->tune_mean_runs > 0) P->mean_P = (int)std::min<long long>(cap, P->tune_mean_runs);
     P->mean_run = (cap + P->mean_P - 1) / P->mean_P;
     P->off_mean = off;
@@ -884,9 +886,10 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // (... and of the versions before `mid` and before the input strides: mid = 1, strides 0)
     // (... and of the version before herm_ny / herm_nx: 0, 0)
     constexpr uint32_t kOldDescSize = (uint32_t)offsetof(xrfthip_desc, inner), kOldDescSize2 = (uint32_t)offsetof(xrfthip_desc, mid), kOldDescSize3 = (uint32_t)offsetof(xrfthip_desc, in_stride_y),
-                       kOldDescSize4 = (uint32_t)offsetof(xrfthip_desc, herm_ny), kOldDescSize5 = (uint32_t)offsetof(xrfthip_desc, mean_batch);  // (... and before mean_batch: 0)
+                       kOldDescSize4 = (uint32_t)offsetof(xrfthip_desc, herm_ny), kOldDescSize5 = (uint32_t)offsetof(xrfthip_desc, mean_batch),  // (... and before mean_batch: 0)
+                       kOldDescSize6 = (uint32_t)offsetof(xrfthip_desc, seg_hop);  // (... and before seg_hop / seg_reserved: 0, 0 -- the two came together, no size between)
     if (!plan || !desc || (desc->struct_size != sizeof(xrfthip_desc) && desc->struct_size != kOldDescSize && desc->struct_size != kOldDescSize2 && desc->struct_size != kOldDescSize3 &&
-                           desc->struct_size != kOldDescSize4 && desc->struct_size != kOldDescSize5)) return XRFTHIP_BAD_ARG;
+                           desc->struct_size != kOldDescSize4 && desc->struct_size != kOldDescSize5 && desc->struct_size != kOldDescSize6)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);
     dcopy.struct_size = sizeof(xrfthip_desc);
@@ -896,6 +899,21 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (dcopy.in_stride_y < 0 || dcopy.in_stride_batch < 0) return XRFTHIP_BAD_ARG;
     if (dcopy.mean_batch < 0) return XRFTHIP_BAD_ARG;
     if (dcopy.mean_batch == 1) dcopy.mean_batch = 0;  // (the plain plan itself)
+    // seg_hop = H >= 1: Welch spectra (fastw.h).  in_stride_batch is the series pitch here (any multiple of 4 bytes: the kernel loads single samples); it is checked,
+    // remembered as w_pitch and cleared, so that nothing of the strided-view rules (16-byte strides and pointers) applies to such a plan
+    if (dcopy.seg_hop < 0 || dcopy.seg_reserved != 0) return XRFTHIP_BAD_ARG;
+    long long w_pitch = 0;
+    if (dcopy.seg_hop > 0) {
+        const xrfthip_desc& s = dcopy;
+        if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.seg_hop > s.nx || (s.flags & (XRFTHIP_AXIS_Y | XRFTHIP_ISO)) || s.inner > 1 || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y) return XRFTHIP_BAD_ARG;
+        if (s.mean_batch < 2 || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
+        if (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != XRFTHIP_OUT_CROSS) return XRFTHIP_BAD_ARG;
+        if (s.nx > (1LL << 30) || s.mean_batch > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;
+        const long long span = (s.mean_batch - 1) * s.seg_hop + s.nx;
+        if (s.in_stride_batch != 0 && s.in_stride_batch < span) return XRFTHIP_BAD_ARG;
+        w_pitch = s.in_stride_batch ? s.in_stride_batch : span;
+        dcopy.in_stride_batch = 0;
+    }
     {   // strides that say what a dense array says are the dense plan (any family serves it)
         const int64_t row = (dcopy.flags & XRFTHIP_C2R_X) ? dcopy.nx / 2 + 1 : dcopy.nx;
         if (dcopy.in_stride_y > 0 && dcopy.in_stride_y < row) return XRFTHIP_BAD_ARG;
@@ -953,7 +971,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // mean_batch = M > 1: the mean over every M consecutive slabs inside the last pass (fasty_mean.h, fasts_mean.h); what has no mean form is "the caller composes"
     if (d.mean_batch > 1) {
         if (d.batch % d.mean_batch != 0 || (d.out_mode != XRFTHIP_OUT_POWER && d.out_mode != XRFTHIP_OUT_CROSS) || (d.flags & XRFTHIP_ISO)) return XRFTHIP_BAD_ARG;
-        if ((d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2 | XRFTHIP_AXIS_Y)) || d.inner > 1 || d.mid > 1 || herm) return XRFTHIP_UNSUPPORTED_LENGTH;
+        if (!d.seg_hop && ((d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2 | XRFTHIP_AXIS_Y)) || d.inner > 1 || d.mid > 1 || herm)) return XRFTHIP_UNSUPPORTED_LENGTH;  // (a Welch plan has its own half output)
     }
     const bool strided = d.in_stride_y != 0 || d.in_stride_batch != 0;
     if (strided && (d.inner > 1 || d.mid > 1 || (d.flags & XRFTHIP_AXIS_Y))) return XRFTHIP_BAD_ARG;  // (those layouts stay dense)
@@ -980,6 +998,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     P->cplx_in = cplx_in;
     P->in16 = in16;
     P->coherence = coherence;
+    P->w_pitch = w_pitch;
     P->dbl = d.dtype == XRFTHIP_F64 || d.dtype == XRFTHIP_C128;
     P->rsize = P->dbl ? 8 : 4;
     P->csize = 2 * P->rsize;
@@ -997,13 +1016,14 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     }
     P->mirror = !cplx_in && !(d.flags & (XRFTHIP_HALF_X | XRFTHIP_AXIS_Y)) && P->width == d.nx / 2 + 1 && d.nx > 1;
     // the families in order of precedence: the first whose try_* does not decline serves the plan (its tables built); none: the generic passes
-    static int (*const kTry[])(xrfthip_plan*) = {try_fasth, try_fasts, try_fastyc, try_fastr, try_fasty, try_fast1d, try_fastm, try_fastmx, try_fastmy, try_fastgy, try_fastg, try_fastn};
+    static int (*const kTry[])(xrfthip_plan*) = {try_fastw, try_fasth, try_fasts, try_fastyc, try_fastr, try_fasty, try_fast1d, try_fastm, try_fastmx, try_fastmy, try_fastgy, try_fastg, try_fastn};
     int rc = kDeclined;
     if (!env_ll("XRFTHIP_NO_FAST", 0))
         for (auto try_family : kTry)
             if ((rc = try_family(P)) != kDeclined) break;
     if (rc == kDeclined) rc = XRFTHIP_OK;
     if (!rc && herm && P->family != Family::FastH) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family reads a half spectrum as columns: the caller composes the stages)
+    if (!rc && d.seg_hop && !P->w_on) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family cuts segments out of a series: the caller composes)
     const bool one_axis = P->family == Family::FastGY || P->family == Family::FastMY;
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_PHASE_IN) && !one_axis) rc = XRFTHIP_BAD_ARG;  // (the generic column tiles have no input phase)
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_HALF_X) && !one_axis) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (... and no half output: the caller transposes)
@@ -1011,7 +1031,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
         set_kernel_attrs_once();
         // nbins must be known before tiles are sized (the LDS histogram shares the tile's allocation): ISO plans are
         // (re)built in xrfthip_plan_set_binmap.  Build now for everything else.
-        if (!(d.flags & XRFTHIP_ISO) && P->family != Family::FastH) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
+        if (!(d.flags & XRFTHIP_ISO) && P->family != Family::FastH && !P->w_on) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
     }
     if (!rc) rc = finalize_plan(P);
     if (rc) { delete P; return rc; }
@@ -1223,7 +1243,7 @@ int xrfthip_exec_ex(const xrfthip_plan* plan, const xrfthip_exec_args* args) {
     if (!d_out && !(d.flags & XRFTHIP_NO_SPECTRUM_OUT)) return XRFTHIP_BAD_ARG;
     if (iso && (!d_iso || !P->binmap.p)) return d_iso ? XRFTHIP_MISSING_TABLE : XRFTHIP_BAD_ARG;
     const bool inner = inner_layout(P);  // (always a workspace)
-    if (!inner && P->family != Family::FastH && P->passes.empty()) return XRFTHIP_MISSING_TABLE;  // (the generic passes stand behind every other family)
+    if (!inner && P->family != Family::FastH && !P->w_on && P->passes.empty()) return XRFTHIP_MISSING_TABLE;  // (the generic passes stand behind every other family)
     // pass-1 blocks: the fields of a plan that hands them over (fasty_pass1_bytes), whole, aligned, apart from each other and from the workspace
     ExecArgs a{d_in0, d_in1, nullptr, (double*)d_iso, (char*)d_workspace, (hipStream_t)args->stream};
     const int nf = cross ? 2 : 1;

@@ -40,7 +40,7 @@ class SpectralPlan:
 
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
-                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0):
+                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
@@ -65,9 +65,11 @@ class SpectralPlan:
         # the mean over every ``mean_batch`` consecutive slabs inside the last pass (xrfthip_desc.mean_batch): batch // M outputs; 0 | 1 = the plain plan
         self.mean_batch = int(mean_batch)
         self.batch_out = self.batch // self.mean_batch if self.mean_batch > 1 else self.batch
-        d = _lib.Desc(C.sizeof(_lib.Desc), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
+        # Welch spectra (xrfthip_desc.seg_hop): the mean_batch segments of nx samples of each series start seg_hop samples apart; in_stride_batch is the series pitch
+        self.seg_hop = int(seg_hop)
+        d = _lib.DescSeg(C.sizeof(_lib.DescSeg), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
                       int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
-                      self.herm_ny, self.herm_nx, self.mean_batch)
+                      self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
         for axis, w in ((0, window_y), (1, window_x)):
             if w is not None:
@@ -145,6 +147,10 @@ class SpectralPlan:
     def _layout_ok(self, t):
         """Does the memory layout of ``t`` match the plan's: contiguous, or -- a plan with input strides -- a view (..., ny, nx) whose last stride is 1, whose row
         stride is the plan's, whose leading dims collapse to ONE batch stride equal to the plan's, and whose first element is 16-byte aligned."""
+        if self.seg_hop:  # (series, samples): rows of at least the segments' span, the plan's pitch apart, samples adjacent; 4-byte alignment is the dtype's
+            span = (self.mean_batch - 1) * self.seg_hop + self.nx
+            return (t.dim() == 2 and t.shape[0] == self.batch_out and t.shape[1] >= span and t.stride(1) == 1
+                    and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or span)))
         if not (self.in_stride_y or self.in_stride_batch):
             return t.is_contiguous()
         sy, sb = strides_of(t, self.ndim)
@@ -161,10 +167,10 @@ class SpectralPlan:
         take part in the reuse of the column pass (``reuse_column_pass``)."""
         dev = in0.device
         nx_in = self.nx // 2 + 1 if (self.flags & _lib.C2R_X) else self.nx
-        if in0.dtype != self.dtype or not self._layout_ok(in0) or in0.numel() != self.batch * self.ny * nx_in * self.inner * self.mid:
+        if in0.dtype != self.dtype or not self._layout_ok(in0) or (not self.seg_hop and in0.numel() != self.batch * self.ny * nx_in * self.inner * self.mid):
             raise ValueError("in0 does not match the plan (dtype / contiguity / size)")
         if self.out_mode in (_lib.OUT_CROSS, _lib.OUT_PHASE, _lib.OUT_COHERENCE):
-            if in1 is None or in1.dtype != self.dtype or not self._layout_ok(in1) or in1.numel() != in0.numel():
+            if in1 is None or in1.dtype != self.dtype or not self._layout_ok(in1) or (not self.seg_hop and in1.numel() != in0.numel()):
                 raise ValueError("in1 does not match the plan")
         want_out = not (self.flags & _lib.NO_SPECTRUM_OUT)
         if want_out and out is None:
