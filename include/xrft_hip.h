@@ -255,7 +255,7 @@ typedef struct xrfthip_desc {
      * of each series is touched.  Accepted: detrend NONE | CONSTANT | LINEAR per segment, as the 1-D plans define it; a window on axis 1; `scale`; XRFTHIP_SHIFT_X;
      * XRFTHIP_HALF_X with or without XRFTHIP_REALDIM_X2 (the one-sided spectrum, nx_out = L / 2 + 1; not together with SHIFT_X); XRFTHIP_ISHIFT_X (a factor (-1)^k
      * that cancels in both products: no effect); a phase table on axis 1 for CROSS (the net factor multiplies the mean, once).
-     * XRFTHIP_BAD_ARG: H < 0, H > L; seg_hop with ndim = 2, XRFTHIP_AXIS_Y, inner / mid, herm_*, XRFTHIP_ISO or in_stride_y; mean_batch < 2; batch % M != 0;
+     * XRFTHIP_BAD_ARG: H < 0, H > L; seg_hop with ndim = 2, XRFTHIP_AXIS_Y, inner (without seg_stride, below) / mid, herm_*, XRFTHIP_ISO or in_stride_y; mean_batch < 2; batch % M != 0;
      * out_mode COMPLEX | PHASE | COHERENCE; a pitch smaller than the span.  XRFTHIP_UNSUPPORTED_LENGTH ("the caller composes": the segments copied out, the plain
      * 1-D plan, xrfthip_reduce_axis): L not a power of two in 64 .. 4096, float64 / complex / float16 / bfloat16 input, the FLIP flags.
      * Sums: no floating-point atomics; the order of every addition is fixed by the plan, so repeated calls return identical bits; at most 16 float32 terms are added in
@@ -264,7 +264,28 @@ typedef struct xrfthip_desc {
      * Served by the Welch form of the rows family (xrfthip_plan_kernel_info: XRFTHIP_K_FASTW).  Descriptors with the struct_size of the six earlier versions are accepted (0).  As with mean_batch, the status of
      * xrfthip_plan_create tells the capability: an older library answers XRFTHIP_BAD_ARG to the larger struct_size. */
     int64_t seg_hop;
-    int64_t seg_reserved; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_hop: struct_size is that of the version before the two, or sizeof(xrfthip_desc) */
+    int64_t seg_reserved; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_hop: no struct_size between the two */
+    /* Welch spectra along a LEADING axis, read where it lies: the layout of a (time, y, x) cube or of (member, time, lat, lon), the spectrum along time at every
+     * grid point, without a transposed copy of the cube.
+     *   seg_stride = S >= 1   elements between consecutive SAMPLES of a series.  Valid with seg_hop = H >= 1 (and everything seg_hop asks for: ndim = 1, ny = 1,
+     *                         nx = L, mean_batch = M >= 2, batch = P * M, mid = 1); `inner` = C_in >= 1 is the number of adjacent series ("columns") of a block,
+     *                         S >= inner.  Sample j of segment s of column e of block p is d_in0[p * in_stride_batch + (s * H + j) * S + e] (and d_in1 of a CROSS
+     *                         plan); in_stride_batch = 0 means ((M - 1) * H + L) * S, any other value is at least ((M - 1) * H + L - 1) * S + inner.  d_out is
+     *                         [P][inner][nx_out], frequency last, real (POWER) or complex (CROSS): each (p, e) holds what the rows form (seg_hop alone) writes for
+     *                         that series.  S > inner is a box of a wider grid; S = 1 with inner = 1 is the rows form itself, the same plan and the same bits.
+     *                         0 = off: `inner` > 1 with seg_hop stays XRFTHIP_BAD_ARG.
+     * Alignment: d_in0 / d_in1 4-byte aligned, any S, any inner, any pitch.  No byte outside the addressed samples is read: the gap between inner and S is never touched.
+     * Accepted: everything the rows form accepts (detrend per segment, a window, `scale`, SHIFT_X, HALF_X with or without REALDIM_X2, ISHIFT_X without effect, a phase
+     * table for CROSS).  XRFTHIP_BAD_ARG: S < 0, S > 0 with seg_hop = 0, S < inner, a pitch below the span above, seg_reserved2 != 0, and everything seg_hop refuses.
+     * XRFTHIP_UNSUPPORTED_LENGTH ("the caller arranges -- one transposed copy, then the rows form -- or composes"): L not a power of two in 64 .. 512, everything the
+     * rows form declines, XRFTHIP_FASTW_COLS=0 in the environment when the plan is created.
+     * The sums are the rows form's: pairs of segments of the SAME column packed as a + i b, at most 16 float32 terms in a row, then float64, no atomics, a fixed order
+     * (repeated calls return identical bits); a non-finite sample makes exactly its own column's output non-finite.  The float64 partials in the workspace are
+     * [P * inner][runs][L] (xrfthip_workspace_bytes includes them): a caller with a wide grid and a small workspace runs it in boxes of columns (S > inner).
+     * Still XRFTHIP_K_FASTW: a second layout of the same form.  Descriptors with the struct_size of the seven earlier versions are accepted (0, 0); an older library
+     * answers XRFTHIP_BAD_ARG to the larger struct_size.  Offsets are computed in 64 bits. */
+    int64_t seg_stride;
+    int64_t seg_reserved2; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_stride: no struct_size between the two */
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;

@@ -68,10 +68,18 @@ class Desc(C.Structure):
 
 
 class DescSeg(C.Structure):
-    """xrfthip_desc as the library has it now: ``Desc`` (the version up to mean_batch, still accepted under its own struct_size) and the two words appended together."""
+    """``Desc`` (the version up to mean_batch, still accepted under its own struct_size) and the two words appended together; itself still accepted under its own size."""
     _fields_ = Desc._fields_ + [
         ("seg_hop", C.c_int64),  # H >= 1: Welch spectra -- the M segments of nx samples of a series start H samples apart (in_stride_batch: the series pitch); 0: off
         ("seg_reserved", C.c_int64),  # 0
+    ]
+
+
+class DescCols(C.Structure):
+    """xrfthip_desc as the library has it now: ``DescSeg`` and the two words appended together after it."""
+    _fields_ = DescSeg._fields_ + [
+        ("seg_stride", C.c_int64),  # S >= 1 (with seg_hop): the column layout -- `inner` adjacent series whose samples lie S elements apart (in_stride_batch: the block pitch); 0: off
+        ("seg_reserved2", C.c_int64),  # 0
     ]
 
 
@@ -92,7 +100,7 @@ def _bind(dll):
     dll.xrfthip_strerror.restype = C.c_char_p
     dll.xrfthip_strerror.argtypes = [C.c_int]
     dll.xrfthip_last_hip_error.restype = C.c_int
-    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc or a DescSeg, by reference)
+    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg or a DescCols, by reference)
     dll.xrfthip_plan_destroy.argtypes = [vp]
     dll.xrfthip_plan_set_window.argtypes = [vp, C.c_int, vp, i64]
     dll.xrfthip_plan_set_phase.argtypes = [vp, C.c_int, vp, i64]

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import collections
 import math
+import os
 import threading
 import warnings
 from collections import OrderedDict
@@ -1975,7 +1976,7 @@ def _welch_segments(da, dim, nperseg, hop):
 
 def _welch_series(da, dim):
     """(series, samples) float32 device tensor with unit stride along the samples and one pitch between the series, and that pitch: the array itself where ``dim`` is
-    the trailing, contiguous axis; else arranged first (one transposed copy)."""
+    the trailing, contiguous axis; else arranged first (one transposed copy: what the column layout of the plan, _welch_fused_columns, did not take)."""
     t = _to_device(da.data)
     ax = da.get_axis_num(dim)
     if ax != t.dim() - 1:
@@ -1985,12 +1986,114 @@ def _welch_series(da, dim):
     return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
 
 
+# The float64 partials of a column plan are twice the float32 result per run (2 GB for a 720 x 1440 grid at nperseg = 256): wider grids run in blocks of columns,
+# each a view of the same array (seg_stride > inner), whose plan's workspace stays within this many bytes.  (A starting value: not measured.)
+_WELCH_COLS_WS_CAP = 256 << 20
+_WELCH_COLS_ALIGN = 32  # blocks are whole groups of columns (fastw.h, kWCols): every column is summed as in the unblocked call
+
+
+def _collapse(sizes, strides):
+    """(count, stride) of dims that are ONE run of equally spaced elements (size-1 dims skipped; no dims: (1, 0)), or None."""
+    n, st = 1, 0
+    for k, v in zip(reversed(sizes), reversed(strides)):  # innermost first: each outer stride is (extent x stride) of what lies inside it
+        if k == 1:
+            continue
+        if n > 1 and v != n * st:
+            return None
+        if n == 1:
+            st = v
+        n *= k
+    return n, st
+
+
+def _welch_columns(t, ax, span):
+    """The (blocks, samples, columns) view of a float32 device tensor that a column plan reads where it lies (xrfthip_desc.seg_stride), with its block pitch and its
+    sample stride -- or None: ``ax`` is the trailing axis, the dims behind it are not one unit-stride run, the dims in front not one pitch, or rows would overlap."""
+    if ax == t.dim() - 1 or os.environ.get("XRFTHIP_FASTW_COLS", "1") == "0":  # (the knob of the library, honoured before a cached plan could answer)
+        return None
+    back = _collapse(t.shape[ax + 1:], t.stride()[ax + 1:])
+    front = _collapse(t.shape[:ax], t.stride()[:ax])
+    if back is None or front is None:
+        return None
+    inner, s_in = back
+    blocks, pitch = front
+    ss = t.stride(ax)
+    if (inner > 1 and s_in != 1) or ss < inner or (inner == 1 and ss == 1):  # (unit sample stride: the rows layout, no copy either)
+        return None
+    if blocks > 1 and pitch < (span - 1) * ss + inner:
+        return None
+    return torch.as_strided(t, (blocks, t.shape[ax], inner), (pitch if blocks > 1 else t.shape[ax] * ss, ss, 1), t.storage_offset()), (pitch if blocks > 1 else 0), ss
+
+
+def _welch_plan(kw):
+    """The cached plan of a Welch call, or None where the library answers "the caller arranges or composes" (remembered in _MEAN_REFUSED)."""
+    key = _plan_key(None, kw)
+    with _plan_lock:
+        if key in _MEAN_REFUSED:
+            return None
+    try:
+        return _get_plan(**kw)
+    except _lib.XrftHipError as e:
+        if e.status != _lib.UNSUPPORTED_LENGTH:
+            raise
+        with _plan_lock:
+            _MEAN_REFUSED[key] = True
+            while len(_MEAN_REFUSED) > 64:
+                _MEAN_REFUSED.popitem(last=False)
+        return None
+
+
+def _welch_fused_columns(c, da, da2, dim, nperseg, hop, m, kw):
+    """The (blocks, columns, nx_out) result of the column plan(s) on the arrays where they lie, or None: a view that does not collapse, two fields with different
+    strides, a length the column layout declines.  Wide grids run in blocks of columns (_WELCH_COLS_WS_CAP): full blocks share one plan, the tail has one more."""
+    span = (m - 1) * hop + nperseg
+    ax = da.get_axis_num(dim)
+    t = _to_device(da.data)
+    v = _welch_columns(t, ax, span)
+    if v is None:
+        return None
+    view, pitch, ss = v
+    view2 = None
+    if da2 is not None:
+        t2 = _to_device(da2.data)
+        if t2.shape != t.shape:
+            raise ValueError("The two datasets have different dimensions")
+        if t2.stride() != t.stride():
+            return None
+        view2 = _welch_columns(t2, ax, span)[0]
+    blocks, _, inner = view.shape
+    per_col = blocks * nperseg * 8 * (1 if da2 is None else 2)  # (one run: what a wide grid gets)
+    width = max(_WELCH_COLS_ALIGN, _WELCH_COLS_WS_CAP // per_col // _WELCH_COLS_ALIGN * _WELCH_COLS_ALIGN)
+    out = None
+    for c0 in range(0, inner, width):
+        w = min(width, inner - c0)
+        plan = _welch_plan(dict(kw, batch=blocks * m, inner=w, seg_stride=ss, in_stride_batch=int(pitch)))
+        if plan is None:
+            return None  # (the first block: the length is the same for all)
+        part = [torch.as_strided(x, (blocks, x.shape[1], w), x.stride(), x.storage_offset() + c0) if w != inner else x for x in (view, view2) if x is not None]
+        if w == inner:
+            return plan.execute(*part)[0]
+        if out is None:
+            out = torch.empty((blocks, inner, plan.nx_out), dtype=plan.out_dtype(), device=t.device)
+        if blocks == 1:
+            plan.execute(*part, out=out[0, c0:c0 + w])
+        else:
+            out[:, c0:c0 + w] = plan.execute(*part)[0]
+    return out
+
+
 def _welch_fused(c, c2, da, da2, dim, nperseg, hop, m, mode, scale, flags):
     """The (series, nx_out) result of ONE plan with seg_hop, or None where the call composes: float64 / complex / half data, fewer than two segments, a length or a
-    flag the plan declines (XRFTHIP_UNSUPPORTED_LENGTH: lengths off the power-of-two table, a descending coordinate's flip), an empty array."""
+    flag the plan declines (XRFTHIP_UNSUPPORTED_LENGTH: lengths off the power-of-two table, a descending coordinate's flip), an empty array.  A ``dim`` that is not
+    the trailing axis is read where it lies by the column layout of the plan (seg_stride) where the array can be described by it; else it is arranged first."""
     if m < 2 or any(d is not None and _to_device(d.data).dtype != torch.float32 for d in (da, da2)) or math.prod(da.shape) == 0:
         return None
     fl, win, ph = _flags_tables(c, c.da, None if c2 is None else c2.lag_x, None if c2 is None else c2.reversed)
+    kw = dict(ndim=1, ny=1, nx=nperseg, dtype=torch.float32, out_mode=mode, detrend=c.detrend, flags=fl | flags, scale=float(scale),
+              window_x=win["x"], phase_x=None if mode == _lib.OUT_POWER else ph["x"], mean_batch=m, seg_hop=hop)
+    out = _welch_fused_columns(c, da, da2, dim, nperseg, hop, m, kw)
+    if out is not None:
+        return out
     t, pitch = _welch_series(da, dim)
     t2 = None
     if da2 is not None:
@@ -2000,21 +2103,8 @@ def _welch_fused(c, c2, da, da2, dim, nperseg, hop, m, mode, scale, flags):
         if pitch2 != pitch:
             t, t2 = t.contiguous(), t2.contiguous()
             pitch = t.shape[1]
-    kw = dict(ndim=1, batch=t.shape[0] * m, ny=1, nx=nperseg, dtype=torch.float32, out_mode=mode, detrend=c.detrend, flags=fl | flags, scale=float(scale),
-              window_x=win["x"], phase_x=None if mode == _lib.OUT_POWER else ph["x"], mean_batch=m, seg_hop=hop, in_stride_batch=int(pitch))
-    key = _plan_key(None, kw)
-    with _plan_lock:
-        if key in _MEAN_REFUSED:
-            return None
-    try:
-        plan = _get_plan(**kw)
-    except _lib.XrftHipError as e:
-        if e.status != _lib.UNSUPPORTED_LENGTH:
-            raise
-        with _plan_lock:
-            _MEAN_REFUSED[key] = True
-            while len(_MEAN_REFUSED) > 64:
-                _MEAN_REFUSED.popitem(last=False)
+    plan = _welch_plan(dict(kw, batch=t.shape[0] * m, in_stride_batch=int(pitch)))
+    if plan is None:
         return None
     out, _ = plan.execute(t, t2)
     return out
@@ -2064,8 +2154,9 @@ def welch_power_spectrum(da, dim, nperseg, noverlap=None, real_dim=None, scaling
     ``power_spectrum`` of the first ``nperseg`` samples.  With ``window_correction=True`` and ``window="hann"`` the values are those of
     ``scipy.signal.welch(..., return_onesided=False)`` after an fftshift (``real_dim=dim``: of ``return_onesided=True``).
     float32 series whose ``nperseg`` is a power of two in 64 .. 4096 are read where they lie by ONE pass (xrfthip_desc.seg_hop: neither the copy of the segments nor
-    their spectra reach memory; a ``dim`` that is not the trailing axis costs one transposed copy first); every other call unfolds the segments, runs the plain
-    call and ``.mean``."""
+    their spectra reach memory).  A ``dim`` that is not the trailing axis -- the time axis of a (time, y, x) cube -- is read where it lies too, for ``nperseg`` up
+    to 512, where the dims behind ``dim`` are one unit-stride run and the dims in front one pitch (a contiguous array, a slice of its last dim); longer segments
+    and other views are arranged first (one transposed copy).  Every other call unfolds the segments, runs the plain call and ``.mean``."""
     src = da
     kw = dict(detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol)
     return to_like(_welch_spectrum(da, None, dim, nperseg, noverlap, real_dim, scaling, window_correction, False, kw), src)

@@ -12,6 +12,12 @@
 //                         pairs the last segment with zeros.  Both members of a pair belong to the same output: a non-finite sample reaches its own series only.
 //                         After kMeanChain rounds (or the last) the registers are staged in the tile and added, float64, over the G sequences and into the
 //                         workgroup's own partial [output][run][L] of the workspace, in natural frequency order (first chain: stored).  No atomics.
+//                         The COLUMN layout (xrfthip_desc.seg_stride = S, fastw_kernel<TWO, true>): the series are `inner` adjacent columns of a block whose samples lie
+//                         S elements apart -- a (time, y, x) cube read where it lies.  A workgroup takes one block, one group of C adjacent columns (C = 32 for
+//                         L <= 128: 128 bytes of one time row per wave-load; 16 at L = 256 and 8 at L = 512, what the tile holds) and one run of segments;
+//                         sequence t of the tile is (column t % C, pair t / C), both members of a pair from the SAME column; the load loop runs column fastest,
+//                         then sample, then segment, the offset (s H + j) S + e in 64 bits; columns beyond `inner` in the last group load zeros and write
+//                         nothing; at the end of a chain the float64 sum runs over the G / C pairs of one column, into that column's own partial.
 //   fastw_finish_kernel   sums the runs of an output in order, symmetrises, x 1 / M, real-dim factor, true-phase factor (once, on the mean), fftshift or half output.
 // The order of every addition is fixed by the plan (M, G, the runs): repeated calls return identical bits.  XRFTHIP_ISHIFT_X is a factor (-1)^k on each transform that
 // cancels in |F|^2 and in F0 conj(F1): ignored.
@@ -24,6 +30,9 @@ namespace xrft {
 constexpr int kWThreads = 256;   // threads of a fastw workgroup
 constexpr int kWPoints = 4096;   // complex points of one field's tile: G = min(kWPoints / L, pairs of the longest run) sequences
 constexpr int kWAcc = kWPoints / kWThreads;  // tile positions (float32 sums) per thread and field
+constexpr int kWCols = 32;       // the column layout: adjacent columns per workgroup where the tile holds them (128 bytes of one time row per wave-load)
+constexpr int kWColsMaxL = 512;  // ... and its longest segment: 8 columns of 512 points fill the tile (a 32-byte piece of a time row per row of the load)
+constexpr const char* kWColsResources = "115 VGPRs, no scratch, 4 waves per SIMD (two fields: 164 VGPRs, 3 waves)";  // (scripts/kernel_resources.sh, gfx950: the rows kernels' figures)
 
 struct FastW {
     const float* in0;
@@ -32,28 +41,56 @@ struct FastW {
     const cf* tw;              // W_L^k, k < L
     const unsigned* rev;       // rev[k] = tile position of frequency k after the passes
     const float* win;          // L window values, or null
-    long long pitch;           // samples between series
+    long long pitch;           // samples between series (the column layout: between blocks)
     long long hop;             // samples between segment starts
+    long long sstride;         // the column layout: elements between consecutive samples of a series (S)
     int L, M, P, G;            // segment length, segments per series, runs per series, sequences (pairs of segments) per round
     int seq_stride, pad_shift; // the tile: sequence t at t * seq_stride, point p at p + (p >> pad_shift)
     int nr, radix[XRFT_MAX_PASSES];
     int detrend;
     float scale;
+    int inner, lgC, ngroups;   // the column layout: columns per block, log2 of the columns per workgroup (C), groups of C columns per block
 };
 
-// one field's 2 G segments from `s0` on (those below s_hi; the rest zeros) into its tile, detrended and windowed.  red: 2 * kWThreads doubles, coef: 2 * 2 * G doubles
-__device__ __forceinline__ void fastw_load(const FastW& p, const float* __restrict__ src, long long s0, long long s_hi, cf* tile, double* red, double* coef, int tid) {
+// Who owns the sequences of a tile.  Rows layout (COLS = false): all G sequences are pairs of segments of ONE series.  Column layout: a workgroup has C adjacent
+// columns of one block, sequence t = (column t % C, pair t / C): G / C pairs of every column per round.  Tile segment sg = 2 t + (member of the pair).
+template <bool COLS>
+struct WOwner {
+    int lgC, live;  // log2 C; the columns of this group that exist (the last group of a block may hold fewer than C: the rest are zeros and write nothing)
+    __device__ __forceinline__ int col(int sg) const { return COLS ? ((sg >> 1) & ((1 << lgC) - 1)) : 0; }
+    __device__ __forceinline__ int seg(int sg) const { return COLS ? ((((sg >> 1) >> lgC) << 1) | (sg & 1)) : sg; }  // the segment of its column, from the round's first
+    __device__ __forceinline__ bool has(int sg, long long s0, long long s_hi) const { return s0 + seg(sg) < s_hi && (!COLS || col(sg) < live); }
+};
+
+// one field's 2 G tile segments from segment `s0` on (those below s_hi; the rest zeros) into its tile, detrended and windowed.  red: 2 * kWThreads doubles, coef: 2 * 2 * G doubles
+// src: the first sample of the series (COLS: of the group's first column).  COLS: the load loop runs column fastest, then sample, then segment -- consecutive lanes
+// read consecutive addresses of one time row; the index (s H + j) S + e in 64 bits
+template <bool COLS>
+__device__ __forceinline__ void fastw_load(const FastW& p, const WOwner<COLS>& ow, const float* __restrict__ src, long long s0, long long s_hi, cf* tile, double* red, double* coef, int tid) {
     const int L = p.L, lgL = 31 - __builtin_clz((unsigned)L), nseg = 2 * p.G, total = nseg * L;
     const bool det = p.detrend != 0;
     for (int e = tid; e < total; e += kWThreads) {
-        const int seg = e >> lgL, j = e & (L - 1);
+        int sg, j;
+        long long off;
+        bool on;
+        if (COLS) {
+            const int c = e & ((1 << ow.lgC) - 1), r = e >> ow.lgC, sl = r >> lgL;  // column of the group, (segment of the round, sample)
+            j = r & (L - 1);
+            sg = ((((sl >> 1) << ow.lgC) | c) << 1) | (sl & 1);
+            on = s0 + sl < s_hi && c < ow.live;
+            off = ((s0 + sl) * p.hop + j) * p.sstride + c;
+        } else {
+            sg = e >> lgL; j = e & (L - 1);
+            on = s0 + sg < s_hi;
+            off = (s0 + sg) * p.hop + j;
+        }
         float v = 0.f;
-        if (s0 + seg < s_hi) {
-            v = src[(size_t)((s0 + seg) * p.hop + j)];
+        if (on) {
+            v = src[(size_t)off];
             if (!det && p.win) v *= p.win[j];
         }
-        float* dst = reinterpret_cast<float*>(tile + (seg >> 1) * p.seq_stride + phys(j, p.pad_shift));
-        dst[seg & 1] = v;
+        float* dst = reinterpret_cast<float*>(tile + (sg >> 1) * p.seq_stride + phys(j, p.pad_shift));
+        dst[sg & 1] = v;
     }
     __syncthreads();
     if (!det) return;
@@ -89,7 +126,7 @@ __device__ __forceinline__ void fastw_load(const FastW& p, const float* __restri
         const int sg = e >> lgL, j = e & (L - 1);
         float* dst = reinterpret_cast<float*>(tile + (sg >> 1) * p.seq_stride + phys(j, p.pad_shift)) + (sg & 1);
         float v = 0.f;
-        if (s0 + sg < s_hi) {  // (a missing segment stays zero whatever the window)
+        if (ow.has(sg, s0, s_hi)) {  // (a missing segment stays zero whatever the window)
             v = (float)((double)*dst - (coef[2 * sg] + coef[2 * sg + 1] * ((double)j - c)));
             if (p.win) v *= p.win[j];
         }
@@ -116,7 +153,9 @@ __device__ __forceinline__ void fastw_fft(const FastW& p, cf* tile, int tid) {
 }
 
 // LDS: [tile 0][tile 1 (TWO)][red: 2 kWThreads doubles][coef: 4 G doubles]
-template <bool TWO>
+// COLS: the column layout (xrfthip_desc.seg_stride) -- blockIdx = ((block, group of C columns), run); the float64 sum at the end of a chain runs over the G / C pairs
+// of ONE column, into that column's own partial; columns beyond `inner` in the last group write nothing
+template <bool TWO, bool COLS = false>
 __global__ void __launch_bounds__(kWThreads) fastw_kernel(FastW p) {
     XRFT_DYN_SMEM(smem_raw);
     const int tid = threadIdx.x;
@@ -125,22 +164,30 @@ __global__ void __launch_bounds__(kWThreads) fastw_kernel(FastW p) {
     cf* tile1 = tile0 + (TWO ? tile_elems : 0);
     double* red = reinterpret_cast<double*>(tile0 + (TWO ? 2 : 1) * tile_elems);
     double* coef = red + 2 * kWThreads;
-    const long long o = (long long)blockIdx.x / p.P;
+    const long long u = (long long)blockIdx.x / p.P;  // the series (COLS: the group of columns, over all blocks)
     const int pp = (int)((long long)blockIdx.x % p.P);
     const long long s_lo = (long long)pp * p.M / p.P, s_hi = (long long)(pp + 1) * p.M / p.P;
-    const float* __restrict__ src0 = p.in0 + (size_t)o * (size_t)p.pitch;
-    const float* __restrict__ src1 = TWO ? p.in1 + (size_t)o * (size_t)p.pitch : src0;
+    const long long blk = COLS ? u / p.ngroups : u;
+    const long long c0 = COLS ? (u % p.ngroups) << p.lgC : 0;  // the group's first column
+    WOwner<COLS> ow;
+    ow.lgC = COLS ? p.lgC : 0;
+    ow.live = !COLS ? 1 : ((long long)p.inner - c0 < (1LL << p.lgC) ? (int)((long long)p.inner - c0) : (1 << p.lgC));
+    const int lgC = ow.lgC, Gp = p.G >> lgC;  // pairs of segments of one column per round
+    const float* __restrict__ src0 = p.in0 + (size_t)blk * (size_t)p.pitch + (size_t)c0;
+    const float* __restrict__ src1 = TWO ? p.in1 + (size_t)blk * (size_t)p.pitch + (size_t)c0 : src0;
     constexpr int CW = TWO ? 2 : 1;
-    double* __restrict__ dst = p.part + ((size_t)o * p.P + pp) * (size_t)p.L * CW;
+    // the partial of output o (COLS: o = block * inner + column), run pp: [o][P][L]
+    double* __restrict__ dst = p.part + (((size_t)blk * (size_t)(COLS ? p.inner : 1) + (size_t)c0) * p.P + pp) * (size_t)p.L * CW;
+    const size_t dst_col = (size_t)p.P * (size_t)p.L * CW;  // between the partials of neighbouring columns
     const int L = p.L, lgL = 31 - __builtin_clz((unsigned)L), live = p.G * L;  // tile positions in use
     float acc[kWAcc * CW];
 #pragma unroll
     for (int e = 0; e < kWAcc * CW; ++e) acc[e] = 0.f;
     int chain = 0;
     bool first = true;
-    for (long long s = s_lo; s < s_hi; s += 2 * p.G) {
-        fastw_load(p, src0, s, s_hi, tile0, red, coef, tid);
-        if (TWO) fastw_load(p, src1, s, s_hi, tile1, red, coef, tid);
+    for (long long s = s_lo; s < s_hi; s += 2 * Gp) {
+        fastw_load<COLS>(p, ow, src0, s, s_hi, tile0, red, coef, tid);
+        if (TWO) fastw_load<COLS>(p, ow, src1, s, s_hi, tile1, red, coef, tid);
         fastw_fft(p, tile0, tid);
         if (TWO) fastw_fft(p, tile1, tid);
 #pragma unroll
@@ -158,27 +205,29 @@ __global__ void __launch_bounds__(kWThreads) fastw_kernel(FastW p) {
                 }
             }
         }
-        if (++chain < kMeanChain && s + 2 * p.G < s_hi) { __syncthreads(); continue; }  // (the next round's loads overwrite the tile)
-        // ---- the chain ends: every sum to its own tile position (nobody else reads or writes it), then per frequency the G sequences added in order, float64
+        if (++chain < kMeanChain && s + 2 * Gp < s_hi) { __syncthreads(); continue; }  // (the next round's loads overwrite the tile)
+        // ---- the chain ends: every sum to its own tile position (nobody else reads or writes it), then per frequency the sequences of an output added in order, float64
 #pragma unroll
         for (int q = 0; q < kWAcc; ++q) {
             const int e = tid + q * kWThreads;
             if (e < live) tile0[(e >> lgL) * p.seq_stride + phys(e & (L - 1), p.pad_shift)] = mk<float>(acc[CW * q], TWO ? acc[CW * q + (TWO ? 1 : 0)] : 0.f);
         }
         __syncthreads();
-        for (int k = tid; k < L; k += kWThreads) {
+        for (int w = tid; w < (ow.live << lgL); w += kWThreads) {  // (rows layout: w = k)
+            const int k = w & (L - 1), c = w >> lgL;
             const int pos = phys((int)p.rev[k], p.pad_shift);
             double sr = 0.0, si = 0.0;
-            for (int t = 0; t < p.G; ++t) {
-                const cf v = tile0[t * p.seq_stride + pos];
+            for (int t = 0; t < Gp; ++t) {
+                const cf v = tile0[((t << lgC) + c) * p.seq_stride + pos];
                 sr += (double)v.re;
                 if (TWO) si += (double)v.im;
             }
+            double* __restrict__ d = dst + (size_t)c * dst_col;
             if (TWO) {
-                dst[2 * k] = first ? sr : dst[2 * k] + sr;
-                dst[2 * k + 1] = first ? si : dst[2 * k + 1] + si;
+                d[2 * k] = first ? sr : d[2 * k] + sr;
+                d[2 * k + 1] = first ? si : d[2 * k + 1] + si;
             } else {
-                dst[k] = first ? sr : dst[k] + sr;
+                d[k] = first ? sr : d[k] + sr;
             }
         }
         __syncthreads();

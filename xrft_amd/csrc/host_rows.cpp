@@ -300,10 +300,13 @@ static int run_fastr(const xrfthip_plan* P, const ExecArgs& a) {
 int try_fastw(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
     if (!welch_plan(P)) return kDeclined;
-    const bool len_ok = d.nx >= 64 && d.nx <= 4096 && (d.nx & (d.nx - 1)) == 0;
+    const bool cols = welch_cols(P);
+    // (the column layout: up to 512 points -- the tile holds 8 adjacent columns at least; beyond, the caller arranges the series as rows)
+    const bool len_ok = d.nx >= 64 && d.nx <= (cols ? kWColsMaxL : 4096) && (d.nx & (d.nx - 1)) == 0;
     const uint32_t okw = XRFTHIP_SHIFT_X | XRFTHIP_ISHIFT_X | XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2;
     if (!len_ok || d.dtype != XRFTHIP_F32 || in_half(P) || (d.flags & ~okw) || env_ll("XRFTHIP_FASTW", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
-    if (d.batch / d.mean_batch * 1024 > 0x7fffffffLL) return XRFTHIP_UNSUPPORTED_LENGTH;  // (one launch: outputs x runs workgroups)
+    if (cols && env_ll("XRFTHIP_FASTW_COLS", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
+    if (d.batch / d.mean_batch * (cols ? d.inner : 1) > 0x7fffffffLL / 1024) return XRFTHIP_UNSUPPORTED_LENGTH;  // (one launch: outputs x runs workgroups; one finish workgroup per output)
     P->family = P->chosen = Family::FastR;  // (the rows family: its Welch form)
     P->w_on = true;
     FftTables& t = P->tables[(int)d.nx];
@@ -319,10 +322,17 @@ int try_fastw(xrfthip_plan* P) {
 static void layout_fastw(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
     layout_one_pass(P);
-    P->ws_bytes = mean_layout(P, 0, 1, d.batch);
+    // the column layout: C adjacent columns per workgroup -- 32 (128 bytes of a time row) where the tile holds them, else what it holds
+    int C = 1;
+    if (welch_cols(P)) {
+        C = (int)std::min<long long>(kWCols, kWPoints / d.nx);  // (whatever `inner` is: the pairs per round, hence the order of a column's sums, do not depend on its neighbours)
+    }
+    P->w_C = C;
+    const long long ngroups = (std::max<long long>(d.inner, 1) + C - 1) / C;
+    P->ws_bytes = mean_layout(P, 0, 1, d.batch * (welch_cols(P) ? ngroups : 1));  // (the launch: groups x runs workgroups per block)
     const long long pairs = (P->mean_run + 1) / 2;
-    int G = 1;
-    while (G < pairs && G * d.nx < kWPoints) G *= 2;
+    int G = C;
+    while (G / C < pairs && G * d.nx < kWPoints) G *= 2;
     P->w_G = G;
     long long ss = d.nx + (d.nx >> 4) + 1;
     if ((ss & 1) == 0) ++ss;  // (an odd stride: the sequences of a tile start on different banks)
@@ -342,17 +352,26 @@ static int run_fastw(const xrfthip_plan* P, const ExecArgs& a) {
     p.tw = (const cf*)t.tw.p; p.rev = (const unsigned*)t.rev.p;
     p.win = (const float*)P->win[1].p;
     p.pitch = P->w_pitch; p.hop = d.seg_hop;
+    const bool cols = welch_cols(P);
+    const long long ngroups = cols ? (d.inner + P->w_C - 1) / P->w_C : 1, ncols = cols ? d.inner : 1;
+    p.sstride = cols ? d.seg_stride : 1; p.inner = (int)ncols; p.ngroups = (int)ngroups;
+    p.lgC = 0;
+    while ((1 << p.lgC) < P->w_C) ++p.lgC;
     p.L = (int)d.nx; p.M = (int)d.mean_batch; p.P = P->mean_P; p.G = P->w_G;
     p.seq_stride = P->w_stride; p.pad_shift = 4;
     p.nr = (int)t.radix.size();
     for (int i = 0; i < p.nr; ++i) p.radix[i] = t.radix[i];
     p.detrend = d.detrend;
     p.scale = (float)d.scale;
-    const long long nout = d.batch / d.mean_batch, nwg = nout * P->mean_P;
-    if (nwg > 0x7fffffffLL) return XRFTHIP_BAD_ARG;
+    const long long nblk = d.batch / d.mean_batch, nout = nblk * ncols, nwg = nblk * ngroups * P->mean_P;
+    if (nwg > 0x7fffffffLL || nout > 0x7fffffffLL) return XRFTHIP_BAD_ARG;
     const dim3 grid((unsigned)nwg), blk((unsigned)kWThreads);
     xrfthip_plan::ProfRec* rec = prof_begin(P, "fastw_segments", st);
-    if (two) { auto k = &fastw_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
+    if (cols) {
+        if (two) { auto k = &fastw_kernel<true, true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
+        else { auto k = &fastw_kernel<false, true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
+    }
+    else if (two) { auto k = &fastw_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
     else { auto k = &fastw_kernel<false>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
     prof_end(rec, st);
     HIP_TRY(hipGetLastError());
@@ -382,6 +401,12 @@ static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*
                "fastw_kernel: 115 VGPRs, no scratch, 4 waves per SIMD (two fields: 164 VGPRs, 3 waves); 4 algorithmic bytes per sample of the series through memory\n",
             (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, (long long)d.nx, (long long)d.seg_hop, plan->w_pitch, kWThreads, 2 * plan->w_G, plan->w_G,
             rad.c_str(), kWAcc * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1), plan->w_lds);
+    if (welch_cols(plan))
+        appendf(s, "  [fastw columns] the series lie along a leading axis, read where they lie: %lld blocks of %lld adjacent columns, sample stride %lld (block pitch %lld); "
+                   "a workgroup takes %d adjacent columns (%lld groups per block; %d bytes of one time row per wave-load) and %d pairs of segments of each per round, "
+                   "sequence t = (column t %% %d, pair t / %d); the float64 sums per column; fastw_kernel<cols>: %s\n",
+                (long long)(d.batch / d.mean_batch), (long long)d.inner, (long long)d.seg_stride, plan->w_pitch, plan->w_C, (long long)((d.inner + plan->w_C - 1) / plan->w_C),
+                4 * plan->w_C, plan->w_G / plan->w_C, plan->w_C, plan->w_C, kWColsResources);
 }
 static void describe_fasts(const xrfthip_plan* plan, std::string& s, const char* in_note) {
     const SGeomRt G = sgeom(plan->d.ny, plan->d.nx);
@@ -436,6 +461,7 @@ void set_attrs_rows() {
     const int m = (int)kLdsMax;
 #define SETF(K) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, m)
     SETF((fastw_kernel<false>)); SETF((fastw_kernel<true>));  // (two tiles of 4096 points and their padding)
+    SETF((fastw_kernel<false, true>)); SETF((fastw_kernel<true, true>));
     SETF((fasts_power_kernel<8, 8, 0, 0>)); SETF((fasts_power_kernel<8, 4, 0, 0>)); SETF((fasts_power_kernel<4, 8, 0, 0>));
     SETF((fasts_power_kernel<8, 8, 0>)); SETF((fasts_power_kernel<8, 8, 1>)); SETF((fasts_power_kernel<8, 8, 2>));  // (above 64 KB of dynamic LDS)
     SETF((fasts_power_kernel<8, 4, 0>)); SETF((fasts_power_kernel<8, 4, 1>)); SETF((fasts_power_kernel<8, 4, 2>));

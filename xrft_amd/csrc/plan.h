@@ -480,6 +480,7 @@ struct xrfthip_plan {
     long long w_pitch = 0;
     bool w_on = false;  // the plan is FastR's Welch form (try_fastw took it): launcher, describe text, kernel kind (XRFTHIP_K_FASTW) and layout are that form's
     int w_G = 1, w_stride = 0;
+    int w_C = 1;  // the column layout (xrfthip_desc.seg_stride): adjacent columns per workgroup; sequence t of the tile is (column t % w_C, pair t / w_C); 1: the rows layout
     size_t w_lds = 0;
     ~xrfthip_plan() { for (auto* b : extra) delete b; prof_clear(); delete sub_x; delete sub_y; }
 };
@@ -591,6 +592,7 @@ inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1; }
 inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || (P->family == Family::FastS && !P->coherence) || (P->family == Family::FastR && P->w_on); }  // (FastS has no two-field form)
 size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs);  // (xrft_hip.cpp: mean_P and the partials behind `off`; returns the new end)
 int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStream_t st);  // (... and the finishing kernel, after the last group)
+inline bool welch_cols(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_stride > 0; }  // (... along a leading axis: d.inner adjacent series, samples d.seg_stride apart; S = 1 was normalised to 0, the rows layout)
 inline bool welch_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0; }  // (the descriptor asks for the mean over overlapping segments: served by FastR's Welch form or not at all)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's

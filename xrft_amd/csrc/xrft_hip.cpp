@@ -502,7 +502,7 @@ void describe_passes(std::string& s, const std::vector<Pass>& v, const char* nam
 }  // namespace
 
 void appendf(std::string& s, const char* fmt, ...) {
-    char buf[512];
+    char buf[1024];  // (the longest describe line, [fastw], is about 800 characters)
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
@@ -653,7 +653,8 @@ size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs
     P->mean_run = (cap + P->mean_P - 1) / P->mean_P;
     P->off_mean = off;
     // (doubles per sample: a power 1, a cross spectrum 2, a coherence 4 -- re C, im C, A, B)
-    const size_t bytes = (size_t)(d.batch / M) * (size_t)P->mean_P * (size_t)(d.ny / 2 + 1) * (size_t)d.nx * sizeof(double) * (P->coherence ? 4 : d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1);
+    const size_t cols = welch_cols(P) ? (size_t)d.inner : 1;  // (the column layout of a Welch plan: every column an output)
+    const size_t bytes = (size_t)(d.batch / M) * cols * (size_t)P->mean_P * (size_t)(d.ny / 2 + 1) * (size_t)d.nx * sizeof(double) * (P->coherence ? 4 : d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1);
     return (off + bytes + 255) & ~(size_t)255;
 }
 
@@ -887,9 +888,10 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // (... and of the version before herm_ny / herm_nx: 0, 0)
     constexpr uint32_t kOldDescSize = (uint32_t)offsetof(xrfthip_desc, inner), kOldDescSize2 = (uint32_t)offsetof(xrfthip_desc, mid), kOldDescSize3 = (uint32_t)offsetof(xrfthip_desc, in_stride_y),
                        kOldDescSize4 = (uint32_t)offsetof(xrfthip_desc, herm_ny), kOldDescSize5 = (uint32_t)offsetof(xrfthip_desc, mean_batch),  // (... and before mean_batch: 0)
-                       kOldDescSize6 = (uint32_t)offsetof(xrfthip_desc, seg_hop);  // (... and before seg_hop / seg_reserved: 0, 0 -- the two came together, no size between)
+                       kOldDescSize6 = (uint32_t)offsetof(xrfthip_desc, seg_hop),  // (... and before seg_hop / seg_reserved: 0, 0 -- the two came together, no size between)
+                       kOldDescSize7 = (uint32_t)offsetof(xrfthip_desc, seg_stride);  // (... and before seg_stride / seg_reserved2: likewise)
     if (!plan || !desc || (desc->struct_size != sizeof(xrfthip_desc) && desc->struct_size != kOldDescSize && desc->struct_size != kOldDescSize2 && desc->struct_size != kOldDescSize3 &&
-                           desc->struct_size != kOldDescSize4 && desc->struct_size != kOldDescSize5 && desc->struct_size != kOldDescSize6)) return XRFTHIP_BAD_ARG;
+                           desc->struct_size != kOldDescSize4 && desc->struct_size != kOldDescSize5 && desc->struct_size != kOldDescSize6 && desc->struct_size != kOldDescSize7)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);
     dcopy.struct_size = sizeof(xrfthip_desc);
@@ -901,17 +903,27 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (dcopy.mean_batch == 1) dcopy.mean_batch = 0;  // (the plain plan itself)
     // seg_hop = H >= 1: Welch spectra (fastw.h).  in_stride_batch is the series pitch here (any multiple of 4 bytes: the kernel loads single samples); it is checked,
     // remembered as w_pitch and cleared, so that nothing of the strided-view rules (16-byte strides and pointers) applies to such a plan
-    if (dcopy.seg_hop < 0 || dcopy.seg_reserved != 0) return XRFTHIP_BAD_ARG;
+    // seg_stride = S >= 1 (with seg_hop): the column layout of the same form -- `inner` adjacent series whose samples lie S elements apart, blocks in_stride_batch apart.
+    // S = 1 (inner = 1) says what the rows form says: normalised to it, the same plan
+    if (dcopy.seg_hop < 0 || dcopy.seg_reserved != 0 || dcopy.seg_stride < 0 || dcopy.seg_reserved2 != 0) return XRFTHIP_BAD_ARG;
+    if (dcopy.seg_stride > 0 && (dcopy.seg_hop == 0 || dcopy.seg_stride < dcopy.inner)) return XRFTHIP_BAD_ARG;
+    if (dcopy.seg_stride == 1) dcopy.seg_stride = 0;
     long long w_pitch = 0;
     if (dcopy.seg_hop > 0) {
         const xrfthip_desc& s = dcopy;
-        if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.seg_hop > s.nx || (s.flags & (XRFTHIP_AXIS_Y | XRFTHIP_ISO)) || s.inner > 1 || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y) return XRFTHIP_BAD_ARG;
+        if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.seg_hop > s.nx || (s.flags & (XRFTHIP_AXIS_Y | XRFTHIP_ISO)) || (s.inner > 1 && !s.seg_stride) || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y) return XRFTHIP_BAD_ARG;
         if (s.mean_batch < 2 || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
         if (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != XRFTHIP_OUT_CROSS) return XRFTHIP_BAD_ARG;
         if (s.nx > (1LL << 30) || s.mean_batch > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;
         const long long span = (s.mean_batch - 1) * s.seg_hop + s.nx;
-        if (s.in_stride_batch != 0 && s.in_stride_batch < span) return XRFTHIP_BAD_ARG;
-        w_pitch = s.in_stride_batch ? s.in_stride_batch : span;
+        if (s.seg_stride) {  // (the offsets stay far inside 64 bits: span < 2^62, S and inner below 2^31)
+            if (s.seg_stride > (1LL << 31) - 1 || s.inner > (1LL << 31) - 1 || span > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;
+            if (s.in_stride_batch != 0 && s.in_stride_batch < (span - 1) * s.seg_stride + s.inner) return XRFTHIP_BAD_ARG;
+            w_pitch = s.in_stride_batch ? s.in_stride_batch : span * s.seg_stride;
+        } else {
+            if (s.in_stride_batch != 0 && s.in_stride_batch < span) return XRFTHIP_BAD_ARG;
+            w_pitch = s.in_stride_batch ? s.in_stride_batch : span;
+        }
         dcopy.in_stride_batch = 0;
     }
     {   // strides that say what a dense array says are the dense plan (any family serves it)
@@ -983,8 +995,8 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     }
 
     // half input is read dense, by the trailing-axes families that half_family() names: everything else is "the caller widens" (xrfthip_convert, then the float32 plan)
-    if (in16 && (strided || d.inner > 1 || d.mid > 1 || (d.flags & XRFTHIP_AXIS_Y))) return XRFTHIP_UNSUPPORTED_LENGTH;
-    if (d.inner > 1 || d.mid > 1) return create_inner_plan(plan, d);
+    if (in16 && (strided || d.inner > 1 || d.mid > 1 || d.seg_stride || (d.flags & XRFTHIP_AXIS_Y))) return XRFTHIP_UNSUPPORTED_LENGTH;
+    if ((d.inner > 1 && !d.seg_stride) || d.mid > 1) return create_inner_plan(plan, d);  // (inner with seg_stride: the columns of a Welch plan, fastw.h)
 
     xrfthip_plan* P = new (std::nothrow) xrfthip_plan();
     if (!P) return XRFTHIP_ALLOC_FAILED;
@@ -1202,7 +1214,7 @@ int xrfthip_plan_describe(const xrfthip_plan* plan, char* buf, size_t buflen) {
     if (mean_plan(plan))
         appendf(s, "  [mean over the batch] mean_batch=%lld: %lld outputs, each the mean of %lld consecutive slabs summed inside the last pass (at most %d float32 terms in a row, then "
                    "float64), P=%d runs per output (run=%lld slabs at most per workgroup) with a float64 partial each (%zuB of the workspace), summed in order and written once by mean_finish; the spectra of the single slabs are never stored\n",
-                (long long)d.mean_batch, (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, kMeanChain, plan->mean_P, plan->mean_run, plan->ws_bytes - plan->off_mean);
+                (long long)d.mean_batch, (long long)(d.batch / d.mean_batch * (welch_cols(plan) ? d.inner : 1)), (long long)d.mean_batch, kMeanChain, plan->mean_P, plan->mean_run, plan->ws_bytes - plan->off_mean);
     if (mean_plan(plan) && plan->coherence)
         appendf(s, "  [coherence] the partial holds re C, im C, A, B per sample (C = sum F0 conj F1, A = sum |F0|^2, B = sum |F1|^2); mean_finish writes |C|^2 / (A B), real, "
                    "no clamp; scale, 1 / M and the phase tables cancel\n");

@@ -40,7 +40,7 @@ class SpectralPlan:
 
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
-                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0):
+                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0, seg_stride=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
@@ -67,9 +67,12 @@ class SpectralPlan:
         self.batch_out = self.batch // self.mean_batch if self.mean_batch > 1 else self.batch
         # Welch spectra (xrfthip_desc.seg_hop): the mean_batch segments of nx samples of each series start seg_hop samples apart; in_stride_batch is the series pitch
         self.seg_hop = int(seg_hop)
-        d = _lib.DescSeg(C.sizeof(_lib.DescSeg), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
+        # ... along a leading axis (xrfthip_desc.seg_stride): ``inner`` adjacent series whose samples lie seg_stride elements apart, blocks in_stride_batch apart;
+        # the result is (blocks, inner, nx_out).  1 (with inner = 1) says what the rows layout says
+        self.seg_stride = int(seg_stride)
+        d = _lib.DescCols(C.sizeof(_lib.DescCols), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
                       int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
-                      self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0)
+                      self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0, self.seg_stride, 0)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
         for axis, w in ((0, window_y), (1, window_x)):
             if w is not None:
@@ -147,6 +150,11 @@ class SpectralPlan:
     def _layout_ok(self, t):
         """Does the memory layout of ``t`` match the plan's: contiguous, or -- a plan with input strides -- a view (..., ny, nx) whose last stride is 1, whose row
         stride is the plan's, whose leading dims collapse to ONE batch stride equal to the plan's, and whose first element is 16-byte aligned."""
+        if self.seg_hop and self.seg_stride > 1:  # (blocks, samples, columns): exactly the view the plan addresses -- columns adjacent, samples seg_stride apart, blocks the plan's pitch apart
+            span = (self.mean_batch - 1) * self.seg_hop + self.nx
+            return (t.dim() == 3 and t.shape[0] == self.batch_out and t.shape[1] >= span and t.shape[2] == self.inner
+                    and (self.inner <= 1 or t.stride(2) == 1) and t.stride(1) == self.seg_stride
+                    and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or span * self.seg_stride)))
         if self.seg_hop:  # (series, samples): rows of at least the segments' span, the plan's pitch apart, samples adjacent; 4-byte alignment is the dtype's
             span = (self.mean_batch - 1) * self.seg_hop + self.nx
             return (t.dim() == 2 and t.shape[0] == self.batch_out and t.shape[1] >= span and t.stride(1) == 1
@@ -175,6 +183,8 @@ class SpectralPlan:
         want_out = not (self.flags & _lib.NO_SPECTRUM_OUT)
         if want_out and out is None:
             shape = (self.batch_out, self.ny_out, self.nx_out) + ((self.inner,) if self.inner > 1 else ())
+            if self.seg_hop and self.seg_stride > 1:  # (the column layout of a Welch plan: frequency last)
+                shape = (self.batch_out, self.inner, self.nx_out)
             if self.mid > 1:
                 shape = (self.batch, self.ny_out, self.mid, self.nx_out, self.inner)
             if self.herm_ny:
