@@ -800,3 +800,59 @@ def test_caller_buffers_are_held_to_the_plan():
 def test_inverse_transform_over_two_axes_that_are_not_the_trailing_pair():
     """xrft.ifft of (y, x, t) / (t, y, x) spectra over [y, x] / [t, x]: one axis at a time where the axes lie, no transposed copy."""
     cases.run_inverse_non_trailing_pairs()
+
+
+def test_ifft_host_side_runs_once_per_labels_and_arguments(monkeypatch):
+    """ifft remembers its host side (_ifft_host) on the labelled array per argument set: two identical calls derive it once, another lag derives it again."""
+    import warnings
+
+    import xrft_amd as xa
+    from xrft_amd import _inverse
+
+    rng = np.random.default_rng(3)
+    x = xa.DataArray(rng.standard_normal((3, 32)), ("t", "x"), {"t": np.arange(3), "x": np.arange(32) * 0.5})
+    calls = []
+    host = _inverse._ifft_host
+
+    def counted(*a, **k):
+        calls.append(a[2])  # (the lag)
+        return host(*a, **k)
+
+    monkeypatch.setattr(_inverse, "_ifft_host", counted)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        ft = xa.fft(x, dim=["x"])
+        a = xa.ifft(ft, dim=["freq_x"], lag=[0.0])
+        b = xa.ifft(ft, dim=["freq_x"], lag=[0.0])
+        assert len(calls) == 1 and np.array_equal(np.asarray(a.values), np.asarray(b.values)) and np.array_equal(a["x"].values, b["x"].values)
+        c = xa.ifft(ft, dim=["freq_x"], lag=[2.0])
+        assert calls == [[0.0], [2.0]] and np.array_equal(c["x"].values, a["x"].values + 2.0)
+        xa.ifft(ft, dim=["freq_x"], lag=[2.0])
+        assert len(calls) == 2
+
+
+def test_a_declined_welch_plan_is_not_asked_for_again(monkeypatch):
+    """welch_power_spectrum with nperseg = 100 (no plan cuts such segments: the call composes): the refusal is remembered, the second identical call constructs no
+    plan with the Welch descriptor."""
+    import xrft_amd as xa
+    from xrft_amd import engine
+
+    rng = np.random.default_rng(4)
+    x = xa.DataArray(rng.standard_normal((3, 1000)).astype(np.float32), ("s", "time"), {"s": np.arange(3), "time": np.arange(1000) * 0.5})
+    made = []
+    plan_type = engine.SpectralPlan
+
+    class Counted(plan_type):
+        def __init__(self, *a, **k):
+            made.append(k.get("seg_hop", 0))
+            super().__init__(*a, **k)
+
+    monkeypatch.setattr(engine, "SpectralPlan", Counted)
+    api.clear_plan_cache()
+    a = xa.welch_power_spectrum(x, "time", 100, window="hann", detrend="linear")
+    assert [h for h in made if h] == [50] and len(api._MEAN_REFUSED) == 1
+    n = len(api._MEAN_REFUSED)
+    del made[:]
+    b = xa.welch_power_spectrum(x, "time", 100, window="hann", detrend="linear")
+    assert not [h for h in made if h] and len(api._MEAN_REFUSED) == n and np.array_equal(np.asarray(a.values), np.asarray(b.values))
+    api.clear_plan_cache()

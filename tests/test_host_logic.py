@@ -200,3 +200,94 @@ def test_swap_xy_is_an_involution_that_maps_every_x_bit_to_its_y_bit():
     for flags in range(0, 1 << 17, 37):
         assert api._swap_xy(api._swap_xy(flags)) == flags
     assert api._swap_xy(every | other) == every | other
+
+
+def test_declined_keys_are_a_bounded_set_in_insertion_order():
+    from xrft_amd import _plans
+
+    s = _plans._DeclinedKeys()
+    for k in range(64):
+        s.add(("key", k))
+    assert len(s) == 64 and all(("key", k) in s for k in range(64))
+    s.add(("key", 5))                       # a key added again is not duplicated (and evicts nothing)
+    assert len(s) == 64 and ("key", 0) in s
+    s.add(("key", 64))                      # the 65th key evicts the first and no other
+    assert len(s) == 64 and ("key", 0) not in s and all(("key", k) in s for k in range(1, 65))
+    s.clear()
+    assert len(s) == 0 and ("key", 64) not in s
+    # the three sets of the API are the objects of _plans, and clear_plan_cache empties all of them
+    sets = (api._HALF_REFUSED, api._STRIDED_REFUSED, api._MEAN_REFUSED)
+    assert sets == (_plans._HALF_REFUSED, _plans._STRIDED_REFUSED, _plans._MEAN_REFUSED) and len({id(x) for x in sets}) == 3
+    for x in sets:
+        x.add(("test", id(x)))
+    assert all(len(x) >= 1 for x in sets)
+    api.clear_plan_cache()
+    assert [len(x) for x in sets] == [0, 0, 0]
+
+
+def test_label_memo_computes_once_per_labels_and_key():
+    from xrft_amd._hostside import _label_memo
+
+    da = xa.DataArray(np.zeros((4, 8)), ("t", "x"), {"t": np.arange(4), "x": np.arange(8) * 0.5})
+    runs = []
+
+    def compute():
+        runs.append(len(runs))
+        return ("value", len(runs))
+
+    assert _label_memo(da, "k", compute) == ("value", 1) and _label_memo(da, "k", compute) == ("value", 1) and len(runs) == 1
+    assert _label_memo(da, "other", compute) == ("value", 2) and len(runs) == 2  # another key: computed, both stored
+    assert set(da._memo[1]) == {"k", "other"}
+    assert _label_memo(da, None, compute) == ("value", 3) and set(da._memo[1]) == {"k", "other"}  # no key: computed, not stored
+    da.coords["x"].values = np.arange(8) * 0.25   # a coordinate reassigned: computed again, the store starts again
+    assert _label_memo(da, "k", compute) == ("value", 4) and set(da._memo[1]) == {"k"}
+    assert _label_memo(da, "k", compute) == ("value", 4) and len(runs) == 4
+    before = da._memo
+    da.coords["x"].values.setflags(write=True)    # writeable again: computed every time, nothing stored
+    assert _label_memo(da, "k", compute) == ("value", 5) and _label_memo(da, "k", compute) == ("value", 6)
+    assert da._memo is before and set(da._memo[1]) == {"k"}
+
+
+def test_label_memo_store_is_reset_after_more_than_16_keys():
+    from xrft_amd._hostside import _label_memo
+
+    da = xa.DataArray(np.zeros((4, 8)), ("t", "x"), {"t": np.arange(4), "x": np.arange(8) * 0.5})
+    for k in range(17):
+        _label_memo(da, k, lambda k=k: k)
+    assert set(da._memo[1]) == set(range(17))      # 17 keys: the reset comes with the next new key
+    _label_memo(da, 17, lambda: 17)
+    assert set(da._memo[1]) == {17}
+    assert _label_memo(da, 17, lambda: "not computed") == 17
+
+
+def test_dim_list_and_real_dim_last():
+    from xrft_amd._hostside import _dim_list, _real_dim_last
+
+    da = _da()
+    assert _dim_list(da, None) == ["time", "x", "y"] and _dim_list(da, "x") == ["x"]
+    assert _dim_list(da, ("y", "x")) == ["y", "x"] and _dim_list(da, ["x"]) == ["x"]
+    given = ["x", "y"]
+    assert _dim_list(da, given) == given and _dim_list(da, given) is not given
+    assert _real_dim_last(da, ["x", "y"], "x") == ["y", "x"] and _real_dim_last(da, ["x", "y"], "y") == ["x", "y"]
+    assert _real_dim_last(da, ["time", "x", "y"], "x") == ["time", "y", "x"]
+    assert _real_dim_last(da, ["y"], "x") == ["y", "x"]  # (an existing dim that was not listed joins the list, as in the reference)
+    with pytest.raises(ValueError) as e:
+        _real_dim_last(da, ["x", "y"], "z")
+    assert str(e.value) == "The dimension along which real FT is taken must be one of the existing dimensions."
+    with pytest.raises(ValueError) as e:
+        _real_dim_last(da, ["x", "y"], "z", "real IFT")
+    assert str(e.value) == "The dimension along which real IFT is taken must be one of the existing dimensions."
+
+
+def test_axis_roles_and_freq_name():
+    from xrft_amd._hostside import _axis_roles, _freq_name
+
+    da = _da()  # dims (time, x, y)
+    assert _axis_roles(da, ["x"], None) == (None, "x") and _axis_roles(da, ["time"], "time") == (None, "time")
+    assert _axis_roles(da, ["x", "y"], None) == ("x", "y")      # in memory order
+    assert _axis_roles(da, ["y", "x"], None) == ("x", "y")      # listed the other way round: x = the one stored last
+    assert _axis_roles(da, ["y", "time"], None) == ("time", "y")
+    assert _axis_roles(da, ["y", "x"], "x") == ("y", "x")       # real_dim: x = the last listed dim, wherever it lies
+    assert _axis_roles(da, ["x", "y"], "y") == ("x", "y")
+    assert _freq_name("x", "freq_") == "freq_x" and _freq_name("freq_x", "freq_") == "x"
+    assert _freq_name("frequency", "freq_") == "freq_frequency" and _freq_name("kx", "k") == "x" and _freq_name("x", "") == "x"

@@ -106,7 +106,7 @@ class DataArray:
         self.name = name
         self.attrs = dict(attrs or {})
         self._chunks = None  # {dim: tuple of chunk lengths}: metadata only (see .chunk)
-        self._memo = None    # what the API derived from this array's labels on earlier calls (xrft_amd/api.py:_analyze), with its guard
+        self._memo = None    # what the API derived from this array's labels on earlier calls (xrft_amd/_hostside.py:_label_memo), with its guard
         self.coords = {}
         if coords is not None:
             if isinstance(coords, dict):
@@ -125,7 +125,7 @@ class DataArray:
     @classmethod
     def _trusted(cls, data, dims, coords):
         """A result the library itself has just labelled: ``coords`` are Coordinate objects under their own names whose lengths match ``data`` by construction,
-        non-transform coordinates are the input's own (immutable) objects -- no copies, no checks (xrft_amd/api.py:_label_output; ~10 us of a 40-us call)."""
+        non-transform coordinates are the input's own (immutable) objects -- no copies, no checks (xrft_amd/_hostside.py:_label_output; ~10 us of a 40-us call)."""
         self = cls.__new__(cls)
         self.data = data
         self.dims = tuple(dims)
