@@ -97,6 +97,13 @@ typedef enum xrfthip_detrend_kind {
 #define XRFTHIP_SHIFT_X 0x004u  /* fftshift the output along x */
 #define XRFTHIP_ISHIFT_Y 0x008u /* ifftshift the input along y (true_phase, xrft.py:440) */
 #define XRFTHIP_ISHIFT_X 0x010u /* ifftshift the input along x */
+/* On an XRFTHIP_INVERSE plan ISHIFT_* rotates the (fftshifted) input samples themselves; a window and an XRFTHIP_PHASE_IN table are indexed by the SOURCE position
+ * of a sample, before the rotation: sample s is multiplied by window[s] (and phase[s]) and then moved to (s - n/2) mod n (n/2 rounded down), as
+ * numpy.fft.ifftshift of the windowed input does.  A forward plan computes the same; a family may fold the rotation of an even n into the output as the sign (-1)^k.
+ * The one-axis kernel families index a window by the transform's own sample: xrfthip_plan_set_window hands an inverse plan with ISHIFT along the windowed axis to
+ * the generic passes (xrfthip_plan_kernel_info says so), and answers XRFTHIP_BAD_ARG, leaving the plan without that window, where there is no generic form
+ * (XRFTHIP_AXIS_Y with XRFTHIP_PHASE_IN, below).
+ * Without XRFTHIP_PHASE_IN the phase tables multiply the RESULT of an inverse plan as they do a forward plan's: out[k] = phase[k] * ifft(...)[k] * scale. */
 #define XRFTHIP_FLIP_Y 0x020u   /* np.flip the input along y before the ifftshift (descending coordinate); CROSS/PHASE: field 1 (d_in1) */
 #define XRFTHIP_FLIP_X 0x040u   /* np.flip the input along x; CROSS/PHASE: field 1 */
 #define XRFTHIP_REALDIM_X2 0x080u /* with HALF_X and POWER|CROSS: multiply by [1,2,...,2,(1)] (xrft.py:673-682) */

@@ -363,7 +363,7 @@ __global__ void __launch_bounds__(fastg_max_threads<T>(), (sizeof(T) == 4 ? 4 : 
                 CT z = src[(size_t)is * nx + ms];
                 if ((CIN && p.ph_in)) z = cmul(z, p.one_d ? wxc[ms] : cmul(wyc[is], wxc[ms]));
                 if ((CIN && p.inv)) z.im = -z.im;
-                if (p.win_y) { const T w = (p.one_d ? (T)1 : wys[i]) * wxs[m]; z = mk<T>(z.re * w, z.im * w); }
+                if (p.win_y) { const T w = (p.one_d ? (T)1 : wys[is]) * wxs[ms]; z = mk<T>(z.re * w, z.im * w); }  // (the window of the source position)
                 tile[i * rs + m] = z;
             }
         } else {  // (npk = ny nx real samples)
@@ -728,7 +728,7 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4 ? 3 : 2)) fastgy_kernel(F
                 s[0] += (double)z.re; s[2] += (double)z.im;
                 s[1] = fma(ri, (double)z.re, s[1]); s[3] = fma(ri, (double)z.im, s[3]);
             } else if (p.win_y) {
-                const T w = reinterpret_cast<const T*>(p.win_y)[i];
+                const T w = reinterpret_cast<const T*>(p.win_y)[i];  // (the transform's own row: a window on a rotated input goes to the generic passes, one_axis_tables)
                 z = mk<T>(z.re * w, z.im * w);
             }
             tile[(RADER ? (int)pin[i] : i) * GS + g] = z;

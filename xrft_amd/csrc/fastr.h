@@ -578,7 +578,7 @@ __global__ void __launch_bounds__((R2Geom<R2, R3>::T), (R2Geom<R2, R3>::WPS)) fa
             for (int g = 0; g < 2; ++g) {
                 float w[16];
 #pragma unroll
-                for (int j = 0; j < 16; ++j) w[j] = p.win[tid + T * (16 * g + j)];  // (indexed by the transform's sample index, as fastm_xonly_kernel)
+                for (int j = 0; j < 16; ++j) w[j] = p.win[tid + T * (16 * g + j)];  // (indexed by the transform's own sample index: a window on a rotated input goes to the generic passes, one_axis_tables)
 #pragma unroll
                 for (int j = 0; j < 16; ++j) a[16 * g + j] = cscale(a[16 * g + j], w[j]);
                 fastr_sched_fence();

@@ -124,12 +124,11 @@ __global__ void __launch_bounds__(YCols<NY>::THR, (YCols<NY>::THR >= 512 ? 4 : Y
             b[q] = cmul(b[q], cmul(py, pxb));
         }
     }
-    if (p.win_on) {  // (indexed by the transform's own sample index, as the one-axis kernels do)
-        const int x0 = xb * CW + 2 * g;
-        const float wxa = p.win_x[x0], wxb = p.win_x[x0 + 1];
+    if (p.win_on) {  // (indexed by the SOURCE position, as the input phase: the window multiplies before the rotation)
+        const float wxa = p.win_x[xs0], wxb = p.win_x[xs0 + 1];
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const float wy = p.win_y[u + NT * q];
+            const float wy = p.win_y[u + NT * ((q + qrot) & 15)];
             a[q] = cscale(a[q], wy * wxa);
             b[q] = cscale(b[q], wy * wxb);
         }
@@ -212,7 +211,7 @@ __global__ void __launch_bounds__((YRows<NX>::THR), (YRows<NX>::THR / 128 < 1 ? 
         if (p.win_on) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const float w = p.win_x[u + NT * q];
+                const float w = p.win_x[u + NT * q];  // (the transform's own sample index: a window on a rotated input goes to the generic passes, one_axis_tables)
                 a[q] = cscale(a[q], w);
                 b[q] = cscale(b[q], w);
             }
@@ -426,7 +425,8 @@ __global__ void __launch_bounds__((YRows<M>::THR), (YRows<M>::THR >= 256 ? 2 : 1
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int q = 8 * h + j;
-                const cf x = z[q], pc = cconj(pr[j]);
+                cf x = z[q], pc = cconj(pr[j]);
+                if (q == 0 && u == 0) { x.im = 0.f; pc.im = 0.f; }  // (k = 0 and its partner, the Nyquist sample: numpy's irfft takes their real parts)
                 const cf e = mk<float>(x.re + pc.re, x.im + pc.im), d = mk<float>(x.re - pc.re, x.im - pc.im);  // 2E, X - conj P
                 // conj(W_nx^k) = conj(W_nx^u W_32^q)
                 const cf w = cconj(cmul(wut, mk<float>(C32[q], -S32[q])));

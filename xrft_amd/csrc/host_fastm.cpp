@@ -899,8 +899,8 @@ static bool fastn_uses_bluestein(const xrfthip_plan* P) { return P->n_blue_m > 0
 #ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
 const FamilyOps kOpsFastM = {Family::FastM, run_fastm, describe_fastm, info_fastm, two_pass_tables, layout_passes, fastm_build_tfirst, nullptr, true, nullptr, true, true, true};
 const FamilyOps kOpsFastN = {Family::FastN, run_fastm, describe_fastn, info_fastm, two_pass_tables, layout_passes, fastm_build_tfirst, fastn_uses_bluestein, true, nullptr, true, true, true};
-const FamilyOps kOpsFastMX = {Family::FastMX, run_fastmx, describe_fastmx, info_fastmx, fast_phase_tables, layout_passes, nullptr, nullptr, false, nullptr, true};
-const FamilyOps kOpsFastMY = {Family::FastMY, run_fastmy, describe_fastmy, info_fastmy, fast_phase_tables, layout_passes, nullptr, nullptr, false, nullptr, true};
+const FamilyOps kOpsFastMX = {Family::FastMX, run_fastmx, describe_fastmx, info_fastmx, one_axis_tables, layout_passes, nullptr, nullptr, false, nullptr, true};
+const FamilyOps kOpsFastMY = {Family::FastMY, run_fastmy, describe_fastmy, info_fastmy, one_axis_tables, layout_passes, nullptr, nullptr, false, nullptr, true};
 #endif
 
 

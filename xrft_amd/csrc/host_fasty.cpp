@@ -31,6 +31,24 @@ int fast_phase_tables(xrfthip_plan* P) {
     return XRFTHIP_OK;
 }
 
+// The one-axis families (FastMX, FastMY, FastGY, FastRComplex, FastRRows) read the window by the transform's own sample index, and the ISHIFT of an inverse plan
+// rotates the samples on load: the window would multiply the DESTINATION of a sample.  The header's order is window, then rotation, so such a plan goes to the
+// generic passes, which index window and input phase by the source position (their kernels are the forward transforms' too: the source-index form moved registers
+// and scratch of instantiations the forward plans run).  An AXIS_Y plan with PHASE_IN has no generic form: XRFTHIP_BAD_ARG, as the header says of it.
+int one_axis_tables(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const int rc = fast_phase_tables(P);
+    if (rc || !(d.flags & XRFTHIP_INVERSE)) return rc;
+    if (!((P->win[0].p && (d.flags & XRFTHIP_ISHIFT_Y)) || (P->win[1].p && (d.flags & XRFTHIP_ISHIFT_X)))) return rc;
+    if ((d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_PHASE_IN)) {  // (the refused window is dropped: the plan stays what it was before the call)
+        P->host_win_y.clear();
+        (void)upload_real_table(P, P->win[0], nullptr, 0, 0);
+        return XRFTHIP_BAD_ARG;
+    }
+    settle_family(P, true);
+    return XRFTHIP_OK;
+}
+
 // an isotropic cross spectrum with a true-phase factor that is not 1 (two fields with different lags): its radial sums would need
 // the factor per sample, which neither FastG's pass nor FastY's column pass carries (settle_family)
 bool cross_iso_phase(const xrfthip_plan* P) {

@@ -451,8 +451,8 @@ static void layout_fastr(xrfthip_plan* P) { if (P->w_on) layout_fastw(P); else l
 #ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
 const FamilyOps kOpsFastS = {Family::FastS, run_fasts, describe_fasts, info_fasts, fast_phase_tables, layout_fasts, fasts_build_tfirst, nullptr, true};
 const FamilyOps kOpsFastR = {Family::FastR, run_fastr, describe_fastr, info_fastr, fast_phase_tables, layout_fastr, nullptr, nullptr, true};
-const FamilyOps kOpsFastRComplex = {Family::FastRComplex, run_fastr, describe_fastr_complex, info_fastr, fast_phase_tables, layout_one_pass};
-const FamilyOps kOpsFastRRows = {Family::FastRRows, run_fastr, describe_fastr_rows, info_fastr, fast_phase_tables, layout_one_pass};
+const FamilyOps kOpsFastRComplex = {Family::FastRComplex, run_fastr, describe_fastr_complex, info_fastr, one_axis_tables, layout_one_pass};
+const FamilyOps kOpsFastRRows = {Family::FastRRows, run_fastr, describe_fastr_rows, info_fastr, one_axis_tables, layout_one_pass};
 #endif
 
 

@@ -531,6 +531,7 @@ void prof_end(xrfthip_plan::ProfRec* r, hipStream_t st);
 // host_fasty.cpp
 bool cross_iso_phase(const xrfthip_plan* P);
 int fast_phase_tables(xrfthip_plan* P);
+int one_axis_tables(xrfthip_plan* P);  // ... and a window on the rotated input of an inverse one-axis plan handed to the generic passes
 int two_pass_tables(xrfthip_plan* P);
 YGeomRt ycols_geom(long long ny);
 YGeomRt yrows_geom(long long nx, bool fs = false);

@@ -384,6 +384,7 @@ template <typename T>
 __device__ __forceinline__ void emit(const Epilogue& ep, long long b, int ky, int kx, C2<T> V, bool conj_it) {
     // V is F (COMPLEX), or F0 conj(F1) (CROSS), or (|F|^2, 0) (POWER), before phase and scale
     if (conj_it) V.im = -V.im;
+    if (ep.conj_out) V.im = -V.im;  // (an inverse transform's conj out BEFORE the output phase: the table multiplies the result, as in every specialised family)
     if (ep.mode != 1) {
         if (ep.ph_y) V = cmul(V, reinterpret_cast<const C2<T>*>(ep.ph_y)[ky]);
         if (ep.ph_x) V = cmul(V, reinterpret_cast<const C2<T>*>(ep.ph_x)[kx]);
@@ -391,7 +392,6 @@ __device__ __forceinline__ void emit(const Epilogue& ep, long long b, int ky, in
     T s = (T)ep.scale;
     if (ep.realdim_x2 && !(kx == 0 || ((ep.nx & 1) == 0 && kx == ep.nx / 2))) s *= (T)2;
     V = cscale(V, s);
-    if (ep.conj_out) V.im = -V.im;
     if (ep.out) {
         const long long off = b * ep.slab_stride + (long long)shift_dst(ky, ep.ny, ep.shift_y) * ep.row_stride + shift_dst(kx, ep.nx, ep.shift_x);
         if (ep.mode == 3) reinterpret_cast<T*>(ep.out)[off] = (T)atan2((double)V.im, (double)V.re);  // np.angle
