@@ -146,7 +146,7 @@ typedef struct xrfthip_desc {
     int32_t detrend;  /* xrfthip_detrend_kind */
     uint32_t flags;
     double scale;            /* COMPLEX: multiplies F (prod(dx) for true_amplitude); POWER/CROSS: multiplies the product */
-    int32_t slabs_per_group; /* 0 = auto: slabs pushed through all passes together (keeps the intermediate in MALL) */
+    int32_t slabs_per_group; /* 0 = auto: slabs pushed through all passes together (keeps the intermediate in MALL); a two-pass plan with XRFTHIP_ISO runs at most 65535 per group (xrfthip_plan_describe: group=) */
     int32_t reserved;
     /* Layout with the independent elements INNERMOST: with inner > 1 the arrays are [batch][ny][nx][inner] and the transform runs over
      * (ny, nx) for every (batch, inner) element -- two ADJACENT transform axes anywhere in a C-contiguous array (the reference transforms
@@ -221,7 +221,7 @@ typedef struct xrfthip_desc {
      * XRFTHIP_BAD_ARG: a negative M, batch % M != 0, out_mode COMPLEX | PHASE, XRFTHIP_ISO.  XRFTHIP_UNSUPPORTED_LENGTH means "the caller composes" (the plain plan, then
      * xrfthip_reduce_axis with scale = 1 / M): every kernel family without a mean form -- all but the two-pass float32 slabs (XRFTHIP_K_FASTY on 2-D plans; float16 /
      * bfloat16 and strided input included: the column pass is the plain plan's) and the one-pass float32 slabs of 64 | 128 points per axis (XRFTHIP_K_FASTS, dense
-     * float32 input, POWER; a 256 x 256 mean plan is served by FASTY) -- hence also XRFTHIP_HALF_X / REALDIM_X2, XRFTHIP_AXIS_Y, inner / mid and herm_*; a later
+     * float32 input, POWER; a 256 x 256 mean plan is served by FASTY) -- hence also XRFTHIP_HALF_X / REALDIM_X2, XRFTHIP_AXIS_Y, inner / mid and herm_*, and more than 2^31 - 1 output rows ((batch / M) * ny); a later
      * xrfthip_plan_set_* call that would move the plan to such a family answers the same.  Of these classes a plan takes, by default, those whose mean form measured
      * not slower than the composition it replaces (profiles/r15_batch_mean.txt: every FASTY class; FASTS slabs of 128 rows); FASTS slabs of 64 rows answer
      * XRFTHIP_UNSUPPORTED_LENGTH as well unless XRFTHIP_MEAN_ALL=1 is in the environment when the plan is created (docs/TUNING.md).

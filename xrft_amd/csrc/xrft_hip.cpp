@@ -597,6 +597,11 @@ void layout_passes(xrfthip_plan* P) {
         G = (long long)std::max<size_t>(1, target / std::max<size_t>(slab_w, 1));
     }
     G = std::max<long long>(1, std::min<long long>(G, std::max<long long>(d.batch, 1)));
+    // radial sums fused into the row pass (fasty always, fastm / fastn where fastm_iso_fused says so) end in iso_reduce_kernel with the group's slabs on grid.y: a larger
+    // group -- only a caller's slabs_per_group asks for one -- runs as several.  Held for every y-first plan with radial sums, whether or not the sums are fused (which
+    // is only known once the bin map is set; run_radial_sums chunks grid.y itself): the group, hence the workspace, does not depend on the map.  xrfthip_plan_describe
+    // prints the group that runs
+    if (fast && (d.flags & XRFTHIP_ISO)) G = std::min<long long>(G, 65535);
     P->G = (int)G;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const int nf = (d.out_mode == XRFTHIP_OUT_CROSS || d.out_mode == XRFTHIP_OUT_PHASE) ? 2 : 1;
@@ -984,6 +989,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (d.mean_batch > 1) {
         if (d.batch % d.mean_batch != 0 || (d.out_mode != XRFTHIP_OUT_POWER && d.out_mode != XRFTHIP_OUT_CROSS) || (d.flags & XRFTHIP_ISO)) return XRFTHIP_BAD_ARG;
         if (!d.seg_hop && ((d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2 | XRFTHIP_AXIS_Y)) || d.inner > 1 || d.mid > 1 || herm)) return XRFTHIP_UNSUPPORTED_LENGTH;  // (a Welch plan has its own half output)
+        if ((d.batch / d.mean_batch) * d.ny > 0x7fffffffLL) return XRFTHIP_UNSUPPORTED_LENGTH;  // (mean_finish_kernel: one workgroup per output row, run_mean_finish; refused before anything runs)
     }
     const bool strided = d.in_stride_y != 0 || d.in_stride_batch != 0;
     if (strided && (d.inner > 1 || d.mid > 1 || (d.flags & XRFTHIP_AXIS_Y))) return XRFTHIP_BAD_ARG;  // (those layouts stay dense)
