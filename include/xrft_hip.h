@@ -293,6 +293,28 @@ typedef struct xrfthip_desc {
      * answers XRFTHIP_BAD_ARG to the larger struct_size.  Offsets are computed in 64 bits. */
     int64_t seg_stride;
     int64_t seg_reserved2; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_stride: no struct_size between the two */
+    /* Spectrograms: the spectrum of EVERY segment, kept -- the other half of what seg_hop cuts out of a series (scipy.signal.spectrogram / stft; the reference's
+     * power_spectrum(da, dim="time", chunks_to_segments=True, ...) without .mean("time_segment"), with an overlap).  One pass reads the segments where they lie and
+     * writes each segment's spectrum once: neither the copy of the segments (twice the series at half overlap) nor a transposed copy of a cube exists.
+     *   seg_keep = 1   Valid with seg_hop = H >= 1 (and what seg_hop asks for: ndim = 1, ny = 1, nx = L, dtype XRFTHIP_F32), mean_batch = M >= 1 the segments per
+     *                  series (ONE segment is allowed), batch = P * M.  out_mode POWER | COMPLEX.  d_out is [P][M][nx_out], element (p, s, c) what the plain 1-D plan
+     *                  writes at place c for segment s of series p: |X_k|^2 scale, real float32 (POWER), or X_k scale, complex64 (COMPLEX); with seg_stride = S
+     *                  (the column layout, `inner` adjacent series) d_out is [P][M][nx_out][inner], the columns innermost -- the place the time axis had.
+     *                  0 = off: everything about the descriptor is as without the field (mean_batch = 1 and OUT_COMPLEX with seg_hop stay XRFTHIP_BAD_ARG).
+     * Input addressing, alignment (4 bytes) and the pitch rules are seg_hop's / seg_stride's; no byte outside the addressed samples is read.  Accepted: detrend NONE |
+     * CONSTANT | LINEAR per segment, a window on axis 1, `scale`, XRFTHIP_SHIFT_X, XRFTHIP_HALF_X (k = 0 .. L / 2; not with SHIFT_X) with or without XRFTHIP_REALDIM_X2
+     * (POWER), XRFTHIP_ISHIFT_X with POWER (no effect: no bit changes).
+     * XRFTHIP_BAD_ARG: seg_keep not 0 | 1, seg_keep without seg_hop, seg_reserved3 != 0, out_mode CROSS | PHASE | COHERENCE, XRFTHIP_REALDIM_X2 with COMPLEX, and
+     * everything seg_hop / seg_stride refuse.  XRFTHIP_UNSUPPORTED_LENGTH ("the caller composes": the segments copied out, the plain 1-D plan): L not a power of two
+     * in 64 .. 4096 (columns: 64 .. 512), input that is not float32, the FLIP flags, XRFTHIP_ISHIFT_X or a phase table (xrfthip_plan_set_phase) together with
+     * COMPLEX, a launch beyond 2^31 - 1 workgroups, XRFTHIP_FASTW=0 or XRFTHIP_FASTW_KEEP=0 in the environment when the plan is created; and, by default, the one class
+     * that measured slower than its composition (profiles/r21_spectrogram.txt): L = 4096 with H = L, unless XRFTHIP_MEAN_ALL=1 is in the environment (docs/TUNING.md).
+     * Every segment is a transform of its own (packed with itself, x_2j + i x_2j+1, L / 2 points): a non-finite sample makes exactly the segments that hold it
+     * non-finite, and every other (series, segment) keeps its bits.  No sums across segments, no atomics, no workspace (xrfthip_workspace_bytes is 0); repeated calls
+     * return identical bits.  Still XRFTHIP_K_FASTW: a third form of the same family (xrfthip_plan_describe prints a [fastw segments kept] line).  Descriptors with the
+     * struct_size of the eight earlier versions are accepted (0, 0); an older library answers XRFTHIP_BAD_ARG to the larger struct_size. */
+    int64_t seg_keep;
+    int64_t seg_reserved3; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_keep: no struct_size between the two */
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;

@@ -76,10 +76,18 @@ class DescSeg(C.Structure):
 
 
 class DescCols(C.Structure):
-    """xrfthip_desc as the library has it now: ``DescSeg`` and the two words appended together after it."""
+    """``DescSeg`` and the two words appended together after it; still accepted under its own struct_size."""
     _fields_ = DescSeg._fields_ + [
         ("seg_stride", C.c_int64),  # S >= 1 (with seg_hop): the column layout -- `inner` adjacent series whose samples lie S elements apart (in_stride_batch: the block pitch); 0: off
         ("seg_reserved2", C.c_int64),  # 0
+    ]
+
+
+class DescKeep(C.Structure):
+    """xrfthip_desc as the library has it now: ``DescCols`` and the two words appended together after it."""
+    _fields_ = DescCols._fields_ + [
+        ("seg_keep", C.c_int64),  # 1 (with seg_hop): every segment's spectrum kept, POWER | COMPLEX -- [series][M][nx_out] out ([blocks][M][nx_out][inner] with seg_stride); 0: off
+        ("seg_reserved3", C.c_int64),  # 0
     ]
 
 
@@ -100,7 +108,7 @@ def _bind(dll):
     dll.xrfthip_strerror.restype = C.c_char_p
     dll.xrfthip_strerror.argtypes = [C.c_int]
     dll.xrfthip_last_hip_error.restype = C.c_int
-    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg or a DescCols, by reference)
+    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg, a DescCols or a DescKeep, by reference)
     dll.xrfthip_plan_destroy.argtypes = [vp]
     dll.xrfthip_plan_set_window.argtypes = [vp, C.c_int, vp, i64]
     dll.xrfthip_plan_set_phase.argtypes = [vp, C.c_int, vp, i64]

@@ -1018,11 +1018,8 @@ def _welch_spectrum(da, da2, dim, nperseg, noverlap, real_dim, scaling, window_c
     c, c2, mode, scale, flags = _spectrum(head, head2, [dim], real_dim, scaling, window_correction, true_phase, dict(kwargs))
     if c.detrend == _lib.DETREND_LINEAR:  # (_refuse_nonfinite has seen the first segment: the refusal of the composed call covers every segment)
         for d in (da, da2):
-            if d is None:
-                continue
-            lo, hi = torch.aminmax(_to_device(d.data).narrow(d.get_axis_num(dim), 0, (m - 1) * hop + nperseg))  # (a reduction: no array of flags; a NaN propagates into both)
-            if not bool(torch.isfinite(lo) & torch.isfinite(hi)):
-                raise ValueError("array must not contain infs or NaNs")
+            if d is not None:
+                _refuse_nonfinite_span(d, dim, (m - 1) * hop + nperseg)
     out = _welch_fused(c, c2, da, da2, dim, nperseg, hop, m, mode, scale, flags)
     if out is not None:
         return _label_output(c, head, out, [d for d in head.dims if d != dim], _direct_lag_attrs(c) if c2 is not None and c.true_phase else None)  # (as _cross_result)
@@ -1069,6 +1066,122 @@ def welch_coherence(da1, da2, dim, nperseg, noverlap=None, real_dim=None, scalin
     cs = from_any(_welch_spectrum(da1, da2, dim, nperseg, noverlap, real_dim, scaling, window_correction, true_phase, kw, least=2))
     p1, p2 = (from_any(_welch_spectrum(d, None, dim, nperseg, noverlap, real_dim, scaling, window_correction, False, kw)) for d in (da1, da2))
     return to_like(_coherence_result(cs, p1, p2, da1, da2), src)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Spectrograms: the spectrum of EVERY overlapping segment (scipy.signal.spectrogram / stft; the reference's power_spectrum(da, dim="time",
+# chunks_to_segments=True, ...) without .mean("time_segment"), with an overlap).  Fused where a plan takes the call (xrfthip_desc.seg_keep: the segments read where
+# they lie, every spectrum written once, no copy of the segments), else composed: the segments unfolded, the public call, the dims moved (a view).
+# ------------------------------------------------------------------------------------------------------
+def _spectrogram_result(lab, data, da, dim, nperseg, hop, m):
+    """The labelled result: ``da.dims`` with ``dim`` replaced, where it lay, by (<dim>_segment, freq_<dim>); the coordinates, attrs and name of ``lab`` (a labelled
+    spectrum of the segments, or of the first one: its last dim is freq_<dim>), and the <dim>_segment coordinate -- the middle of each segment's samples,
+    c[s hop] + (c[s hop + nperseg - 1] - c[s hop]) / 2 (datetime64 included).  ``data``: the values in that order, or None: those of ``lab``, moved (a view)."""
+    sname, fname = dim + "_segment", lab.dims[-1]
+    final = [x for d in da.dims for x in ((sname, fname) if d == dim else (d,))]
+    if data is None:
+        data = lab.transpose(*final).data
+    v = np.asarray(da[dim].values)
+    lo, hi = v[0:(m - 1) * hop + 1:hop], v[nperseg - 1:(m - 1) * hop + nperseg:hop]
+    coords = dict(lab.coords)
+    coords[sname] = Coordinate((sname,), lo + (hi - lo) / 2, None, sname)
+    return DataArray(data, final, coords, lab.name, lab.attrs)
+
+
+def _spectrogram_composed(da, dim, nperseg, hop, m, complex_, kw):
+    """The definition of the result: the segments unfolded (a view), ``power_spectrum`` / ``fft(true_phase=False)`` along their samples, the dims moved."""
+    seg = _welch_segments(da, dim, nperseg, hop)
+    full = fft(seg, dim=[dim], true_phase=False, **kw) if complex_ else power_spectrum(seg, dim=[dim], **kw)
+    return _spectrogram_result(from_any(full), None, da, dim, nperseg, hop, m)
+
+
+def _spectrogram_fused(c, da, dim, nperseg, hop, m, mode, scale, flags):
+    """The values of ONE plan with seg_keep in the order of the result's dims, or None where the call composes: data that are not float32, an empty array, a length or a
+    flag the plan declines (XRFTHIP_UNSUPPORTED_LENGTH, remembered), XRFTHIP_FASTW_KEEP=0.  The trailing axis is read where it lies (a pitch included); a leading or
+    middle axis through the column layout (seg_stride, ``nperseg`` <= 512) where the array can be described by it -- the result then lies in its final order."""
+    t = _to_device(da.data)
+    if t.dtype != torch.float32 or math.prod(t.shape) == 0 or os.environ.get("XRFTHIP_FASTW_KEEP", "1") == "0":  # (the knob of the library, honoured before a cached plan could answer)
+        return None
+    fl, win, _ = _flags_tables(c, c.da, None, None)
+    kw = dict(ndim=1, ny=1, nx=nperseg, dtype=torch.float32, out_mode=mode, detrend=c.detrend, flags=fl | flags, scale=float(scale), window_x=win["x"], mean_batch=m,
+              seg_hop=hop, seg_keep=1)
+    ax = da.get_axis_num(dim)
+    if ax != t.dim() - 1:
+        v = _welch_columns(t, ax, (m - 1) * hop + nperseg)
+        if v is None:
+            return None
+        view, pitch, ss = v
+        plan = _rung(_MEAN_REFUSED, None, dict(kw, batch=view.shape[0] * m, inner=view.shape[2], seg_stride=ss, in_stride_batch=int(pitch)))
+        if plan is None:
+            return None
+        return plan.execute(view)[0].reshape(tuple(t.shape[:ax]) + (m, plan.nx_out) + tuple(t.shape[ax + 1:]))  # ([block][segment][frequency][column]: the final order)
+    rows, pitch = _welch_series(da, dim)
+    plan = _rung(_MEAN_REFUSED, None, dict(kw, batch=rows.shape[0] * m, in_stride_batch=int(pitch)))
+    if plan is None:
+        return None
+    return plan.execute(rows)[0].reshape(tuple(t.shape[:-1]) + (m, plan.nx_out))
+
+
+def _refuse_nonfinite_span(d, dim, n):
+    """scipy.signal.detrend's refusal over the first ``n`` samples along ``dim`` (a reduction: no array of flags; a NaN propagates into both ends)."""
+    lo, hi = torch.aminmax(_to_device(d.data).narrow(d.get_axis_num(dim), 0, n))
+    if not bool(torch.isfinite(lo) & torch.isfinite(hi)):
+        raise ValueError("array must not contain infs or NaNs")
+
+
+def _spectrogram(da, dim, nperseg, noverlap, complex_, analyse, kw):
+    da = from_any(da)
+    nperseg, hop, m = _welch_args(da, dim, nperseg, noverlap)
+    if kw.get("real_dim") is not None and kw["real_dim"] != dim:
+        raise ValueError(f"real_dim must be {dim!r}, the one transform dimension, or None")
+    # the labels, the scaling and the tables are those of ONE segment's spectrum
+    head = _welch_segments(da, dim, nperseg, hop).isel(**{dim + "_segment": 0})
+    c, mode, scale, flags = analyse(head)
+    if c.detrend == _lib.DETREND_LINEAR and math.prod(da.shape):  # (_refuse_nonfinite has seen the first segment: the refusal of the composed call covers every segment)
+        _refuse_nonfinite_span(da, dim, (m - 1) * hop + nperseg)
+    out = _spectrogram_fused(c, da, dim, nperseg, hop, m, mode, scale, flags)
+    if out is None:
+        return _spectrogram_composed(da, dim, nperseg, hop, m, complex_, kw)
+    other = [d for d in head.dims if d != dim]
+    lab = _label_output(c, head, out.new_empty(()).expand([head.sizes[d] for d in other] + [out.shape[da.get_axis_num(dim) + 1]]), other)
+    return _spectrogram_result(lab, out, da, dim, nperseg, hop, m)
+
+
+def spectrogram(da, dim, nperseg, noverlap=None, real_dim=None, scaling="density", window_correction=False, detrend=None, window=None, shift=True, spacing_tol=1e-3):
+    """The power spectrum of every segment of ``da`` along ``dim``: the series is cut into segments of ``nperseg`` samples that overlap by ``noverlap`` (default
+    ``nperseg // 2``; trailing samples that do not fill a segment are dropped; one segment is allowed) and the result is ``power_spectrum`` of each -- detrend and
+    window per segment -- kept, not averaged: ``welch_power_spectrum`` is its mean over ``<dim>_segment``.  Dims: those of ``da`` with ``dim`` replaced, where it
+    lay, by ``(<dim>_segment, freq_<dim>)``; ``freq_<dim>``, attrs and scaling are those of ``power_spectrum`` of the first ``nperseg`` samples; ``<dim>_segment``
+    carries the middle of each segment's samples, ``c[s hop] + (c[s hop + nperseg - 1] - c[s hop]) / 2`` (datetime64 too); coordinates that do not depend on
+    ``dim`` are kept.  With ``window_correction=True``, ``window="hann"`` and ``real_dim=dim`` the values are ``scipy.signal.spectrogram(..., mode="psd")``'s.
+    float32 data whose ``nperseg`` is a power of two in 64 .. 4096 are read where they lie by ONE pass that writes every segment's spectrum once
+    (xrfthip_desc.seg_keep): no copy of the segments (twice the series at half overlap) exists.  A ``dim`` that is not the trailing axis -- the time axis of a
+    (time, y, x) cube -- is read where it lies too, for ``nperseg`` up to 512, and the result is written in its final order (no transposed copy); every other call
+    unfolds the segments, runs ``power_spectrum`` and moves the dims (a view).  A linear detrend refuses non-finite samples inside the used span (ValueError)."""
+    src = da
+    kw = dict(real_dim=real_dim, scaling=scaling, window_correction=window_correction, detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol)
+
+    def analyse(head):
+        c, _, mode, scale, flags = _spectrum(head, None, [dim], real_dim, scaling, window_correction, False, dict(detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol))
+        return c, mode, scale, flags
+
+    return to_like(_spectrogram(da, dim, nperseg, noverlap, False, analyse, kw), src)
+
+
+def stft(da, dim, nperseg, noverlap=None, real_dim=None, detrend=None, window=None, shift=True, true_amplitude=False, spacing_tol=1e-3):
+    """The short-time Fourier transform: ``fft(..., true_phase=False)`` of every segment of ``da`` along ``dim`` (see ``spectrogram`` for the segments, the dims and
+    the coordinates); complex.  There is no ``true_phase`` argument: each segment's phase refers to its OWN first sample, not to the origin of the series'
+    coordinate (scipy.signal.stft's convention up to its scaling and padding).  ``true_amplitude=True`` multiplies by the spacing of ``dim``, as ``fft`` does.
+    Fused and composed as ``spectrogram`` is (XRFTHIP_OUT_COMPLEX)."""
+    src = da
+    kw = dict(real_dim=real_dim, detrend=detrend, window=window, shift=shift, true_amplitude=true_amplitude, spacing_tol=spacing_tol)
+
+    def analyse(head):
+        c = _analyze(head, spacing_tol, [dim], real_dim, shift, detrend, window, False, False, "freq_", None)
+        _refuse_nonfinite(c)
+        return c, _lib.OUT_COMPLEX, (math.prod(c.delta_x) if true_amplitude else 1.0), 0
+
+    return to_like(_spectrogram(da, dim, nperseg, noverlap, True, analyse, kw), src)
 
 
 def _cross_result(c, c2, mode, scale, flags):

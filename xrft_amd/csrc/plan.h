@@ -15,8 +15,8 @@
 //                    the last pass of a three-axis spectrum (fasth.h)
 //                    (FastG, FastGY, FastH)
 //   host_rows.cpp    the register-resident one-pass kernels: small float32 slabs (fasts.h), long rows and complex rows (fastr.h)
-//                    and Welch spectra, overlapping segments of a series averaged in one pass (fastw.h)
-//                    (FastS, FastR and its Welch form, FastRComplex, FastRRows)
+//                    and Welch spectra, overlapping segments of a series averaged in one pass (fastw.h), or every segment's spectrum kept (fastk.h)
+//                    (FastS, FastR and its Welch forms, FastRComplex, FastRRows)
 //   host_inner.cpp   two transform axes that are not the trailing pair (xrfthip_desc.inner / .mid): the fused passes and the composite plan
 //                    (FusedInner, Composite)
 //   ops.cpp          the stand-alone operations of the ABI (detrend, spectrum tail, gather, convert, reduce, isotropize, ...)
@@ -62,6 +62,7 @@
 #include "fastg.h"
 #include "fasth.h"
 #include "fastw.h"
+#include "fastk.h"
 #ifdef XRFT_SPLIT_TUS  /* the library built from several translation units: the fasty / fastm kernels are instantiated in inst_g*.cpp */
 namespace xrft {
 #define XRFT_KW extern template __global__
@@ -482,6 +483,10 @@ struct xrfthip_plan {
     int w_G = 1, w_stride = 0;
     int w_C = 1;  // the column layout (xrfthip_desc.seg_stride): adjacent columns per workgroup; sequence t of the tile is (column t % w_C, pair t / w_C); 1: the rows layout
     size_t w_lds = 0;
+    // ... its "segments kept" form (xrfthip_desc.seg_keep, fastk.h): w_G segments (sequences of L / 2 points) per round, w_rounds rounds per series (group of columns),
+    // W_L^k of the unpacking; no workspace
+    int w_rounds = 1;
+    DevBuf w_twr;
     ~xrfthip_plan() { for (auto* b : extra) delete b; prof_clear(); delete sub_x; delete sub_y; }
 };
 
@@ -589,12 +594,13 @@ inline bool dbl_phase_tables(const xrfthip_plan* P) { return P->dbl && family_op
 inline bool herm_field_plan(const xrfthip_plan* P) { return P && P->d.herm_ny > 0 && (P->d.flags & XRFTHIP_HERM_FIELD); }  // (... whose last pass writes the complex field)
 // The mean over the batch inside the last pass (xrfthip_desc.mean_batch, normalised by xrfthip_plan_create: 0 = off, else M > 1): the families with a mean form are
 // FastY's two-pass slabs and FastS below 256 points per axis with dense float32 input; every other family answers XRFTHIP_UNSUPPORTED_LENGTH (the caller composes).
-inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1; }
+inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1 && !P->d.seg_keep; }  // (seg_keep: mean_batch counts the segments of a series, every spectrum kept)
 inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || (P->family == Family::FastS && !P->coherence) || (P->family == Family::FastR && P->w_on); }  // (FastS has no two-field form)
 size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs);  // (xrft_hip.cpp: mean_P and the partials behind `off`; returns the new end)
 int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStream_t st);  // (... and the finishing kernel, after the last group)
 inline bool welch_cols(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_stride > 0; }  // (... along a leading axis: d.inner adjacent series, samples d.seg_stride apart; S = 1 was normalised to 0, the rows layout)
 inline bool welch_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0; }  // (the descriptor asks for the mean over overlapping segments: served by FastR's Welch form or not at all)
+inline bool keep_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_keep == 1; }  // (... every segment's spectrum kept, none averaged: the "segments kept" form, fastk.h)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's
 // input take them: pass 1 of the two-pass families, the load of the one-pass families.  The intermediate and the output are dense.

@@ -894,9 +894,10 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     constexpr uint32_t kOldDescSize = (uint32_t)offsetof(xrfthip_desc, inner), kOldDescSize2 = (uint32_t)offsetof(xrfthip_desc, mid), kOldDescSize3 = (uint32_t)offsetof(xrfthip_desc, in_stride_y),
                        kOldDescSize4 = (uint32_t)offsetof(xrfthip_desc, herm_ny), kOldDescSize5 = (uint32_t)offsetof(xrfthip_desc, mean_batch),  // (... and before mean_batch: 0)
                        kOldDescSize6 = (uint32_t)offsetof(xrfthip_desc, seg_hop),  // (... and before seg_hop / seg_reserved: 0, 0 -- the two came together, no size between)
-                       kOldDescSize7 = (uint32_t)offsetof(xrfthip_desc, seg_stride);  // (... and before seg_stride / seg_reserved2: likewise)
+                       kOldDescSize7 = (uint32_t)offsetof(xrfthip_desc, seg_stride),  // (... and before seg_stride / seg_reserved2: likewise)
+                       kOldDescSize8 = (uint32_t)offsetof(xrfthip_desc, seg_keep);  // (... and before seg_keep / seg_reserved3: likewise)
     if (!plan || !desc || (desc->struct_size != sizeof(xrfthip_desc) && desc->struct_size != kOldDescSize && desc->struct_size != kOldDescSize2 && desc->struct_size != kOldDescSize3 &&
-                           desc->struct_size != kOldDescSize4 && desc->struct_size != kOldDescSize5 && desc->struct_size != kOldDescSize6 && desc->struct_size != kOldDescSize7)) return XRFTHIP_BAD_ARG;
+                           desc->struct_size != kOldDescSize4 && desc->struct_size != kOldDescSize5 && desc->struct_size != kOldDescSize6 && desc->struct_size != kOldDescSize7 && desc->struct_size != kOldDescSize8)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);
     dcopy.struct_size = sizeof(xrfthip_desc);
@@ -905,7 +906,10 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (dcopy.mid == 0) dcopy.mid = 1;
     if (dcopy.in_stride_y < 0 || dcopy.in_stride_batch < 0) return XRFTHIP_BAD_ARG;
     if (dcopy.mean_batch < 0) return XRFTHIP_BAD_ARG;
-    if (dcopy.mean_batch == 1) dcopy.mean_batch = 0;  // (the plain plan itself)
+    // seg_keep = 1 (with seg_hop): every segment's spectrum kept (fastk.h).  mean_batch is the segments per series there, 1 included, and nothing is averaged
+    if ((dcopy.seg_keep != 0 && dcopy.seg_keep != 1) || dcopy.seg_reserved3 != 0 || (dcopy.seg_keep && dcopy.seg_hop <= 0)) return XRFTHIP_BAD_ARG;
+    const bool keep = dcopy.seg_keep == 1;
+    if (dcopy.mean_batch == 1 && !keep) dcopy.mean_batch = 0;  // (the plain plan itself)
     // seg_hop = H >= 1: Welch spectra (fastw.h).  in_stride_batch is the series pitch here (any multiple of 4 bytes: the kernel loads single samples); it is checked,
     // remembered as w_pitch and cleared, so that nothing of the strided-view rules (16-byte strides and pointers) applies to such a plan
     // seg_stride = S >= 1 (with seg_hop): the column layout of the same form -- `inner` adjacent series whose samples lie S elements apart, blocks in_stride_batch apart.
@@ -917,8 +921,8 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (dcopy.seg_hop > 0) {
         const xrfthip_desc& s = dcopy;
         if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.seg_hop > s.nx || (s.flags & (XRFTHIP_AXIS_Y | XRFTHIP_ISO)) || (s.inner > 1 && !s.seg_stride) || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y) return XRFTHIP_BAD_ARG;
-        if (s.mean_batch < 2 || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
-        if (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != XRFTHIP_OUT_CROSS) return XRFTHIP_BAD_ARG;
+        if (s.mean_batch < (keep ? 1 : 2) || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
+        if (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != (keep ? XRFTHIP_OUT_COMPLEX : XRFTHIP_OUT_CROSS)) return XRFTHIP_BAD_ARG;
         if (s.nx > (1LL << 30) || s.mean_batch > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;
         const long long span = (s.mean_batch - 1) * s.seg_hop + s.nx;
         if (s.seg_stride) {  // (the offsets stay far inside 64 bits: span < 2^62, S and inner below 2^31)
@@ -986,7 +990,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
         (cplx_in || !(d.flags & XRFTHIP_HALF_X) || (d.flags & (XRFTHIP_SHIFT_Y | XRFTHIP_FLIP_Y | XRFTHIP_INVERSE)))) return XRFTHIP_BAD_ARG;
 
     // mean_batch = M > 1: the mean over every M consecutive slabs inside the last pass (fasty_mean.h, fasts_mean.h); what has no mean form is "the caller composes"
-    if (d.mean_batch > 1) {
+    if (d.mean_batch > 1 && !keep) {
         if (d.batch % d.mean_batch != 0 || (d.out_mode != XRFTHIP_OUT_POWER && d.out_mode != XRFTHIP_OUT_CROSS) || (d.flags & XRFTHIP_ISO)) return XRFTHIP_BAD_ARG;
         if (!d.seg_hop && ((d.flags & (XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2 | XRFTHIP_AXIS_Y)) || d.inner > 1 || d.mid > 1 || herm)) return XRFTHIP_UNSUPPORTED_LENGTH;  // (a Welch plan has its own half output)
         if ((d.batch / d.mean_batch) * d.ny > 0x7fffffffLL) return XRFTHIP_UNSUPPORTED_LENGTH;  // (mean_finish_kernel: one workgroup per output row, run_mean_finish; refused before anything runs)
@@ -1083,6 +1087,7 @@ int xrfthip_plan_set_phase(xrfthip_plan* plan, int axis, const double* h_phase, 
         return finalize_plan(plan);
     }
     if (!plan || axis < 0 || axis > 1 || herm_plan(plan)) return XRFTHIP_BAD_ARG;  // (herm: the twin of a sample at a Nyquist index does not carry the conjugate factor)
+    if (keep_plan(plan) && plan->d.out_mode == XRFTHIP_OUT_COMPLEX && h_phase) return XRFTHIP_UNSUPPORTED_LENGTH;  // (the "segments kept" form writes X itself: the caller composes)
     // an input phase of a c2r transform covers the stored half of the x axis only
     const int64_t want = axis == 0 ? plan->d.ny : ((plan->d.flags & XRFTHIP_C2R_X) ? plan->d.nx / 2 + 1 : plan->d.nx);
     if (h_phase && n != want) return XRFTHIP_BAD_ARG;

@@ -40,7 +40,7 @@ class SpectralPlan:
 
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
-                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0, seg_stride=0):
+                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0, seg_stride=0, seg_keep=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
@@ -70,9 +70,14 @@ class SpectralPlan:
         # ... along a leading axis (xrfthip_desc.seg_stride): ``inner`` adjacent series whose samples lie seg_stride elements apart, blocks in_stride_batch apart;
         # the result is (blocks, inner, nx_out).  1 (with inner = 1) says what the rows layout says
         self.seg_stride = int(seg_stride)
-        d = _lib.DescCols(C.sizeof(_lib.DescCols), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
+        # every segment's spectrum kept (xrfthip_desc.seg_keep): mean_batch counts the segments of a series (1 is allowed), nothing is averaged; the result is
+        # (series, mean_batch, nx_out), or (blocks, mean_batch, nx_out, inner) in the column layout
+        self.seg_keep = int(seg_keep)
+        if self.seg_keep:
+            self.batch_out = self.batch // max(self.mean_batch, 1)
+        d = _lib.DescKeep(C.sizeof(_lib.DescKeep), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
                       int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
-                      self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0, self.seg_stride, 0)
+                      self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0, self.seg_stride, 0, self.seg_keep, 0)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
         for axis, w in ((0, window_y), (1, window_x)):
             if w is not None:
@@ -185,13 +190,15 @@ class SpectralPlan:
             shape = (self.batch_out, self.ny_out, self.nx_out) + ((self.inner,) if self.inner > 1 else ())
             if self.seg_hop and self.seg_stride > 1:  # (the column layout of a Welch plan: frequency last)
                 shape = (self.batch_out, self.inner, self.nx_out)
+            if self.seg_hop and self.seg_keep:  # (every segment's spectrum: the segments where the time axis lay, the columns innermost)
+                shape = (self.batch_out, self.mean_batch, self.nx_out) + ((self.inner,) if self.seg_stride > 1 else ())
             if self.mid > 1:
                 shape = (self.batch, self.ny_out, self.mid, self.nx_out, self.inner)
             if self.herm_ny:
                 shape = (self.batch, self.ny, self.herm_ny, self.herm_nx)
             out = torch.empty(shape, dtype=self.out_dtype(), device=dev)
         elif want_out:  # a caller's buffer (graph capture, composed passes): held to the plan before the device sees its pointer
-            need = self.batch_out * self.ny_out * self.nx_out * self.inner * self.mid
+            need = self.batch_out * self.ny_out * self.nx_out * self.inner * self.mid * (self.mean_batch if self.seg_keep else 1)
             if out.dtype != self.out_dtype() or not out.is_contiguous() or out.numel() != need or out.device != dev:
                 raise ValueError(f"out does not match the plan (dtype {self.out_dtype()}, contiguous, {need} elements on {dev})")
         iso_dtype = torch.complex128 if self.out_mode == _lib.OUT_CROSS else torch.float64
