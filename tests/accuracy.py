@@ -160,6 +160,12 @@ ROWS = [
     ("no-fast", dict(ny=4096, nx=4096), {"XRFTHIP_NO_FAST": "1"}, L.K_GENERIC, "main"),
     ("no-fast-rows", dict(ndim=1, nx=65536), {"XRFTHIP_NO_FAST": "1"}, L.K_GENERIC, "main"),
     ("generic-prime", dict(ndim=1, nx=1031, dtype=F64), {}, L.K_GENERIC, "main"),
+    # the segment families (seg_hop) at hop = nx: the segments are the rows of the (batch, nx) input, so the model below is theirs as it stands -- the mean over every
+    # mean_batch rows (segment_mean), or every row's own spectrum.  Overlap, odd counts, runs and the column layout: tests/welch.py, welch_cols.py, spectrogram.py
+    ("fastw", dict(ndim=1, nx=256, mean_batch=2, seg_hop=256, detrend=L.DETREND_LINEAR), {}, L.K_FASTW, "fastw"),
+    ("fastw-cross", dict(ndim=1, nx=1024, mean_batch=2, seg_hop=1024, out_mode=L.OUT_CROSS), {}, L.K_FASTW, "fastw"),
+    ("fastk", dict(ndim=1, nx=256, mean_batch=1, seg_hop=256, seg_keep=1, out_mode=L.OUT_COMPLEX), {}, L.K_FASTW, "fastw segments kept"),
+    ("fastk-power", dict(ndim=1, nx=1024, mean_batch=1, seg_hop=1024, seg_keep=1, detrend=L.DETREND_LINEAR), {}, L.K_FASTW, "fastw segments kept"),
 ]
 
 
@@ -263,6 +269,17 @@ def reference(kw, x0, x1=None, binmap=None, nbins=0, phase_x=None):
     return out, iso
 
 
+def segment_rows(kw, t):
+    """The (batch, nx) samples of a seg_hop descriptor with hop = nx as its plan reads them: (series, mean_batch nx), every row of `t` a segment."""
+    return t.reshape(-1, max(kw.get("mean_batch", 0), 1) * kw["nx"]) if t is not None and kw.get("seg_hop") else t
+
+
+def segment_mean(kw, out):
+    """A mean plan's result from the model's per-row one: the mean over every mean_batch consecutive rows (not of a seg_keep plan: there mean_batch only counts)."""
+    m = kw.get("mean_batch", 0)
+    return out.reshape((-1, m) + out.shape[1:]).mean(axis=1) if m > 1 and not kw.get("seg_keep") else out
+
+
 def tensor(a, dtype):
     """The samples `a` (float64 / complex128) rounded to the plan's dtype, as a CPU tensor, and their exact float64 image."""
     t = torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
@@ -360,6 +377,8 @@ FAMILY_FORMS = {
     "FastR": {(L.K_FASTR, "fastr")},
     "FastRComplex": {(L.K_FASTR, "fastr complex rows")},
     "FastRRows": {(L.K_FASTR, "fasty complex rows")},
+    "FastW": {(L.K_FASTW, "fastw")},
+    "FastK": {(L.K_FASTW, "fastw segments kept")},
     "FastYC": {(L.K_FASTY, "fasty complex")},
     "FastYCFourStep": {(L.K_FASTY, "fasty complex rows, four-step")},
     "FastY": {(L.K_FASTY, "fasty")},
@@ -450,6 +469,8 @@ def run_ladder(kw, sig, dev, seed=0):
         kw["batch"] = int(sig[5:])
     else:
         kw["batch"] = 1 if points(kw) > SMALL else 2
+    if kw.get("mean_batch", 0) > 1:  # (a mean plan: that many outputs, mean_batch rows each)
+        kw["batch"] *= kw["mean_batch"]
     rng = np.random.default_rng(seed)
     extra = {}
     if iso:
@@ -468,7 +489,7 @@ def run_ladder(kw, sig, dev, seed=0):
     if mode in (L.OUT_CROSS, L.OUT_PHASE):
         x1, x164 = tensor(signal(kw, "noise", np.random.default_rng(seed + 1)), dt)
         x1 = x1.to(dev)
-    out, isoo = p.execute(x.to(dev), x1)
+    out, isoo = p.execute(segment_rows(kw, x.to(dev)), segment_rows(kw, x1))
     n = points(kw)
     det = kw.get("detrend", L.DETREND_NONE)
     kap = kappa(x64.reshape(shape), detrended(x64.reshape(shape), axes, det)) if det else 0.0
@@ -478,6 +499,7 @@ def run_ladder(kw, sig, dev, seed=0):
         c = assert_accurate(got, cref, dt, n, kap, what=f"{sig} phase")
     else:
         ref, iref = reference(kw, x64, x164, extra.get("binmap"), extra.get("nbins", 0))
+        ref = segment_mean(kw, ref)  # (a segment row's mean over its segments: the model above is per row and stays as it is)
         c = assert_accurate(out.cpu().numpy().reshape(ref.shape), ref, dt, n, kap, flat=(sig == "noise" and mode == L.OUT_COMPLEX), what=sig)
         if iref is not None:
             c = max(c, assert_accurate(isoo.cpu().numpy().reshape(iref.shape), iref, dt, n, kap, what=f"{sig} iso"))

@@ -208,6 +208,8 @@ HALF = ["win+ishift+phase"]  # (SHIFT_* with HALF_X is BAD_ARG)
 INV = ["win", "shift", "ishift", "flip", "phase", "scale", "win+ishift", "ishift+shift", "all-nodetrend", "noflip-nodetrend", "phasein", "win+ishift+phasein", "all-nodetrend-phasein", "noflip-nodetrend-phasein"]
 C2R = ["ishift", "shift", "phasein"]  # (ISHIFT_Y; SHIFT_Y | SHIFT_X; PHASE_IN on y and x)
 ISO = ["win+shift"]
+SEG = ["win", "shift", "ishift", "const+scale", "win+shift+ishift+scale+const"]  # (the segment families take no flip; the phase table only a two-field mean, held by tests/welch.py)
+SEG_X = ["win", "shift", "const+scale", "win+shift+scale+const"]                 # (... and a kept complex spectrum no input rotation)
 HERM = ["win", "shift", "ishift", "scale", "win+shift+ishift+scale"]  # (herm_ny / herm_nx: a window along t, the rotations, scale; no phase table, no detrend, no flip)
 
 CX, PW, CR = L.OUT_COMPLEX, L.OUT_POWER, L.OUT_CROSS
@@ -247,6 +249,10 @@ BASE = [
     ("fusedm", dict(ny=64, nx=96, mid=3, out_mode=CX), {}, L.K_FASTN, "inner layout", FWD),
     ("composite", dict(ny=128, nx=256, mid=4, dtype=C64, out_mode=CX), {}, L.K_COMPOSITE, "inner layout", FWD),
     ("generic-prime", dict(ndim=1, nx=1031, dtype=F64, out_mode=CX), {}, L.K_GENERIC, "main", FWD),
+    # the segment families at hop = nx (accuracy.ROWS): BATCH = mean_batch rows are the three segments of one series
+    ("fastw", dict(ndim=1, nx=256, mean_batch=BATCH, seg_hop=256), {}, L.K_FASTW, "fastw", SEG),
+    ("fastk-power", dict(ndim=1, nx=256, mean_batch=1, seg_hop=256, seg_keep=1), {}, L.K_FASTW, "fastw segments kept", SEG),
+    ("fastk", dict(ndim=1, nx=256, mean_batch=1, seg_hop=256, seg_keep=1, out_mode=CX), {}, L.K_FASTW, "fastw segments kept", SEG_X),
     # inverse transforms (complex input, complex output)
     ("fastyc-inverse", dict(ny=256, nx=256, dtype=C64, out_mode=CX, flags=IV), {}, L.K_FASTY, "fasty complex", INV),
     ("fastr-complex-inverse", dict(ndim=1, nx=16384, dtype=C64, out_mode=CX, flags=IV), {}, L.K_FASTR, "fastr complex rows", INV),
@@ -355,11 +361,12 @@ def run(kw, tokens, expect, dev, seed=0):
     shape, axes, _ = A._axes(kw)
     xs = [A.tensor(v, dt) for v in inputs(kw, seed)]
     x1, x164 = (xs[1][0].to(dev), xs[1][1]) if len(xs) == 2 else (None, None)
-    out, isoo = p.execute(xs[0][0].to(dev), x1)
+    out, isoo = p.execute(A.segment_rows(kw, xs[0][0].to(dev)), A.segment_rows(kw, x1))
     x64 = xs[0][1]
     det = kw.get("detrend", L.DETREND_NONE)
     kap = A.kappa(x64.reshape(shape), A.detrended(x64.reshape(shape), axes, det)) if det else 0.0
     ref, iref = reference(kw, tab, x64, x164, extra.get("binmap"), extra.get("nbins", 0))
+    ref = A.segment_mean(kw, ref)  # (a segment row's mean over its segments: the model above is per row and stays as it is)
     n = A.points(kw)
     what = "+".join(tokens)
     # the max-norm bound is for a flat spectrum: noise through OUT_COMPLEX.  Noise + OFFSET under a detrend is not one -- the offset is a zero-frequency term of

@@ -64,10 +64,10 @@ EXACT = {
 #                                        a row's rounding depends on its partner, the row before or behind it
 #   "fastg rows"                         g_rows rows share one tile (host_fastg.cpp:75, fastg.h:44, :288 with slab = a group of rows); a row's place in the tile decides
 #                                        which lanes hold and reduce it -- not followed further
-#   "fasty complex rows"                 R.rk rows per workgroup of fastyc_rows_kernel (host_rows.cpp:219)
+#   "fasty complex rows"                 R.rk rows per workgroup of fastyc_rows_kernel (host_rows.cpp:217)
 #   "main" (the generic passes), "inner layout" (the composite runs them)   tiles of T consecutive sequences across slab borders (tile_fft.h:556-561); T need not divide 48
 #   the mean forms                       a run adds its slabs in an order that depends on how the outputs fall on the groups (host_fasty.cpp:372-375: the outputs a
-#                                        group reaches; fastw: host_rows.cpp:331-336, pairs of segments per round)
+#                                        group reaches; fastw: host_welch.inc:47-48, pairs of segments per round)
 # Observed (profiles/r23_extents.txt): every case of rungs A and B, these included, returned the same bits for every copy of a slab -- with a period of 48 the partners
 # and the orders repeat at these group and tile sizes; a change of either may break that without breaking the contract, so they are not held to it.
 

@@ -53,7 +53,7 @@ def test_every_family_is_executed():
     asserted = {(r[3], r[4]) for r in A.ROWS + A.MODES}
     missing = [f for f, forms in A.FAMILY_FORMS.items() if not forms & asserted]
     assert not missing, missing
-    assert {k for k, _t in asserted} == set(range(13))
+    assert {k for k, _t in asserted} == set(range(14))
 
 
 @pytest.mark.parametrize("n", [1 << 16, 1 << 20])

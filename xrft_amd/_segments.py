@@ -1,0 +1,367 @@
+"""The segment surface of the call API: Welch spectra (welch_power_spectrum, welch_cross_spectrum, welch_coherence) and spectrograms (spectrogram, stft) -- the spectra
+of the overlapping segments of a series, averaged or kept.  Fused where a segment plan takes the call (xrfthip_desc.seg_hop: csrc/fastw.h, fastk.h), else composed from
+the calls of api.py on the unfolded segments.  api.py re-exports the public names.
+
+This module sits ON TOP of api.py and is imported by it, behind the definitions it uses (`_api.` below: resolved at call time; the two tuning constants
+`api._WELCH_COLS_WS_CAP` / `_WELCH_COLS_ALIGN` live there too, where the tests patch them).  Import `xrft_amd` or `xrft_amd.api`, never this module first."""
+from __future__ import annotations
+
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import api as _api  # (the calls the composed paths and the analysis of ONE segment go through; api.py imports this module behind them)
+from ._hostside import _analyze, _direct_lag_attrs, _flags_tables, _label_output, _to_device
+from ._plans import _MEAN_REFUSED, _rung
+from .labeled import Coordinate, DataArray, from_any, to_like
+
+# ------------------------------------------------------------------------------------------------------
+# Welch spectra: the mean spectrum of the overlapping segments of a long series (scipy.signal.welch / csd / coherence; the reference's
+# power_spectrum(da, dim="time", chunks_to_segments=True, window="hann", detrend="linear").mean("time_segment") with an overlap).  Fused where a plan takes the call
+# (xrfthip_desc.seg_hop: the segments read where they lie, no segment's spectrum stored), else composed: the segments unfolded, the public call, .mean.
+# ------------------------------------------------------------------------------------------------------
+def _welch_args(da, dim, nperseg, noverlap, least=1):
+    """(hop, number of segments) after the checks; trailing samples that do not fill a segment are dropped (as scipy.signal.welch does)."""
+    if not isinstance(dim, str):
+        raise ValueError(f"dim must be the name of ONE dimension (the axis the segments are cut from), not {dim!r}")
+    n = da.sizes[dim] if dim in da.dims else da.get_axis_num(dim)
+    nperseg = int(nperseg)
+    if nperseg < 1 or nperseg > n:
+        raise ValueError(f"nperseg = {nperseg} is not in 1 .. {n}, the length of {dim!r}")
+    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
+    if noverlap < 0 or noverlap >= nperseg:
+        raise ValueError(f"noverlap = {noverlap} must be in 0 .. nperseg - 1 = {nperseg - 1}")
+    hop = nperseg - noverlap
+    m = (n - nperseg) // hop + 1
+    if m < least:
+        raise ValueError(f"{m} segment(s) of {nperseg} samples fit {dim!r} ({n} samples, hop {hop}): at least {least} are needed")
+    return nperseg, hop, m
+
+
+def _welch_segments(da, dim, nperseg, hop):
+    """The labelled array of segments, a VIEW of the device data (tensor.unfold): ``dim`` becomes ``<dim>_segment`` where it lay and the samples of a segment are the
+    new last dim ``dim``, whose coordinate is the first ``nperseg`` values of the series' (every segment has the same spacing; the lag is the first segment's)."""
+    t = _to_device(da.data)
+    ax = da.get_axis_num(dim)
+    seg = t.unfold(ax, nperseg, hop)
+    dims = list(da.dims)
+    dims[ax] = dim + "_segment"
+    dims.append(dim)
+    coords = {}
+    for k, v in da.coords.items():
+        if k == dim:
+            coords[k] = Coordinate((dim,), np.asarray(v.values)[:nperseg], v.attrs, k)
+        elif dim not in v.dims:
+            coords[k] = v
+    return DataArray(seg, dims, coords, da.name, da.attrs)
+
+
+def _welch_series(t, ax):
+    """(series, samples) float32 device tensor with unit stride along the samples and one pitch between the series, and that pitch: the array itself where ``ax`` is
+    the trailing, contiguous axis; else arranged first (one transposed copy: what the column layout of the plan, _welch_columns, did not take)."""
+    if ax != t.dim() - 1:
+        t = t.movedim(ax, -1)
+    if not (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+        t = t.contiguous().reshape(-1, t.shape[-1])
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def _collapse(sizes, strides):
+    """(count, stride) of dims that are ONE run of equally spaced elements (size-1 dims skipped; no dims: (1, 0)), or None."""
+    n, st = 1, 0
+    for k, v in zip(reversed(sizes), reversed(strides)):  # innermost first: each outer stride is (extent x stride) of what lies inside it
+        if k == 1:
+            continue
+        if n > 1 and v != n * st:
+            return None
+        if n == 1:
+            st = v
+        n *= k
+    return n, st
+
+
+def _welch_columns(t, ax, span):
+    """The (blocks, samples, columns) view of a float32 device tensor that a column plan reads where it lies (xrfthip_desc.seg_stride), with its block pitch and its
+    sample stride -- or None: ``ax`` is the trailing axis, the dims behind it are not one unit-stride run, the dims in front not one pitch, or rows would overlap."""
+    if ax == t.dim() - 1 or os.environ.get("XRFTHIP_FASTW_COLS", "1") == "0":  # (the knob of the library, honoured before a cached plan could answer)
+        return None
+    back = _collapse(t.shape[ax + 1:], t.stride()[ax + 1:])
+    front = _collapse(t.shape[:ax], t.stride()[:ax])
+    if back is None or front is None:
+        return None
+    inner, s_in = back
+    blocks, pitch = front
+    ss = t.stride(ax)
+    if (inner > 1 and s_in != 1) or ss < inner or (inner == 1 and ss == 1):  # (unit sample stride: the rows layout, no copy either)
+        return None
+    if blocks > 1 and pitch < (span - 1) * ss + inner:
+        return None
+    return torch.as_strided(t, (blocks, t.shape[ax], inner), (pitch if blocks > 1 else t.shape[ax] * ss, ss, 1), t.storage_offset()), (pitch if blocks > 1 else 0), ss
+
+
+def _segment_kw(c, c2, nperseg, hop, m, mode, scale, flags, keep=False):
+    """The keywords of a segment plan (xrfthip_desc.seg_hop; seg_keep: every spectrum kept) but for its batch and strides (_segment_view): flags, window and -- a
+    two-field mean only -- the net true-phase table are those of ONE segment's spectrum."""
+    fl, win, ph = _flags_tables(c, c.da, None if c2 is None else c2.lag_x, None if c2 is None else c2.reversed)
+    return dict(ndim=1, ny=1, nx=nperseg, dtype=torch.float32, out_mode=mode, detrend=c.detrend, flags=fl | flags, scale=float(scale), window_x=win["x"],
+                phase_x=ph["x"] if mode == _lib.OUT_CROSS else None, mean_batch=m, seg_hop=hop, seg_keep=int(keep))
+
+
+def _segment_view(t, ax, span, m, columns):
+    """(the view of a float32 device tensor that a segment plan executes on, the descriptor's batch and strides) for series along ``ax`` whose segments span ``span``
+    samples.  ``columns``: the (blocks, samples, columns) view read where it lies (inner / seg_stride), or None where the array cannot be described by it
+    (_welch_columns); else (series, samples) rows, arranged first where they are not rows already (_welch_series)."""
+    if columns:
+        v = _welch_columns(t, ax, span)
+        if v is None:
+            return None
+        view, pitch, ss = v
+        return view, dict(batch=view.shape[0] * m, inner=view.shape[2], seg_stride=ss, in_stride_batch=int(pitch))
+    rows, pitch = _welch_series(t, ax)
+    return rows, dict(batch=rows.shape[0] * m, in_stride_batch=int(pitch))
+
+
+def _segment_plan(kw, extras):
+    """The plan of the keywords, or None: "the caller arranges or composes" (XRFTHIP_UNSUPPORTED_LENGTH, remembered)."""
+    return _rung(_MEAN_REFUSED, None, dict(kw, **extras))
+
+
+def _welch_fused_columns(kw, t, t2, ax, span, m):
+    """The (blocks, columns, nx_out) result of the column plan(s) on the arrays where they lie, or None: a view that does not collapse, two fields with different
+    strides, a length the column layout declines.  Wide grids run in blocks of columns (api._WELCH_COLS_WS_CAP): full blocks share one plan, the tail has one more."""
+    v = _segment_view(t, ax, span, m, True)
+    if v is None:
+        return None
+    view, extras = v
+    view2 = None
+    if t2 is not None:
+        if t2.shape != t.shape:
+            raise ValueError("The two datasets have different dimensions")
+        if t2.stride() != t.stride():
+            return None
+        view2 = _segment_view(t2, ax, span, m, True)[0]
+    blocks, _, inner = view.shape
+    per_col = blocks * kw["nx"] * 8 * (1 if t2 is None else 2)  # (one run: what a wide grid gets)
+    width = max(_api._WELCH_COLS_ALIGN, _api._WELCH_COLS_WS_CAP // per_col // _api._WELCH_COLS_ALIGN * _api._WELCH_COLS_ALIGN)
+    out = None
+    for c0 in range(0, inner, width):
+        w = min(width, inner - c0)
+        plan = _segment_plan(kw, dict(extras, inner=w))
+        if plan is None:
+            return None  # (the first block: the length is the same for all)
+        part = [torch.as_strided(x, (blocks, x.shape[1], w), x.stride(), x.storage_offset() + c0) if w != inner else x for x in (view, view2) if x is not None]
+        if w == inner:
+            return plan.execute(*part)[0]
+        if out is None:
+            out = torch.empty((blocks, inner, plan.nx_out), dtype=plan.out_dtype(), device=t.device)
+        if blocks == 1:
+            plan.execute(*part, out=out[0, c0:c0 + w])
+        else:
+            out[:, c0:c0 + w] = plan.execute(*part)[0]
+    return out
+
+
+def _welch_fused(c, c2, da, da2, dim, nperseg, hop, m, mode, scale, flags):
+    """The (series, nx_out) result of ONE plan with seg_hop, or None where the call composes: float64 / complex / half data, fewer than two segments, a length or a
+    flag the plan declines (XRFTHIP_UNSUPPORTED_LENGTH: lengths off the power-of-two table, a descending coordinate's flip), an empty array.  A ``dim`` that is not
+    the trailing axis is read where it lies by the column layout of the plan (seg_stride) where the array can be described by it; else it is arranged first."""
+    if m < 2 or any(d is not None and _to_device(d.data).dtype != torch.float32 for d in (da, da2)) or math.prod(da.shape) == 0:
+        return None
+    kw = _segment_kw(c, c2, nperseg, hop, m, mode, scale, flags)
+    ax, span = da.get_axis_num(dim), (m - 1) * hop + nperseg
+    t, t2 = _to_device(da.data), None if da2 is None else _to_device(da2.data)
+    out = _welch_fused_columns(kw, t, t2, ax, span, m)
+    if out is not None:
+        return out
+    t, extras = _segment_view(t, ax, span, m, False)
+    if t2 is not None:
+        t2, extras2 = _segment_view(t2, ax, span, m, False)
+        if t2.shape != t.shape:
+            raise ValueError("The two datasets have different dimensions")
+        if extras2 != extras:  # (two pitches: both arranged)
+            t, t2 = t.contiguous(), t2.contiguous()
+            extras = dict(extras, in_stride_batch=t.shape[1])
+    plan = _segment_plan(kw, extras)
+    if plan is None:
+        return None
+    out, _ = plan.execute(t, t2)
+    return out
+
+
+def _welch_spectrum(da, da2, dim, nperseg, noverlap, real_dim, scaling, window_correction, true_phase, kwargs, least=1):
+    da = from_any(da)
+    da2 = None if da2 is None else from_any(da2)
+    nperseg, hop, m = _welch_args(da, dim, nperseg, noverlap, least)
+    if da2 is not None and (tuple(da2.dims) != tuple(da.dims) or da2.shape != da.shape):
+        raise ValueError("The two datasets have different dimensions")
+    if real_dim is not None and real_dim != dim:
+        raise ValueError(f"real_dim must be {dim!r}, the one transform dimension, or None")
+    unknown = set(kwargs) - {"detrend", "window", "shift", "spacing_tol"}
+    if unknown:
+        raise TypeError(f"got an unexpected keyword argument {sorted(unknown)[0]!r}")
+    seg = _welch_segments(da, dim, nperseg, hop)
+    seg2 = None if da2 is None else _welch_segments(da2, dim, nperseg, hop)
+    sname = dim + "_segment"
+    # the labels, the scaling and the tables are those of ONE segment's spectrum
+    head = seg.isel(**{sname: 0})
+    head2 = None if seg2 is None else seg2.isel(**{sname: 0})
+    c, c2, mode, scale, flags = _api._spectrum(head, head2, [dim], real_dim, scaling, window_correction, true_phase, dict(kwargs))
+    if c.detrend == _lib.DETREND_LINEAR:  # (_refuse_nonfinite has seen the first segment: the refusal of the composed call covers every segment)
+        for d in (da, da2):
+            if d is not None:
+                _refuse_nonfinite_span(d, dim, (m - 1) * hop + nperseg)
+    out = _welch_fused(c, c2, da, da2, dim, nperseg, hop, m, mode, scale, flags)
+    if out is not None:
+        return _label_output(c, head, out, [d for d in head.dims if d != dim], _direct_lag_attrs(c) if c2 is not None and c.true_phase else None)  # (as _cross_result)
+    kw = dict(dim=[dim], real_dim=real_dim, scaling=scaling, window_correction=window_correction, **kwargs)
+    full = _api.power_spectrum(seg, **kw) if seg2 is None else _api.cross_spectrum(seg, seg2, true_phase=true_phase, **kw)
+    return full.mean(sname)
+
+
+def welch_power_spectrum(da, dim, nperseg, noverlap=None, real_dim=None, scaling="density", window_correction=False, detrend=None, window=None, shift=True,
+                         spacing_tol=1e-3):
+    """Welch's estimate of the power spectrum along ``dim``: the series is cut into segments of ``nperseg`` samples that overlap by ``noverlap`` (default
+    ``nperseg // 2``; trailing samples that do not fill a segment are dropped, as scipy.signal.welch does), and the result is the mean over the segments of
+    ``power_spectrum`` of each -- detrend and window per segment.  Dims: the other dims in their order, then ``freq_<dim>``; coordinates and attrs are those of
+    ``power_spectrum`` of the first ``nperseg`` samples.  With ``window_correction=True`` and ``window="hann"`` the values are those of
+    ``scipy.signal.welch(..., return_onesided=False)`` after an fftshift (``real_dim=dim``: of ``return_onesided=True``).
+    float32 series whose ``nperseg`` is a power of two in 64 .. 4096 are read where they lie by ONE pass (xrfthip_desc.seg_hop: neither the copy of the segments nor
+    their spectra reach memory).  A ``dim`` that is not the trailing axis -- the time axis of a (time, y, x) cube -- is read where it lies too, for ``nperseg`` up
+    to 512, where the dims behind ``dim`` are one unit-stride run and the dims in front one pitch (a contiguous array, a slice of its last dim); longer segments
+    and other views are arranged first (one transposed copy).  Every other call unfolds the segments, runs the plain call and ``.mean``."""
+    src = da
+    kw = dict(detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol)
+    return to_like(_welch_spectrum(da, None, dim, nperseg, noverlap, real_dim, scaling, window_correction, False, kw), src)
+
+
+def welch_cross_spectrum(da1, da2, dim, nperseg, noverlap=None, real_dim=None, scaling="density", window_correction=False, detrend=None, window=None, shift=True,
+                         spacing_tol=1e-3, true_phase=True):
+    """Welch's estimate of the cross spectrum: the mean over the overlapping segments of ``cross_spectrum(seg1, seg2)``, ``F1 conj(F2)`` (see
+    ``welch_power_spectrum``).  scipy.signal.csd(x, y) forms ``conj(X) Y``: for coordinates that start at 0 (or ``true_phase=False``)
+    ``welch_cross_spectrum(x, y, ...)`` with ``window_correction=True`` is ``conj(scipy.signal.csd(x, y, return_onesided=False))`` after an fftshift, which is
+    ``csd(y, x)``."""
+    src = da1
+    kw = dict(detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol)
+    return to_like(_welch_spectrum(da1, da2, dim, nperseg, noverlap, real_dim, scaling, window_correction, true_phase, kw), src)
+
+
+def welch_coherence(da1, da2, dim, nperseg, noverlap=None, real_dim=None, scaling="density", window_correction=False, detrend=None, window=None, shift=True,
+                    spacing_tol=1e-3, true_phase=True):
+    """Magnitude-squared coherence ``|<F1 conj F2>|^2 / (<|F1|^2> <|F2|^2>)``, ``<.>`` the mean over the overlapping segments: scipy.signal.coherence.  The three
+    means are ``welch_cross_spectrum`` and ``welch_power_spectrum`` of each series; the division is the library's (xrfthip_coherence; no clamp).  Fewer than two
+    segments: ValueError (of one spectrum the coherence is 1 everywhere)."""
+    src = da1
+    da1, da2 = from_any(da1), from_any(da2)
+    kw = dict(detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol)
+    cs = from_any(_welch_spectrum(da1, da2, dim, nperseg, noverlap, real_dim, scaling, window_correction, true_phase, kw, least=2))
+    p1, p2 = (from_any(_welch_spectrum(d, None, dim, nperseg, noverlap, real_dim, scaling, window_correction, False, kw)) for d in (da1, da2))
+    return to_like(_api._coherence_result(cs, p1, p2, da1, da2), src)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Spectrograms: the spectrum of EVERY overlapping segment (scipy.signal.spectrogram / stft; the reference's power_spectrum(da, dim="time",
+# chunks_to_segments=True, ...) without .mean("time_segment"), with an overlap).  Fused where a plan takes the call (xrfthip_desc.seg_keep: the segments read where
+# they lie, every spectrum written once, no copy of the segments), else composed: the segments unfolded, the public call, the dims moved (a view).
+# ------------------------------------------------------------------------------------------------------
+def _spectrogram_result(lab, data, da, dim, nperseg, hop, m):
+    """The labelled result: ``da.dims`` with ``dim`` replaced, where it lay, by (<dim>_segment, freq_<dim>); the coordinates, attrs and name of ``lab`` (a labelled
+    spectrum of the segments, or of the first one: its last dim is freq_<dim>), and the <dim>_segment coordinate -- the middle of each segment's samples,
+    c[s hop] + (c[s hop + nperseg - 1] - c[s hop]) / 2 (datetime64 included).  ``data``: the values in that order, or None: those of ``lab``, moved (a view)."""
+    sname, fname = dim + "_segment", lab.dims[-1]
+    final = [x for d in da.dims for x in ((sname, fname) if d == dim else (d,))]
+    if data is None:
+        data = lab.transpose(*final).data
+    v = np.asarray(da[dim].values)
+    lo, hi = v[0:(m - 1) * hop + 1:hop], v[nperseg - 1:(m - 1) * hop + nperseg:hop]
+    coords = dict(lab.coords)
+    coords[sname] = Coordinate((sname,), lo + (hi - lo) / 2, None, sname)
+    return DataArray(data, final, coords, lab.name, lab.attrs)
+
+
+def _spectrogram_composed(da, dim, nperseg, hop, m, complex_, kw):
+    """The definition of the result: the segments unfolded (a view), ``power_spectrum`` / ``fft(true_phase=False)`` along their samples, the dims moved."""
+    seg = _welch_segments(da, dim, nperseg, hop)
+    full = _api.fft(seg, dim=[dim], true_phase=False, **kw) if complex_ else _api.power_spectrum(seg, dim=[dim], **kw)
+    return _spectrogram_result(from_any(full), None, da, dim, nperseg, hop, m)
+
+
+def _spectrogram_fused(c, da, dim, nperseg, hop, m, mode, scale, flags):
+    """The values of ONE plan with seg_keep in the order of the result's dims, or None where the call composes: data that are not float32, an empty array, a length or a
+    flag the plan declines (XRFTHIP_UNSUPPORTED_LENGTH, remembered), XRFTHIP_FASTW_KEEP=0.  The trailing axis is read where it lies (a pitch included); a leading or
+    middle axis through the column layout (seg_stride, ``nperseg`` <= 512) where the array can be described by it -- the result then lies in its final order."""
+    t = _to_device(da.data)
+    if t.dtype != torch.float32 or math.prod(t.shape) == 0 or os.environ.get("XRFTHIP_FASTW_KEEP", "1") == "0":  # (the knob of the library, honoured before a cached plan could answer)
+        return None
+    kw = _segment_kw(c, None, nperseg, hop, m, mode, scale, flags, keep=True)
+    ax = da.get_axis_num(dim)
+    v = _segment_view(t, ax, (m - 1) * hop + nperseg, m, ax != t.dim() - 1)
+    plan = None if v is None else _segment_plan(kw, v[1])
+    if plan is None:
+        return None
+    # (the column layout writes [block][segment][frequency][column]: the final order)
+    return plan.execute(v[0])[0].reshape(tuple(t.shape[:ax]) + (m, plan.nx_out) + tuple(t.shape[ax + 1:]))
+
+
+def _refuse_nonfinite_span(d, dim, n):
+    """scipy.signal.detrend's refusal over the first ``n`` samples along ``dim`` (a reduction: no array of flags; a NaN propagates into both ends)."""
+    lo, hi = torch.aminmax(_to_device(d.data).narrow(d.get_axis_num(dim), 0, n))
+    if not bool(torch.isfinite(lo) & torch.isfinite(hi)):
+        raise ValueError("array must not contain infs or NaNs")
+
+
+def _spectrogram(da, dim, nperseg, noverlap, complex_, analyse, kw):
+    da = from_any(da)
+    nperseg, hop, m = _welch_args(da, dim, nperseg, noverlap)
+    if kw.get("real_dim") is not None and kw["real_dim"] != dim:
+        raise ValueError(f"real_dim must be {dim!r}, the one transform dimension, or None")
+    # the labels, the scaling and the tables are those of ONE segment's spectrum
+    head = _welch_segments(da, dim, nperseg, hop).isel(**{dim + "_segment": 0})
+    c, mode, scale, flags = analyse(head)
+    if c.detrend == _lib.DETREND_LINEAR and math.prod(da.shape):  # (_refuse_nonfinite has seen the first segment: the refusal of the composed call covers every segment)
+        _refuse_nonfinite_span(da, dim, (m - 1) * hop + nperseg)
+    out = _spectrogram_fused(c, da, dim, nperseg, hop, m, mode, scale, flags)
+    if out is None:
+        return _spectrogram_composed(da, dim, nperseg, hop, m, complex_, kw)
+    other = [d for d in head.dims if d != dim]
+    lab = _label_output(c, head, out.new_empty(()).expand([head.sizes[d] for d in other] + [out.shape[da.get_axis_num(dim) + 1]]), other)
+    return _spectrogram_result(lab, out, da, dim, nperseg, hop, m)
+
+
+def spectrogram(da, dim, nperseg, noverlap=None, real_dim=None, scaling="density", window_correction=False, detrend=None, window=None, shift=True, spacing_tol=1e-3):
+    """The power spectrum of every segment of ``da`` along ``dim``: the series is cut into segments of ``nperseg`` samples that overlap by ``noverlap`` (default
+    ``nperseg // 2``; trailing samples that do not fill a segment are dropped; one segment is allowed) and the result is ``power_spectrum`` of each -- detrend and
+    window per segment -- kept, not averaged: ``welch_power_spectrum`` is its mean over ``<dim>_segment``.  Dims: those of ``da`` with ``dim`` replaced, where it
+    lay, by ``(<dim>_segment, freq_<dim>)``; ``freq_<dim>``, attrs and scaling are those of ``power_spectrum`` of the first ``nperseg`` samples; ``<dim>_segment``
+    carries the middle of each segment's samples, ``c[s hop] + (c[s hop + nperseg - 1] - c[s hop]) / 2`` (datetime64 too); coordinates that do not depend on
+    ``dim`` are kept.  With ``window_correction=True``, ``window="hann"`` and ``real_dim=dim`` the values are ``scipy.signal.spectrogram(..., mode="psd")``'s.
+    float32 data whose ``nperseg`` is a power of two in 64 .. 4096 are read where they lie by ONE pass that writes every segment's spectrum once
+    (xrfthip_desc.seg_keep): no copy of the segments (twice the series at half overlap) exists.  A ``dim`` that is not the trailing axis -- the time axis of a
+    (time, y, x) cube -- is read where it lies too, for ``nperseg`` up to 512, and the result is written in its final order (no transposed copy); every other call
+    unfolds the segments, runs ``power_spectrum`` and moves the dims (a view).  A linear detrend refuses non-finite samples inside the used span (ValueError)."""
+    src = da
+    kw = dict(real_dim=real_dim, scaling=scaling, window_correction=window_correction, detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol)
+
+    def analyse(head):
+        c, _, mode, scale, flags = _api._spectrum(head, None, [dim], real_dim, scaling, window_correction, False, dict(detrend=detrend, window=window, shift=shift, spacing_tol=spacing_tol))
+        return c, mode, scale, flags
+
+    return to_like(_spectrogram(da, dim, nperseg, noverlap, False, analyse, kw), src)
+
+
+def stft(da, dim, nperseg, noverlap=None, real_dim=None, detrend=None, window=None, shift=True, true_amplitude=False, spacing_tol=1e-3):
+    """The short-time Fourier transform: ``fft(..., true_phase=False)`` of every segment of ``da`` along ``dim`` (see ``spectrogram`` for the segments, the dims and
+    the coordinates); complex.  There is no ``true_phase`` argument: each segment's phase refers to its OWN first sample, not to the origin of the series'
+    coordinate (scipy.signal.stft's convention up to its scaling and padding).  ``true_amplitude=True`` multiplies by the spacing of ``dim``, as ``fft`` does.
+    Fused and composed as ``spectrogram`` is (XRFTHIP_OUT_COMPLEX)."""
+    src = da
+    kw = dict(real_dim=real_dim, detrend=detrend, window=window, shift=shift, true_amplitude=true_amplitude, spacing_tol=spacing_tol)
+
+    def analyse(head):
+        c = _analyze(head, spacing_tol, [dim], real_dim, shift, detrend, window, False, False, "freq_", None)
+        _api._refuse_nonfinite(c)
+        return c, _lib.OUT_COMPLEX, (math.prod(c.delta_x) if true_amplitude else 1.0), 0
+
+    return to_like(_spectrogram(da, dim, nperseg, noverlap, True, analyse, kw), src)

@@ -20,130 +20,49 @@
 
 namespace xrft {
 
-constexpr int kKSegs = 2 * kWPoints;  // samples of a round: NS = kKSegs / L segments fill the tile
 constexpr const char* kKResources = "fastk_kernel: 91 VGPRs, no scratch, 5 waves per SIMD";  // (scripts/kernel_resources.sh, gfx950: all four instances)
 
 struct FastK {
+    SegTile t;                 // (tw: W_n^k, k < n = L / 2; rev: of the n-point transform)
     const float* in;
     void* out;
-    const cf* tw;              // W_n^k, k < n = L / 2
     const cf* twr;             // W_L^k, k <= n (the unpacking)
-    const unsigned* rev;       // rev[k] = tile position of frequency k of the n-point transform after the passes
-    const float* win;          // L window values, or null
-    long long pitch;           // samples between series (the column layout: between blocks)
-    long long hop;             // samples between segment starts
-    long long sstride;         // the column layout: elements between consecutive samples of a series (S)
-    int L, M, NS, rounds;      // segment length, segments per series, segments (sequences) of the tile, rounds per series (group of columns)
-    int seq_stride, pad_shift; // the tile: sequence t at t * seq_stride, point p at p + (p >> pad_shift)
-    int nr, radix[XRFT_MAX_PASSES];
-    int detrend;
-    float scale;
-    int inner, lgC, ngroups;   // the column layout: columns per block, log2 of the columns per workgroup (C), groups of C columns per block
+    int NS, rounds;            // segments (sequences) of the tile, rounds per series (group of columns)
     int nx_out, shift, realdim2;  // L or L / 2 + 1; L / 2 or 0; interior bins of the half output doubled (POWER)
 };
 
 // LDS: [tile: NS sequences][red: 2 kWThreads doubles][coef: 2 NS doubles]
 template <bool POWER, bool COLS>
-__global__ void __launch_bounds__(kWThreads) fastk_kernel(FastK p) {
+__global__ void __launch_bounds__(kWThreads) fastk_kernel(FastK a) {
+    const SegTile& p = a.t;
     XRFT_DYN_SMEM(smem_raw);
     const int tid = threadIdx.x;
-    const int tile_elems = (p.NS * p.seq_stride + 1) & ~1;  // (16-byte multiples: the doubles behind the tile stay aligned)
+    const int tile_elems = (a.NS * p.seq_stride + 1) & ~1;  // (16-byte multiples: the doubles behind the tile stay aligned)
     cf* tile = reinterpret_cast<cf*>(smem_raw);
     double* red = reinterpret_cast<double*>(tile + tile_elems);
     double* coef = red + 2 * kWThreads;
-    const long long u = (long long)blockIdx.x / p.rounds;  // the series (COLS: the group of columns, over all blocks)
-    const int rd = (int)((long long)blockIdx.x % p.rounds);
-    const int lgC = COLS ? p.lgC : 0, cmask = (1 << lgC) - 1, spr = p.NS >> lgC;  // segments of one column per round
+    const int rd = (int)((long long)blockIdx.x % a.rounds);
+    const SegUnit un = seg_unit<COLS>(p, (long long)blockIdx.x / a.rounds);
+    const int lgC = COLS ? p.lgC : 0, cmask = (1 << lgC) - 1, spr = a.NS >> lgC;  // segments of one column per round
     const long long s0 = (long long)rd * spr;                                      // the round's first segment
-    const long long blk = COLS ? u / p.ngroups : u;
-    const long long c0 = COLS ? (u % p.ngroups) << lgC : 0;  // the group's first column
-    const int live = !COLS ? 1 : ((long long)p.inner - c0 < (1LL << lgC) ? (int)((long long)p.inner - c0) : (1 << lgC));
+    const long long blk = un.blk, c0 = un.c0;
+    const int live = un.live;
     const int nseg = (long long)p.M - s0 < spr ? (int)((long long)p.M - s0) : spr;  // segments of this round that exist
-    const float* __restrict__ src = p.in + (size_t)blk * (size_t)p.pitch + (size_t)c0;
-    const int L = p.L, lgL = 31 - __builtin_clz((unsigned)L), n = L >> 1, total = p.NS * L, ss = p.seq_stride, psh = p.pad_shift;
-    const bool det = p.detrend != 0;
-    // ---- the samples: tile sequence sg = (segment sl of the round, column c), sample j at component j & 1 of point j >> 1
-    for (int e = tid; e < total; e += kWThreads) {
-        int sl, j, c;
-        if (COLS) { c = e & cmask; const int r = e >> lgC; sl = r >> lgL; j = r & (L - 1); }
-        else { c = 0; sl = e >> lgL; j = e & (L - 1); }
-        const int sg = (sl << lgC) | c;
-        float v = 0.f;
-        if (sl < nseg && c < live) {
-            const long long off = COLS ? ((s0 + sl) * p.hop + j) * p.sstride + c : (s0 + sl) * p.hop + j;
-            v = src[(size_t)off];
-            if (!det && p.win) v *= p.win[j];
-        }
-        reinterpret_cast<float*>(tile + sg * ss + phys(j >> 1, psh))[j & 1] = v;
-    }
-    __syncthreads();
-    if (det) {
-        // per segment: sum x and sum (j - c) x, c = (L - 1) / 2, float64; tps threads per segment, then a tree over them (a fixed order)
-        const int tps = kWThreads / p.NS, seg = tid / tps, lane = tid % tps;  // (NS <= 128: tps >= 2, a power of two)
-        const double cm = 0.5 * (double)(L - 1);
-        {
-            const cf* sq = tile + seg * ss;
-            double s0x = 0.0, s1x = 0.0;
-            for (int j = lane; j < L; j += tps) {
-                const double x = (double)reinterpret_cast<const float*>(sq + phys(j >> 1, psh))[j & 1];
-                s0x += x;
-                s1x += ((double)j - cm) * x;
-            }
-            red[2 * tid] = s0x;
-            red[2 * tid + 1] = s1x;
-        }
-        __syncthreads();
-        for (int w = tps >> 1; w >= 1; w >>= 1) {
-            if (lane < w) {
-                red[2 * tid] += red[2 * (tid + w)];
-                red[2 * tid + 1] += red[2 * (tid + w) + 1];
-            }
-            __syncthreads();
-        }
-        if (lane == 0) {
-            const double Ld = (double)L;
-            coef[2 * seg] = red[2 * tid] / Ld;  // the mean
-            coef[2 * seg + 1] = p.detrend == 2 ? red[2 * tid + 1] / (Ld * (Ld * Ld - 1.0) / 12.0) : 0.0;  // the slope of the least-squares line about c
-        }
-        __syncthreads();
-        for (int e = tid; e < total; e += kWThreads) {
-            const int sg = e >> lgL, j = e & (L - 1);
-            float* dst = reinterpret_cast<float*>(tile + sg * ss + phys(j >> 1, psh)) + (j & 1);
-            float v = 0.f;
-            if ((sg >> lgC) < nseg && (sg & cmask) < live) {  // (a missing segment stays zero whatever the window)
-                v = (float)((double)*dst - (coef[2 * sg] + coef[2 * sg + 1] * ((double)j - cm)));
-                if (p.win) v *= p.win[j];
-            }
-            *dst = v;
-        }
-        __syncthreads();
-    }
-    // ---- NS transforms of n = L / 2 points
-    {
-        TileGeom g{};
-        g.n = n; g.T = p.NS; g.seq_stride = ss; g.pad_shift = psh;
-        int len = n;
-        for (int ip = 0; ip < p.nr; ++ip) {
-            const int R = p.radix[ip];
-            switch (R) {
-                case 2: run_pass<float, 2>(tile, g, len, tid, kWThreads, p.tw); break;
-                case 4: run_pass<float, 4>(tile, g, len, tid, kWThreads, p.tw); break;
-                case 8: run_pass<float, 8>(tile, g, len, tid, kWThreads, p.tw); break;
-                default: run_pass<float, 16>(tile, g, len, tid, kWThreads, p.tw); break;
-            }
-            len /= R;
-            __syncthreads();
-        }
-    }
+    const int L = p.L, n = L >> 1, ss = p.seq_stride, psh = p.pad_shift;
+    // ---- the samples, detrended and windowed: tile sequence sg = (segment sl of the round, column c), sample j at component j & 1 of point j >> 1
+    SelfLayout<COLS> lay;
+    lay.lgC = lgC; lay.live = live; lay.s0 = s0; lay.s_hi = p.M;
+    seg_load<COLS>(p, lay, a.in + (size_t)blk * (size_t)p.pitch + (size_t)c0, a.NS, tile, red, coef, tid);
+    seg_fft(p, n, a.NS, tile, tid);  // ---- NS transforms of n = L / 2 points
     // ---- every segment's spectrum, unpacked and stored: element e of the round's output = (segment sl, place c[, column])
-    const int nxo = p.nx_out, total_out = (nseg * nxo) << lgC;
+    const int nxo = a.nx_out, total_out = (nseg * nxo) << lgC;
     const float inv_nxo = 1.0f / (float)nxo;
     const size_t obase = ((size_t)blk * (size_t)p.M + (size_t)s0) * (size_t)nxo;  // (in places: x inner for the column layout)
     for (int e = tid; e < total_out; e += kWThreads) {
         const int col = COLS ? (e & cmask) : 0, r = e >> lgC;
         const int sl = fdiv(r, inv_nxo), c = r - sl * nxo;
         if (COLS && col >= live) continue;
-        const int k = (c - p.shift) & (L - 1);
+        const int k = (c - a.shift) & (L - 1);
         const bool up = k > n;             // X_k = conj X_{L-k}
         const int kk = up ? L - k : k;     // 0 .. n
         const int ka = kk == n ? 0 : kk, kb = kk == 0 ? 0 : n - kk;
@@ -152,14 +71,14 @@ __global__ void __launch_bounds__(kWThreads) fastk_kernel(FastK p) {
         const cf zc = cconj(sq[phys((int)p.rev[kb], psh)]);
         const cf E = cscale(zk + zc, 0.5f);
         const cf O = cscale(mul_mi(zk - zc), 0.5f);
-        cf X = E + cmul(p.twr[kk], O);
+        cf X = E + cmul(a.twr[kk], O);
         const size_t oi = COLS ? (obase + (size_t)r) * (size_t)p.inner + (size_t)c0 + (size_t)col : obase + (size_t)r;
         if (POWER) {
-            const float f = (p.realdim2 && k > 0 && k < n) ? 2.0f * p.scale : p.scale;
-            reinterpret_cast<float*>(p.out)[oi] = (X.re * X.re + X.im * X.im) * f;
+            const float f = (a.realdim2 && k > 0 && k < n) ? 2.0f * p.scale : p.scale;
+            reinterpret_cast<float*>(a.out)[oi] = (X.re * X.re + X.im * X.im) * f;
         } else {
             if (up) X = cconj(X);
-            reinterpret_cast<cf*>(p.out)[oi] = cscale(X, p.scale);
+            reinterpret_cast<cf*>(a.out)[oi] = cscale(X, p.scale);
         }
     }
 }

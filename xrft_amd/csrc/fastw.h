@@ -23,173 +23,61 @@
 // cancels in |F|^2 and in F0 conj(F1): ignored.
 #pragma once
 #include "fasty_mean.h"
-#include "tile_fft.h"
+#include "seg_tile.h"
 
 namespace xrft {
 
-constexpr int kWThreads = 256;   // threads of a fastw workgroup
-constexpr int kWPoints = 4096;   // complex points of one field's tile: G = min(kWPoints / L, pairs of the longest run) sequences
-constexpr int kWAcc = kWPoints / kWThreads;  // tile positions (float32 sums) per thread and field
-constexpr int kWCols = 32;       // the column layout: adjacent columns per workgroup where the tile holds them (128 bytes of one time row per wave-load)
-constexpr int kWColsMaxL = 512;  // ... and its longest segment: 8 columns of 512 points fill the tile (a 32-byte piece of a time row per row of the load)
+constexpr int kWAcc = kWPoints / kWThreads;  // tile positions (float32 sums) per thread and field: G = min(kWPoints / L, pairs of the longest run) sequences
 constexpr const char* kWColsResources = "115 VGPRs, no scratch, 4 waves per SIMD (two fields: 164 VGPRs, 3 waves)";  // (scripts/kernel_resources.sh, gfx950: the rows kernels' figures)
 
 struct FastW {
+    SegTile t;                 // (tw: W_L^k, k < L)
     const float* in0;
     const float* in1;          // the second field (CROSS), same layout
     double* part;              // [output][P][L] float64 (x2 complex: CROSS)
-    const cf* tw;              // W_L^k, k < L
-    const unsigned* rev;       // rev[k] = tile position of frequency k after the passes
-    const float* win;          // L window values, or null
-    long long pitch;           // samples between series (the column layout: between blocks)
-    long long hop;             // samples between segment starts
-    long long sstride;         // the column layout: elements between consecutive samples of a series (S)
-    int L, M, P, G;            // segment length, segments per series, runs per series, sequences (pairs of segments) per round
-    int seq_stride, pad_shift; // the tile: sequence t at t * seq_stride, point p at p + (p >> pad_shift)
-    int nr, radix[XRFT_MAX_PASSES];
-    int detrend;
-    float scale;
-    int inner, lgC, ngroups;   // the column layout: columns per block, log2 of the columns per workgroup (C), groups of C columns per block
+    int P, G;                  // runs per series, sequences (pairs of segments) per round
 };
-
-// Who owns the sequences of a tile.  Rows layout (COLS = false): all G sequences are pairs of segments of ONE series.  Column layout: a workgroup has C adjacent
-// columns of one block, sequence t = (column t % C, pair t / C): G / C pairs of every column per round.  Tile segment sg = 2 t + (member of the pair).
-template <bool COLS>
-struct WOwner {
-    int lgC, live;  // log2 C; the columns of this group that exist (the last group of a block may hold fewer than C: the rest are zeros and write nothing)
-    __device__ __forceinline__ int col(int sg) const { return COLS ? ((sg >> 1) & ((1 << lgC) - 1)) : 0; }
-    __device__ __forceinline__ int seg(int sg) const { return COLS ? ((((sg >> 1) >> lgC) << 1) | (sg & 1)) : sg; }  // the segment of its column, from the round's first
-    __device__ __forceinline__ bool has(int sg, long long s0, long long s_hi) const { return s0 + seg(sg) < s_hi && (!COLS || col(sg) < live); }
-};
-
-// one field's 2 G tile segments from segment `s0` on (those below s_hi; the rest zeros) into its tile, detrended and windowed.  red: 2 * kWThreads doubles, coef: 2 * 2 * G doubles
-// src: the first sample of the series (COLS: of the group's first column).  COLS: the load loop runs column fastest, then sample, then segment -- consecutive lanes
-// read consecutive addresses of one time row; the index (s H + j) S + e in 64 bits
-template <bool COLS>
-__device__ __forceinline__ void fastw_load(const FastW& p, const WOwner<COLS>& ow, const float* __restrict__ src, long long s0, long long s_hi, cf* tile, double* red, double* coef, int tid) {
-    const int L = p.L, lgL = 31 - __builtin_clz((unsigned)L), nseg = 2 * p.G, total = nseg * L;
-    const bool det = p.detrend != 0;
-    for (int e = tid; e < total; e += kWThreads) {
-        int sg, j;
-        long long off;
-        bool on;
-        if (COLS) {
-            const int c = e & ((1 << ow.lgC) - 1), r = e >> ow.lgC, sl = r >> lgL;  // column of the group, (segment of the round, sample)
-            j = r & (L - 1);
-            sg = ((((sl >> 1) << ow.lgC) | c) << 1) | (sl & 1);
-            on = s0 + sl < s_hi && c < ow.live;
-            off = ((s0 + sl) * p.hop + j) * p.sstride + c;
-        } else {
-            sg = e >> lgL; j = e & (L - 1);
-            on = s0 + sg < s_hi;
-            off = (s0 + sg) * p.hop + j;
-        }
-        float v = 0.f;
-        if (on) {
-            v = src[(size_t)off];
-            if (!det && p.win) v *= p.win[j];
-        }
-        float* dst = reinterpret_cast<float*>(tile + (sg >> 1) * p.seq_stride + phys(j, p.pad_shift));
-        dst[sg & 1] = v;
-    }
-    __syncthreads();
-    if (!det) return;
-    // per segment: sum x and sum (j - c) x, c = (L - 1) / 2, float64; tps threads per segment, then a tree over them (a fixed order)
-    const int tps = kWThreads / nseg, seg = tid / tps, lane = tid % tps;  // (nseg <= 128: tps >= 2, a power of two)
-    const double c = 0.5 * (double)(L - 1);
-    {
-        const float* col = reinterpret_cast<const float*>(tile + (seg >> 1) * p.seq_stride) + (seg & 1);
-        double s0x = 0.0, s1x = 0.0;
-        for (int j = lane; j < L; j += tps) {
-            const double x = (double)col[2 * phys(j, p.pad_shift)];
-            s0x += x;
-            s1x += ((double)j - c) * x;
-        }
-        red[2 * tid] = s0x;
-        red[2 * tid + 1] = s1x;
-    }
-    __syncthreads();
-    for (int w = tps >> 1; w >= 1; w >>= 1) {
-        if (lane < w) {
-            red[2 * tid] += red[2 * (tid + w)];
-            red[2 * tid + 1] += red[2 * (tid + w) + 1];
-        }
-        __syncthreads();
-    }
-    if (lane == 0) {
-        const double Ld = (double)L;
-        coef[2 * seg] = red[2 * tid] / Ld;  // the mean
-        coef[2 * seg + 1] = p.detrend == 2 ? red[2 * tid + 1] / (Ld * (Ld * Ld - 1.0) / 12.0) : 0.0;  // the slope of the least-squares line about c
-    }
-    __syncthreads();
-    for (int e = tid; e < total; e += kWThreads) {
-        const int sg = e >> lgL, j = e & (L - 1);
-        float* dst = reinterpret_cast<float*>(tile + (sg >> 1) * p.seq_stride + phys(j, p.pad_shift)) + (sg & 1);
-        float v = 0.f;
-        if (ow.has(sg, s0, s_hi)) {  // (a missing segment stays zero whatever the window)
-            v = (float)((double)*dst - (coef[2 * sg] + coef[2 * sg + 1] * ((double)j - c)));
-            if (p.win) v *= p.win[j];
-        }
-        *dst = v;
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ void fastw_fft(const FastW& p, cf* tile, int tid) {
-    TileGeom g{};
-    g.n = p.L; g.T = p.G; g.seq_stride = p.seq_stride; g.pad_shift = p.pad_shift;
-    int L = p.L;
-    for (int ip = 0; ip < p.nr; ++ip) {
-        const int R = p.radix[ip];
-        switch (R) {
-            case 2: run_pass<float, 2>(tile, g, L, tid, kWThreads, p.tw); break;
-            case 4: run_pass<float, 4>(tile, g, L, tid, kWThreads, p.tw); break;
-            case 8: run_pass<float, 8>(tile, g, L, tid, kWThreads, p.tw); break;
-            default: run_pass<float, 16>(tile, g, L, tid, kWThreads, p.tw); break;
-        }
-        L /= R;
-        __syncthreads();
-    }
-}
 
 // LDS: [tile 0][tile 1 (TWO)][red: 2 kWThreads doubles][coef: 4 G doubles]
 // COLS: the column layout (xrfthip_desc.seg_stride) -- blockIdx = ((block, group of C columns), run); the float64 sum at the end of a chain runs over the G / C pairs
 // of ONE column, into that column's own partial; columns beyond `inner` in the last group write nothing
 template <bool TWO, bool COLS = false>
-__global__ void __launch_bounds__(kWThreads) fastw_kernel(FastW p) {
+__global__ void __launch_bounds__(kWThreads) fastw_kernel(FastW a) {
+    const SegTile& p = a.t;
     XRFT_DYN_SMEM(smem_raw);
     const int tid = threadIdx.x;
-    const int tile_elems = (p.G * p.seq_stride + 1) & ~1;  // (16-byte multiples: the doubles behind the tiles stay aligned)
+    const int tile_elems = (a.G * p.seq_stride + 1) & ~1;  // (16-byte multiples: the doubles behind the tiles stay aligned)
     cf* tile0 = reinterpret_cast<cf*>(smem_raw);
     cf* tile1 = tile0 + (TWO ? tile_elems : 0);
     double* red = reinterpret_cast<double*>(tile0 + (TWO ? 2 : 1) * tile_elems);
     double* coef = red + 2 * kWThreads;
-    const long long u = (long long)blockIdx.x / p.P;  // the series (COLS: the group of columns, over all blocks)
-    const int pp = (int)((long long)blockIdx.x % p.P);
-    const long long s_lo = (long long)pp * p.M / p.P, s_hi = (long long)(pp + 1) * p.M / p.P;
-    const long long blk = COLS ? u / p.ngroups : u;
-    const long long c0 = COLS ? (u % p.ngroups) << p.lgC : 0;  // the group's first column
-    WOwner<COLS> ow;
+    const int pp = (int)((long long)blockIdx.x % a.P);
+    const long long s_lo = (long long)pp * p.M / a.P, s_hi = (long long)(pp + 1) * p.M / a.P;
+    const SegUnit un = seg_unit<COLS>(p, (long long)blockIdx.x / a.P);
+    const long long blk = un.blk, c0 = un.c0;
+    PairLayout<COLS> ow;
     ow.lgC = COLS ? p.lgC : 0;
-    ow.live = !COLS ? 1 : ((long long)p.inner - c0 < (1LL << p.lgC) ? (int)((long long)p.inner - c0) : (1 << p.lgC));
-    const int lgC = ow.lgC, Gp = p.G >> lgC;  // pairs of segments of one column per round
-    const float* __restrict__ src0 = p.in0 + (size_t)blk * (size_t)p.pitch + (size_t)c0;
-    const float* __restrict__ src1 = TWO ? p.in1 + (size_t)blk * (size_t)p.pitch + (size_t)c0 : src0;
+    ow.live = un.live;
+    ow.s_hi = s_hi;
+    const int lgC = ow.lgC, Gp = a.G >> lgC;  // pairs of segments of one column per round
+    const float* __restrict__ src0 = a.in0 + (size_t)blk * (size_t)p.pitch + (size_t)c0;
+    const float* __restrict__ src1 = TWO ? a.in1 + (size_t)blk * (size_t)p.pitch + (size_t)c0 : src0;
     constexpr int CW = TWO ? 2 : 1;
     // the partial of output o (COLS: o = block * inner + column), run pp: [o][P][L]
-    double* __restrict__ dst = p.part + (((size_t)blk * (size_t)(COLS ? p.inner : 1) + (size_t)c0) * p.P + pp) * (size_t)p.L * CW;
-    const size_t dst_col = (size_t)p.P * (size_t)p.L * CW;  // between the partials of neighbouring columns
-    const int L = p.L, lgL = 31 - __builtin_clz((unsigned)L), live = p.G * L;  // tile positions in use
+    double* __restrict__ dst = a.part + (((size_t)blk * (size_t)(COLS ? p.inner : 1) + (size_t)c0) * a.P + pp) * (size_t)p.L * CW;
+    const size_t dst_col = (size_t)a.P * (size_t)p.L * CW;  // between the partials of neighbouring columns
+    const int L = p.L, lgL = 31 - __builtin_clz((unsigned)L), live = a.G * L;  // tile positions in use
     float acc[kWAcc * CW];
 #pragma unroll
     for (int e = 0; e < kWAcc * CW; ++e) acc[e] = 0.f;
     int chain = 0;
     bool first = true;
     for (long long s = s_lo; s < s_hi; s += 2 * Gp) {
-        fastw_load<COLS>(p, ow, src0, s, s_hi, tile0, red, coef, tid);
-        if (TWO) fastw_load<COLS>(p, ow, src1, s, s_hi, tile1, red, coef, tid);
-        fastw_fft(p, tile0, tid);
-        if (TWO) fastw_fft(p, tile1, tid);
+        ow.s0 = s;
+        seg_load<COLS>(p, ow, src0, 2 * a.G, tile0, red, coef, tid);
+        if (TWO) seg_load<COLS>(p, ow, src1, 2 * a.G, tile1, red, coef, tid);
+        seg_fft(p, L, a.G, tile0, tid);
+        if (TWO) seg_fft(p, L, a.G, tile1, tid);
 #pragma unroll
         for (int q = 0; q < kWAcc; ++q) {
             const int e = tid + q * kWThreads;

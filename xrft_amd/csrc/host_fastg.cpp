@@ -632,7 +632,7 @@ static bool fastgy_uses_bluestein(const xrfthip_plan* P) { return P->gy_blue_m >
 #ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
 const FamilyOps kOpsFastG = {Family::FastG, run_fastg, describe_fastg, info_fastg, finalize_fastg, layout_one_pass, fastg_build_iso, nullptr, true, fastg_strided_if, true};  // (any bin map: per-bin position lists)
 const FamilyOps kOpsFastGY = {Family::FastGY, run_fastgy, describe_fastgy, info_fastgy, one_axis_tables, layout_one_pass, nullptr, fastgy_uses_bluestein, false, nullptr, true};
-const FamilyOps kOpsFastH = {Family::FastH, run_fasth, describe_fasth, info_fasth, fasth_phase_tables, layout_one_pass};  // (phase tables of the field form only; no other family to hand the plan to)
+const FamilyOps kOpsFastH = {Family::FastH, run_fasth, describe_fasth, info_fasth, fasth_phase_tables, layout_one_pass, nullptr, nullptr, false, nullptr, false, false, false, false, true};  // (phase tables of the field form only; no other family to hand the plan to)
 #endif
 
 template int fastn_rader_tables<float>(xrfthip_plan*);

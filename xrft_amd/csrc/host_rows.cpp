@@ -185,9 +185,7 @@ int try_fastr(xrfthip_plan* P) {
 }
 
 // one pass over 65536-sample float32 rows (fastr.h): a 1024-thread workgroup per row, or a resident set walking the rows
-static int run_fastw(const xrfthip_plan* P, const ExecArgs& a);
 static int run_fastr(const xrfthip_plan* P, const ExecArgs& a) {
-    if (P->family == Family::FastR && P->w_on) return run_fastw(P, a);  // (the Welch form)
     const xrfthip_desc& d = P->d;
     const void* in = a.in0; void* out = a.out; hipStream_t st = a.stream;
     const bool cin = P->family == Family::FastRComplex;
@@ -295,224 +293,9 @@ static int run_fastr(const xrfthip_plan* P, const ExecArgs& a) {
     return XRFTHIP_OK;
 }
 
-// FastR's Welch form (xrfthip_desc.seg_hop, fastw.h): the mean power / cross spectrum of the overlapping L-sample segments of each series, one pass over the series.
-// xrfthip_plan_create has checked the descriptor's shape (XRFTHIP_BAD_ARG); what is declined here is "the caller composes"
-// ... its "segments kept" form (xrfthip_desc.seg_keep, fastk.h): the tile holds NS = min(8192 / L, what M needs) segments, each an L / 2-point sequence; the column
-// layout C = min(32, 8192 / L) adjacent columns and NS / C segments of each; one workgroup per (series or group of columns, round)
-struct KeepGeom { int C, NS; long long rounds, nwg; };
-static KeepGeom keep_geom(const xrfthip_plan* P) {
-    const xrfthip_desc& d = P->d;
-    const int full = (int)(kKSegs / d.nx);
-    KeepGeom g{};
-    g.C = welch_cols(P) ? std::min<int>(kWCols, full) : 1;
-    g.NS = g.C;
-    while (g.NS / g.C < d.mean_batch && g.NS < full) g.NS *= 2;
-    const long long spr = g.NS / g.C, units = d.batch / d.mean_batch * (welch_cols(P) ? (d.inner + g.C - 1) / g.C : 1);
-    g.rounds = (d.mean_batch + spr - 1) / spr;
-    g.nwg = (units > 0 && g.rounds > 0x7fffffffLL / units) ? -1 : units * g.rounds;
-    return g;
-}
-
-int try_fastw(xrfthip_plan* P) {
-    const xrfthip_desc& d = P->d;
-    if (!welch_plan(P)) return kDeclined;
-    const bool cols = welch_cols(P);
-    if (keep_plan(P)) {
-        const bool pw = d.out_mode == XRFTHIP_OUT_POWER;
-        const bool len_k = d.nx >= 64 && d.nx <= (cols ? kWColsMaxL : 4096) && (d.nx & (d.nx - 1)) == 0;
-        const uint32_t okk = XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | (pw ? (XRFTHIP_REALDIM_X2 | XRFTHIP_ISHIFT_X) : 0u);  // (ISHIFT_X: (-1)^k on the transform, gone in |X|^2)
-        if (!len_k || d.dtype != XRFTHIP_F32 || in_half(P) || (d.flags & ~okk) || env_ll("XRFTHIP_FASTW", 1) == 0 || env_ll("XRFTHIP_FASTW_KEEP", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
-        if (cols && env_ll("XRFTHIP_FASTW_COLS", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
-        if (keep_geom(P).nwg < 0) return XRFTHIP_UNSUPPORTED_LENGTH;  // (one launch of at most 2^31 - 1 workgroups: declined, never truncated)
-        // ... and by default only the classes that measured faster than the composition they replace (profiles/r21_spectrogram.txt): fourteen of sixteen, 0.54 .. 0.92 of its
-        // time.  L = 4096 without overlap lost -- (256, 4194304) 9.7 against 8.2 ms, one-sided 8.7 against 8.2: there the composition copies nothing (the segments are a
-        // reshape) and runs the register-resident row kernel of fastr.h.  XRFTHIP_MEAN_ALL=1: every class this kernel takes
-        if (d.nx == 4096 && d.seg_hop == d.nx && env_ll("XRFTHIP_MEAN_ALL", 0) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
-        P->family = P->chosen = Family::FastR;
-        P->w_on = true;
-        FftTables& t = P->tables[(int)d.nx / 2];
-        int rc = build_tables<float>(t, (int)d.nx / 2);  // W_n^k of the packed transform (n = L / 2), its radices, and where they leave frequency k
-        if (rc) return rc;
-        for (int r : t.radix)
-            if (r != 2 && r != 4 && r != 8 && r != 16) return XRFTHIP_UNSUPPORTED_LENGTH;
-        return plan_twiddle(P, P->w_twr, d.nx, d.nx / 2 + 1);  // W_L^k, k <= L / 2: the unpacking
-    }
-    // (the column layout: up to 512 points -- the tile holds 8 adjacent columns at least; beyond, the caller arranges the series as rows)
-    const bool len_ok = d.nx >= 64 && d.nx <= (cols ? kWColsMaxL : 4096) && (d.nx & (d.nx - 1)) == 0;
-    const uint32_t okw = XRFTHIP_SHIFT_X | XRFTHIP_ISHIFT_X | XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2;
-    if (!len_ok || d.dtype != XRFTHIP_F32 || in_half(P) || (d.flags & ~okw) || env_ll("XRFTHIP_FASTW", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
-    if (cols && env_ll("XRFTHIP_FASTW_COLS", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
-    if (d.batch / d.mean_batch * (cols ? d.inner : 1) > 0x7fffffffLL / 1024) return XRFTHIP_UNSUPPORTED_LENGTH;  // (one launch: outputs x runs workgroups; one finish workgroup per output)
-    P->family = P->chosen = Family::FastR;  // (the rows family: its Welch form)
-    P->w_on = true;
-    FftTables& t = P->tables[(int)d.nx];
-    const int rc = build_tables<float>(t, (int)d.nx);  // W_L^k, the radices of the in-place passes, and where they leave frequency k
-    if (rc) return rc;
-    for (int r : t.radix)
-        if (r != 2 && r != 4 && r != 8 && r != 16) return XRFTHIP_UNSUPPORTED_LENGTH;
-    return XRFTHIP_OK;
-}
-
-// FastW's workspace: the float64 partial of every run of every output (one launch, one workgroup per run); then the tile of a workgroup: as many pairs of segments
-// per round as the longest run has, a power of two, kWPoints points at most
-static void layout_fastw(xrfthip_plan* P) {
-    const xrfthip_desc& d = P->d;
-    layout_one_pass(P);
-    if (keep_plan(P)) {  // (no workspace: every output element is written once by the thread that computed it)
-        const KeepGeom g = keep_geom(P);
-        P->w_C = g.C; P->w_G = g.NS; P->w_rounds = (int)g.rounds;
-        const long long n = d.nx / 2;
-        long long ss = n + (n >> 4) + 1;
-        if ((ss & 1) == 0) ++ss;  // (an odd stride: the sequences of a tile start on different banks)
-        P->w_stride = (int)ss;
-        P->w_lds = (((size_t)g.NS * (size_t)ss + 1) & ~(size_t)1) * sizeof(cf) + (size_t)(2 * kWThreads + 2 * g.NS) * sizeof(double);
-        return;
-    }
-    // the column layout: C adjacent columns per workgroup -- 32 (128 bytes of a time row) where the tile holds them, else what it holds
-    int C = 1;
-    if (welch_cols(P)) {
-        C = (int)std::min<long long>(kWCols, kWPoints / d.nx);  // (whatever `inner` is: the pairs per round, hence the order of a column's sums, do not depend on its neighbours)
-    }
-    P->w_C = C;
-    const long long ngroups = (std::max<long long>(d.inner, 1) + C - 1) / C;
-    P->ws_bytes = mean_layout(P, 0, 1, d.batch * (welch_cols(P) ? ngroups : 1));  // (the launch: groups x runs workgroups per block)
-    const long long pairs = (P->mean_run + 1) / 2;
-    int G = C;
-    while (G / C < pairs && G * d.nx < kWPoints) G *= 2;
-    P->w_G = G;
-    long long ss = d.nx + (d.nx >> 4) + 1;
-    if ((ss & 1) == 0) ++ss;  // (an odd stride: the sequences of a tile start on different banks)
-    P->w_stride = (int)ss;
-    const size_t tile = (((size_t)G * (size_t)ss + 1) & ~(size_t)1) * sizeof(cf);
-    P->w_lds = tile * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1) + (size_t)(2 * kWThreads + 4 * G) * sizeof(double);
-}
-
-// the "segments kept" form: one launch, nothing else
-static int run_fastk(const xrfthip_plan* P, const ExecArgs& a) {
-    const xrfthip_desc& d = P->d;
-    hipStream_t st = a.stream;
-    const FftTables& t = P->tables.at((int)d.nx / 2);
-    const bool cols = welch_cols(P), pw = d.out_mode == XRFTHIP_OUT_POWER;
-    FastK p{};
-    p.in = (const float*)a.in0; p.out = a.out;
-    p.tw = (const cf*)t.tw.p; p.twr = (const cf*)P->w_twr.p; p.rev = (const unsigned*)t.rev.p;
-    p.win = (const float*)P->win[1].p;
-    p.pitch = P->w_pitch; p.hop = d.seg_hop; p.sstride = cols ? d.seg_stride : 1;
-    p.L = (int)d.nx; p.M = (int)d.mean_batch; p.NS = P->w_G; p.rounds = P->w_rounds;
-    p.seq_stride = P->w_stride; p.pad_shift = 4;
-    p.nr = (int)t.radix.size();
-    for (int i = 0; i < p.nr; ++i) p.radix[i] = t.radix[i];
-    p.detrend = d.detrend;
-    p.scale = (float)d.scale;
-    p.inner = cols ? (int)d.inner : 1;
-    p.ngroups = cols ? (int)((d.inner + P->w_C - 1) / P->w_C) : 1;
-    p.lgC = ilog2i(P->w_C);
-    p.nx_out = (int)P->nx_out;
-    p.shift = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0;
-    p.realdim2 = (d.flags & XRFTHIP_REALDIM_X2) ? 1 : 0;
-    const long long nwg = d.batch / d.mean_batch * p.ngroups * (long long)p.rounds;
-    if (nwg > 0x7fffffffLL) return XRFTHIP_BAD_ARG;  // (try_fastw declined it)
-    const dim3 grid((unsigned)nwg), blk((unsigned)kWThreads);
-    xrfthip_plan::ProfRec* rec = prof_begin(P, "fastk_segments", st);
-    if (cols) {
-        if (pw) { auto k = &fastk_kernel<true, true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
-        else { auto k = &fastk_kernel<false, true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
-    }
-    else if (pw) { auto k = &fastk_kernel<true, false>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
-    else { auto k = &fastk_kernel<false, false>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
-    prof_end(rec, st);
-    HIP_TRY(hipGetLastError());
-    return XRFTHIP_OK;
-}
-
-static int run_fastw(const xrfthip_plan* P, const ExecArgs& a) {
-    if (keep_plan(P)) return run_fastk(P, a);
-    const xrfthip_desc& d = P->d;
-    hipStream_t st = a.stream;
-    const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
-    const FftTables& t = P->tables.at((int)d.nx);
-    FastW p{};
-    p.in0 = (const float*)a.in0; p.in1 = (const float*)a.in1;
-    p.part = reinterpret_cast<double*>(a.ws + P->off_mean);
-    p.tw = (const cf*)t.tw.p; p.rev = (const unsigned*)t.rev.p;
-    p.win = (const float*)P->win[1].p;
-    p.pitch = P->w_pitch; p.hop = d.seg_hop;
-    const bool cols = welch_cols(P);
-    const long long ngroups = cols ? (d.inner + P->w_C - 1) / P->w_C : 1, ncols = cols ? d.inner : 1;
-    p.sstride = cols ? d.seg_stride : 1; p.inner = (int)ncols; p.ngroups = (int)ngroups;
-    p.lgC = 0;
-    while ((1 << p.lgC) < P->w_C) ++p.lgC;
-    p.L = (int)d.nx; p.M = (int)d.mean_batch; p.P = P->mean_P; p.G = P->w_G;
-    p.seq_stride = P->w_stride; p.pad_shift = 4;
-    p.nr = (int)t.radix.size();
-    for (int i = 0; i < p.nr; ++i) p.radix[i] = t.radix[i];
-    p.detrend = d.detrend;
-    p.scale = (float)d.scale;
-    const long long nblk = d.batch / d.mean_batch, nout = nblk * ncols, nwg = nblk * ngroups * P->mean_P;
-    if (nwg > 0x7fffffffLL || nout > 0x7fffffffLL) return XRFTHIP_BAD_ARG;
-    const dim3 grid((unsigned)nwg), blk((unsigned)kWThreads);
-    xrfthip_plan::ProfRec* rec = prof_begin(P, "fastw_segments", st);
-    if (cols) {
-        if (two) { auto k = &fastw_kernel<true, true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
-        else { auto k = &fastw_kernel<false, true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
-    }
-    else if (two) { auto k = &fastw_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
-    else { auto k = &fastw_kernel<false>; XRFT_LAUNCH(k, grid, blk, P->w_lds, st, p); }
-    prof_end(rec, st);
-    HIP_TRY(hipGetLastError());
-    rec = prof_begin(P, "fastw_finish", st);
-    const int nxo = (int)P->nx_out, shift = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0, rd2 = (d.flags & XRFTHIP_REALDIM_X2) ? 1 : 0;
-    const double half_inv_m = 0.5 / (double)d.mean_batch;
-    const cf* ph = reinterpret_cast<const cf*>(P->fph[1].p);
-    const dim3 fgrid((unsigned)nout), fblk(256);
-    if (two) { auto k = &fastw_finish_kernel<true>; XRFT_LAUNCH(k, fgrid, fblk, 0, st, (const double*)p.part, a.out, p.L, nxo, p.P, half_inv_m, shift, rd2, ph, (P->fph_on && ph) ? 1 : 0); }
-    else { auto k = &fastw_finish_kernel<false>; XRFT_LAUNCH(k, fgrid, fblk, 0, st, (const double*)p.part, a.out, p.L, nxo, p.P, half_inv_m, shift, rd2, ph, 0); }
-    prof_end(rec, st);
-    HIP_TRY(hipGetLastError());
-    return XRFTHIP_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// the rows of FastS, FastR (with its Welch form), FastRComplex and FastRRows (plan.h, FamilyOps)
+// the rows of FastS, FastR, FastRComplex and FastRRows (plan.h, FamilyOps)
 // ---------------------------------------------------------------------------------------------------------------
-static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*) {
-    const xrfthip_desc& d = plan->d;
-    if (keep_plan(plan)) {
-        const FftTables& tk = plan->tables.at((int)d.nx / 2);
-        std::string radk;
-        for (int r : tk.radix) appendf(radk, "%s%d", radk.empty() ? "" : "x", r);
-        const long long units = d.batch / d.mean_batch * (welch_cols(plan) ? (d.inner + plan->w_C - 1) / plan->w_C : 1);
-        appendf(s, "  [fastw segments kept] spectrograms, one pass: %lld series of %lld segments of %lld samples, hop %lld (series pitch %lld), each segment read where it lies with "
-                   "4-byte loads and its own spectrum written once (%s); one %d-thread workgroup per (series, round): %lld x %d workgroups, %d segments per round, each packed "
-                   "with itself (x_2j + i x_2j+1) as a %lld-point sequence of an LDS tile, detrend and window in the tile, radix %s in place, unpacked X_k = E_k + W_L^k O_k, "
-                   "lanes store consecutive output elements; no workspace, no partial sums, no atomics; lds=%zuB; %s; %d algorithmic bytes per output element and 4 per "
-                   "sample read\n",
-                (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, (long long)d.nx, (long long)d.seg_hop, plan->w_pitch, d.out_mode == XRFTHIP_OUT_POWER ? "|X|^2, real" : "X, complex",
-                kWThreads, units, plan->w_rounds, plan->w_G / plan->w_C, (long long)d.nx / 2, radk.c_str(), plan->w_lds, kKResources, d.out_mode == XRFTHIP_OUT_POWER ? 4 : 8);
-        if (welch_cols(plan))
-            appendf(s, "  [fastw columns] the series lie along a leading axis, read where they lie: %lld blocks of %lld adjacent columns, sample stride %lld (block pitch %lld); "
-                       "a workgroup takes %d adjacent columns (%lld groups per block; %d bytes of one time row per wave-load) and %d segments of each per round, "
-                       "sequence t = (column t %% %d, segment t / %d); the result is [block][segment][frequency][column], stores coalesced across columns, no transposed copy\n",
-                    (long long)(d.batch / d.mean_batch), (long long)d.inner, (long long)d.seg_stride, plan->w_pitch, plan->w_C, (long long)((d.inner + plan->w_C - 1) / plan->w_C),
-                    4 * plan->w_C, plan->w_G / plan->w_C, plan->w_C, plan->w_C);
-        return;
-    }
-    const FftTables& t = plan->tables.at((int)d.nx);
-    std::string rad;
-    for (int r : t.radix) appendf(rad, "%s%d", rad.empty() ? "" : "x", r);
-    appendf(s, "  [fastw] Welch spectra, one pass: %lld series of %lld segments of %lld samples, hop %lld (series pitch %lld), each segment read where it lies with 4-byte loads; "
-               "one %d-thread workgroup per run, %d segments per round packed in pairs (a + i b) as %d sequences of an LDS tile, detrend and window in the tile, radix "
-               "%s in place, |Z|^2 (Z conj Z') summed in %d float32 registers per thread, the pair symmetrised once by fastw_finish; lds=%zuB; "
-               "fastw_kernel: 115 VGPRs, no scratch, 4 waves per SIMD (two fields: 164 VGPRs, 3 waves); 4 algorithmic bytes per sample of the series through memory\n",
-            (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, (long long)d.nx, (long long)d.seg_hop, plan->w_pitch, kWThreads, 2 * plan->w_G, plan->w_G,
-            rad.c_str(), kWAcc * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1), plan->w_lds);
-    if (welch_cols(plan))
-        appendf(s, "  [fastw columns] the series lie along a leading axis, read where they lie: %lld blocks of %lld adjacent columns, sample stride %lld (block pitch %lld); "
-                   "a workgroup takes %d adjacent columns (%lld groups per block; %d bytes of one time row per wave-load) and %d pairs of segments of each per round, "
-                   "sequence t = (column t %% %d, pair t / %d); the float64 sums per column; fastw_kernel<cols>: %s\n",
-                (long long)(d.batch / d.mean_batch), (long long)d.inner, (long long)d.seg_stride, plan->w_pitch, plan->w_C, (long long)((d.inner + plan->w_C - 1) / plan->w_C),
-                4 * plan->w_C, plan->w_G / plan->w_C, plan->w_C, plan->w_C, kWColsResources);
-}
 static void describe_fasts(const xrfthip_plan* plan, std::string& s, const char* in_note) {
     const SGeomRt G = sgeom(plan->d.ny, plan->d.nx);
     appendf(s, "  [fasts] one pass, one %d-thread workgroup per %lld x %lld slab (%d fit a CU): the packed columns' transform, their split and the rows' "
@@ -520,9 +303,7 @@ static void describe_fasts(const xrfthip_plan* plan, std::string& s, const char*
                "rows staged in LDS and written whole with the fftshift and the Hermitian mirror, lds=%zuB; 8 algorithmic bytes per sample through memory%s\n",
             G.thr, (long long)plan->d.ny, (long long)plan->d.nx, G.per_cu, (long long)plan->d.ny / 32, (long long)plan->d.nx / 32, G.lds, in_note);
 }
-static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*);
 static void describe_fastr(const xrfthip_plan* plan, std::string& s, const char* in_note) {
-    if (plan->w_on) { describe_fastw(plan, s, in_note); return; }
     const long long nxr = plan->d.nx;
     appendf(s, "  [fastr] one pass, one %lld-thread workgroup per %lld-sample row (grid %lld): the packed %lld-point complex transform in registers (32 per thread, "
                "r32x%dx%d, LDS exchanges%s), real split through the LDS, lds=%zuB; per-row detrend + window + full (or half) spectrum; "
@@ -547,15 +328,11 @@ static void describe_fastr_rows(const xrfthip_plan* plan, std::string& s, const 
                "16 algorithmic bytes per point through memory\n", R.thr, R.rk, (long long)plan->d.nx, (plan->d.flags & XRFTHIP_INVERSE) ? "inverse" : "forward");
 }
 static void info_fasts(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTS; *n = 1; }
-static void info_fastr(const xrfthip_plan* plan, int32_t* k, int32_t* n) {
-    if (plan->family == Family::FastR && plan->w_on) { *k = XRFTHIP_K_FASTW; *n = keep_plan(plan) ? plan->w_G : 2 * plan->w_G; return; }  // (the Welch form: segments per round)
-    *k = XRFTHIP_K_FASTR; *n = 1;
-}
-static void layout_fastr(xrfthip_plan* P) { if (P->w_on) layout_fastw(P); else layout_one_pass(P); }
+static void info_fastr(const xrfthip_plan*, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTR; *n = 1; }
 // (the entries in the order of struct FamilyOps: family, run, describe, kernel_info, finalize, layout, binmap, uses_bluestein, reads_strided)
 #ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
 const FamilyOps kOpsFastS = {Family::FastS, run_fasts, describe_fasts, info_fasts, fast_phase_tables, layout_fasts, fasts_build_tfirst, nullptr, true};
-const FamilyOps kOpsFastR = {Family::FastR, run_fastr, describe_fastr, info_fastr, fast_phase_tables, layout_fastr, nullptr, nullptr, true};
+const FamilyOps kOpsFastR = {Family::FastR, run_fastr, describe_fastr, info_fastr, fast_phase_tables, layout_one_pass, nullptr, nullptr, true};
 const FamilyOps kOpsFastRComplex = {Family::FastRComplex, run_fastr, describe_fastr_complex, info_fastr, one_axis_tables, layout_one_pass};
 const FamilyOps kOpsFastRRows = {Family::FastRRows, run_fastr, describe_fastr_rows, info_fastr, one_axis_tables, layout_one_pass};
 #endif
@@ -565,9 +342,6 @@ const FamilyOps kOpsFastRRows = {Family::FastRRows, run_fastr, describe_fastr_ro
 void set_attrs_rows() {
     const int m = (int)kLdsMax;
 #define SETF(K) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, m)
-    SETF((fastw_kernel<false>)); SETF((fastw_kernel<true>));  // (two tiles of 4096 points and their padding)
-    SETF((fastw_kernel<false, true>)); SETF((fastw_kernel<true, true>));
-    SETF((fastk_kernel<true, false>)); SETF((fastk_kernel<false, false>)); SETF((fastk_kernel<true, true>)); SETF((fastk_kernel<false, true>));
     SETF((fasts_power_kernel<8, 8, 0, 0>)); SETF((fasts_power_kernel<8, 4, 0, 0>)); SETF((fasts_power_kernel<4, 8, 0, 0>));
     SETF((fasts_power_kernel<8, 8, 0>)); SETF((fasts_power_kernel<8, 8, 1>)); SETF((fasts_power_kernel<8, 8, 2>));  // (above 64 KB of dynamic LDS)
     SETF((fasts_power_kernel<8, 4, 0>)); SETF((fasts_power_kernel<8, 4, 1>)); SETF((fasts_power_kernel<8, 4, 2>));
@@ -594,3 +368,4 @@ void set_attrs_rows() {
     SETF((fastr2_kernel<16, 16, 0, false>)); SETF((fastr2_kernel<16, 16, 0, true>)); SETF((fastr2_kernel<16, 16, 1, false>)); SETF((fastr2_kernel<16, 16, 1, true>));
 #undef SETF
 }
+#include "host_welch.inc"  // Family::FastW, Family::FastK: Welch spectra and spectrograms

@@ -1,0 +1,224 @@
+// host_welch.inc -- a file of its own, compiled as the tail of host_rows.cpp's translation unit and not as a unit of its own: the unit lists live in the build scripts
+// (__graft_entry__.py, tests/emu/build_emu.py), and the test tree of an earlier commit, run against these sources with its own build_emu.py, links only the units it lists.
+// The segment families (xrfthip_desc.seg_hop): the overlapping L-sample segments of a series, read where they lie, detrended, windowed and transformed in an LDS tile.
+//   FastW   Welch spectra (fastw.h): the mean power / cross spectrum of a series' segments, two segments packed per sequence (a + i b), float64 partial per run
+//   FastK   spectrograms (xrfthip_desc.seg_keep, fastk.h): every segment's spectrum kept, a segment packed with itself as a sequence of L / 2 points, no workspace
+// Both in the rows layout (one series per workgroup) or the column layout (xrfthip_desc.seg_stride: C adjacent columns of a (time, ..) block per workgroup).
+
+// xrfthip_plan_create's checks of seg_hop / seg_stride / seg_keep (XRFTHIP_BAD_ARG; what try_fastw declines is "the caller composes"), on its own copy of the descriptor: seg_stride = 1 is the rows layout and becomes it;
+// in_stride_batch is the series pitch here (any multiple of 4 bytes: the kernels load single samples) -- it is checked, returned as *pitch and cleared, so that
+// nothing of the strided-view rules (16-byte strides and pointers) applies to such a plan.  mean_batch counts the segments of a series (1 included when they are kept)
+int seg_desc_check(xrfthip_desc& s, long long* pitch) {
+    *pitch = 0;
+    if ((s.seg_keep != 0 && s.seg_keep != 1) || s.seg_reserved3 != 0 || (s.seg_keep && s.seg_hop <= 0)) return XRFTHIP_BAD_ARG;
+    const bool keep = s.seg_keep == 1;
+    if (s.seg_hop < 0 || s.seg_reserved != 0 || s.seg_stride < 0 || s.seg_reserved2 != 0) return XRFTHIP_BAD_ARG;
+    if (s.seg_stride > 0 && (s.seg_hop == 0 || s.seg_stride < s.inner)) return XRFTHIP_BAD_ARG;
+    if (s.seg_stride == 1) s.seg_stride = 0;
+    if (s.seg_hop == 0) return XRFTHIP_OK;
+    if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.seg_hop > s.nx || (s.flags & (XRFTHIP_AXIS_Y | XRFTHIP_ISO)) || (s.inner > 1 && !s.seg_stride) || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y) return XRFTHIP_BAD_ARG;
+    if (s.mean_batch < (keep ? 1 : 2) || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
+    if (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != (keep ? XRFTHIP_OUT_COMPLEX : XRFTHIP_OUT_CROSS)) return XRFTHIP_BAD_ARG;
+    if (s.nx > (1LL << 30) || s.mean_batch > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;
+    const long long span = (s.mean_batch - 1) * s.seg_hop + s.nx, S = s.seg_stride ? s.seg_stride : 1;
+    // (the column layout: the offsets stay far inside 64 bits -- span < 2^62, S and inner below 2^31)
+    if (s.seg_stride && (s.seg_stride > (1LL << 31) - 1 || s.inner > (1LL << 31) - 1 || span > (1LL << 31) - 1)) return XRFTHIP_BAD_ARG;
+    const long long dense = s.seg_stride ? (span - 1) * S + s.inner : span;  // the samples one series (block of columns) reaches
+    if (s.in_stride_batch != 0 && s.in_stride_batch < dense) return XRFTHIP_BAD_ARG;
+    *pitch = s.in_stride_batch ? s.in_stride_batch : span * S;
+    s.in_stride_batch = 0;
+    return XRFTHIP_OK;
+}
+
+static int seg_n(const xrfthip_plan* P) { return (int)(keep_plan(P) ? P->d.nx / 2 : P->d.nx); }  // points of a tile sequence: a pair of segments, or a segment packed with itself
+
+// The tile of a workgroup: C adjacent columns (32 -- 128 bytes of a time row -- where the tile holds them, else what it holds, whatever `inner` is: the order of a
+// column's sums does not depend on its neighbours; 1 in the rows layout) times as many sequences of each as `need` asks for, a power of two, kWPoints points at most
+static int seg_cols(const xrfthip_plan* P) { return welch_cols(P) ? std::min<int>(kWCols, kWPoints / seg_n(P)) : 1; }  // C
+static long long seg_ngroups(const xrfthip_plan* P) { return welch_cols(P) ? (P->d.inner + seg_cols(P) - 1) / seg_cols(P) : 1; }  // groups of C columns per block
+static SegGeom seg_geom(const xrfthip_plan* P, long long need) {
+    const xrfthip_desc& d = P->d;
+    const bool keep = keep_plan(P);
+    const long long n = seg_n(P), cap = kWPoints / n;  // points of a sequence, sequences the tile holds
+    SegGeom g;
+    g.C = seg_cols(P);
+    g.lgC = ilog2i(g.C);
+    g.ngroups = seg_ngroups(P);
+    g.seqs = g.C;
+    while (g.seqs / g.C < need && g.seqs < cap) g.seqs *= 2;
+    long long ss = n + (n >> 4) + 1;
+    if ((ss & 1) == 0) ++ss;  // (an odd stride: the sequences of a tile start on different banks)
+    g.stride = (int)ss;
+    const size_t tile = (((size_t)g.seqs * (size_t)ss + 1) & ~(size_t)1) * sizeof(cf);
+    // [tile per field][red: 2 kWThreads doubles][coef: 2 doubles per segment]
+    g.lds = tile * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1) + (size_t)(2 * kWThreads + 2 * (keep ? 1 : 2) * g.seqs) * sizeof(double);
+    const long long spr = g.seqs / g.C;  // FastK: segments of a column per round, one workgroup per (series or group of columns, round)
+    g.rounds = keep ? (d.mean_batch + spr - 1) / spr : 1;
+    return g;
+}
+static long long seg_units(const xrfthip_plan* P, const SegGeom& g) { return P->d.batch / P->d.mean_batch * g.ngroups; }  // series, or groups of columns over all blocks
+
+// FastW / FastK: float32 series, segments of 64 .. 4096 samples, a power of two (the column layout: up to 512 -- the tile holds 8 adjacent columns at least; beyond,
+// the caller arranges the series as rows)
+int try_fastw(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    if (!welch_plan(P)) return kDeclined;
+    const bool cols = welch_cols(P), keep = keep_plan(P);
+    const bool len_ok = d.nx >= 64 && d.nx <= (cols ? kWColsMaxL : 4096) && (d.nx & (d.nx - 1)) == 0;
+    // (ISHIFT_X: (-1)^k on the transform, gone in |X|^2 and in X conj X')
+    const uint32_t ok = XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | (d.out_mode != XRFTHIP_OUT_COMPLEX ? (XRFTHIP_REALDIM_X2 | XRFTHIP_ISHIFT_X) : 0u);
+    if (!len_ok || d.dtype != XRFTHIP_F32 || in_half(P) || (d.flags & ~ok) || env_ll("XRFTHIP_FASTW", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
+    if ((keep && env_ll("XRFTHIP_FASTW_KEEP", 1) == 0) || (cols && env_ll("XRFTHIP_FASTW_COLS", 1) == 0)) return XRFTHIP_UNSUPPORTED_LENGTH;
+    // one launch of at most 2^31 - 1 workgroups -- FastW: outputs x runs (at most 1024), one finish workgroup per output; FastK: units x rounds.  Declined, never truncated
+    if (keep) {
+        const SegGeom g = seg_geom(P, d.mean_batch);
+        const long long units = seg_units(P, g);
+        if (units > 0 && g.rounds > 0x7fffffffLL / units) return XRFTHIP_UNSUPPORTED_LENGTH;
+        // ... and by default only the classes that measured faster than the composition they replace (profiles/r21_spectrogram.txt): fourteen of sixteen, 0.54 .. 0.92 of its
+        // time.  L = 4096 without overlap lost -- (256, 4194304) 9.7 against 8.2 ms, one-sided 8.7 against 8.2: there the composition copies nothing (the segments are a
+        // reshape) and runs the register-resident row kernel of fastr.h.  XRFTHIP_MEAN_ALL=1: every class this kernel takes
+        if (d.nx == 4096 && d.seg_hop == d.nx && env_ll("XRFTHIP_MEAN_ALL", 0) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
+    } else if (d.batch / d.mean_batch * (cols ? d.inner : 1) > 0x7fffffffLL / 1024) return XRFTHIP_UNSUPPORTED_LENGTH;
+    P->family = P->chosen = keep ? Family::FastK : Family::FastW;
+    FftTables& t = P->tables[seg_n(P)];
+    const int rc = build_tables<float>(t, seg_n(P));  // W_n^k, the radices of the in-place passes, and where they leave frequency k
+    if (rc) return rc;
+    for (int r : t.radix) if (r != 2 && r != 4 && r != 8 && r != 16) return XRFTHIP_UNSUPPORTED_LENGTH;
+    return keep ? plan_twiddle(P, P->w_twr, d.nx, d.nx / 2 + 1) : XRFTHIP_OK;  // (FastK: W_L^k, k <= L / 2, the unpacking)
+}
+
+// FastW's workspace: the float64 partial of every run of every output (one launch, one workgroup per run); then the tile: as many pairs of segments per round as
+// the longest run has.  FastK: no workspace (every output element is written once by the thread that computed it), as many segments per round as a series has
+static void layout_fastw(xrfthip_plan* P) {
+    layout_one_pass(P);
+    P->ws_bytes = mean_layout(P, 0, 1, P->d.batch * seg_ngroups(P));  // (the launch: groups x runs workgroups per block)
+    P->w = seg_geom(P, (P->mean_run + 1) / 2);
+}
+static void layout_fastk(xrfthip_plan* P) { layout_one_pass(P); P->w = seg_geom(P, P->d.mean_batch); }
+
+// the head of the two kernels' arguments (seg_tile.h)
+static void seg_args(const xrfthip_plan* P, SegTile& p) {
+    const xrfthip_desc& d = P->d;
+    const FftTables& t = P->tables.at(seg_n(P));
+    const bool cols = welch_cols(P);
+    p.tw = (const cf*)t.tw.p; p.rev = (const unsigned*)t.rev.p;
+    p.win = (const float*)P->win[1].p;
+    p.pitch = P->w_pitch; p.hop = d.seg_hop; p.sstride = cols ? d.seg_stride : 1;
+    p.L = (int)d.nx; p.M = (int)d.mean_batch;
+    p.seq_stride = P->w.stride; p.pad_shift = 4;
+    p.nr = (int)t.radix.size();
+    for (int i = 0; i < p.nr; ++i) p.radix[i] = t.radix[i];
+    p.detrend = d.detrend;
+    p.scale = (float)d.scale;
+    p.inner = cols ? (int)d.inner : 1; p.lgC = P->w.lgC; p.ngroups = (int)P->w.ngroups;
+}
+
+// the launch of a segment kernel, K<A, column layout>, over nwg workgroups under a profiling label
+#define SEG_LAUNCH(K, A, LABEL, NWG, ARG) do { \
+        const dim3 grid((unsigned)(NWG)), blk((unsigned)kWThreads); \
+        xrfthip_plan::ProfRec* rec = prof_begin(P, LABEL, st); \
+        if (welch_cols(P)) { if (A) { auto k = &K<true, true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, ARG); } else { auto k = &K<false, true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, ARG); } } \
+        else if (A) { auto k = &K<true, false>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, ARG); } else { auto k = &K<false, false>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, ARG); } \
+        prof_end(rec, st); \
+        HIP_TRY(hipGetLastError()); } while (0)
+
+// FastK: one launch, nothing else
+static int run_fastk(const xrfthip_plan* P, const ExecArgs& a) {
+    const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
+    FastK p{};
+    seg_args(P, p.t);
+    p.in = (const float*)a.in0; p.out = a.out;
+    p.twr = (const cf*)P->w_twr.p;
+    p.NS = P->w.seqs; p.rounds = (int)P->w.rounds;
+    p.nx_out = (int)P->nx_out;
+    p.shift = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0;
+    p.realdim2 = (d.flags & XRFTHIP_REALDIM_X2) ? 1 : 0;
+    const long long nwg = seg_units(P, P->w) * P->w.rounds;
+    if (nwg > 0x7fffffffLL) return XRFTHIP_BAD_ARG;  // (try_fastw declined it)
+    SEG_LAUNCH(fastk_kernel, d.out_mode == XRFTHIP_OUT_POWER, "fastk_segments", nwg, p);
+    return XRFTHIP_OK;
+}
+
+// FastW: the segments' launch, then one finish workgroup per output
+static int run_fastw(const xrfthip_plan* P, const ExecArgs& a) {
+    const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
+    const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
+    FastW p{};
+    seg_args(P, p.t);
+    p.in0 = (const float*)a.in0; p.in1 = (const float*)a.in1;
+    p.part = reinterpret_cast<double*>(a.ws + P->off_mean);
+    p.P = P->mean_P; p.G = P->w.seqs;
+    const long long nout = d.batch / d.mean_batch * p.t.inner, nwg = seg_units(P, P->w) * P->mean_P;
+    if (nwg > 0x7fffffffLL || nout > 0x7fffffffLL) return XRFTHIP_BAD_ARG;
+    SEG_LAUNCH(fastw_kernel, two, "fastw_segments", nwg, p);
+    xrfthip_plan::ProfRec* rec = prof_begin(P, "fastw_finish", st);
+    const int nxo = (int)P->nx_out, shift = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0, rd2 = (d.flags & XRFTHIP_REALDIM_X2) ? 1 : 0;
+    const double half_inv_m = 0.5 / (double)d.mean_batch;
+    const cf* ph = reinterpret_cast<const cf*>(P->fph[1].p);
+    const dim3 fgrid((unsigned)nout), fblk(256);
+    if (two) { auto k = &fastw_finish_kernel<true>; XRFT_LAUNCH(k, fgrid, fblk, 0, st, (const double*)p.part, a.out, p.t.L, nxo, p.P, half_inv_m, shift, rd2, ph, (P->fph_on && ph) ? 1 : 0); }
+    else { auto k = &fastw_finish_kernel<false>; XRFT_LAUNCH(k, fgrid, fblk, 0, st, (const double*)p.part, a.out, p.t.L, nxo, p.P, half_inv_m, shift, rd2, ph, 0); }
+    prof_end(rec, st);
+    HIP_TRY(hipGetLastError());
+    return XRFTHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the rows of FastW and FastK (plan.h, FamilyOps)
+// ---------------------------------------------------------------------------------------------------------------
+static std::string seg_radices(const xrfthip_plan* plan) {
+    std::string rad;
+    for (int r : plan->tables.at(seg_n(plan)).radix) appendf(rad, "%s%d", rad.empty() ? "" : "x", r);
+    return rad;
+}
+// the column layout's line: `unit` ("pair" | "segment") is what a sequence of the tile holds, `units` its plural as the line says it
+static void describe_cols(const xrfthip_plan* plan, std::string& s, const char* units, const char* unit, const char* tail) {
+    const xrfthip_desc& d = plan->d;
+    const SegGeom& g = plan->w;
+    if (!welch_cols(plan)) return;
+    appendf(s, "  [fastw columns] the series lie along a leading axis, read where they lie: %lld blocks of %lld adjacent columns, sample stride %lld (block pitch %lld); "
+               "a workgroup takes %d adjacent columns (%lld groups per block; %d bytes of one time row per wave-load) and %d %s of each per round, "
+               "sequence t = (column t %% %d, %s t / %d); %s\n",
+            (long long)(d.batch / d.mean_batch), (long long)d.inner, (long long)d.seg_stride, plan->w_pitch, g.C, g.ngroups, 4 * g.C, g.seqs / g.C, units, g.C, unit, g.C, tail);
+}
+static void describe_fastk(const xrfthip_plan* plan, std::string& s, const char*) {
+    const xrfthip_desc& d = plan->d;
+    const SegGeom& g = plan->w;
+    appendf(s, "  [fastw segments kept] spectrograms, one pass: %lld series of %lld segments of %lld samples, hop %lld (series pitch %lld), each segment read where it lies with "
+               "4-byte loads and its own spectrum written once (%s); one %d-thread workgroup per (series, round): %lld x %lld workgroups, %d segments per round, each packed "
+               "with itself (x_2j + i x_2j+1) as a %lld-point sequence of an LDS tile, detrend and window in the tile, radix %s in place, unpacked X_k = E_k + W_L^k O_k, "
+               "lanes store consecutive output elements; no workspace, no partial sums, no atomics; lds=%zuB; %s; %d algorithmic bytes per output element and 4 per "
+               "sample read\n",
+            (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, (long long)d.nx, (long long)d.seg_hop, plan->w_pitch, d.out_mode == XRFTHIP_OUT_POWER ? "|X|^2, real" : "X, complex",
+            kWThreads, seg_units(plan, g), g.rounds, g.seqs / g.C, (long long)d.nx / 2, seg_radices(plan).c_str(), g.lds, kKResources, d.out_mode == XRFTHIP_OUT_POWER ? 4 : 8);
+    describe_cols(plan, s, "segments", "segment", "the result is [block][segment][frequency][column], stores coalesced across columns, no transposed copy");
+}
+static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*) {
+    const xrfthip_desc& d = plan->d;
+    const SegGeom& g = plan->w;
+    appendf(s, "  [fastw] Welch spectra, one pass: %lld series of %lld segments of %lld samples, hop %lld (series pitch %lld), each segment read where it lies with 4-byte loads; "
+               "one %d-thread workgroup per run, %d segments per round packed in pairs (a + i b) as %d sequences of an LDS tile, detrend and window in the tile, radix "
+               "%s in place, |Z|^2 (Z conj Z') summed in %d float32 registers per thread, the pair symmetrised once by fastw_finish; lds=%zuB; "
+               "fastw_kernel: 115 VGPRs, no scratch, 4 waves per SIMD (two fields: 164 VGPRs, 3 waves); 4 algorithmic bytes per sample of the series through memory\n",
+            (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, (long long)d.nx, (long long)d.seg_hop, plan->w_pitch, kWThreads, 2 * g.seqs, g.seqs,
+            seg_radices(plan).c_str(), kWAcc * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1), g.lds);
+    describe_cols(plan, s, "pairs of segments", "pair", (std::string("the float64 sums per column; fastw_kernel<cols>: ") + kWColsResources).c_str());
+}
+static void info_fastw(const xrfthip_plan* plan, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTW; *n = 2 * plan->w.seqs; }  // (per_workgroup: the segments of a round)
+static void info_fastk(const xrfthip_plan* plan, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTW; *n = plan->w.seqs; }
+// (the entries in the order of struct FamilyOps; reads_strided is false -- the series pitch is w_pitch, d.in_stride_batch is 0 -- and the last entry, no_generic_passes, true)
+#ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
+const FamilyOps kOpsFastW = {Family::FastW, run_fastw, describe_fastw, info_fastw, fast_phase_tables, layout_fastw, nullptr, nullptr, false, nullptr, false, false, false, false, true};
+const FamilyOps kOpsFastK = {Family::FastK, run_fastk, describe_fastk, info_fastk, fast_phase_tables, layout_fastk, nullptr, nullptr, false, nullptr, false, false, false, false, true};
+#endif
+
+// kernels of this unit that take more than 64 KB of dynamic LDS (two tiles of 4096 points and their padding): called once through set_kernel_attrs_once()
+void set_attrs_welch() {
+    const int m = (int)kLdsMax;
+#define SETF(K) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, m)
+    SETF((fastw_kernel<false>)); SETF((fastw_kernel<true>)); SETF((fastw_kernel<false, true>)); SETF((fastw_kernel<true, true>));
+    SETF((fastk_kernel<true, false>)); SETF((fastk_kernel<false, false>)); SETF((fastk_kernel<true, true>)); SETF((fastk_kernel<false, true>));
+#undef SETF
+}

@@ -15,8 +15,10 @@
 //                    the last pass of a three-axis spectrum (fasth.h)
 //                    (FastG, FastGY, FastH)
 //   host_rows.cpp    the register-resident one-pass kernels: small float32 slabs (fasts.h), long rows and complex rows (fastr.h)
-//                    and Welch spectra, overlapping segments of a series averaged in one pass (fastw.h), or every segment's spectrum kept (fastk.h)
-//                    (FastS, FastR and its Welch forms, FastRComplex, FastRRows)
+//                    (FastS, FastR, FastRComplex, FastRRows)
+//   host_welch.inc   ... and, included at its end (one translation unit), the segments of a series in an LDS tile: Welch spectra, averaged in one pass
+//                    (fastw.h), or every segment's spectrum kept (fastk.h); the descriptor checks of xrfthip_desc.seg_*
+//                    (FastW, FastK)
 //   host_inner.cpp   two transform axes that are not the trailing pair (xrfthip_desc.inner / .mid): the fused passes and the composite plan
 //                    (FusedInner, Composite)
 //   ops.cpp          the stand-alone operations of the ABI (detrend, spectrum tail, gather, convert, reduce, isotropize, ...)
@@ -337,9 +339,11 @@ enum class Family {
     FastGY,          // one pass along one axis that is not the contiguous one, or along rows with one Rader prime (gy_rows) (fastg.h)
     FastMX,          // short rows, table lengths (fastm.h, fastm_xonly_kernel)
     FastMY,          // one axis that is not the contiguous one, table lengths (fastm.h, fastm_yonly_kernel)
-    FastR,           // one pass over a long real float32 row in registers (fastr.h); its Welch form (xrfthip_plan::w_on: xrfthip_desc.seg_hop, fastw.h) walks the overlapping segments of a series
+    FastR,           // one pass over a long real float32 row in registers (fastr.h)
     FastRComplex,    // ... complex rows of 2048 .. 16384 points (fastc_kernel)
     FastRRows,       // complex rows of 256 .. 4096 points: the row pass of fasty_c2c.h on the input's own rows
+    FastW,           // xrfthip_desc.seg_hop, Welch spectra: the mean spectrum of the overlapping segments of a series, rows or column layout (fastw.h)
+    FastK,           // ... with xrfthip_desc.seg_keep, spectrograms: every segment's spectrum kept (fastk.h)
     FastYC,          // the two passes of fasty_c2c.h over complex float32 slabs
     FastYCFourStep,  // ... over ONE long complex sequence per batch entry, the four-step form of pass 2
     FastY,           // the two y-first passes over real float32 slabs of powers of two (fasty.h)
@@ -353,6 +357,16 @@ constexpr int kDeclined = 1;  // a try_* that does not take the descriptor (XRFT
 
 }  // namespace xrfth
 using namespace xrfth;
+
+// FastW / FastK: the LDS tile of a workgroup (host_welch.inc).  Sequence t of the tile is (column t % C, pair of segments | segment t / C)
+struct SegGeom {
+    int C = 1, lgC = 0;      // the column layout (xrfthip_desc.seg_stride): adjacent columns per workgroup and their log2; 1: the rows layout
+    long long ngroups = 1;   // ... groups of C columns per block
+    int seqs = 1;            // sequences of the tile: FastW pairs of segments (of L points), FastK segments (of L / 2 points)
+    int stride = 0;          // points between sequences: padded, odd
+    size_t lds = 0;          // dynamic LDS of the launch
+    long long rounds = 1;    // FastK only: rounds per series (group of columns), one workgroup each (FastW walks its runs inside the workgroup: 1)
+};
 
 struct xrfthip_plan {
     xrfthip_desc d{};
@@ -476,16 +490,10 @@ struct xrfthip_plan {
     // XRFTHIP_OUT_COHERENCE: the descriptor says OUT_CROSS from xrfthip_plan_create on -- every check, table, family and the column pass are the CROSS mean plan's -- and
     // this remembers what the row pass sums (fasty_rows_mean_kernel<NX, 3>: re C, im C, A, B per sample) and what mean_finish writes (|C|^2 / (A B), real)
     bool coherence = false;
-    // FastR's Welch form (xrfthip_desc.seg_hop): samples between series (the descriptor's in_stride_batch, or the dense span; d.in_stride_batch is 0 from xrfthip_plan_create on),
-    // the pairs of segments one workgroup transforms per round and its tile
+    // FastW / FastK (xrfthip_desc.seg_hop): samples between series (the descriptor's in_stride_batch, or the dense span; d.in_stride_batch is 0 from xrfthip_plan_create on),
+    // the tile of a workgroup (the family's layout entry), and FastK's W_L^k of the unpacking
     long long w_pitch = 0;
-    bool w_on = false;  // the plan is FastR's Welch form (try_fastw took it): launcher, describe text, kernel kind (XRFTHIP_K_FASTW) and layout are that form's
-    int w_G = 1, w_stride = 0;
-    int w_C = 1;  // the column layout (xrfthip_desc.seg_stride): adjacent columns per workgroup; sequence t of the tile is (column t % w_C, pair t / w_C); 1: the rows layout
-    size_t w_lds = 0;
-    // ... its "segments kept" form (xrfthip_desc.seg_keep, fastk.h): w_G segments (sequences of L / 2 points) per round, w_rounds rounds per series (group of columns),
-    // W_L^k of the unpacking; no workspace
-    int w_rounds = 1;
+    SegGeom w;
     DevBuf w_twr;
     ~xrfthip_plan() { for (auto* b : extra) delete b; prof_clear(); delete sub_x; delete sub_y; }
 };
@@ -515,9 +523,10 @@ struct FamilyOps {
     bool two_pass_y = false;                                               // columns -> [fit] -> rows: the y-first intermediate, per-column sums and corrections
     bool fastm_pipeline = false;                                           // ... of fastm.h / fastn.h
     bool inner_layout = false;                                             // xrfthip_desc.inner / .mid: a header and a workspace of their own, no tile passes
+    bool no_generic_passes = false;                                        // the family serves every plan it takes: no tile passes are built behind it
 };
 const FamilyOps& family_ops(Family f);
-extern const FamilyOps kOpsComposite, kOpsFusedInner, kOpsFastS, kOpsFastG, kOpsFastGY, kOpsFastMX, kOpsFastMY, kOpsFastR, kOpsFastRComplex, kOpsFastRRows, kOpsFastYC,
+extern const FamilyOps kOpsComposite, kOpsFusedInner, kOpsFastS, kOpsFastG, kOpsFastGY, kOpsFastMX, kOpsFastMY, kOpsFastR, kOpsFastRComplex, kOpsFastRRows, kOpsFastW, kOpsFastK, kOpsFastYC,
     kOpsFastYCFourStep, kOpsFastY, kOpsFastY1D, kOpsFastM, kOpsFastN, kOpsFastH;
 
 // ---- host functions more than one translation unit of the library calls (xrft_hip.cpp, host_*.cpp, ops.cpp)
@@ -566,6 +575,9 @@ void set_attrs_fasty();
 void set_attrs_fastm();
 void set_attrs_fastg();
 void set_attrs_rows();
+void set_attrs_welch();
+// host_welch.inc: the checks of xrfthip_desc.seg_* (xrfthip_plan_create, on its copy of the descriptor); *pitch: samples between series
+int seg_desc_check(xrfthip_desc& d, long long* pitch);
 
 // the families' try_* (xrfthip_plan_create calls them in this order; the first that does not return kDeclined decides)
 int try_fastw(xrfthip_plan* P);
@@ -595,12 +607,12 @@ inline bool herm_field_plan(const xrfthip_plan* P) { return P && P->d.herm_ny > 
 // The mean over the batch inside the last pass (xrfthip_desc.mean_batch, normalised by xrfthip_plan_create: 0 = off, else M > 1): the families with a mean form are
 // FastY's two-pass slabs and FastS below 256 points per axis with dense float32 input; every other family answers XRFTHIP_UNSUPPORTED_LENGTH (the caller composes).
 inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1 && !P->d.seg_keep; }  // (seg_keep: mean_batch counts the segments of a series, every spectrum kept)
-inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || (P->family == Family::FastS && !P->coherence) || (P->family == Family::FastR && P->w_on); }  // (FastS has no two-field form)
+inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || (P->family == Family::FastS && !P->coherence) || P->family == Family::FastW; }  // (FastS has no two-field form)
 size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs);  // (xrft_hip.cpp: mean_P and the partials behind `off`; returns the new end)
 int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStream_t st);  // (... and the finishing kernel, after the last group)
 inline bool welch_cols(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_stride > 0; }  // (... along a leading axis: d.inner adjacent series, samples d.seg_stride apart; S = 1 was normalised to 0, the rows layout)
-inline bool welch_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0; }  // (the descriptor asks for the mean over overlapping segments: served by FastR's Welch form or not at all)
-inline bool keep_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_keep == 1; }  // (... every segment's spectrum kept, none averaged: the "segments kept" form, fastk.h)
+inline bool welch_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0; }  // (the descriptor asks for the segments of a series: served by FastW / FastK or not at all)
+inline bool keep_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_keep == 1; }  // (... every segment's spectrum kept, none averaged: Family::FastK, fastk.h)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's
 // input take them: pass 1 of the two-pass families, the load of the one-pass families.  The intermediate and the output are dense.

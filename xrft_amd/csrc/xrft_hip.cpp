@@ -458,6 +458,7 @@ void set_kernel_attrs_once() {
     set_attrs_fastm();
     set_attrs_fastg();
     set_attrs_rows();
+    set_attrs_welch();
 }
 
 template <typename T>
@@ -859,7 +860,7 @@ static const FamilyOps kOpsGeneric = {Family::Generic, run_generic, nullptr, gen
 const FamilyOps& family_ops(Family f) {
     static const FamilyOps* const kRows[] = {  // in the order of enum class Family
         &kOpsGeneric, &kOpsComposite, &kOpsFusedInner, &kOpsFastS, &kOpsFastG, &kOpsFastGY, &kOpsFastMX, &kOpsFastMY, &kOpsFastR, &kOpsFastRComplex, &kOpsFastRRows,
-        &kOpsFastYC, &kOpsFastYCFourStep, &kOpsFastY, &kOpsFastY1D, &kOpsFastM, &kOpsFastN, &kOpsFastH};
+        &kOpsFastW, &kOpsFastK, &kOpsFastYC, &kOpsFastYCFourStep, &kOpsFastY, &kOpsFastY1D, &kOpsFastM, &kOpsFastN, &kOpsFastH};
     static_assert(sizeof kRows / sizeof kRows[0] == kFamilyCount, "one row of FamilyOps per Family");
     return *kRows[(int)f];
 }
@@ -891,13 +892,13 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // (a descriptor of the version before `inner` was appended is accepted: inner = 1)
     // (... and of the versions before `mid` and before the input strides: mid = 1, strides 0)
     // (... and of the version before herm_ny / herm_nx: 0, 0)
-    constexpr uint32_t kOldDescSize = (uint32_t)offsetof(xrfthip_desc, inner), kOldDescSize2 = (uint32_t)offsetof(xrfthip_desc, mid), kOldDescSize3 = (uint32_t)offsetof(xrfthip_desc, in_stride_y),
-                       kOldDescSize4 = (uint32_t)offsetof(xrfthip_desc, herm_ny), kOldDescSize5 = (uint32_t)offsetof(xrfthip_desc, mean_batch),  // (... and before mean_batch: 0)
-                       kOldDescSize6 = (uint32_t)offsetof(xrfthip_desc, seg_hop),  // (... and before seg_hop / seg_reserved: 0, 0 -- the two came together, no size between)
-                       kOldDescSize7 = (uint32_t)offsetof(xrfthip_desc, seg_stride),  // (... and before seg_stride / seg_reserved2: likewise)
-                       kOldDescSize8 = (uint32_t)offsetof(xrfthip_desc, seg_keep);  // (... and before seg_keep / seg_reserved3: likewise)
-    if (!plan || !desc || (desc->struct_size != sizeof(xrfthip_desc) && desc->struct_size != kOldDescSize && desc->struct_size != kOldDescSize2 && desc->struct_size != kOldDescSize3 &&
-                           desc->struct_size != kOldDescSize4 && desc->struct_size != kOldDescSize5 && desc->struct_size != kOldDescSize6 && desc->struct_size != kOldDescSize7 && desc->struct_size != kOldDescSize8)) return XRFTHIP_BAD_ARG;
+    // (... and before each later group of fields, which then read 0: mean_batch; seg_hop / seg_reserved; seg_stride / seg_reserved2; seg_keep / seg_reserved3 -- each pair
+    // came together, no size between)
+    static const uint32_t kDescSizes[] = {
+        (uint32_t)sizeof(xrfthip_desc), (uint32_t)offsetof(xrfthip_desc, inner), (uint32_t)offsetof(xrfthip_desc, mid), (uint32_t)offsetof(xrfthip_desc, in_stride_y),
+        (uint32_t)offsetof(xrfthip_desc, herm_ny), (uint32_t)offsetof(xrfthip_desc, mean_batch), (uint32_t)offsetof(xrfthip_desc, seg_hop), (uint32_t)offsetof(xrfthip_desc, seg_stride),
+        (uint32_t)offsetof(xrfthip_desc, seg_keep)};
+    if (!plan || !desc || std::find(std::begin(kDescSizes), std::end(kDescSizes), desc->struct_size) == std::end(kDescSizes)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);
     dcopy.struct_size = sizeof(xrfthip_desc);
@@ -906,35 +907,11 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (dcopy.mid == 0) dcopy.mid = 1;
     if (dcopy.in_stride_y < 0 || dcopy.in_stride_batch < 0) return XRFTHIP_BAD_ARG;
     if (dcopy.mean_batch < 0) return XRFTHIP_BAD_ARG;
-    // seg_keep = 1 (with seg_hop): every segment's spectrum kept (fastk.h).  mean_batch is the segments per series there, 1 included, and nothing is averaged
-    if ((dcopy.seg_keep != 0 && dcopy.seg_keep != 1) || dcopy.seg_reserved3 != 0 || (dcopy.seg_keep && dcopy.seg_hop <= 0)) return XRFTHIP_BAD_ARG;
+    // seg_hop / seg_stride / seg_keep: the segments of a series (host_welch.inc).  With seg_keep, mean_batch is the segments per series, 1 included, and nothing is averaged
+    long long w_pitch = 0;
+    if (seg_desc_check(dcopy, &w_pitch)) return XRFTHIP_BAD_ARG;
     const bool keep = dcopy.seg_keep == 1;
     if (dcopy.mean_batch == 1 && !keep) dcopy.mean_batch = 0;  // (the plain plan itself)
-    // seg_hop = H >= 1: Welch spectra (fastw.h).  in_stride_batch is the series pitch here (any multiple of 4 bytes: the kernel loads single samples); it is checked,
-    // remembered as w_pitch and cleared, so that nothing of the strided-view rules (16-byte strides and pointers) applies to such a plan
-    // seg_stride = S >= 1 (with seg_hop): the column layout of the same form -- `inner` adjacent series whose samples lie S elements apart, blocks in_stride_batch apart.
-    // S = 1 (inner = 1) says what the rows form says: normalised to it, the same plan
-    if (dcopy.seg_hop < 0 || dcopy.seg_reserved != 0 || dcopy.seg_stride < 0 || dcopy.seg_reserved2 != 0) return XRFTHIP_BAD_ARG;
-    if (dcopy.seg_stride > 0 && (dcopy.seg_hop == 0 || dcopy.seg_stride < dcopy.inner)) return XRFTHIP_BAD_ARG;
-    if (dcopy.seg_stride == 1) dcopy.seg_stride = 0;
-    long long w_pitch = 0;
-    if (dcopy.seg_hop > 0) {
-        const xrfthip_desc& s = dcopy;
-        if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.seg_hop > s.nx || (s.flags & (XRFTHIP_AXIS_Y | XRFTHIP_ISO)) || (s.inner > 1 && !s.seg_stride) || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y) return XRFTHIP_BAD_ARG;
-        if (s.mean_batch < (keep ? 1 : 2) || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
-        if (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != (keep ? XRFTHIP_OUT_COMPLEX : XRFTHIP_OUT_CROSS)) return XRFTHIP_BAD_ARG;
-        if (s.nx > (1LL << 30) || s.mean_batch > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;
-        const long long span = (s.mean_batch - 1) * s.seg_hop + s.nx;
-        if (s.seg_stride) {  // (the offsets stay far inside 64 bits: span < 2^62, S and inner below 2^31)
-            if (s.seg_stride > (1LL << 31) - 1 || s.inner > (1LL << 31) - 1 || span > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;
-            if (s.in_stride_batch != 0 && s.in_stride_batch < (span - 1) * s.seg_stride + s.inner) return XRFTHIP_BAD_ARG;
-            w_pitch = s.in_stride_batch ? s.in_stride_batch : span * s.seg_stride;
-        } else {
-            if (s.in_stride_batch != 0 && s.in_stride_batch < span) return XRFTHIP_BAD_ARG;
-            w_pitch = s.in_stride_batch ? s.in_stride_batch : span;
-        }
-        dcopy.in_stride_batch = 0;
-    }
     {   // strides that say what a dense array says are the dense plan (any family serves it)
         const int64_t row = (dcopy.flags & XRFTHIP_C2R_X) ? dcopy.nx / 2 + 1 : dcopy.nx;
         if (dcopy.in_stride_y > 0 && dcopy.in_stride_y < row) return XRFTHIP_BAD_ARG;
@@ -1045,7 +1022,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
             if ((rc = try_family(P)) != kDeclined) break;
     if (rc == kDeclined) rc = XRFTHIP_OK;
     if (!rc && herm && P->family != Family::FastH) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family reads a half spectrum as columns: the caller composes the stages)
-    if (!rc && d.seg_hop && !P->w_on) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family cuts segments out of a series: the caller composes)
+    if (!rc && d.seg_hop && P->family != Family::FastW && P->family != Family::FastK) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family cuts segments out of a series: the caller composes)
     const bool one_axis = P->family == Family::FastGY || P->family == Family::FastMY;
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_PHASE_IN) && !one_axis) rc = XRFTHIP_BAD_ARG;  // (the generic column tiles have no input phase)
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_HALF_X) && !one_axis) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (... and no half output: the caller transposes)
@@ -1053,7 +1030,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
         set_kernel_attrs_once();
         // nbins must be known before tiles are sized (the LDS histogram shares the tile's allocation): ISO plans are
         // (re)built in xrfthip_plan_set_binmap.  Build now for everything else.
-        if (!(d.flags & XRFTHIP_ISO) && P->family != Family::FastH && !P->w_on) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
+        if (!(d.flags & XRFTHIP_ISO) && !family_ops(P->family).no_generic_passes) rc = P->dbl ? build_plan_t<double>(*P) : build_plan_t<float>(*P);
     }
     if (!rc) rc = finalize_plan(P);
     if (rc) { delete P; return rc; }
@@ -1266,7 +1243,7 @@ int xrfthip_exec_ex(const xrfthip_plan* plan, const xrfthip_exec_args* args) {
     if (!d_out && !(d.flags & XRFTHIP_NO_SPECTRUM_OUT)) return XRFTHIP_BAD_ARG;
     if (iso && (!d_iso || !P->binmap.p)) return d_iso ? XRFTHIP_MISSING_TABLE : XRFTHIP_BAD_ARG;
     const bool inner = inner_layout(P);  // (always a workspace)
-    if (!inner && P->family != Family::FastH && !P->w_on && P->passes.empty()) return XRFTHIP_MISSING_TABLE;  // (the generic passes stand behind every other family)
+    if (!inner && !family_ops(P->family).no_generic_passes && P->passes.empty()) return XRFTHIP_MISSING_TABLE;  // (the generic passes stand behind every other family)
     // pass-1 blocks: the fields of a plan that hands them over (fasty_pass1_bytes), whole, aligned, apart from each other and from the workspace
     ExecArgs a{d_in0, d_in1, nullptr, (double*)d_iso, (char*)d_workspace, (hipStream_t)args->stream};
     const int nf = cross ? 2 : 1;
