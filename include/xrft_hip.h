@@ -315,6 +315,32 @@ typedef struct xrfthip_desc {
      * struct_size of the eight earlier versions are accepted (0, 0); an older library answers XRFTHIP_BAD_ARG to the larger struct_size. */
     int64_t seg_keep;
     int64_t seg_reserved3; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_keep: no struct_size between the two */
+    /* Synthesis: the inverse of what seg_keep with COMPLEX and XRFTHIP_HALF_X writes -- a series rebuilt from the half spectra of its M overlapping segments in ONE pass
+     * (scipy.signal.istft): every segment inverse-transformed, multiplied by the window, overlap-added at s * H and divided by the sum of the squared windows.  The
+     * inverse-transformed segments (twice the series at half overlap) never reach memory.
+     *   seg_synth = 1   Valid with seg_hop = H, 1 <= H <= L; ndim = 1, ny = 1, nx = L; dtype XRFTHIP_C64, out_mode XRFTHIP_OUT_COMPLEX, detrend NONE; flags exactly
+     *                   XRFTHIP_INVERSE | XRFTHIP_C2R_X; mean_batch = M >= 1 the segments per series, batch = P * M; seg_keep = 0, seg_stride = 0, inner <= 1.
+     *                   d_in0 is [P][M][L / 2 + 1] complex64, bin k of segment s of series p at d_in0[p * in_stride_batch + s * (L / 2 + 1) + k]: in_stride_batch is
+     *                   HERE the pitch between series in complex elements, 0 = dense, M * (L / 2 + 1).  d_out is [P][span] float32, dense, span = (M - 1) * H + L:
+     *                     out[p][n] = num / den  where den > 1e-10, else num (scipy's rule: the first sample under a periodic Hann window),
+     *                     num = sum_s w[n - s H] x_s[n - s H] scale,  den = sum_s w^2[n - s H],  over the segments s that cover n, in ascending s, float32,
+     *                   x_s the unnormalised inverse real transform of segment s (the caller folds 1 / L into `scale`, as for every XRFTHIP_INVERSE plan) and w the
+     *                   window on axis 1 (xrfthip_plan_set_window, L values; none: ones).  The imaginary parts of bins 0 and L / 2 are ignored, as the other C2R_X
+     *                   plans and numpy.fft.irfft ignore them.
+     *                   0 = off: everything about the descriptor is as without the field (seg_hop with XRFTHIP_INVERSE stays XRFTHIP_BAD_ARG).
+     * Alignment: d_in0 8-byte aligned, d_out 4-byte aligned.  No byte outside the addressed input is read; every output sample is written exactly once, by one thread:
+     * no atomics, no partial sums, no workspace (xrfthip_workspace_bytes is 0), and a sample's bits depend on its own covering segments only -- not on P, on M or on
+     * the workgroups.  A non-finite bin makes exactly the samples of its own segment non-finite.
+     * XRFTHIP_BAD_ARG: seg_synth not 0 | 1, seg_synth without seg_hop or with seg_keep, seg_reserved4 != 0, any other out_mode, dtype, detrend or flag (XRFTHIP_ISO
+     * included), a phase table (xrfthip_plan_set_phase), a pitch below M * (L / 2 + 1), and everything seg_hop refuses.  XRFTHIP_UNSUPPORTED_LENGTH ("the caller
+     * composes or arranges"): L not a power of two in 64 .. 4096; seg_stride > 0 (a column layout of the synthesis does not exist); 2 (R - 1) > NS with
+     * R = ceil(L / H) the segments that meet in a sample and NS = 8192 / L the segments of a workgroup's tile (a workgroup transforms again the last R - 1 segments
+     * of its predecessor: at most half its work); span >= 2^31; a launch beyond 2^31 - 1 workgroups; XRFTHIP_FASTW=0 or XRFTHIP_FASTW_SYNTH=0 in the environment
+     * when the plan is created (docs/TUNING.md).
+     * Still XRFTHIP_K_FASTW: a fourth form of the same family (xrfthip_plan_describe prints a [fastw overlap-add] line).  Descriptors with the struct_size of the nine
+     * earlier versions are accepted (0, 0); an older library answers XRFTHIP_BAD_ARG to the larger struct_size.  Offsets are computed in 64 bits. */
+    int64_t seg_synth;
+    int64_t seg_reserved4; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_synth: no struct_size between the two */
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;

@@ -84,10 +84,18 @@ class DescCols(C.Structure):
 
 
 class DescKeep(C.Structure):
-    """xrfthip_desc as the library has it now: ``DescCols`` and the two words appended together after it."""
+    """``DescCols`` and the two words appended together after it; still accepted under its own struct_size."""
     _fields_ = DescCols._fields_ + [
         ("seg_keep", C.c_int64),  # 1 (with seg_hop): every segment's spectrum kept, POWER | COMPLEX -- [series][M][nx_out] out ([blocks][M][nx_out][inner] with seg_stride); 0: off
         ("seg_reserved3", C.c_int64),  # 0
+    ]
+
+
+class DescSynth(C.Structure):
+    """xrfthip_desc as the library has it now: ``DescKeep`` and the two words appended together after it."""
+    _fields_ = DescKeep._fields_ + [
+        ("seg_synth", C.c_int64),  # 1 (with seg_hop, C64, INVERSE | C2R_X): the series rebuilt from its segments' half spectra -- [series][M][nx / 2 + 1] in, [series][(M - 1) hop + nx] real out; 0: off
+        ("seg_reserved4", C.c_int64),  # 0
     ]
 
 
@@ -108,7 +116,7 @@ def _bind(dll):
     dll.xrfthip_strerror.restype = C.c_char_p
     dll.xrfthip_strerror.argtypes = [C.c_int]
     dll.xrfthip_last_hip_error.restype = C.c_int
-    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg, a DescCols or a DescKeep, by reference)
+    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg, a DescCols, a DescKeep or a DescSynth, by reference)
     dll.xrfthip_plan_destroy.argtypes = [vp]
     dll.xrfthip_plan_set_window.argtypes = [vp, C.c_int, vp, i64]
     dll.xrfthip_plan_set_phase.argtypes = [vp, C.c_int, vp, i64]

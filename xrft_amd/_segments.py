@@ -1,5 +1,5 @@
 """The segment surface of the call API: Welch spectra (welch_power_spectrum, welch_cross_spectrum, welch_coherence) and spectrograms (spectrogram, stft) -- the spectra
-of the overlapping segments of a series, averaged or kept.  Fused where a segment plan takes the call (xrfthip_desc.seg_hop: csrc/fastw.h, fastk.h), else composed from
+of the overlapping segments of a series, averaged or kept -- and the synthesis that rebuilds the series from the kept ones (istft).  Fused where a segment plan takes the call (xrfthip_desc.seg_hop: csrc/fastw.h, fastk.h), else composed from
 the calls of api.py on the unfolded segments.  api.py re-exports the public names.
 
 This module sits ON TOP of api.py and is imported by it, behind the definitions it uses (`_api.` below: resolved at call time; the two tuning constants
@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from . import api as _api  # (the calls the composed paths and the analysis of ONE segment go through; api.py imports this module behind them)
-from ._hostside import _analyze, _direct_lag_attrs, _flags_tables, _label_output, _to_device
+from ._hostside import _analyze, _direct_lag_attrs, _flags_tables, _get_coordinate_spacing, _label_output, _to_device
 from ._plans import _MEAN_REFUSED, _rung
 from .labeled import Coordinate, DataArray, from_any, to_like
 
@@ -365,3 +365,139 @@ def stft(da, dim, nperseg, noverlap=None, real_dim=None, detrend=None, window=No
         return c, _lib.OUT_COMPLEX, (math.prod(c.delta_x) if true_amplitude else 1.0), 0
 
     return to_like(_spectrogram(da, dim, nperseg, noverlap, True, analyse, kw), src)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Synthesis: the series rebuilt from its short-time transform (scipy.signal.istft) -- the inverse of ``stft``.  Fused where a plan takes the call
+# (xrfthip_desc.seg_synth, csrc/fasto.h: inverse transform, window, overlap-add and the division in one pass, no inverse-transformed segment stored), else composed:
+# ``ifft`` of every segment, the window, R strided adds, the division.
+# ------------------------------------------------------------------------------------------------------
+def _istft_args(ds, dim, nperseg, noverlap, real_dim):
+    """(axis of <dim>_segment, nperseg, hop, segments) after the checks."""
+    if not isinstance(dim, str):
+        raise ValueError(f"dim must be the name of ONE dimension (the axis the series is rebuilt along), not {dim!r}")
+    sname, fname = dim + "_segment", "freq_" + dim
+    if sname not in ds.dims or fname not in ds.dims:
+        raise ValueError(f"the short-time transform along {dim!r} has the dimensions {sname!r} and {fname!r}: {tuple(ds.dims)} lacks one of them")
+    ax = ds.get_axis_num(sname)
+    if ds.get_axis_num(fname) != ax + 1:
+        raise ValueError(f"{sname!r} and {fname!r} must be adjacent, in this order (as stft returns them), not {tuple(ds.dims)}")
+    if real_dim is not None and real_dim != dim:
+        raise ValueError(f"real_dim must be {dim!r}, the one transform dimension, or None")
+    nf = ds.sizes[fname]
+    implied = 2 * (nf - 1) if real_dim is not None else nf
+    nperseg = implied if nperseg is None else int(nperseg)
+    if nperseg != implied or nperseg < 1:
+        raise ValueError(f"nperseg = {nperseg} disagrees with the length of {fname!r}: {nf} frequencies are those of {implied} samples")
+    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
+    if noverlap < 0 or noverlap >= nperseg:
+        raise ValueError(f"noverlap = {noverlap} must be in 0 .. nperseg - 1 = {nperseg - 1}")
+    return ax, nperseg, nperseg - noverlap, ds.sizes[sname]
+
+
+def _istft_envelope(w, hop, m):
+    """D[n] = sum_s w^2[n - s hop] over the span of ``m`` segments, float64, with 1 where D <= 1e-10 (scipy.signal.istft's rule: such samples stay undivided)."""
+    nperseg = len(w)
+    d = np.zeros((m - 1) * hop + nperseg)
+    w2 = np.asarray(w, dtype=np.float64) ** 2
+    r = -(-nperseg // hop)
+    for q in range(min(r, m)):  # (the segments s = q mod R do not overlap one another)
+        np.lib.stride_tricks.as_strided(d[q * hop:], ((m - q + r - 1) // r, nperseg), (r * hop * 8, 8))[...] += w2
+    return np.where(d > 1e-10, d, 1.0)
+
+
+def _istft_composed(ds, ax, fname, nperseg, hop, m, w, real, kw):
+    """The definition of the result, values only, the series last: ``ifft`` along freq_<dim> of every segment (true_phase=False; ``shift=True``: of the reference's two
+    output shifts the one of true_phase=False and the one of shift cancel, the samples come out in their order, whatever the layout of the frequency axis), times the
+    window, overlap-added at s hop -- the segments s = q mod R, R = ceil(nperseg / hop), do not overlap one another: R strided adds in ascending q, no index_add_, no
+    atomics -- and divided by the summed squared windows."""
+    import warnings
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        x = from_any(_api.ifft(ds, dim=[fname], real_dim=fname if real else None, shift=True, true_phase=False, lag=[0.0], **kw))
+    v = _to_device(x.data).movedim((ax, ax + 1), (-2, -1))
+    rdt = v.real.dtype if v.is_complex() else v.dtype
+    if w is not None:
+        v = v * torch.tensor(np.asarray(w, dtype=np.float64), dtype=rdt, device=v.device)
+    span = (m - 1) * hop + nperseg
+    out = torch.zeros(tuple(v.shape[:-2]) + (span,), dtype=v.dtype, device=v.device)
+    r = -(-nperseg // hop)
+    for q in range(min(r, m)):
+        mq = (m - q + r - 1) // r
+        dst = torch.as_strided(out, tuple(out.shape[:-1]) + (mq, nperseg), tuple(out.stride()[:-1]) + (r * hop, 1), q * hop)
+        dst += v[..., q::r, :]
+    out /= torch.from_numpy(_istft_envelope(np.ones(nperseg) if w is None else w, hop, m)).to(rdt).to(v.device)
+    return out
+
+
+def _istft_fused(t, ax, nperseg, hop, m, w, scale):
+    """The values of ONE plan with seg_synth, the series last, or None where the call composes: spectra that are not complex64, an empty array, a length or an overlap
+    the plan declines (XRFTHIP_UNSUPPORTED_LENGTH, remembered), XRFTHIP_FASTW_SYNTH=0.  The pair (<dim>_segment, freq_<dim>) is read where it lies as the trailing
+    axes with one pitch between the series; elsewhere the spectrogram is arranged first (one transposed copy)."""
+    if t.dtype != torch.complex64 or math.prod(t.shape) == 0 or os.environ.get("XRFTHIP_FASTW_SYNTH", "1") == "0":  # (the knob of the library, honoured before a cached plan could answer)
+        return None
+    nb = nperseg // 2 + 1
+    v = t if ax == t.dim() - 2 else t.movedim((ax, ax + 1), (-2, -1))
+    lead = _collapse(v.shape[:-2], v.stride()[:-2])
+    if v.stride(-1) == 1 and (m == 1 or v.stride(-2) == nb) and lead is not None and (lead[0] == 1 or lead[1] >= m * nb):
+        rows = torch.as_strided(v, (lead[0], m, nb), (lead[1] if lead[0] > 1 else m * nb, nb, 1), v.storage_offset())
+        pitch = lead[1] if lead[0] > 1 else 0
+    else:
+        rows, pitch = v.contiguous().reshape(-1, m, nb), 0
+    kw = dict(ndim=1, ny=1, nx=nperseg, dtype=torch.complex64, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=_lib.INVERSE | _lib.C2R_X, scale=float(scale),
+              window_x=w, mean_batch=m, seg_hop=hop, seg_synth=1, batch=rows.shape[0] * m, in_stride_batch=int(pitch))
+    plan = _segment_plan(kw, {})
+    if plan is None:
+        return None
+    return plan.execute(rows)[0].reshape(tuple(v.shape[:-2]) + ((m - 1) * hop + nperseg,))
+
+
+def istft(ds, dim, nperseg=None, noverlap=None, real_dim=None, window=None, shift=True, true_amplitude=False, spacing_tol=1e-3):
+    """The inverse short-time Fourier transform: the series along ``dim`` rebuilt from ``ds = stft(da, dim, nperseg, noverlap, real_dim=..., window=..., shift=...,
+    true_amplitude=...)``, whose dims are those of ``da`` with ``dim`` replaced by ``(<dim>_segment, freq_<dim>)`` (adjacent, in this order).  Every segment's spectrum
+    goes through ``ifft`` along ``freq_<dim>`` (``true_phase=False``: the inverse of what ``stft`` applied per segment), is multiplied by the window
+    (``scipy.signal.windows.<window>(nperseg, sym=False)``, the one of the analysis; None: ones), the segments are overlap-added at ``s * hop`` and the sum is divided
+    by ``D[n] = sum_s w^2[n - s hop]`` -- where ``D[n] <= 1e-10`` (the first sample under a periodic Hann window) the sum is returned undivided, the rule of
+    ``scipy.signal.istft``.  ``nperseg=None``: the length of ``freq_<dim>`` (``2 (len - 1)`` with ``real_dim=dim``); ``noverlap=None``: ``nperseg // 2``, the default
+    of ``stft``.  ``shift`` says how ``stft`` laid ``freq_<dim>`` out; the coordinate itself tells the order, and either layout gives the same series.
+    The result has ``dim`` back where ``<dim>_segment`` lay, ``(M - 1) hop + nperseg`` samples long (what ``stft`` dropped at the end cannot come back); real with
+    ``real_dim=dim``, complex otherwise, as ``ifft``.  Its coordinate is ``t0 + dt arange(span)``, ``dt = 1 / (nperseg df)`` with ``df`` the spacing of ``freq_<dim>``
+    (checked with ``spacing_tol``), ``t0 = segment[0] - (nperseg - 1) dt / 2`` where ``<dim>_segment`` carries a numeric coordinate (the middle of the first segment's
+    samples), else 0; coordinates that do not depend on the two replaced dims are kept; no name, no attrs, as ``ifft``.
+    There is no ``detrend`` argument: a per-segment detrend cannot be undone, and ``istft(stft(..., detrend=...))`` returns the overlap-added DETRENDED segments.
+    complex64 half spectra (``real_dim=dim``) whose ``nperseg`` is a power of two in 64 .. 4096 with ``2 (ceil(nperseg / hop) - 1) <= 8192 / nperseg`` are rebuilt by
+    ONE pass (xrfthip_desc.seg_synth): no inverse-transformed segment reaches memory.  The pair of dims is read where it lies as the trailing axes; elsewhere the
+    spectrogram is arranged first (one transposed copy) and the result moved back as a view.  Every other call -- complex128, a two-sided spectrum, other lengths and
+    overlaps, XRFTHIP_FASTW_SYNTH=0 -- composes the definition above."""
+    src = ds
+    ds = from_any(ds)
+    ax, nperseg, hop, m = _istft_args(ds, dim, nperseg, noverlap, real_dim)
+    sname, fname = dim + "_segment", "freq_" + dim
+    real = real_dim is not None
+    fv = np.asarray(ds[fname].values, dtype=np.float64) if fname in ds.coords else None
+    if fv is None:
+        raise ValueError(f"{fname!r} carries no coordinate: the spacing of {dim!r} comes from it")
+    df = float(_get_coordinate_spacing(np.sort(fv), spacing_tol, fname)) if len(fv) > 1 else 1.0
+    if real and (np.any(np.diff(fv) < 0) or abs(fv[0]) > spacing_tol):
+        raise ValueError(f"with real_dim the coordinate {fname!r} must be ascending from zero frequency (rfftfreq order)")
+    dt = 1.0 / (nperseg * df)
+    w = None if window is None else _api._window_vector(window, nperseg)
+    t = _to_device(ds.data)
+    out = None
+    if real:
+        out = _istft_fused(t if t.is_complex() else t.to(torch.complex64 if t.dtype == torch.float32 else torch.complex128), ax, nperseg, hop, m, w,
+                           (1.0 / dt if true_amplitude else 1.0) / nperseg)
+    if out is None:
+        out = _istft_composed(ds, ax, fname, nperseg, hop, m, w, real, dict(true_amplitude=true_amplitude, spacing_tol=spacing_tol))
+    span = (m - 1) * hop + nperseg
+    t0 = 0.0
+    if sname in ds.coords:
+        sv = np.asarray(ds[sname].values)
+        if sv.dtype.kind in "fiu" and len(sv):
+            t0 = float(sv[0]) - (nperseg - 1) * dt / 2
+    dims = [d for d in ds.dims if d != fname]
+    dims[ax] = dim
+    coords = {k: v for k, v in ds.coords.items() if sname not in v.dims and fname not in v.dims and k != dim}
+    coords[dim] = Coordinate((dim,), t0 + dt * np.arange(span), {"spacing": dt}, dim)
+    return to_like(DataArray(out.movedim(-1, ax), dims, coords, None, None), src)

@@ -3,13 +3,18 @@
 // The segment families (xrfthip_desc.seg_hop): the overlapping L-sample segments of a series, read where they lie, detrended, windowed and transformed in an LDS tile.
 //   FastW   Welch spectra (fastw.h): the mean power / cross spectrum of a series' segments, two segments packed per sequence (a + i b), float64 partial per run
 //   FastK   spectrograms (xrfthip_desc.seg_keep, fastk.h): every segment's spectrum kept, a segment packed with itself as a sequence of L / 2 points, no workspace
-// Both in the rows layout (one series per workgroup) or the column layout (xrfthip_desc.seg_stride: C adjacent columns of a (time, ..) block per workgroup).
+//           ... and its way back, the synthesis (xrfthip_desc.seg_synth, fasto.h; the *_fasto entries below): the series rebuilt from its segments' half spectra --
+//           inverse transform, window, overlap-add and the division by the summed squared windows in one pass, every output sample gathered by one thread; rows
+//           layout only, no workspace.  It is a form of FastK and not an enum value of its own: the segment spectra's family, both directions
+// FastW and FastK in the rows layout (one series per workgroup) or the column layout (xrfthip_desc.seg_stride: C adjacent columns of a (time, ..) block per workgroup).
 
 // xrfthip_plan_create's checks of seg_hop / seg_stride / seg_keep (XRFTHIP_BAD_ARG; what try_fastw declines is "the caller composes"), on its own copy of the descriptor: seg_stride = 1 is the rows layout and becomes it;
 // in_stride_batch is the series pitch here (any multiple of 4 bytes: the kernels load single samples) -- it is checked, returned as *pitch and cleared, so that
 // nothing of the strided-view rules (16-byte strides and pointers) applies to such a plan.  mean_batch counts the segments of a series (1 included when they are kept)
 int seg_desc_check(xrfthip_desc& s, long long* pitch) {
     *pitch = 0;
+    if ((s.seg_synth != 0 && s.seg_synth != 1) || s.seg_reserved4 != 0 || (s.seg_synth && (s.seg_hop <= 0 || s.seg_keep != 0))) return XRFTHIP_BAD_ARG;
+    const bool synth = s.seg_synth == 1;
     if ((s.seg_keep != 0 && s.seg_keep != 1) || s.seg_reserved3 != 0 || (s.seg_keep && s.seg_hop <= 0)) return XRFTHIP_BAD_ARG;
     const bool keep = s.seg_keep == 1;
     if (s.seg_hop < 0 || s.seg_reserved != 0 || s.seg_stride < 0 || s.seg_reserved2 != 0) return XRFTHIP_BAD_ARG;
@@ -17,9 +22,17 @@ int seg_desc_check(xrfthip_desc& s, long long* pitch) {
     if (s.seg_stride == 1) s.seg_stride = 0;
     if (s.seg_hop == 0) return XRFTHIP_OK;
     if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.seg_hop > s.nx || (s.flags & (XRFTHIP_AXIS_Y | XRFTHIP_ISO)) || (s.inner > 1 && !s.seg_stride) || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y) return XRFTHIP_BAD_ARG;
-    if (s.mean_batch < (keep ? 1 : 2) || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
-    if (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != (keep ? XRFTHIP_OUT_COMPLEX : XRFTHIP_OUT_CROSS)) return XRFTHIP_BAD_ARG;
+    if (s.mean_batch < (keep || synth ? 1 : 2) || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
     if (s.nx > (1LL << 30) || s.mean_batch > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;
+    if (synth) {  // half spectra in, the series out: the pitch counts complex elements, M (L / 2 + 1) of them a dense series (seg_stride: try_fastw declines)
+        if (s.dtype != XRFTHIP_C64 || s.out_mode != XRFTHIP_OUT_COMPLEX || s.detrend != XRFTHIP_DETREND_NONE || s.flags != (XRFTHIP_INVERSE | XRFTHIP_C2R_X) || (s.nx & 1)) return XRFTHIP_BAD_ARG;
+        const long long dense = s.mean_batch * (s.nx / 2 + 1);
+        if (s.in_stride_batch != 0 && s.in_stride_batch < dense) return XRFTHIP_BAD_ARG;
+        *pitch = s.in_stride_batch ? s.in_stride_batch : dense;
+        s.in_stride_batch = 0;
+        return XRFTHIP_OK;
+    }
+    if (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != (keep ? XRFTHIP_OUT_COMPLEX : XRFTHIP_OUT_CROSS)) return XRFTHIP_BAD_ARG;
     const long long span = (s.mean_batch - 1) * s.seg_hop + s.nx, S = s.seg_stride ? s.seg_stride : 1;
     // (the column layout: the offsets stay far inside 64 bits -- span < 2^62, S and inner below 2^31)
     if (s.seg_stride && (s.seg_stride > (1LL << 31) - 1 || s.inner > (1LL << 31) - 1 || span > (1LL << 31) - 1)) return XRFTHIP_BAD_ARG;
@@ -30,7 +43,7 @@ int seg_desc_check(xrfthip_desc& s, long long* pitch) {
     return XRFTHIP_OK;
 }
 
-static int seg_n(const xrfthip_plan* P) { return (int)(keep_plan(P) ? P->d.nx / 2 : P->d.nx); }  // points of a tile sequence: a pair of segments, or a segment packed with itself
+static int seg_n(const xrfthip_plan* P) { return (int)(keep_plan(P) || synth_plan(P) ? P->d.nx / 2 : P->d.nx); }  // points of a tile sequence: a pair of segments, or a segment packed with itself
 
 // The tile of a workgroup: C adjacent columns (32 -- 128 bytes of a time row -- where the tile holds them, else what it holds, whatever `inner` is: the order of a
 // column's sums does not depend on its neighbours; 1 in the rows layout) times as many sequences of each as `need` asks for, a power of two, kWPoints points at most
@@ -58,11 +71,40 @@ static SegGeom seg_geom(const xrfthip_plan* P, long long need) {
 }
 static long long seg_units(const xrfthip_plan* P, const SegGeom& g) { return P->d.batch / P->d.mean_batch * g.ngroups; }  // series, or groups of columns over all blocks
 
+// The synthesis form of FastK (seg_synth): R = ceil(L / H) segments meet in a sample, the tile holds NS = 8192 / L; a workgroup advances by F = NS - (R - 1) segments, max(M - R + 1, 1) / F (rounded
+// up) of them serve a series (fasto.h).  Declined: 2 (R - 1) > NS -- more than half of a workgroup's transforms would be repeated
+struct SynthGeom { long long R, NS, F, wgs, span; };
+static SynthGeom synth_geom(const xrfthip_desc& d) {
+    SynthGeom g;
+    g.R = (d.nx + d.seg_hop - 1) / d.seg_hop;
+    g.NS = 2 * kWPoints / d.nx;
+    g.F = g.NS - (g.R - 1);
+    g.wgs = g.F > 0 ? (std::max<long long>(d.mean_batch - g.R + 1, 1) + g.F - 1) / g.F : 0;
+    g.span = (d.mean_batch - 1) * d.seg_hop + d.nx;
+    return g;
+}
+static int try_fasto(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const bool len_ok = d.nx >= 64 && d.nx <= 4096 && (d.nx & (d.nx - 1)) == 0;
+    if (!len_ok || d.seg_stride || env_ll("XRFTHIP_FASTW", 1) == 0 || env_ll("XRFTHIP_FASTW_SYNTH", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
+    const SynthGeom g = synth_geom(d);
+    if (2 * (g.R - 1) > g.NS || g.span > 0x7fffffffLL) return XRFTHIP_UNSUPPORTED_LENGTH;
+    const long long series = d.batch / d.mean_batch;
+    if (series > 0 && g.wgs > 0x7fffffffLL / series) return XRFTHIP_UNSUPPORTED_LENGTH;  // (one launch; declined, never truncated)
+    P->family = P->chosen = Family::FastK;
+    FftTables& t = P->tables[seg_n(P)];
+    const int rc = build_tables<float>(t, seg_n(P));
+    if (rc) return rc;
+    for (int r : t.radix) if (r != 2 && r != 4 && r != 8 && r != 16) return XRFTHIP_UNSUPPORTED_LENGTH;
+    return plan_twiddle(P, P->w_twr, d.nx, d.nx / 2 + 1);  // (W_L^k, k <= L / 2, the packing)
+}
+
 // FastW / FastK: float32 series, segments of 64 .. 4096 samples, a power of two (the column layout: up to 512 -- the tile holds 8 adjacent columns at least; beyond,
 // the caller arranges the series as rows)
 int try_fastw(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
     if (!welch_plan(P)) return kDeclined;
+    if (synth_plan(P)) return try_fasto(P);
     const bool cols = welch_cols(P), keep = keep_plan(P);
     const bool len_ok = d.nx >= 64 && d.nx <= (cols ? kWColsMaxL : 4096) && (d.nx & (d.nx - 1)) == 0;
     // (ISHIFT_X: (-1)^k on the transform, gone in |X|^2 and in X conj X')
@@ -94,7 +136,18 @@ static void layout_fastw(xrfthip_plan* P) {
     P->ws_bytes = mean_layout(P, 0, 1, P->d.batch * seg_ngroups(P));  // (the launch: groups x runs workgroups per block)
     P->w = seg_geom(P, (P->mean_run + 1) / 2);
 }
-static void layout_fastk(xrfthip_plan* P) { layout_one_pass(P); P->w = seg_geom(P, P->d.mean_batch); }
+// ... the synthesis: no workspace either; the tile holds the segments of one workgroup (all of a short series), nothing behind it
+static void layout_fasto(xrfthip_plan* P) {
+    layout_one_pass(P);
+    P->w = seg_geom(P, std::min<long long>(P->d.mean_batch, synth_geom(P->d).NS));
+    P->w.lds = (((size_t)P->w.seqs * (size_t)P->w.stride + 1) & ~(size_t)1) * sizeof(cf);
+    P->w.rounds = synth_geom(P->d).wgs;
+}
+static void layout_fastk(xrfthip_plan* P) {
+    if (synth_plan(P)) return layout_fasto(P);
+    layout_one_pass(P);
+    P->w = seg_geom(P, P->d.mean_batch);
+}
 
 // the head of the two kernels' arguments (seg_tile.h)
 static void seg_args(const xrfthip_plan* P, SegTile& p) {
@@ -123,7 +176,9 @@ static void seg_args(const xrfthip_plan* P, SegTile& p) {
         HIP_TRY(hipGetLastError()); } while (0)
 
 // FastK: one launch, nothing else
+static int run_fasto(const xrfthip_plan* P, const ExecArgs& a);
 static int run_fastk(const xrfthip_plan* P, const ExecArgs& a) {
+    if (synth_plan(P)) return run_fasto(P, a);
     const xrfthip_desc& d = P->d;
     hipStream_t st = a.stream;
     FastK p{};
@@ -137,6 +192,28 @@ static int run_fastk(const xrfthip_plan* P, const ExecArgs& a) {
     const long long nwg = seg_units(P, P->w) * P->w.rounds;
     if (nwg > 0x7fffffffLL) return XRFTHIP_BAD_ARG;  // (try_fastw declined it)
     SEG_LAUNCH(fastk_kernel, d.out_mode == XRFTHIP_OUT_POWER, "fastk_segments", nwg, p);
+    return XRFTHIP_OK;
+}
+
+// ... the synthesis: one launch, nothing else
+static int run_fasto(const xrfthip_plan* P, const ExecArgs& a) {
+    const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
+    const SynthGeom g = synth_geom(d);
+    FastO p{};
+    seg_args(P, p.t);
+    p.in = (const cf*)a.in0; p.out = (float*)a.out;
+    p.twr = (const cf*)P->w_twr.p;
+    p.NS = (int)g.NS; p.F = (int)g.F; p.R = (int)g.R; p.wgs = (int)g.wgs;
+    p.span = g.span;
+    const long long nwg = d.batch / d.mean_batch * g.wgs;
+    if (nwg > 0x7fffffffLL || g.span > 0x7fffffffLL) return XRFTHIP_BAD_ARG;  // (try_fasto declined it)
+    const dim3 grid((unsigned)nwg), blk((unsigned)kWThreads);
+    xrfthip_plan::ProfRec* rec = prof_begin(P, "fasto_overlap_add", st);
+    if (p.t.win) { auto k = &fasto_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
+    else { auto k = &fasto_kernel<false>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
+    prof_end(rec, st);
+    HIP_TRY(hipGetLastError());
     return XRFTHIP_OK;
 }
 
@@ -183,7 +260,9 @@ static void describe_cols(const xrfthip_plan* plan, std::string& s, const char* 
                "sequence t = (column t %% %d, %s t / %d); %s\n",
             (long long)(d.batch / d.mean_batch), (long long)d.inner, (long long)d.seg_stride, plan->w_pitch, g.C, g.ngroups, 4 * g.C, g.seqs / g.C, units, g.C, unit, g.C, tail);
 }
-static void describe_fastk(const xrfthip_plan* plan, std::string& s, const char*) {
+static void describe_fasto(const xrfthip_plan* plan, std::string& s, const char*);
+static void describe_fastk(const xrfthip_plan* plan, std::string& s, const char* note) {
+    if (synth_plan(plan)) return describe_fasto(plan, s, note);
     const xrfthip_desc& d = plan->d;
     const SegGeom& g = plan->w;
     appendf(s, "  [fastw segments kept] spectrograms, one pass: %lld series of %lld segments of %lld samples, hop %lld (series pitch %lld), each segment read where it lies with "
@@ -194,6 +273,17 @@ static void describe_fastk(const xrfthip_plan* plan, std::string& s, const char*
             (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, (long long)d.nx, (long long)d.seg_hop, plan->w_pitch, d.out_mode == XRFTHIP_OUT_POWER ? "|X|^2, real" : "X, complex",
             kWThreads, seg_units(plan, g), g.rounds, g.seqs / g.C, (long long)d.nx / 2, seg_radices(plan).c_str(), g.lds, kKResources, d.out_mode == XRFTHIP_OUT_POWER ? 4 : 8);
     describe_cols(plan, s, "segments", "segment", "the result is [block][segment][frequency][column], stores coalesced across columns, no transposed copy");
+}
+static void describe_fasto(const xrfthip_plan* plan, std::string& s, const char*) {
+    const xrfthip_desc& d = plan->d;
+    const SynthGeom g = synth_geom(d);
+    appendf(s, "  [fastw overlap-add] synthesis, one pass: %lld series of %lld half spectra of %lld bins (series pitch %lld complex elements) to %lld samples each, hop %lld; "
+               "one %d-thread workgroup per (series, run): %lld x %lld workgroups, %lld segments per tile as %lld-point sequences (Z = E + i O from X_k and conj X_n-k), "
+               "conj, radix %s in place, conj; a workgroup advances by %lld segments and repeats %lld of its predecessor's; every sample gathered by one thread: "
+               "sum of w x scale over its %lld covering segments at most, ascending, / sum of w^2 where that is > 1e-10; lanes load consecutive bins and store consecutive "
+               "samples; no workspace, no partial sums, no atomics; lds=%zuB; %s; 8 algorithmic bytes per bin read and 4 per sample written\n",
+            (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, (long long)d.nx / 2 + 1, plan->w_pitch, g.span, (long long)d.seg_hop, kWThreads,
+            (long long)(d.batch / d.mean_batch), g.wgs, g.NS, (long long)d.nx / 2, seg_radices(plan).c_str(), g.F, g.R - 1, g.R, plan->w.lds, kOResources);
 }
 static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*) {
     const xrfthip_desc& d = plan->d;
@@ -209,9 +299,10 @@ static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*
 static void info_fastw(const xrfthip_plan* plan, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTW; *n = 2 * plan->w.seqs; }  // (per_workgroup: the segments of a round)
 static void info_fastk(const xrfthip_plan* plan, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTW; *n = plan->w.seqs; }
 // (the entries in the order of struct FamilyOps; reads_strided is false -- the series pitch is w_pitch, d.in_stride_batch is 0 -- and the last entry, no_generic_passes, true)
+static int finalize_fastk(xrfthip_plan* P) { return synth_plan(P) ? XRFTHIP_OK : fast_phase_tables(P); }  // (the synthesis takes no phase table)
 #ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
 const FamilyOps kOpsFastW = {Family::FastW, run_fastw, describe_fastw, info_fastw, fast_phase_tables, layout_fastw, nullptr, nullptr, false, nullptr, false, false, false, false, true};
-const FamilyOps kOpsFastK = {Family::FastK, run_fastk, describe_fastk, info_fastk, fast_phase_tables, layout_fastk, nullptr, nullptr, false, nullptr, false, false, false, false, true};
+const FamilyOps kOpsFastK = {Family::FastK, run_fastk, describe_fastk, info_fastk, finalize_fastk, layout_fastk, nullptr, nullptr, false, nullptr, false, false, false, false, true};
 #endif
 
 // kernels of this unit that take more than 64 KB of dynamic LDS (two tiles of 4096 points and their padding): called once through set_kernel_attrs_once()

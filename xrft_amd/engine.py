@@ -40,7 +40,7 @@ class SpectralPlan:
 
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
-                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0, seg_stride=0, seg_keep=0):
+                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0, seg_stride=0, seg_keep=0, seg_synth=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
@@ -75,9 +75,14 @@ class SpectralPlan:
         self.seg_keep = int(seg_keep)
         if self.seg_keep:
             self.batch_out = self.batch // max(self.mean_batch, 1)
-        d = _lib.DescKeep(C.sizeof(_lib.DescKeep), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
+        # the series rebuilt from its segments' half spectra (xrfthip_desc.seg_synth; complex64, INVERSE | C2R_X): mean_batch counts the segments of a series, the input
+        # is (series, mean_batch, nx / 2 + 1) -- in_stride_batch the pitch between series in complex elements -- and the result (series, (mean_batch - 1) seg_hop + nx), real
+        self.seg_synth = int(seg_synth)
+        if self.seg_synth:
+            self.batch_out = self.batch // max(self.mean_batch, 1)
+        d = _lib.DescSynth(C.sizeof(_lib.DescSynth), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
                       int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
-                      self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0, self.seg_stride, 0, self.seg_keep, 0)
+                      self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0, self.seg_stride, 0, self.seg_keep, 0, self.seg_synth, 0)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
         for axis, w in ((0, window_y), (1, window_x)):
             if w is not None:
@@ -155,6 +160,10 @@ class SpectralPlan:
     def _layout_ok(self, t):
         """Does the memory layout of ``t`` match the plan's: contiguous, or -- a plan with input strides -- a view (..., ny, nx) whose last stride is 1, whose row
         stride is the plan's, whose leading dims collapse to ONE batch stride equal to the plan's, and whose first element is 16-byte aligned."""
+        if self.seg_hop and self.seg_synth:  # (series, segments, bins): the half spectra adjacent, the segments of a series adjacent, the series the plan's pitch apart
+            nb = self.nx // 2 + 1
+            return (t.dim() == 3 and tuple(t.shape) == (self.batch_out, self.mean_batch, nb) and (t.stride(2) == 1 or nb == 1) and (t.stride(1) == nb or self.mean_batch == 1)
+                    and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or self.mean_batch * nb)))
         if self.seg_hop and self.seg_stride > 1:  # (blocks, samples, columns): exactly the view the plan addresses -- columns adjacent, samples seg_stride apart, blocks the plan's pitch apart
             span = (self.mean_batch - 1) * self.seg_hop + self.nx
             return (t.dim() == 3 and t.shape[0] == self.batch_out and t.shape[1] >= span and t.shape[2] == self.inner
@@ -192,6 +201,8 @@ class SpectralPlan:
                 shape = (self.batch_out, self.inner, self.nx_out)
             if self.seg_hop and self.seg_keep:  # (every segment's spectrum: the segments where the time axis lay, the columns innermost)
                 shape = (self.batch_out, self.mean_batch, self.nx_out) + ((self.inner,) if self.seg_stride > 1 else ())
+            if self.seg_hop and self.seg_synth:  # (the series)
+                shape = (self.batch_out, (self.mean_batch - 1) * self.seg_hop + self.nx)
             if self.mid > 1:
                 shape = (self.batch, self.ny_out, self.mid, self.nx_out, self.inner)
             if self.herm_ny:
@@ -199,6 +210,8 @@ class SpectralPlan:
             out = torch.empty(shape, dtype=self.out_dtype(), device=dev)
         elif want_out:  # a caller's buffer (graph capture, composed passes): held to the plan before the device sees its pointer
             need = self.batch_out * self.ny_out * self.nx_out * self.inner * self.mid * (self.mean_batch if self.seg_keep else 1)
+            if self.seg_hop and self.seg_synth:
+                need = self.batch_out * ((self.mean_batch - 1) * self.seg_hop + self.nx)
             if out.dtype != self.out_dtype() or not out.is_contiguous() or out.numel() != need or out.device != dev:
                 raise ValueError(f"out does not match the plan (dtype {self.out_dtype()}, contiguous, {need} elements on {dev})")
         iso_dtype = torch.complex128 if self.out_mode == _lib.OUT_CROSS else torch.float64
