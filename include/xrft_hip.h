@@ -341,6 +341,35 @@ typedef struct xrfthip_desc {
      * earlier versions are accepted (0, 0); an older library answers XRFTHIP_BAD_ARG to the larger struct_size.  Offsets are computed in 64 bits. */
     int64_t seg_synth;
     int64_t seg_reserved4; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_synth: no struct_size between the two */
+    /* FIR filtering along a series by overlap-save in ONE pass (scipy.signal.convolve(x, h, mode) for K real taps h): every L-sample segment transformed, multiplied
+     * by the response, transformed back, and the V = L - K + 1 samples that do not wrap around kept.  No window, no overlap-add, no division, no gather; nothing but
+     * the series (4 bytes per sample read) and the filtered series (4 bytes per sample written) goes through memory.
+     *   seg_filter = 1   Valid with seg_hop = V, L / 2 <= V <= L (K = L - V + 1 taps); ndim = 1, ny = 1, nx = L; dtype XRFTHIP_F32, out_mode XRFTHIP_OUT_COMPLEX,
+     *                    flags = 0, detrend NONE, no window; seg_keep = seg_synth = seg_stride = 0, inner <= 1.
+     *   seg_in_len = N >= 1       samples per series.  d_in0 is [P] series of N float32, series p at d_in0 + p * in_stride_batch: in_stride_batch is HERE the series
+     *                             pitch in samples, 0 = dense = N, any other value >= N.
+     *   seg_out_len = n_out >= 1  samples per filtered series.  d_out is [P][n_out] float32, dense, NOT complex whatever out_mode says:
+     *                               out[p][n'] = scale * sum_k h[k] x_p[n' + a - k],  x_p = 0 outside [0, N)
+     *   seg_lead = a              0 <= a <= K - 1 and a + n_out <= N + K - 1: the first output sample within the full convolution (scipy's "full": a = 0,
+     *                             n_out = N + K - 1; "same": a = (K - 1) / 2, n_out = N; "valid": a = K - 1, n_out = N - K + 1).
+     *                    mean_batch = M = ceil(n_out / V) the segments per series, batch = P * M.  Segment s holds the samples s V + a - (K - 1) + j, j < L (zeros
+     *                    outside [0, N)) and yields the outputs s V .. s V + V - 1.
+     *                    0 = off: the three companion words must be 0 and everything about the descriptor is as without the fields.
+     * The response: xrfthip_plan_set_phase(plan, 1, H, L / 2 + 1) with H = the L-point transform of the zero-extended taps, bins 0 .. L / 2 (numpy.fft.rfft(h, L)),
+     * interleaved doubles; kept as complex64.  Any other n, or axis 0: XRFTHIP_BAD_ARG.  NULL clears; without a table the response counts as 1 (out[n'] =
+     * scale x[n' + a]: a pure delay).  The imaginary parts of entries 0 and L / 2 are ignored.  The transforms are unnormalised: the caller folds 1 / L into `scale`.
+     * Alignment: d_in0 and d_out 4-byte aligned.  No byte outside [0, N) of a series is read; every output sample is written exactly once, by one thread: no atomics,
+     * no workspace (xrfthip_workspace_bytes is 0), and a sample's bits depend on its own segment's L inputs, on H and on `scale` only -- not on P, on M or on the
+     * workgroups.  Every segment is a transform of its own: a non-finite sample makes exactly the outputs of the (at most two) segments that hold it non-finite.
+     * XRFTHIP_BAD_ARG: seg_filter not 0 | 1, a companion word non-zero with seg_filter = 0, and every violation of the rules above.  XRFTHIP_UNSUPPORTED_LENGTH ("the
+     * caller composes"): L not a power of two in 64 .. 4096; a launch beyond 2^31 - 1 workgroups; XRFTHIP_FASTW=0 or XRFTHIP_FASTW_FILTER=0 in the environment when
+     * the plan is created (docs/TUNING.md).
+     * Still XRFTHIP_K_FASTW: a fifth form of the same family (xrfthip_plan_describe prints a [fastw overlap-save] line).  Descriptors with the struct_size of the ten
+     * earlier versions are accepted (0, 0, 0, 0); an older library answers XRFTHIP_BAD_ARG to the larger struct_size.  Offsets are computed in 64 bits. */
+    int64_t seg_filter;
+    int64_t seg_lead;    /* the four words were appended together: no struct_size between them */
+    int64_t seg_in_len;
+    int64_t seg_out_len;
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;

@@ -92,10 +92,20 @@ class DescKeep(C.Structure):
 
 
 class DescSynth(C.Structure):
-    """xrfthip_desc as the library has it now: ``DescKeep`` and the two words appended together after it."""
+    """``DescKeep`` and the two words appended together after it; still accepted under its own struct_size."""
     _fields_ = DescKeep._fields_ + [
         ("seg_synth", C.c_int64),  # 1 (with seg_hop, C64, INVERSE | C2R_X): the series rebuilt from its segments' half spectra -- [series][M][nx / 2 + 1] in, [series][(M - 1) hop + nx] real out; 0: off
         ("seg_reserved4", C.c_int64),  # 0
+    ]
+
+
+class DescFilt(C.Structure):
+    """xrfthip_desc as the library has it now: ``DescSynth`` and the four words appended together after it."""
+    _fields_ = DescSynth._fields_ + [
+        ("seg_filter", C.c_int64),  # 1 (with seg_hop = V >= nx / 2, F32, flags 0): a series filtered by overlap-save, K = nx - V + 1 taps -- [series][seg_in_len] in, [series][seg_out_len] real out; 0: off
+        ("seg_lead", C.c_int64),  # the first output sample within the full convolution, 0 .. K - 1
+        ("seg_in_len", C.c_int64),  # samples per series
+        ("seg_out_len", C.c_int64),  # samples per filtered series; mean_batch = ceil(seg_out_len / V)
     ]
 
 
@@ -116,7 +126,7 @@ def _bind(dll):
     dll.xrfthip_strerror.restype = C.c_char_p
     dll.xrfthip_strerror.argtypes = [C.c_int]
     dll.xrfthip_last_hip_error.restype = C.c_int
-    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg, a DescCols, a DescKeep or a DescSynth, by reference)
+    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg, a DescCols, a DescKeep, a DescSynth or a DescFilt, by reference)
     dll.xrfthip_plan_destroy.argtypes = [vp]
     dll.xrfthip_plan_set_window.argtypes = [vp, C.c_int, vp, i64]
     dll.xrfthip_plan_set_phase.argtypes = [vp, C.c_int, vp, i64]

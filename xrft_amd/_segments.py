@@ -1,5 +1,5 @@
 """The segment surface of the call API: Welch spectra (welch_power_spectrum, welch_cross_spectrum, welch_coherence) and spectrograms (spectrogram, stft) -- the spectra
-of the overlapping segments of a series, averaged or kept -- and the synthesis that rebuilds the series from the kept ones (istft).  Fused where a segment plan takes the call (xrfthip_desc.seg_hop: csrc/fastw.h, fastk.h), else composed from
+of the overlapping segments of a series, averaged or kept -- the synthesis that rebuilds the series from the kept ones (istft), and FIR filtering along a dim by overlap-save (fir_filter).  Fused where a segment plan takes the call (xrfthip_desc.seg_hop: csrc/fastw.h, fastk.h), else composed from
 the calls of api.py on the unfolded segments.  api.py re-exports the public names.
 
 This module sits ON TOP of api.py and is imported by it, behind the definitions it uses (`_api.` below: resolved at call time; the two tuning constants
@@ -12,10 +12,11 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, engine
 from . import api as _api  # (the calls the composed paths and the analysis of ONE segment go through; api.py imports this module behind them)
 from ._hostside import _analyze, _direct_lag_attrs, _flags_tables, _get_coordinate_spacing, _label_output, _to_device
-from ._plans import _MEAN_REFUSED, _rung
+from ._plans import _MEAN_REFUSED, _digest, _get_plan, _plan_lock, _ro, _rung
+from .padding import _pad_coordinate
 from .labeled import Coordinate, DataArray, from_any, to_like
 
 # ------------------------------------------------------------------------------------------------------
@@ -501,3 +502,197 @@ def istft(ds, dim, nperseg=None, noverlap=None, real_dim=None, window=None, shif
     coords = {k: v for k, v in ds.coords.items() if sname not in v.dims and fname not in v.dims and k != dim}
     coords[dim] = Coordinate((dim,), t0 + dt * np.arange(span), {"spacing": dt}, dim)
     return to_like(DataArray(out.movedim(-1, ax), dims, coords, None, None), src)
+
+
+# ------------------------------------------------------------------------------------------------------
+# FIR filtering along a dim by overlap-save (scipy.signal.convolve along one axis): every L-sample segment transformed, multiplied by the taps' response, transformed
+# back, the samples that do not wrap around kept.  Fused where a plan takes the call (xrfthip_desc.seg_filter, csrc/fastf.h: the series read once, the filtered series
+# written once, nothing in between), else composed at the same L: a zero-extended copy, the segments unfolded, the real 1-D plan, the product, its inverse, the slice.
+# ------------------------------------------------------------------------------------------------------
+_FIR_MODES = ("full", "same", "valid")
+_FIR_RESPONSES = {}  # (digest of the taps, K, L) -> rfft(taps, L), complex128, read-only: the plan key digests it once
+
+
+def _fir_response(taps, l):
+    key = (_digest(taps), len(taps), l)
+    with _plan_lock:
+        h = _FIR_RESPONSES.get(key)
+    if h is None:
+        h = _ro(np.fft.rfft(taps, l))
+        with _plan_lock:
+            if len(_FIR_RESPONSES) > 64:
+                _FIR_RESPONSES.clear()
+            _FIR_RESPONSES[key] = h
+    return h
+
+
+_FIR_DEVICE_RESPONSES = {}  # (id of the memoised response, complex dtype, device) -> (the response, its device copy): the composed route uploads a table once
+
+
+def _fir_device_response(resp, cdt, device):
+    key = (id(resp), cdt, str(device))
+    with _plan_lock:
+        e = _FIR_DEVICE_RESPONSES.get(key)
+    if e is None or e[0] is not resp:
+        e = (resp, torch.from_numpy(np.array(resp)).to(cdt).to(device))
+        with _plan_lock:
+            if len(_FIR_DEVICE_RESPONSES) > 64:
+                _FIR_DEVICE_RESPONSES.clear()
+            _FIR_DEVICE_RESPONSES[key] = e
+    return e[1]
+
+
+def _fir_default_nfft(k, n=None):
+    """The smallest power of two >= max(512, 4 (K - 1)), capped at 4096: the sweep of profiles/r27_fir_filter.txt -- the one-pass kernel is fastest at 256 .. 512 for
+    K <= 129 (512 is within 4 % of the best everywhere) and at 4 (K - 1) and beyond for longer taps.  A series of ``n`` samples that one shorter segment holds whole
+    (N + K - 1 <= L / 2) takes the shorter one, down to max(64, 4 (K - 1)).  K = 2049 fits 4096 exactly (K - 1 = L / 2, the longest taps the one pass takes); longer taps (composed): the
+    smallest power of two >= 2 (K - 1)."""
+    l = 512
+    while l < 4 * (k - 1) and l < 4096:
+        l *= 2
+    while n is not None and l // 2 >= max(64, 4 * (k - 1), n + k - 1):
+        l //= 2
+    while l < 2 * (k - 1):
+        l *= 2
+    return l
+
+
+def _fir_args(da, dim, taps, mode, nfft):
+    """(axis, taps as float64, K, L, a, n_out) after the checks."""
+    if not isinstance(dim, str):
+        raise ValueError(f"dim must be the name of ONE dimension (the axis the filter runs along), not {dim!r}")
+    ax = da.get_axis_num(dim)
+    h = np.asarray(taps)
+    if h.ndim != 1 or h.size < 1:
+        raise ValueError("taps must hold K >= 1 coefficients in one dimension")
+    if h.dtype.kind == "c":
+        raise ValueError("taps must be real (a complex filter is two real ones)")
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    if mode not in _FIR_MODES:
+        raise ValueError(f"mode must be one of {_FIR_MODES}, not {mode!r}")
+    n, k = da.shape[ax], len(h)
+    if mode == "valid" and n < k:
+        raise ValueError(f"mode 'valid' needs at least K = {k} samples along {dim!r}, which has {n}")
+    a, n_out = {"full": (0, n + k - 1), "same": ((k - 1) // 2, n), "valid": (k - 1, n - k + 1)}[mode]
+    if nfft is None:
+        l = _fir_default_nfft(k, n)
+    else:
+        l = int(nfft)
+        if l < k or l < 2:
+            raise ValueError(f"nfft = {l} must be at least K = {k} (and 2): a segment holds the taps")
+        l += l & 1  # (the real transforms take even lengths; the result does not depend on L)
+    return ax, h, k, l, a, n_out
+
+
+def _fir_fused(t, ax, k, l, a, n_out, resp):
+    """The values of ONE plan with seg_filter, the series last, or None where the call composes: data that are not float32, an empty array, L not a power of two in
+    64 .. 4096, K - 1 > L / 2, a class the plan declines (XRFTHIP_UNSUPPORTED_LENGTH, remembered), XRFTHIP_FASTW_FILTER=0.  A trailing ``dim`` is read where it lies,
+    with one pitch between the series; any other is arranged first (one transposed copy)."""
+    if t.dtype != torch.float32 or math.prod(t.shape) == 0 or n_out < 1 or os.environ.get("XRFTHIP_FASTW_FILTER", "1") == "0":  # (the knob of the library, honoured before a cached plan could answer)
+        return None
+    if 2 * (k - 1) > l:  # (the library's XRFTHIP_BAD_ARG: less than half of a transform would be kept; L itself it judges: 64 .. 4096, a power of two)
+        return None
+    hop = l - k + 1
+    m = -(-n_out // hop)
+    v = t if ax == t.dim() - 1 else t.movedim(ax, -1)
+    n = v.shape[-1]
+    lead = _collapse(v.shape[:-1], v.stride()[:-1])
+    if (v.stride(-1) == 1 or n == 1) and lead is not None and (lead[0] == 1 or lead[1] >= n):
+        rows = torch.as_strided(v, (lead[0], n), (lead[1] if lead[0] > 1 else n, 1), v.storage_offset())
+        pitch = lead[1] if lead[0] > 1 else 0
+    else:
+        rows, pitch = v.contiguous().reshape(-1, n), 0
+    kw = dict(ndim=1, ny=1, nx=l, dtype=torch.float32, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0, scale=1.0 / l, phase_x=resp, mean_batch=m,
+              seg_hop=hop, seg_filter=1, seg_lead=a, seg_in_len=n, seg_out_len=n_out, batch=rows.shape[0] * m, in_stride_batch=int(pitch))
+    plan = _segment_plan(kw, {})
+    if plan is None:
+        return None
+    return plan.execute(rows)[0].reshape(tuple(v.shape[:-1]) + (n_out,))
+
+
+def _fir_composed(t, ax, k, l, a, n_out, resp):
+    """The definition of the result, values only, the series last: overlap-save at the same L out of the library's own pieces -- a zero-extended copy of the series,
+    the segments unfolded at hop V = L - K + 1, the real 1-D forward plan, engine.table_mul by the response, the C2R inverse plan, the kept samples sliced out."""
+    v = t.movedim(ax, -1)
+    n = v.shape[-1]
+    cdt = torch.complex64 if t.dtype == torch.float32 else torch.complex128
+    hop = l - k + 1
+    m = -(-n_out // hop)
+    front, span = k - 1 - a, (m - 1) * hop + l
+    xe = torch.zeros(tuple(v.shape[:-1]) + (span,), dtype=t.dtype, device=t.device)
+    ncopy = min(n, span - front)
+    xe[..., front:front + ncopy] = v[..., :ncopy]
+    seg = xe.unfold(-1, l, hop).contiguous().reshape(-1, l)
+    b, nb = seg.shape[0], l // 2 + 1
+    if b == 0:
+        return torch.empty(tuple(v.shape[:-1]) + (n_out,), dtype=t.dtype, device=t.device)
+    spec = _get_plan(ndim=1, batch=b, ny=1, nx=l, dtype=t.dtype, out_mode=_lib.OUT_COMPLEX, flags=_lib.HALF_X).execute(seg)[0].reshape(b, nb)
+    del seg, xe
+    prod = engine.table_mul(spec, _fir_device_response(resp, cdt, t.device), nb)
+    del spec
+    y = _get_plan(ndim=1, batch=b, ny=1, nx=l, dtype=cdt, out_mode=_lib.OUT_COMPLEX, flags=_lib.INVERSE | _lib.C2R_X, scale=1.0 / l).execute(prod)[0]
+    y = y.reshape(tuple(v.shape[:-1]) + (m, l))[..., k - 1:]
+    return y.reshape(tuple(v.shape[:-1]) + (m * hop,))[..., :n_out]
+
+
+def _fir_coordinate(da, dim, mode, k, n, spacing_tol):
+    """The coordinate of ``dim`` in the result, or None where ``da`` carries none: kept ("same"), sliced ("valid"), extended at its spacing ("full")."""
+    if dim not in da.coords:
+        return None
+    c = da.coords[dim]
+    v = np.asarray(c.values)
+    if mode == "same":
+        return c
+    if mode == "valid":
+        return Coordinate((dim,), v[k // 2:k // 2 + n - k + 1], c.attrs, dim)
+    if k == 1:
+        return c
+    if n < 2:
+        raise ValueError(f"the coordinate of {dim!r} has one value: its spacing, by which mode 'full' extends it, is unknown")
+    _get_coordinate_spacing(v, spacing_tol, dim)  # (evenly spaced, or ValueError)
+    return Coordinate((dim,), _pad_coordinate(v, ((k - 1) // 2, k // 2), (v[-1] - v[0]) / (n - 1)), c.attrs, dim)
+
+
+def fir_filter(da, dim, taps, mode="same", nfft=None, spacing_tol=1e-3):
+    """``da`` filtered along ``dim`` by the K real coefficients ``taps`` (a 1-D array or a sequence): ``scipy.signal.convolve(x, taps, mode)`` of every series --
+    ``y_full[m] = sum_k taps[k] x[m - k]`` with x zero outside its N samples, and output sample n' is ``y_full[n' + a]``: ``"full"`` a = 0, N + K - 1 samples;
+    ``"same"`` a = (K - 1) // 2, N samples; ``"valid"`` a = K - 1, N - K + 1 samples (ValueError when N < K).  A low-pass, a band-pass or a smoothing kernel designed
+    with ``scipy.signal.firwin`` is applied this way; the filter is linear and exact up to rounding: no window, no overlap-add.
+    The result keeps the dims, the other coordinates, the name and the attrs of ``da``.  The coordinate of ``dim`` is unchanged ("same"), the slice
+    ``[K // 2 : K // 2 + N - K + 1]`` ("valid"), or extended by (K - 1) // 2 points in front and K // 2 behind at its spacing ("full": the coordinate must be evenly
+    spaced within ``spacing_tol``, else ValueError); a dim without a coordinate stays without one, and coordinates that span ``dim`` besides others are kept only
+    where the length stays.
+    The work is overlap-save with segments of ``nfft`` = L samples, of which V = L - K + 1 are kept: by default the smallest power of two >= max(512, 4 (K - 1)),
+    capped at 4096 (shorter, down to 64, where one shorter segment holds the whole series; profiles/r27_fir_filter.txt); a given ``nfft`` must be at least K (an odd one is raised by one; the result does not depend on it but for rounding).  float32 data with L a power
+    of two in 64 .. 4096 and K - 1 <= L / 2 are filtered by ONE pass (xrfthip_desc.seg_filter): the series is read once and the result written once, no spectrum
+    reaches memory.  A trailing ``dim`` is read where it lies (a batch pitch included); any other is arranged first (one transposed copy) and the result moved back
+    as a view.  Every other call -- float64, other L, longer taps, XRFTHIP_FASTW_FILTER=0 -- composes the same overlap-save from the library's own real 1-D plans and
+    a table product.  float16 / bfloat16 data are widened to float32 first and the result is float32; complex data run as two real calls, the real and the imaginary
+    part."""
+    src = da
+    da = from_any(da)
+    ax, h, k, l, a, n_out = _fir_args(da, dim, taps, mode, nfft)
+    n = da.shape[ax]
+    coord = _fir_coordinate(da, dim, mode, k, n, spacing_tol)
+    t = _to_device(da.data)
+    if t.dtype in (torch.float16, torch.bfloat16):
+        t = engine.convert(t, torch.float32)
+    if t.dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
+        t = t.to(torch.float64)
+    resp = _fir_response(h, l)
+
+    def one(x):
+        if math.prod(x.shape) == 0:  # (nothing to filter: the zeros of an empty sum)
+            return x.new_zeros(tuple(s for i, s in enumerate(x.shape) if i != ax) + (n_out,))
+        out = _fir_fused(x, ax, k, l, a, n_out, resp)
+        return _fir_composed(x, ax, k, l, a, n_out, resp) if out is None else out
+
+    out = torch.complex(one(t.real.contiguous()), one(t.imag.contiguous())) if t.is_complex() else one(t)
+    coords = {}
+    for name, c in da.coords.items():
+        if name == dim:
+            if coord is not None:
+                coords[name] = coord
+        elif dim not in c.dims or n_out == n:
+            coords[name] = c
+    return to_like(DataArray(out.movedim(-1, ax), da.dims, coords, da.name, da.attrs), src)

@@ -6,6 +6,8 @@
 //           ... and its way back, the synthesis (xrfthip_desc.seg_synth, fasto.h; the *_fasto entries below): the series rebuilt from its segments' half spectra --
 //           inverse transform, window, overlap-add and the division by the summed squared windows in one pass, every output sample gathered by one thread; rows
 //           layout only, no workspace.  It is a form of FastK and not an enum value of its own: the segment spectra's family, both directions
+//           ... and both directions in one tile, the FIR filter by overlap-save (xrfthip_desc.seg_filter, fastf.h; the *_fastf entries below): a series' segments
+//           transformed, multiplied by the response, transformed back, the samples that do not wrap around written once; rows layout only, no workspace
 // FastW and FastK in the rows layout (one series per workgroup) or the column layout (xrfthip_desc.seg_stride: C adjacent columns of a (time, ..) block per workgroup).
 
 // xrfthip_plan_create's checks of seg_hop / seg_stride / seg_keep (XRFTHIP_BAD_ARG; what try_fastw declines is "the caller composes"), on its own copy of the descriptor: seg_stride = 1 is the rows layout and becomes it;
@@ -13,6 +15,9 @@
 // nothing of the strided-view rules (16-byte strides and pointers) applies to such a plan.  mean_batch counts the segments of a series (1 included when they are kept)
 int seg_desc_check(xrfthip_desc& s, long long* pitch) {
     *pitch = 0;
+    if ((s.seg_filter != 0 && s.seg_filter != 1) || (!s.seg_filter && (s.seg_lead != 0 || s.seg_in_len != 0 || s.seg_out_len != 0))) return XRFTHIP_BAD_ARG;
+    const bool filt = s.seg_filter == 1;
+    if (filt && (s.seg_hop <= 0 || s.seg_keep != 0 || s.seg_synth != 0 || s.seg_stride != 0)) return XRFTHIP_BAD_ARG;
     if ((s.seg_synth != 0 && s.seg_synth != 1) || s.seg_reserved4 != 0 || (s.seg_synth && (s.seg_hop <= 0 || s.seg_keep != 0))) return XRFTHIP_BAD_ARG;
     const bool synth = s.seg_synth == 1;
     if ((s.seg_keep != 0 && s.seg_keep != 1) || s.seg_reserved3 != 0 || (s.seg_keep && s.seg_hop <= 0)) return XRFTHIP_BAD_ARG;
@@ -22,8 +27,18 @@ int seg_desc_check(xrfthip_desc& s, long long* pitch) {
     if (s.seg_stride == 1) s.seg_stride = 0;
     if (s.seg_hop == 0) return XRFTHIP_OK;
     if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.seg_hop > s.nx || (s.flags & (XRFTHIP_AXIS_Y | XRFTHIP_ISO)) || (s.inner > 1 && !s.seg_stride) || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y) return XRFTHIP_BAD_ARG;
-    if (s.mean_batch < (keep || synth ? 1 : 2) || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
+    if (s.mean_batch < (keep || synth || filt ? 1 : 2) || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
     if (s.nx > (1LL << 30) || s.mean_batch > (1LL << 31) - 1) return XRFTHIP_BAD_ARG;
+    if (filt) {  // a series of N samples in, n_out filtered samples out: K = L - V + 1 taps, at least half of every transform kept; the pitch counts samples
+        const long long K = s.nx - s.seg_hop + 1, cap = 1LL << 60;
+        if (s.dtype != XRFTHIP_F32 || s.out_mode != XRFTHIP_OUT_COMPLEX || s.detrend != XRFTHIP_DETREND_NONE || s.flags != 0 || 2 * s.seg_hop < s.nx) return XRFTHIP_BAD_ARG;
+        if (s.seg_in_len < 1 || s.seg_in_len > cap || s.seg_out_len < 1 || s.seg_out_len > cap || s.seg_lead < 0 || s.seg_lead > K - 1) return XRFTHIP_BAD_ARG;
+        if (s.seg_lead + s.seg_out_len > s.seg_in_len + K - 1 || s.mean_batch != (s.seg_out_len + s.seg_hop - 1) / s.seg_hop) return XRFTHIP_BAD_ARG;
+        if (s.in_stride_batch != 0 && s.in_stride_batch < s.seg_in_len) return XRFTHIP_BAD_ARG;
+        *pitch = s.in_stride_batch ? s.in_stride_batch : s.seg_in_len;
+        s.in_stride_batch = 0;
+        return XRFTHIP_OK;
+    }
     if (synth) {  // half spectra in, the series out: the pitch counts complex elements, M (L / 2 + 1) of them a dense series (seg_stride: try_fastw declines)
         if (s.dtype != XRFTHIP_C64 || s.out_mode != XRFTHIP_OUT_COMPLEX || s.detrend != XRFTHIP_DETREND_NONE || s.flags != (XRFTHIP_INVERSE | XRFTHIP_C2R_X) || (s.nx & 1)) return XRFTHIP_BAD_ARG;
         const long long dense = s.mean_batch * (s.nx / 2 + 1);
@@ -43,7 +58,7 @@ int seg_desc_check(xrfthip_desc& s, long long* pitch) {
     return XRFTHIP_OK;
 }
 
-static int seg_n(const xrfthip_plan* P) { return (int)(keep_plan(P) || synth_plan(P) ? P->d.nx / 2 : P->d.nx); }  // points of a tile sequence: a pair of segments, or a segment packed with itself
+static int seg_n(const xrfthip_plan* P) { return (int)(keep_plan(P) || synth_plan(P) || filter_plan(P) ? P->d.nx / 2 : P->d.nx); }  // points of a tile sequence: a pair of segments, or a segment packed with itself
 
 // The tile of a workgroup: C adjacent columns (32 -- 128 bytes of a time row -- where the tile holds them, else what it holds, whatever `inner` is: the order of a
 // column's sums does not depend on its neighbours; 1 in the rows layout) times as many sequences of each as `need` asks for, a power of two, kWPoints points at most
@@ -99,12 +114,32 @@ static int try_fasto(xrfthip_plan* P) {
     return plan_twiddle(P, P->w_twr, d.nx, d.nx / 2 + 1);  // (W_L^k, k <= L / 2, the packing)
 }
 
+// The filter form of FastK (seg_filter): the tile holds NS = 8192 / L segments, ceil(M / NS) workgroups serve a series (fastf.h); no segment is transformed twice
+static long long filter_wgs(const xrfthip_desc& d) {
+    const long long NS = 2 * kWPoints / d.nx;
+    return (d.mean_batch + NS - 1) / NS;
+}
+static int try_fastf(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const bool len_ok = d.nx >= 64 && d.nx <= 4096 && (d.nx & (d.nx - 1)) == 0;
+    if (!len_ok || env_ll("XRFTHIP_FASTW", 1) == 0 || env_ll("XRFTHIP_FASTW_FILTER", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
+    const long long series = d.batch / d.mean_batch;
+    if (series > 0 && filter_wgs(d) > 0x7fffffffLL / series) return XRFTHIP_UNSUPPORTED_LENGTH;  // (one launch; declined, never truncated)
+    P->family = P->chosen = Family::FastK;
+    FftTables& t = P->tables[seg_n(P)];
+    const int rc = build_tables<float>(t, seg_n(P));
+    if (rc) return rc;
+    for (int r : t.radix) if (r != 2 && r != 4 && r != 8 && r != 16) return XRFTHIP_UNSUPPORTED_LENGTH;
+    return plan_twiddle(P, P->w_twr, d.nx, d.nx / 2 + 1);  // (W_L^k, k <= L / 2, the unpacking and the packing)
+}
+
 // FastW / FastK: float32 series, segments of 64 .. 4096 samples, a power of two (the column layout: up to 512 -- the tile holds 8 adjacent columns at least; beyond,
 // the caller arranges the series as rows)
 int try_fastw(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
     if (!welch_plan(P)) return kDeclined;
     if (synth_plan(P)) return try_fasto(P);
+    if (filter_plan(P)) return try_fastf(P);
     const bool cols = welch_cols(P), keep = keep_plan(P);
     const bool len_ok = d.nx >= 64 && d.nx <= (cols ? kWColsMaxL : 4096) && (d.nx & (d.nx - 1)) == 0;
     // (ISHIFT_X: (-1)^k on the transform, gone in |X|^2 and in X conj X')
@@ -143,8 +178,16 @@ static void layout_fasto(xrfthip_plan* P) {
     P->w.lds = (((size_t)P->w.seqs * (size_t)P->w.stride + 1) & ~(size_t)1) * sizeof(cf);
     P->w.rounds = synth_geom(P->d).wgs;
 }
+// ... the filter: the same
+static void layout_fastf(xrfthip_plan* P) {
+    layout_one_pass(P);
+    P->w = seg_geom(P, std::min<long long>(P->d.mean_batch, 2 * kWPoints / P->d.nx));
+    P->w.lds = (((size_t)P->w.seqs * (size_t)P->w.stride + 1) & ~(size_t)1) * sizeof(cf);
+    P->w.rounds = filter_wgs(P->d);
+}
 static void layout_fastk(xrfthip_plan* P) {
     if (synth_plan(P)) return layout_fasto(P);
+    if (filter_plan(P)) return layout_fastf(P);
     layout_one_pass(P);
     P->w = seg_geom(P, P->d.mean_batch);
 }
@@ -177,8 +220,10 @@ static void seg_args(const xrfthip_plan* P, SegTile& p) {
 
 // FastK: one launch, nothing else
 static int run_fasto(const xrfthip_plan* P, const ExecArgs& a);
+static int run_fastf(const xrfthip_plan* P, const ExecArgs& a);
 static int run_fastk(const xrfthip_plan* P, const ExecArgs& a) {
     if (synth_plan(P)) return run_fasto(P, a);
+    if (filter_plan(P)) return run_fastf(P, a);
     const xrfthip_desc& d = P->d;
     hipStream_t st = a.stream;
     FastK p{};
@@ -212,6 +257,29 @@ static int run_fasto(const xrfthip_plan* P, const ExecArgs& a) {
     xrfthip_plan::ProfRec* rec = prof_begin(P, "fasto_overlap_add", st);
     if (p.t.win) { auto k = &fasto_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
     else { auto k = &fasto_kernel<false>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
+    prof_end(rec, st);
+    HIP_TRY(hipGetLastError());
+    return XRFTHIP_OK;
+}
+
+// ... the filter: one launch, nothing else
+static int run_fastf(const xrfthip_plan* P, const ExecArgs& a) {
+    const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
+    FastF p{};
+    seg_args(P, p.t);
+    p.in = (const float*)a.in0; p.out = (float*)a.out;
+    p.twr = (const cf*)P->w_twr.p;
+    p.resp = (const cf*)P->phase[1].p;
+    p.NS = (int)(2 * kWPoints / d.nx); p.wgs = (int)filter_wgs(d);
+    p.K = (int)(d.nx - d.seg_hop + 1);
+    p.N = d.seg_in_len; p.n_out = d.seg_out_len; p.lead = d.seg_lead;
+    const long long nwg = d.batch / d.mean_batch * filter_wgs(d);
+    if (nwg > 0x7fffffffLL) return XRFTHIP_BAD_ARG;  // (try_fastf declined it)
+    const dim3 grid((unsigned)nwg), blk((unsigned)kWThreads);
+    xrfthip_plan::ProfRec* rec = prof_begin(P, "fastf_overlap_save", st);
+    if (p.resp) { auto k = &fastf_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
+    else { auto k = &fastf_kernel<false>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
     prof_end(rec, st);
     HIP_TRY(hipGetLastError());
     return XRFTHIP_OK;
@@ -261,8 +329,10 @@ static void describe_cols(const xrfthip_plan* plan, std::string& s, const char* 
             (long long)(d.batch / d.mean_batch), (long long)d.inner, (long long)d.seg_stride, plan->w_pitch, g.C, g.ngroups, 4 * g.C, g.seqs / g.C, units, g.C, unit, g.C, tail);
 }
 static void describe_fasto(const xrfthip_plan* plan, std::string& s, const char*);
+static void describe_fastf(const xrfthip_plan* plan, std::string& s, const char*);
 static void describe_fastk(const xrfthip_plan* plan, std::string& s, const char* note) {
     if (synth_plan(plan)) return describe_fasto(plan, s, note);
+    if (filter_plan(plan)) return describe_fastf(plan, s, note);
     const xrfthip_desc& d = plan->d;
     const SegGeom& g = plan->w;
     appendf(s, "  [fastw segments kept] spectrograms, one pass: %lld series of %lld segments of %lld samples, hop %lld (series pitch %lld), each segment read where it lies with "
@@ -285,6 +355,18 @@ static void describe_fasto(const xrfthip_plan* plan, std::string& s, const char*
             (long long)(d.batch / d.mean_batch), (long long)d.mean_batch, (long long)d.nx / 2 + 1, plan->w_pitch, g.span, (long long)d.seg_hop, kWThreads,
             (long long)(d.batch / d.mean_batch), g.wgs, g.NS, (long long)d.nx / 2, seg_radices(plan).c_str(), g.F, g.R - 1, g.R, plan->w.lds, kOResources);
 }
+static void describe_fastf(const xrfthip_plan* plan, std::string& s, const char*) {
+    const xrfthip_desc& d = plan->d;
+    appendf(s, "  [fastw overlap-save] FIR filter, one pass: %lld series of N = %lld samples (series pitch %lld) to %lld samples each from sample %lld of the full convolution, "
+               "K = %lld taps, segments of L = %lld samples of which V = %lld are kept; one %d-thread workgroup per (series, run): %lld x %lld workgroups, %lld segments "
+               "per tile, each read where it lies with guarded 4-byte loads (zeros outside the series) and packed with itself as a %lld-point sequence; radix %s in "
+               "place, per pair (k, n - k) unpacked, multiplied by the response (%s), packed and conjugated in registers and stored in natural order, radix %s again; "
+               "lanes store consecutive samples, each written once; no workspace, no second tile, no atomics; lds=%zuB; %s; 4 algorithmic bytes per sample read and 4 per "
+               "sample written\n",
+            (long long)(d.batch / d.mean_batch), (long long)d.seg_in_len, plan->w_pitch, (long long)d.seg_out_len, (long long)d.seg_lead, (long long)(d.nx - d.seg_hop + 1),
+            (long long)d.nx, (long long)d.seg_hop, kWThreads, (long long)(d.batch / d.mean_batch), filter_wgs(d), (long long)(2 * kWPoints / d.nx), (long long)d.nx / 2,
+            seg_radices(plan).c_str(), plan->phase[1].p ? "L / 2 + 1 complex64 entries" : "none set: ones, a delay", seg_radices(plan).c_str(), plan->w.lds, kFResources);
+}
 static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*) {
     const xrfthip_desc& d = plan->d;
     const SegGeom& g = plan->w;
@@ -299,7 +381,7 @@ static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*
 static void info_fastw(const xrfthip_plan* plan, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTW; *n = 2 * plan->w.seqs; }  // (per_workgroup: the segments of a round)
 static void info_fastk(const xrfthip_plan* plan, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTW; *n = plan->w.seqs; }
 // (the entries in the order of struct FamilyOps; reads_strided is false -- the series pitch is w_pitch, d.in_stride_batch is 0 -- and the last entry, no_generic_passes, true)
-static int finalize_fastk(xrfthip_plan* P) { return synth_plan(P) ? XRFTHIP_OK : fast_phase_tables(P); }  // (the synthesis takes no phase table)
+static int finalize_fastk(xrfthip_plan* P) { return synth_plan(P) || filter_plan(P) ? XRFTHIP_OK : fast_phase_tables(P); }  // (the synthesis takes no phase table; the filter's is its response, read as it was set)
 #ifndef __HIP_DEVICE_COMPILE__  /* host data: the device pass would emit a const object, and the launchers it points to do not exist there */
 const FamilyOps kOpsFastW = {Family::FastW, run_fastw, describe_fastw, info_fastw, fast_phase_tables, layout_fastw, nullptr, nullptr, false, nullptr, false, false, false, false, true};
 const FamilyOps kOpsFastK = {Family::FastK, run_fastk, describe_fastk, info_fastk, finalize_fastk, layout_fastk, nullptr, nullptr, false, nullptr, false, false, false, false, true};

@@ -66,6 +66,7 @@
 #include "fastw.h"
 #include "fastk.h"
 #include "fasto.h"
+#include "fastf.h"
 #ifdef XRFT_SPLIT_TUS  /* the library built from several translation units: the fasty / fastm kernels are instantiated in inst_g*.cpp */
 namespace xrft {
 #define XRFT_KW extern template __global__
@@ -344,7 +345,7 @@ enum class Family {
     FastRComplex,    // ... complex rows of 2048 .. 16384 points (fastc_kernel)
     FastRRows,       // complex rows of 256 .. 4096 points: the row pass of fasty_c2c.h on the input's own rows
     FastW,           // xrfthip_desc.seg_hop, Welch spectra: the mean spectrum of the overlapping segments of a series, rows or column layout (fastw.h)
-    FastK,           // ... with xrfthip_desc.seg_keep, spectrograms: every segment's spectrum kept (fastk.h); with seg_synth the way back, the series rebuilt from them (fasto.h)
+    FastK,           // ... with xrfthip_desc.seg_keep, spectrograms: every segment's spectrum kept (fastk.h); with seg_synth the way back, the series rebuilt from them (fasto.h); with seg_filter both in one tile, a series filtered by overlap-save (fastf.h)
     FastYC,          // the two passes of fasty_c2c.h over complex float32 slabs
     FastYCFourStep,  // ... over ONE long complex sequence per batch entry, the four-step form of pass 2
     FastY,           // the two y-first passes over real float32 slabs of powers of two (fasty.h)
@@ -607,7 +608,7 @@ inline bool dbl_phase_tables(const xrfthip_plan* P) { return P->dbl && family_op
 inline bool herm_field_plan(const xrfthip_plan* P) { return P && P->d.herm_ny > 0 && (P->d.flags & XRFTHIP_HERM_FIELD); }  // (... whose last pass writes the complex field)
 // The mean over the batch inside the last pass (xrfthip_desc.mean_batch, normalised by xrfthip_plan_create: 0 = off, else M > 1): the families with a mean form are
 // FastY's two-pass slabs and FastS below 256 points per axis with dense float32 input; every other family answers XRFTHIP_UNSUPPORTED_LENGTH (the caller composes).
-inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1 && !P->d.seg_keep && !P->d.seg_synth; }  // (seg_keep, seg_synth: mean_batch counts the segments of a series, nothing is averaged)
+inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1 && !P->d.seg_keep && !P->d.seg_synth && !P->d.seg_filter; }  // (seg_keep, seg_synth, seg_filter: mean_batch counts the segments of a series, nothing is averaged)
 inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || (P->family == Family::FastS && !P->coherence) || P->family == Family::FastW; }  // (FastS has no two-field form)
 size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs);  // (xrft_hip.cpp: mean_P and the partials behind `off`; returns the new end)
 int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStream_t st);  // (... and the finishing kernel, after the last group)
@@ -615,6 +616,7 @@ inline bool welch_cols(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.
 inline bool welch_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0; }  // (the descriptor asks for the segments of a series: served by FastW / FastK or not at all)
 inline bool keep_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_keep == 1; }  // (... every segment's spectrum kept, none averaged: Family::FastK, fastk.h)
 inline bool synth_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_synth == 1; }  // (... the series rebuilt from its segments' half spectra: the synthesis form of Family::FastK, fasto.h)
+inline bool filter_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_filter == 1; }  // (... a series filtered by overlap-save: the filter form of Family::FastK, fastf.h)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's
 // input take them: pass 1 of the two-pass families, the load of the one-pass families.  The intermediate and the output are dense.

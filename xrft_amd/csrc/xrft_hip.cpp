@@ -892,12 +892,12 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // (a descriptor of the version before `inner` was appended is accepted: inner = 1)
     // (... and of the versions before `mid` and before the input strides: mid = 1, strides 0)
     // (... and of the version before herm_ny / herm_nx: 0, 0)
-    // (... and before each later group of fields, which then read 0: mean_batch; seg_hop / seg_reserved; seg_stride / seg_reserved2; seg_keep / seg_reserved3; seg_synth / seg_reserved4 -- each
-    // pair came together, no size between)
+    // (... and before each later group of fields, which then read 0: mean_batch; seg_hop / seg_reserved; seg_stride / seg_reserved2; seg_keep / seg_reserved3; seg_synth / seg_reserved4; seg_filter / seg_lead /
+    // seg_in_len / seg_out_len -- each group came together, no size between)
     static const uint32_t kDescSizes[] = {
         (uint32_t)sizeof(xrfthip_desc), (uint32_t)offsetof(xrfthip_desc, inner), (uint32_t)offsetof(xrfthip_desc, mid), (uint32_t)offsetof(xrfthip_desc, in_stride_y),
         (uint32_t)offsetof(xrfthip_desc, herm_ny), (uint32_t)offsetof(xrfthip_desc, mean_batch), (uint32_t)offsetof(xrfthip_desc, seg_hop), (uint32_t)offsetof(xrfthip_desc, seg_stride),
-        (uint32_t)offsetof(xrfthip_desc, seg_keep), (uint32_t)offsetof(xrfthip_desc, seg_synth)};
+        (uint32_t)offsetof(xrfthip_desc, seg_keep), (uint32_t)offsetof(xrfthip_desc, seg_synth), (uint32_t)offsetof(xrfthip_desc, seg_filter)};
     if (!plan || !desc || std::find(std::begin(kDescSizes), std::end(kDescSizes), desc->struct_size) == std::end(kDescSizes)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);
@@ -907,11 +907,11 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     if (dcopy.mid == 0) dcopy.mid = 1;
     if (dcopy.in_stride_y < 0 || dcopy.in_stride_batch < 0) return XRFTHIP_BAD_ARG;
     if (dcopy.mean_batch < 0) return XRFTHIP_BAD_ARG;
-    // seg_hop / seg_stride / seg_keep / seg_synth: the segments of a series (host_welch.inc).  With seg_keep or seg_synth, mean_batch is the segments per series, 1
-    // included, and nothing is averaged
+    // seg_hop / seg_stride / seg_keep / seg_synth / seg_filter: the segments of a series (host_welch.inc).  With seg_keep, seg_synth or seg_filter, mean_batch is the
+    // segments per series, 1 included, and nothing is averaged
     long long w_pitch = 0;
     if (seg_desc_check(dcopy, &w_pitch)) return XRFTHIP_BAD_ARG;
-    const bool keep = dcopy.seg_keep == 1 || dcopy.seg_synth == 1;
+    const bool keep = dcopy.seg_keep == 1 || dcopy.seg_synth == 1 || dcopy.seg_filter == 1;
     if (dcopy.mean_batch == 1 && !keep) dcopy.mean_batch = 0;  // (the plain plan itself)
     {   // strides that say what a dense array says are the dense plan (any family serves it)
         const int64_t row = (dcopy.flags & XRFTHIP_C2R_X) ? dcopy.nx / 2 + 1 : dcopy.nx;
@@ -1047,6 +1047,7 @@ int xrfthip_plan_destroy(xrfthip_plan* plan) {
 int xrfthip_plan_set_window(xrfthip_plan* plan, int axis, const double* h_window, int64_t n) {
     if (!plan || axis < 0 || axis > 1) return XRFTHIP_BAD_ARG;
     if (herm_plan(plan) && axis == 1) return XRFTHIP_BAD_ARG;  // (the two-axis stage that wrote the half spectrum windowed y and x)
+    if (filter_plan(plan) && h_window) return XRFTHIP_BAD_ARG;  // (overlap-save takes no window: a windowed segment is not a linear filter's)
     if (h_window && n != (axis == 0 ? plan->d.ny : plan->d.nx)) return XRFTHIP_BAD_ARG;
     if (plan->sub_x) return xrfthip_plan_set_window(axis == 0 ? plan->sub_y : plan->sub_x, (axis == 1 && plan->sub_x_1d) ? 1 : 0, h_window, n);  // (each one-axis plan transforms its "y"; a 1-D x stage its x)
     if (axis == 0) plan->host_win_y.assign(h_window ? h_window : nullptr, h_window ? h_window + n : nullptr);
@@ -1066,6 +1067,10 @@ int xrfthip_plan_set_phase(xrfthip_plan* plan, int axis, const double* h_phase, 
     }
     if (!plan || axis < 0 || axis > 1 || herm_plan(plan)) return XRFTHIP_BAD_ARG;  // (herm: the twin of a sample at a Nyquist index does not carry the conjugate factor)
     if (synth_plan(plan) && h_phase) return XRFTHIP_BAD_ARG;  // (the synthesis has no phase: each segment's spectrum refers to its own first sample)
+    if (filter_plan(plan)) {  // the filter's response: L / 2 + 1 entries on axis 1, kept as complex64 next to the plan's other tables (fastf.h reads phase[1])
+        if (axis != 1 || (h_phase && n != plan->d.nx / 2 + 1)) return XRFTHIP_BAD_ARG;
+        return upload_real_table(plan, plan->phase[1], h_phase, n, 1);
+    }
     if (keep_plan(plan) && plan->d.out_mode == XRFTHIP_OUT_COMPLEX && h_phase) return XRFTHIP_UNSUPPORTED_LENGTH;  // (the "segments kept" form writes X itself: the caller composes)
     // an input phase of a c2r transform covers the stored half of the x axis only
     const int64_t want = axis == 0 ? plan->d.ny : ((plan->d.flags & XRFTHIP_C2R_X) ? plan->d.nx / 2 + 1 : plan->d.nx);

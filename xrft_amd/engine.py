@@ -40,7 +40,8 @@ class SpectralPlan:
 
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
-                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0, seg_stride=0, seg_keep=0, seg_synth=0):
+                 slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0, seg_stride=0, seg_keep=0, seg_synth=0,
+                 seg_filter=0, seg_lead=0, seg_in_len=0, seg_out_len=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
@@ -80,9 +81,16 @@ class SpectralPlan:
         self.seg_synth = int(seg_synth)
         if self.seg_synth:
             self.batch_out = self.batch // max(self.mean_batch, 1)
-        d = _lib.DescSynth(C.sizeof(_lib.DescSynth), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
+        # a series filtered by overlap-save (xrfthip_desc.seg_filter; float32, flags 0): nx = L the segment length, seg_hop = V the samples kept of each, mean_batch =
+        # ceil(seg_out_len / V) the segments of a series; the input is (series, seg_in_len) -- in_stride_batch the pitch between series in samples -- and the result
+        # (series, seg_out_len), real float32, from sample seg_lead of the full convolution; phase_x carries the response, nx / 2 + 1 entries
+        self.seg_filter, self.seg_lead, self.seg_in_len, self.seg_out_len = int(seg_filter), int(seg_lead), int(seg_in_len), int(seg_out_len)
+        if self.seg_filter:
+            self.batch_out = self.batch // max(self.mean_batch, 1)
+        d = _lib.DescFilt(C.sizeof(_lib.DescFilt), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
                       int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
-                      self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0, self.seg_stride, 0, self.seg_keep, 0, self.seg_synth, 0)
+                      self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0, self.seg_stride, 0, self.seg_keep, 0, self.seg_synth, 0,
+                      self.seg_filter, self.seg_lead, self.seg_in_len, self.seg_out_len)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
         for axis, w in ((0, window_y), (1, window_x)):
             if w is not None:
@@ -154,7 +162,7 @@ class SpectralPlan:
         return out
 
     def out_dtype(self):
-        real = self.out_mode in (_lib.OUT_POWER, _lib.OUT_PHASE, _lib.OUT_COHERENCE) or (self.flags & _lib.C2R_X)
+        real = self.out_mode in (_lib.OUT_POWER, _lib.OUT_PHASE, _lib.OUT_COHERENCE) or (self.flags & _lib.C2R_X) or self.seg_filter  # (the filtered series is real)
         return _REAL_OF[self.dtype] if real else _CPLX_OF[self.dtype]
 
     def _layout_ok(self, t):
@@ -164,6 +172,9 @@ class SpectralPlan:
             nb = self.nx // 2 + 1
             return (t.dim() == 3 and tuple(t.shape) == (self.batch_out, self.mean_batch, nb) and (t.stride(2) == 1 or nb == 1) and (t.stride(1) == nb or self.mean_batch == 1)
                     and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or self.mean_batch * nb)))
+        if self.seg_hop and self.seg_filter:  # (series, samples): exactly seg_in_len samples a series, adjacent, the series the plan's pitch apart
+            return (t.dim() == 2 and tuple(t.shape) == (self.batch_out, self.seg_in_len) and (t.stride(1) == 1 or self.seg_in_len == 1)
+                    and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or self.seg_in_len)))
         if self.seg_hop and self.seg_stride > 1:  # (blocks, samples, columns): exactly the view the plan addresses -- columns adjacent, samples seg_stride apart, blocks the plan's pitch apart
             span = (self.mean_batch - 1) * self.seg_hop + self.nx
             return (t.dim() == 3 and t.shape[0] == self.batch_out and t.shape[1] >= span and t.shape[2] == self.inner
@@ -203,6 +214,8 @@ class SpectralPlan:
                 shape = (self.batch_out, self.mean_batch, self.nx_out) + ((self.inner,) if self.seg_stride > 1 else ())
             if self.seg_hop and self.seg_synth:  # (the series)
                 shape = (self.batch_out, (self.mean_batch - 1) * self.seg_hop + self.nx)
+            if self.seg_hop and self.seg_filter:  # (the filtered series)
+                shape = (self.batch_out, self.seg_out_len)
             if self.mid > 1:
                 shape = (self.batch, self.ny_out, self.mid, self.nx_out, self.inner)
             if self.herm_ny:
@@ -212,6 +225,8 @@ class SpectralPlan:
             need = self.batch_out * self.ny_out * self.nx_out * self.inner * self.mid * (self.mean_batch if self.seg_keep else 1)
             if self.seg_hop and self.seg_synth:
                 need = self.batch_out * ((self.mean_batch - 1) * self.seg_hop + self.nx)
+            if self.seg_hop and self.seg_filter:
+                need = self.batch_out * self.seg_out_len
             if out.dtype != self.out_dtype() or not out.is_contiguous() or out.numel() != need or out.device != dev:
                 raise ValueError(f"out does not match the plan (dtype {self.out_dtype()}, contiguous, {need} elements on {dev})")
         iso_dtype = torch.complex128 if self.out_mode == _lib.OUT_CROSS else torch.float64
