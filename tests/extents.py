@@ -18,10 +18,23 @@ batch_mean.bound, welch.bound, coherence.bound.  No tolerance of its own.
 check() is the one checker: the windows (whole periods: the first, the last, every period that holds a boundary slab) slab by slab against float64; EVERY slab on
 the device against its member of the first period, || out[k] - out[k % 48] || <= 2 bound || out[k % 48] || and finite -- bit for bit where EXACT says so --; the
 guard bands around output, radial sums and workspace unchanged.  run_banded() executes through xrfthip_exec with its own pointers: output, sums and workspace carved
-from one device buffer, 1 MiB of 0xA5 in front of and behind each, the workspace exactly xrfthip_workspace_bytes, the output 0xFF (NaN) before the call."""
+from one device buffer, 1 MiB of 0xA5 in front of and behind each, the workspace exactly xrfthip_workspace_bytes, the output 0xFF (NaN) before the call.
+
+The segment kernels (spectrogram fastk.h, istft fasto.h, fir_filter fastf.h: the three non-Welch forms of Family::FastK) have cases of their own on every rung,
+because their offsets grow INSIDE a series: (s0 + sl) hop + j, s0 (n + 1), first / idx < N / o0, obase + r.  Beside the batch-direction cases (48 series or columns,
+tiled) the period lies ALONG one series (run_along, check(along=Along(...))): a pattern of 48 H (48 V) samples, or 48 half spectra, repeated; N a whole number of
+periods.  The reference is spectrogram.reference / istft.model / fir_filter.model on a SHORT series of four periods, whose first, second and last periods are exactly
+the first, every interior and the last period of the long one, and whose K - 1 / L - H samples behind the last whole period are its tail.  The first and last periods
+(the zeros outside a filtered series, the segments an overlap-add lacks at its ends) are held to float64 only, every interior period to the bits of the first interior
+one (SEGMENT_EXACT).  Rung A: 70 080 series or columns, several workgroups each, the last one short.  Rung B: one series of 2^26 segments per kernel (sample offsets
+beyond 2^31 inside the series: 17 to 26 GiB), dense batches of short series, and the column layout's output beyond 2^31 elements inside one block.  Rung C: a series
+pitch of 2^30 + 5, a sample stride of 2^20.  Rung D: check_segment_guards().
+Not covered: API-level calls at these sizes (xrft_amd.istft on a span past 2^31 - 1, where the fused plan declines and the composed route runs), 2^32 complex
+elements of istft input, L = 4096 variants of the one-series cases (the same code path with other constants)."""
 import contextlib
 import ctypes as C
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -33,6 +46,9 @@ import accuracy as A
 import batch_mean as B
 import coherence as CO
 import decorations as D
+import fir_filter as FF
+import istft as IS
+import spectrogram as SP
 import strided as S
 import welch as W
 import welch_cols as WC
@@ -126,16 +142,19 @@ def second_period(v, seed):
 LIMITS = (("2^31 elements", 1 << 31, False), ("2^32 bytes", 1 << 32, True), ("2^33 bytes", 1 << 33, True))
 
 
-def boundaries(n, in_elems, in_esz, out_elems, out_esz, period=PERIOD):
+MORE_LIMITS = LIMITS + (("2^34 bytes", 1 << 34, True),)  # (the synthesis reads 8-byte elements: 2^31 of them)
+
+
+def boundaries(n, in_elems, in_esz, out_elems, out_esz, period=PERIOD, limits=LIMITS):
     """{name: the first of `n` slabs whose input / output element offset is at or above 2^31, whose byte offset is at or above 2^32 / 2^33} -- those the case reaches.
     in_elems / out_elems: elements per slab (per output of the period's index); a wrap distance that is a whole number of slabs is no multiple of the period."""
     out = {}
     for side, per, esz in (("input", in_elems, in_esz), ("output", out_elems, out_esz)):
         if not per:
             continue
-        for wrap, step in ((1 << 31, per), (1 << 32, per), (1 << 32, per * esz), (1 << 33, per * esz)):  # 2^31, 2^32 elements; 2^32, 2^33 bytes
-            assert wrap % step != 0 or (wrap // step) % period != 0, (side, wrap, step)
-        for name, lim, in_bytes in LIMITS:
+        for wrap, step in ((1 << 31, per), (1 << 32, per), (1 << 32, per * esz), (1 << 33, per * esz)) + (((1 << 34, per * esz),) if limits is MORE_LIMITS else ()):
+            assert wrap % step != 0 or (wrap // step) % period != 0, (side, wrap, step)  # 2^31, 2^32 elements; 2^32, 2^33 (2^34) bytes
+        for name, lim, in_bytes in limits:
             step = per * esz if in_bytes else per
             k = -(-lim // step)
             if k < n:
@@ -178,10 +197,92 @@ def absolute_accurate(bnd):
     return f
 
 
-def check(out, ref, bnd, bounds, accurate, exact=False, bands=(), period=PERIOD, what="", chunk_bytes=256 << 20, absolute=False):
+class Along:
+    """The period lies ALONG a series (the segment kernels): the slabs are the series' segments (blocks of kept samples), and its two ends are not copies of its
+    middle -- the zeros outside a filtered series, the segments an overlap-add lacks at its ends.
+    member: the period of `out` every interior period is compared with, and the period of `ref` it is checked against (the first interior one);
+    edges: {period of out: period of ref} -- held to float64 only, each a window; ref: [periods of the SHORT series x period, ...], computed on four periods;
+    tail: (got, check(got, what)) -- the K - 1 / L - H samples behind the last whole period, held to float64 and finite;
+    whole: accurate(got [period, e], ref [period, e], period of ref, what) takes a whole period (a norm-wise bound over its 48 segments), bnd is then one ABSOLUTE
+    bound per period of ref and the all-period form || out[q] - out[member] ||_2 <= 2 bnd[member]."""
+
+    def __init__(self, member=1, edges=None, tail=None, whole=False):
+        self.member, self.edges, self.tail, self.whole = member, dict(edges or {}), tail, whole
+
+
+def _check_along(out, ref, bnd, bounds, accurate, exact, bands, period, what, chunk_bytes, along):
+    n = out.shape[0]
+    nq = n // period
+    mb = along.member
+    assert n % period == 0 and ref.shape[0] % period == 0 and 0 <= mb < min(nq, ref.shape[0] // period) and mb not in along.edges, (n, period, ref.shape, mb)
+    assert all(0 <= q < nq and 0 <= rp < ref.shape[0] // period for q, rp in along.edges.items()), (along.edges, nq)
+    o2 = _real2d(out)
+    # 2. windows against the float64 reference: the edges, the first and the last period, every one that holds a boundary
+    wins = {0: "first", nq - 1: "last"}
+    for name, k in bounds.items():
+        assert 0 <= k < n, (name, k, n)
+        wins.setdefault(k // period, name)
+    for q in along.edges:
+        wins.setdefault(q, "edge")
+    for q, name in sorted(wins.items()):
+        rp = along.edges.get(q, mb)
+        host = out[q * period:(q + 1) * period].cpu().numpy()
+        if along.whole:
+            accurate(host, ref[rp * period:(rp + 1) * period], rp, f"{what} period {q} ({name})")
+        else:
+            for j in range(period):
+                accurate(host[j], ref[rp * period + j], rp * period + j, f"{what} slab {q * period + j} (period {q}: {name})")
+    if along.tail is not None:
+        got, tail_ok = along.tail
+        got = got.cpu().numpy()
+        assert np.isfinite(got).all(), f"{what}: the tail behind the last whole period holds a value that is not finite"
+        tail_ok(got, f"{what} tail")
+    # 3. every interior period against the member period, on the device
+    base = o2[mb * period:(mb + 1) * period]
+    assert bool(torch.isfinite(base).all()), f"{what}: a value of the member period is not finite"
+    if along.whole:
+        lim = torch.full((1, 1), (2.0 * float(np.asarray(bnd, dtype=np.float64).reshape(-1)[mb])) ** 2, dtype=torch.float64, device=out.device)
+    else:
+        b2 = torch.as_tensor(np.broadcast_to(np.asarray(bnd, dtype=np.float64), (ref.shape[0],))[mb * period:(mb + 1) * period].copy(), device=out.device)
+        lim = ((2.0 * b2) ** 2 * base.double().pow(2).sum(1)).reshape(1, period)
+    interior = torch.ones(nq, dtype=torch.bool, device=out.device)
+    for q in along.edges:
+        interior[q] = False
+    per_chunk = max(1, chunk_bytes // max(1, period * o2.shape[1] * o2.element_size()))
+    same = True
+    for q0 in range(0, nq, per_chunk):
+        q1 = min(nq, q0 + per_chunk)
+        c = o2[q0 * period:q1 * period].reshape(q1 - q0, period, -1)
+        fin = torch.isfinite(c).all(2)
+        if not bool(fin.all()):
+            q, j = [int(v[0]) for v in torch.nonzero(~fin, as_tuple=True)]
+            raise AssertionError(f"{what}: slab {(q0 + q) * period + j} holds a value that is not finite")
+        ins = interior[q0:q1].reshape(-1, 1)
+        d = (c - base).double().pow(2).sum(2)
+        if along.whole:
+            d = d.sum(1, keepdim=True)
+        bad = (d > lim) & ins
+        if bool(bad.any()):
+            q, j = [int(v[0]) for v in torch.nonzero(bad, as_tuple=True)]
+            unit = f"period {q0 + q}" if along.whole else f"slab {(q0 + q) * period + j}"
+            raise AssertionError(f"{what}: {unit} is {float(d[q, j]) ** 0.5:.3e} from its member of period {mb}, more than {float(lim.reshape(-1)[j if not along.whole else 0]) ** 0.5:.3e}")
+        same = same and bool(((c == base).all(2) | ~ins).all())
+    print(f"{what}: {n} slabs along the series, windows {sorted(set(wins.values()))}, bit-identical across the batch: {same}")
+    if exact:
+        assert same, f"{what}: an interior period differs in its bits from period {mb}"
+    for i, band in enumerate(bands):
+        assert bool((band == PATTERN).all()), f"{what}: guard band {i} was written"
+    return same
+
+
+def check(out, ref, bnd, bounds, accurate, exact=False, bands=(), period=PERIOD, what="", chunk_bytes=256 << 20, absolute=False, along=None):
     """out: [n, ...] tensor on any device, n a multiple of `period`; ref: [period, ...] float64 / complex128; bnd: the bound (a number, or one per member of the
     period); bounds: {name: slab index} from boundaries(); accurate(got, ref_j, j, what): the window check; bands: uint8 tensors that must still hold PATTERN.
-    absolute: the all-slab form is || out[k] - out[k % period] || <= 2 bound sqrt(elements) (a coherence).  Returns whether every slab equalled its member bit for bit."""
+    absolute: the all-slab form is || out[k] - out[k % period] || <= 2 bound sqrt(elements) (a coherence).  along: an Along -- the period lies along a series, whose
+    first and last periods are edges (class Along); left out, nothing changes.  Returns whether every slab equalled its member bit for bit."""
+    if along is not None:
+        assert not absolute
+        return _check_along(out, ref, bnd, bounds, accurate, exact, bands, period, what, chunk_bytes, along)
     n = out.shape[0]
     assert n % period == 0 and n >= period and ref.shape[0] == period, (n, period, ref.shape)
     o2 = _real2d(out)
@@ -254,6 +355,12 @@ class Banded:
 
 def out_shape(plan):
     """(outputs, elements per output) of a plan's result."""
+    if getattr(plan, "seg_synth", 0):  # (the series)
+        return plan.batch_out, (plan.mean_batch - 1) * plan.seg_hop + plan.nx
+    if getattr(plan, "seg_filter", 0):  # (the filtered series)
+        return plan.batch_out, plan.seg_out_len
+    if getattr(plan, "seg_keep", 0):  # (every segment's spectrum; the column layout: [block][segment][frequency][column])
+        return plan.batch_out, plan.mean_batch * plan.nx_out * (plan.inner if plan.seg_stride > 1 else 1)
     if plan.herm_ny:
         return plan.batch, plan.ny * plan.herm_ny * plan.herm_nx
     if plan.seg_hop and plan.seg_stride > 1:
@@ -692,6 +799,415 @@ def run_welch_cols_strided(cid, dev, s=1 << 20, c=(64, 32, 69, 2, 40), beyond=1 
         release(dev)
 
 
+# ---------------------------------------------------------------------------------- the segment kernels: spectrogram, istft, fir_filter
+# The three non-Welch forms of Family::FastK (fastk.h, fasto.h, fastf.h; launched from host_welch.inc).  Their workload is ONE very long series, so their offsets grow
+# inside a series: the period of 48 lies ALONG it (run_along) -- a pattern of 48 H (48 V) samples, 48 half spectra, repeated -- as well as across the batch
+# (run_batch, run_keep_cols: 48 series or columns, tiled, the scheme of the Welch runners above).
+# Reference: spectrogram.reference, istft.model, fir_filter.model (scipy's direct float64 convolution) on a SHORT series of four periods: with N a whole number of
+# periods, its first, second and last periods are exactly the first, every interior and the last period of the long series, and the K - 1 / L - H samples behind
+# its last whole period are the long series' tail.  Bound: what those files' check_plan functions apply -- accuracy.bound per segment; istft.the_bound and
+# fir_filter.the_bound with A over ONE period's 48 segments (the batch runners: over one series' segments).  No tolerance of the ladder's own.
+#
+# All three are held to bit identity, across the batch and along the series (an interior period has the bits of the first interior period), from the code:
+SEGMENT_EXACT = {
+    "spectrogram": "fastk.h:44-50: a workgroup is one round of ONE series (one group of columns); :61-75 every output element from its own segment's sequence, a "
+                   "segment packed with itself, computed and stored by one thread; seg_tile.h:86-110 the detrend's sums per segment over a fixed tree",
+    "istft": "fasto.h:42-48: a workgroup is NS consecutive segments of ONE series; :79-91 every sample gathered by one thread over its own covering segments in "
+             "ascending order, the place in the tile (m, sl) enters the addresses only",
+    "fir_filter": "fastf.h:45-59: a workgroup is NS consecutive segments of ONE series, each packed with itself, the guard idx < N per sample; :104-112 every kept "
+                  "sample written once from its own segment",
+}
+FORM = "linear-hann-shift"
+
+
+class Worst:
+    """The largest figure / bound a case met (printed once per case, before the checker's verdict on the bits)."""
+
+    def __init__(self):
+        self.ratio = 0.0
+
+    def within(self, fig, bnd, what):
+        fig = np.asarray(fig, dtype=np.float64)
+        ok = np.isfinite(fig).all() and bool((fig <= bnd).all())
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.ratio = max(self.ratio, float(np.max(np.where(np.asarray(bnd) > 0, fig / bnd, np.where(fig > 0, np.inf, 0.0)))))
+        assert ok, f"{what}: {float(np.max(fig)):.3e} against the bound {float(np.max(bnd)):.3e}"
+
+
+def _rows_rms(got, ref):
+    """accuracy.errors' first figure, || got - ref ||_2 / || ref ||_2, for every row at once."""
+    wide = np.complex128 if np.iscomplexobj(ref) else np.float64
+    d = np.abs(np.asarray(got).astype(wide) - ref) ** 2
+    return np.sqrt(d.mean(-1) / (np.abs(ref) ** 2).mean(-1))
+
+
+def _keep_dt(mode):
+    return "float32" if mode == L.OUT_POWER else "complex64"
+
+
+def _amp(v):
+    return float(np.sqrt(np.sum(np.abs(v) ** 2)))
+
+
+def _rows_plan(l, h, m, p, mode):
+    plan = SP.make_plan((l, h, m, p), FORM, mode)
+    SP.assert_keep_plan(plan)
+    assert "[fastw columns]" not in plan.describe(), plan.describe()
+    return plan
+
+
+# ---- the period along the series: .plan(q) for q periods, .pattern (one period of input elements), elements per member in and out, the tails, .reference(qs)
+def keep_along(l, h, mode=L.OUT_POWER):
+    """A spectrogram of ONE series: a pattern of 48 H samples (stretch j of H samples scaled by 1 + j / 48) repeated, L - H samples more; slab = a segment's spectrum."""
+    x, x64 = A.tensor(period_field((h,), (0,), False, seed=31), A.F32)
+    dt = _keep_dt(mode)
+
+    def reference(qs):
+        xs = np.concatenate([np.tile(x64.reshape(-1), qs), x64.reshape(-1)[:l - h]])[None]
+        case = (l, h, qs * PERIOD, 1)
+        ref, kaps = SP.reference(case, FORM, xs, mode)[0], SP.kappas(case, FORM, xs)[0]
+        bnd = np.array([A.bound(dt, l, k) for k in kaps])
+        worst = Worst()
+
+        def accurate(got, r, j, what):
+            worst.within(A.errors(got.reshape(r.shape), r)[0], bnd[j], what)
+        return SimpleNamespace(ref=ref, bnd=bnd, accurate=accurate, tail=None, whole=False, worst=worst)
+
+    return SimpleNamespace(plan=lambda q: _rows_plan(l, h, q * PERIOD, 1, mode), reference=reference, pattern=x.reshape(-1), in_step=h, in_tail=l - h, out_step=l,
+                           out_periods=lambda q: q, out_tail=0, limits=LIMITS)
+
+
+def synth_spectra(l, h, m, p, wname):
+    """[p][m][L / 2 + 1] complex64 and its complex128 image: istft.spectra (the stft of spectrogram.series), segment j (p = 1) or series j further scaled by 1 + j / 48."""
+    z = IS.spectra((l, h, m, p), wname).astype(np.complex128)
+    z *= (1.0 + np.arange(PERIOD) / PERIOD).reshape((1, -1, 1) if p == 1 else (-1, 1, 1))
+    return A.tensor(z, torch.complex64)
+
+
+def _synth_plan(l, h, m, p, wname):
+    plan = IS.make_plan((l, h, m, p), wname)
+    IS.assert_synth_plan(plan)
+    return plan
+
+
+def synth_along(l, h, wname="hann"):
+    """An istft of ONE series: 48 distinct half spectra, repeated; slab = H samples, the L - H samples behind the last segment's start + H the tail.  The samples of
+    a period are those of its 48 segments' hops: A over 48 segments bounds the first period (segments 0 .. 47 alone cover it) and an interior or last one (it holds
+    the tails of the R - 1 segments before it and lacks the tails of its own last R - 1: the same 48 segments' errors, once each)."""
+    spec, spec128 = synth_spectra(l, h, PERIOD, 1, wname)
+    w, r = IS.window(wname, l), IS.ceil_div(l, h)
+
+    def reference(qs):
+        m = qs * PERIOD
+        zs = np.tile(spec128[0], (qs, 1))[None]
+        ref, dp, _ = IS.model(zs, l, h, w, 1.0 / l)
+        segs = IS.inverse_segments(zs, l, 1.0 / l)[0]
+        body = m * h
+        bnd = np.array([IS.the_bound(l, h, _amp(segs[rp * PERIOD:(rp + 1) * PERIOD])) for rp in range(qs)])
+        dpp = dp[:body].reshape(qs, -1)
+        worst = Worst()
+
+        def accurate(got, rr, rp, what):
+            worst.within(IS.figure(got.reshape(-1), rr.reshape(-1), dpp[rp]), bnd[rp], what)
+
+        def tail(got, what):  # (covered by the last R - 1 segments)
+            worst.within(IS.figure(got, ref[0, body:], dp[body:]), IS.the_bound(l, h, _amp(segs[m - (r - 1):])), what)
+        return SimpleNamespace(ref=ref[0, :body].reshape(m, h), bnd=bnd, accurate=accurate, tail=tail, whole=True, worst=worst)
+
+    return SimpleNamespace(plan=lambda q: _synth_plan(l, h, q * PERIOD, 1, wname), reference=reference, pattern=spec.reshape(-1), in_step=l // 2 + 1, in_tail=0,
+                           out_step=h, out_periods=lambda q: q, out_tail=l - h, limits=MORE_LIMITS)
+
+
+def _filter_plan(l, k, n, p, mode, taps):
+    plan = FF.make_plan((l, k, n, p), mode, taps)
+    FF.assert_filter_plan(plan)
+    return plan
+
+
+def _filter_unit(x64, taps, l, a, n_out, segs):
+    """(2 b + 4 u) Hmax of fir_filter.the_bound: the bound per unit of A."""
+    return FF.the_bound(x64, taps, l, a, n_out) / _amp(segs)
+
+
+def filter_along(l, k, mode="same", kind="normal"):
+    """A fir_filter of ONE series: a pattern of 48 V samples (stretch j of V samples scaled by 1 + j / 48) repeated, N a whole number of periods; slab = the V
+    samples kept of a segment; the tail: K - 1 samples ("full"), none ("same"), a period less K - 1 samples behind one period fewer ("valid")."""
+    v = l - k + 1
+    x, x64 = A.tensor(period_field((v,), (0,), False, seed=33), A.F32)
+    taps = FF.taps_of(kind, k)
+    per = PERIOD * v
+
+    def sizes(q):
+        a, n_out = FF.offsets(mode, q * per, k)
+        return q * per, a, n_out
+
+    def reference(qs):
+        n, a, n_out = sizes(qs)
+        xs = np.tile(x64.reshape(-1), qs)[None]
+        ref = FF.model(xs, taps, mode)[0]
+        segs = FF.segment_inputs(xs, l, k, a, n_out)[0]
+        unit = _filter_unit(xs, taps, l, a, n_out, segs)
+        nq = n_out // per
+        bnd = np.array([unit * _amp(segs[rp * PERIOD:(rp + 1) * PERIOD]) for rp in range(nq)])
+        worst = Worst()
+
+        def accurate(got, rr, rp, what):
+            worst.within(FF.figure(got.reshape(-1), rr.reshape(-1)), bnd[rp], what)
+
+        def tail(got, what):
+            worst.within(FF.figure(got, ref[nq * per:]), unit * _amp(segs[nq * PERIOD:]), what)
+        return SimpleNamespace(ref=ref[:nq * per].reshape(nq * PERIOD, v), bnd=bnd, accurate=accurate, tail=tail, whole=True, worst=worst)
+
+    return SimpleNamespace(plan=lambda q: _filter_plan(l, k, q * per, 1, mode, taps), reference=reference, pattern=x.reshape(-1), in_step=v, in_tail=0, out_step=v,
+                           out_periods=lambda q: sizes(q)[2] // per, out_tail=sizes(4)[2] % per, limits=LIMITS)
+
+
+def along_input(pattern, q, tail, dev):
+    """The pattern q times and `tail` elements of it more, built in place on the device."""
+    pat = pattern.to(dev)
+    body = q * pat.numel()
+    buf = torch.empty(body + tail, dtype=pat.dtype, device=dev)
+    buf[:body].view(q, -1).copy_(pat.reshape(1, -1).expand(q, -1))
+    buf[body:].copy_(pat[:tail])
+    return buf
+
+
+def run_along(cid, c, q, dev, qs=4):
+    """One series of q periods: the first and the last period (edges) and every period that holds a boundary against the short series' float64 reference, every
+    interior period bit for bit against the first interior one, the tail, the guard bands.  Returns (plan, the boundaries reached, whether the bits repeated)."""
+    assert q >= 3 and qs >= 4
+    plan = c.plan(q)
+    nqo, nqs = c.out_periods(q), c.out_periods(qs)
+    n_in, body = q * PERIOD * c.in_step + c.in_tail, nqo * PERIOD * c.out_step
+    series, e = out_shape(plan)
+    assert series == 1 and e == body + c.out_tail and plan.workspace_bytes == 0, (series, e, body, c.out_tail)
+    isz, osz = esize(c.pattern.dtype), esize(plan.out_dtype())
+    need = device_bytes(plan, n_in * isz)
+    print(f"{cid}: one series of {q} periods of {PERIOD} segments, {n_in} elements in and {e} out, {need / 2 ** 30:.2f} GiB of device memory (workspace {plan.workspace_bytes} bytes)")
+    ok, why = enough_memory(need, dev)
+    if not ok:
+        raise NeedsMemory(why)
+    bounds = boundaries(nqo * PERIOD, c.in_step, isz, c.out_step, osz, limits=c.limits)
+    try:
+        x = along_input(c.pattern, q, c.in_tail, dev)
+        out, _, bands = run_banded(plan, x)
+        del x
+        flat = out.reshape(-1)
+        r = c.reference(qs)
+        along = Along(1, {0: 0, nqo - 1: nqs - 1}, (flat[body:], r.tail) if c.out_tail else None, r.whole)
+        same = check(flat[:body].reshape(nqo * PERIOD, c.out_step), r.ref, r.bnd, bounds, r.accurate, exact=True, bands=bands, what=cid, along=along)
+        print(f"{cid}: boundaries {bounds}; worst figure / bound {r.worst.ratio:.3f}")
+        return plan, bounds, same
+    finally:
+        out = flat = bands = along = None
+        release(dev)
+
+
+# ---- the period across the batch: 48 series, tiled
+def keep_batch(l, h, m, mode=L.OUT_POWER):
+    sp = (m - 1) * h + l
+    x, x64 = A.tensor(period_field((sp,), (0,), False, seed=35), A.F32)
+    dt = _keep_dt(mode)
+
+    def reference():
+        case = (l, h, m, PERIOD)
+        ref, kaps = SP.reference(case, FORM, x64, mode), SP.kappas(case, FORM, x64)
+        bnd = np.array([[A.bound(dt, l, k) for k in ks] for ks in kaps])
+        worst = Worst()
+
+        def accurate(got, r, j, what):  # (every segment within the bound of one transform, as spectrogram.assert_segments)
+            worst.within(_rows_rms(got.reshape(r.shape), r), bnd[j], what)
+        return SimpleNamespace(ref=ref, bnd=bnd.max(1), accurate=accurate, worst=worst)
+
+    return SimpleNamespace(plan=lambda p: _rows_plan(l, h, m, p, mode), reference=reference, data=x, limits=LIMITS)
+
+
+def synth_batch(l, h, m, wname="hann"):
+    spec, spec128 = synth_spectra(l, h, m, PERIOD, wname)
+    w = IS.window(wname, l)
+
+    def reference():
+        ref, dp, _ = IS.model(spec128, l, h, w, 1.0 / l)
+        segs = IS.inverse_segments(spec128, l, 1.0 / l)
+        bnd = np.array([IS.the_bound(l, h, _amp(s)) for s in segs])
+        worst = Worst()
+
+        def accurate(got, r, j, what):
+            worst.within(IS.figure(got, r, dp), bnd[j], what)
+        # (the all-slab pass holds these kernels to bit identity; the relative figure it takes only words the message of a slab that differs)
+        return SimpleNamespace(ref=ref, bnd=bnd / np.sqrt((ref ** 2).sum(1)), accurate=accurate, worst=worst)
+
+    return SimpleNamespace(plan=lambda p: _synth_plan(l, h, m, p, wname), reference=reference, data=spec.reshape(PERIOD, -1), limits=MORE_LIMITS)
+
+
+def filter_batch(l, k, n, mode="same", kind="normal"):
+    x, x64 = A.tensor(period_field((n,), (0,), False, seed=37), A.F32)
+    taps = FF.taps_of(kind, k)
+    a, n_out = FF.offsets(mode, n, k)
+
+    def reference():
+        ref = FF.model(x64, taps, mode)
+        segs = FF.segment_inputs(x64, l, k, a, n_out)
+        unit = _filter_unit(x64, taps, l, a, n_out, segs)
+        bnd = np.array([unit * _amp(s) for s in segs])
+        worst = Worst()
+
+        def accurate(got, r, j, what):
+            worst.within(FF.figure(got, r), bnd[j], what)
+        return SimpleNamespace(ref=ref, bnd=bnd / np.sqrt((ref ** 2).sum(1)), accurate=accurate, worst=worst)
+
+    return SimpleNamespace(plan=lambda p: _filter_plan(l, k, n, p, mode, taps), reference=reference, data=x, limits=LIMITS)
+
+
+def run_batch(cid, c, p, dev):
+    """p dense series of a PERIOD of 48: the windows series by series against float64, every series bit for bit against its member of the first period, the bands."""
+    assert p % PERIOD == 0
+    plan = c.plan(p)
+    n, e = out_shape(plan)
+    in_elems = c.data[0].numel()
+    isz, osz = esize(c.data.dtype), esize(plan.out_dtype())
+    assert n == p and plan.workspace_bytes == 0
+    need = device_bytes(plan, p * in_elems * isz)
+    print(f"{cid}: {p} series, {in_elems} elements in and {e} out each, {need / 2 ** 30:.2f} GiB of device memory (workspace {plan.workspace_bytes} bytes)")
+    ok, why = enough_memory(need, dev)
+    if not ok:
+        raise NeedsMemory(why)
+    bounds = boundaries(p, in_elems, isz, e, osz, limits=c.limits)
+    try:
+        x = tiled(c.data, p, dev)
+        out, _, bands = run_banded(plan, x)
+        del x
+        r = c.reference()
+        same = check(out, r.ref, r.bnd, bounds, r.accurate, exact=True, bands=bands, what=cid)
+        print(f"{cid}: boundaries {bounds}; worst figure / bound {r.worst.ratio:.3f}")
+        return plan, bounds, same
+    finally:
+        out = bands = None
+        release(dev)
+
+
+def run_keep_cols(cid, l, h, m, blocks, inner, dev):
+    """Spectrogram columns (POWER): `blocks` dense blocks of `inner` adjacent columns (seg_stride = inner) of a PERIOD of 48 columns; block b carries a further factor
+    2^b, which scales its spectra by 4^b exactly and is taken out again before the check (run_welch_cols).  The result [block][segment][frequency][column] is checked
+    with the columns first.  Returns (plan, the boundaries the output rows [segment][frequency] reach, bits)."""
+    assert inner % PERIOD == 0
+    c = (l, h, m, blocks, inner, inner, 0, None, 0)
+    kb = keep_batch(l, h, m, L.OUT_POWER)
+    sp = kb.data.shape[1]
+    plan = SP.make_col_plan(c, FORM, L.OUT_POWER)
+    SP.assert_keep_plan(plan, c)
+    n, e = out_shape(plan)
+    assert (n, e) == (blocks, m * l * inner)
+    need = device_bytes(plan, blocks * sp * inner * 4) + n * e * 4  # (... and the copy with the columns first)
+    print(f"{cid}: {blocks} blocks of {inner} columns, {m} segments, {need / 2 ** 30:.2f} GiB of device memory (workspace {plan.workspace_bytes} bytes)")
+    ok, why = enough_memory(need, dev)
+    if not ok:
+        raise NeedsMemory(why)
+    bounds = boundaries(blocks * inner, 1, 4, 1, 4)  # (a column's first sample and first output: one element further per column)
+    reached = boundaries(blocks * m * l, 0, 4, inner, 4)  # (an output row [block][segment][frequency]: `inner` elements further per row)
+    try:
+        cols = kb.data.to(dev).t().contiguous()                                              # [span][48]
+        t0 = cols.repeat(1, inner // PERIOD).unsqueeze(0).repeat(blocks, 1, 1)               # [blocks][span][inner]
+        if blocks > 1:
+            t0 = (t0 * (2.0 ** torch.arange(blocks, device=dev, dtype=torch.float32)).reshape(-1, 1, 1)).contiguous()
+        assert plan._layout_ok(t0)
+        out, _, bands = run_banded(plan, t0)
+        del t0, cols
+        if blocks > 1:
+            out.reshape(blocks, -1).mul_((0.25 ** torch.arange(blocks, device=dev, dtype=torch.float32)).reshape(-1, 1))  # (a power of two: exact)
+        first = out.reshape(blocks, m * l, inner).transpose(1, 2).reshape(blocks * inner, m * l)
+        r = kb.reference()
+        same = check(first, r.ref, r.bnd, bounds, r.accurate, exact=True, bands=bands, what=cid)
+        print(f"{cid}: boundaries of the output rows {reached}; worst figure / bound {r.worst.ratio:.3f}")
+        return plan, reached, same
+    finally:
+        out = first = bands = None
+        release(dev)
+
+
+# ---- rung C: through the pitch.  The buffer is allocated and never filled; only the series are written
+def _pitched(cid, dev, total, dtype, shape, strides, x, plan, extra=0):
+    need = total * esize(dtype) + extra + (1 << 30)
+    print(f"{cid}: strides {strides}: the last element at {total - 1} (byte {(total - 1) * esize(dtype)}), {need / 2 ** 30:.2f} GiB of device memory")
+    ok, why = enough_memory(need, dev)
+    if not ok:
+        raise NeedsMemory(why)
+    buf = torch.empty(total, dtype=dtype, device=dev)
+    view = torch.as_strided(buf, shape, strides)
+    view.copy_(torch.from_numpy(x).to(dev))
+    out, _ = plan.execute(view)
+    return out.cpu().numpy()
+
+
+def run_keep_rows_pitched(cid, dev, pitch=(1 << 30) + 5, case=(64, 32, 3, 3), mode=L.OUT_POWER):
+    l, h, m, p = case
+    sp = W.span(case)
+    x = SP.series(case)
+    plan = SP.make_plan(case, FORM, mode, pitch=pitch)
+    SP.assert_keep_plan(plan)
+    try:
+        got = _pitched(cid, dev, (p - 1) * pitch + sp, torch.float32, (p, sp), (pitch, 1), x, plan)
+        SP.assert_segments(case, got, SP.reference(case, FORM, x, mode), SP.kappas(case, FORM, x), mode, cid)
+        assert np.array_equal(got, SP.run(SP.make_plan(case, FORM, mode), x)), f"{cid}: the pitched plan differs from the dense plan"
+        return plan
+    finally:
+        release(dev)
+
+
+def run_keep_cols_strided(cid, dev, s=1 << 20, c=(64, 32, 69, 2, 40), beyond=1 << 31, mode=L.OUT_POWER):
+    """Spectrogram columns whose samples lie `s` elements apart (run_welch_cols_strided): past 2^31 elements inside ONE block."""
+    l, h, m, p, inner = c
+    case = (l, h, m, p, inner, s, 0, None, 0)
+    sp = WC.span(case)
+    pitch = sp * s
+    assert (sp - 1) * s + inner > beyond
+    x = SP.cube(case)
+    plan = SP.make_col_plan(case, FORM, mode, in_stride_batch=pitch)
+    SP.assert_keep_plan(plan, case)
+    try:
+        out = _pitched(cid, dev, (p - 1) * pitch + (sp - 1) * s + inner, torch.float32, (p, sp, inner), (pitch, s, 1), x, plan)
+        assert out.shape == (p, m, plan.nx_out, inner), out.shape
+        got = np.ascontiguousarray(np.transpose(out, (0, 3, 1, 2))).reshape(p * inner, m, plan.nx_out)
+        rc, rows = (l, h, m, p * inner), WC.as_rows(x)
+        SP.assert_segments(rc, got, SP.reference(rc, FORM, rows, mode), SP.kappas(rc, FORM, rows), mode, cid)
+        dense = case[:5] + (inner, 0, None, 0)
+        assert np.array_equal(got, SP.run_cols(SP.make_col_plan(dense, FORM, mode), dense, x)), f"{cid}: the strided plan differs from the plan on the arranged copy"
+        return plan
+    finally:
+        release(dev)
+
+
+def run_synth_pitched(cid, dev, pitch=(1 << 30) + 5, case=(64, 32, 3, 3), wname="hann"):
+    l, h, m, p = case
+    nb = l // 2 + 1
+    spec = IS.spectra(case, wname)
+    plan = IS.make_plan(case, wname, pitch=pitch)
+    IS.assert_synth_plan(plan)
+    try:
+        got = _pitched(cid, dev, (p - 1) * pitch + m * nb, torch.complex64, (p, m, nb), (pitch, nb, 1), spec, plan)
+        ref, dp, a = IS.model(spec, l, h, IS.window(wname, l), 1.0 / l)
+        IS.assert_within(cid, got, ref, dp, l, h, a)
+        assert np.array_equal(got, IS.run(IS.make_plan(case, wname), spec)), f"{cid}: the pitched plan differs from the dense plan"
+        return plan
+    finally:
+        release(dev)
+
+
+def run_filter_pitched(cid, dev, pitch=(1 << 30) + 5, case=(256, 65, 700, 3), mode="same", kind="normal"):
+    l, k, n, p = case
+    a, n_out = FF.offsets(mode, n, k)
+    x, taps = FF.series(case), FF.taps_of(kind, k)
+    plan = FF.make_plan(case, mode, taps, pitch=pitch)
+    FF.assert_filter_plan(plan)
+    try:
+        got = _pitched(cid, dev, (p - 1) * pitch + n, torch.float32, (p, n), (pitch, 1), x, plan)
+        FF.assert_within(cid, got, FF.model(x, taps, mode), FF.the_bound(x, taps, l, a, n_out))
+        assert np.array_equal(got, FF.run(FF.make_plan(case, mode, taps), x)), f"{cid}: the pitched plan differs from the dense plan"
+        return plan
+    finally:
+        release(dev)
+
+
 # ---------------------------------------------------------------------------------- rung D: the guards (plan creation only)
 def status(**kw):
     """The status of xrfthip_plan_create for make() arguments (0: the plan exists)."""
@@ -767,6 +1283,36 @@ def check_guards():
     assert status(**hk, ny=2, nx=(1 << 29) + 1, herm_ny=1, herm_nx=1 << 30) == 0 and status(**hk, ny=2, nx=(1 << 29) + 1, herm_ny=1, herm_nx=(1 << 30) + 1) == bad
     # (herm_ny: NOT pinned by itself -- nx = herm_ny (herm_nx / 2 + 1) >= herm_ny, so one step past it the guard of nx refuses first; herm_nx is pinned above)
     assert status(**hk, ny=1, nx=1 << 30, herm_ny=1 << 30, herm_nx=1) != bad and status(**hk, ny=1, nx=(1 << 30) + 1, herm_ny=(1 << 30) + 1, herm_nx=1) == bad
+    check_segment_guards()
+
+
+def check_segment_guards():
+    """The spectrogram, istft and fir_filter plans (host_welch.inc): the four "one launch; declined, never truncated" guards with 1000 workgroups per series, the
+    istft span, the segments of a series, seg_in_len.  Pinned elsewhere and not repeated: one workgroup per series at 2^31 - 1 / 2^31 series and an istft span of
+    2^31 from hop = L (istft.check_status_codes, fir_filter.check_status_codes); seg_in_len, seg_out_len and seg_lead at and below 0 (fir_filter.check_status_codes)."""
+    bad, unsup, big = L.BAD_ARG, L.UNSUPPORTED_LENGTH, (1 << 31) - 1
+    # istft: span = (M - 1) H + L <= 2^31 - 1 (fasto.h:74-77 keeps lo, hi in 64 bits and m0, count as ints inside the span)
+    m = (1 << 31) - 64
+    assert (m - 1) + 64 == big
+    assert IS._status(nx=64, seg_hop=1, mean_batch=m, batch=m) == 0 and IS._status(nx=64, seg_hop=1, mean_batch=m + 1, batch=m + 1) == unsup
+    # one launch of series x workgroups <= 2^31 - 1: istft (R = 2, F = 127: 1000 workgroups serve 127 001 segments), spectrogram (128 segments a round), fir (V = 57)
+    p = big // 1000
+    assert IS._status(nx=64, seg_hop=32, mean_batch=127001, batch=127001 * p) == 0 and IS._status(nx=64, seg_hop=32, mean_batch=127001, batch=127001 * (p + 1)) == unsup
+    assert SP._status(nx=64, seg_hop=32, mean_batch=128000, batch=128000 * p) == 0 and SP._status(nx=64, seg_hop=32, mean_batch=128000, batch=128000 * (p + 1)) == unsup
+    for pp, want in ((p, 0), (p + 1, unsup)):
+        assert FF._status(**FF.plan_kw((64, 8, 57 * 128 * 1000, pp), "same")) == want, pp
+    # the segments of a series: mean_batch <= 2^31 - 1 (SegTile.M is an int)
+    assert SP._status(nx=64, seg_hop=1, mean_batch=big, batch=big) == 0 and SP._status(nx=64, seg_hop=1, mean_batch=big + 1, batch=big + 1) == bad
+    for n, want in ((32 * big - 16, 0), (32 * big + 40, bad)):
+        kw = FF.plan_kw((64, 33, n, 1), "same")
+        assert kw["mean_batch"] == (big if want == 0 else big + 2)
+        assert FF._status(**kw) == want, n
+    # fir_filter's seg_in_len: 2^60 (a small seg_out_len: the segments follow the output)
+    fk = FF.plan_kw((64, 8, 100, 1), "same")
+    assert FF._status(**dict(fk, seg_in_len=1 << 60)) == 0 and FF._status(**dict(fk, seg_in_len=(1 << 60) + 1)) == bad
+    # the column-layout spectrogram: a span of 2^31 - 1 samples (the seg_keep = 1 twin of the Welch line above)
+    assert SP._status(nx=64, seg_hop=1, mean_batch=m, batch=m, inner=4, seg_stride=4) == 0
+    assert SP._status(nx=64, seg_hop=1, mean_batch=m + 1, batch=m + 1, inner=4, seg_stride=4) == bad
 
 
 def group_of(plan):

@@ -1,6 +1,8 @@
 """The extent ladder's CPU side (tests/extents.py): the checker shown to bite -- no library, synthetic outputs --, rung D (the host guards at the limit and one
 step past it: plan creation only), the group rule of the fused radial sums, and a few cases of rungs A and B through the whole harness at a batch of 96 on the
-emulated library (the MI355X runs them at 70 080 slabs and beyond 2^31 elements: tests/test_gpu_extents.py)."""
+emulated library (the MI355X runs them at 70 080 slabs and beyond 2^31 elements: tests/test_gpu_extents.py).  The spectrogram, istft and fir_filter runners -- the
+period along ONE series, across the batch, through the pitch -- each run once at four to six periods and 96 series, and the checker's form for them (extents.Along:
+edge periods, an interior member, a tail) has its own mutants."""
 import os
 import sys
 
@@ -95,6 +97,104 @@ def test_the_checker_fails_on_an_unwritten_last_slab():
         _check(ref, out, bands, {"pretend wrap": BOUNDARY})
 
 
+# ---- ... with the period along a series (extents.Along): the first and the last period differ from the interior, a tail lies behind the last whole period
+TAIL = 5
+
+
+def _synthetic_along():
+    """The same 480 slabs as the segments of ONE series: period 0 and period 9 are edges (values of their own), periods 1 .. 8 repeat; 5 values behind them.  The
+    reference is that of a short series of four periods: first, interior, interior, last."""
+    rng = np.random.default_rng(22)
+    scale = (1.0 + np.arange(E.PERIOD) / E.PERIOD).reshape(-1, 1)
+    first, inner, last = (rng.standard_normal((E.PERIOD, POINTS)) * scale for _ in range(3))
+    ref = np.concatenate([first, inner, inner, last])
+    out = torch.from_numpy(np.concatenate([first] + [inner] * (SLABS // E.PERIOD - 2) + [last])).to(torch.float32)
+    tail_ref = rng.standard_normal(TAIL)
+    tail = torch.from_numpy(tail_ref).to(torch.float32)
+    bands = [torch.full((64,), E.PATTERN, dtype=torch.uint8) for _ in range(2)]
+    return ref, out, tail, tail_ref, bands
+
+
+def _check_along(ref, out, tail, tail_ref, bands, bounds, exact=False):
+    def tail_ok(got, what):
+        assert np.abs(got - tail_ref).max() <= 2.0 ** -23 * np.abs(tail_ref).max(), what
+    along = E.Along(1, {0: 0, SLABS // E.PERIOD - 1: 3}, (tail, tail_ok))
+    return E.check(out, ref, A.bound(A.F32, POINTS), bounds, E.plain_accurate(A.F32, POINTS, 0.0), exact=exact, bands=bands, what="synthetic", along=along)
+
+
+def test_the_checker_passes_a_clean_series_whose_ends_differ():
+    ref, out, tail, tail_ref, bands = _synthetic_along()
+    assert not torch.equal(out[:E.PERIOD], out[E.PERIOD:2 * E.PERIOD]) and not torch.equal(out[-E.PERIOD:], out[E.PERIOD:2 * E.PERIOD])
+    assert _check_along(ref, out, tail, tail_ref, bands, {"pretend wrap": BOUNDARY}, exact=True) is True
+    with pytest.raises(AssertionError):  # (without the argument the first period is the member: the interior differs from it)
+        _check(ref[:E.PERIOD], out, bands, {})
+
+
+def test_the_checker_fails_on_an_index_wrapped_along_the_series():
+    """Every period from the boundary's on replaced by the one a wrap distance earlier (100 slabs: another member of the period)."""
+    ref, out, tail, tail_ref, bands = _synthetic_along()
+    out[BOUNDARY:] = out[BOUNDARY - WRAP:SLABS - WRAP].clone()
+    with pytest.raises(AssertionError, match="pretend wrap"):
+        _check_along(ref, out, tail, tail_ref, bands, {"pretend wrap": BOUNDARY})
+    with pytest.raises(AssertionError, match="last"):
+        _check_along(ref, out, tail, tail_ref, bands, {})
+    ref, out, tail, tail_ref, bands = _synthetic_along()
+    out[BOUNDARY:400] = out[BOUNDARY - WRAP:400 - WRAP].clone()  # (confined to the middle, the boundary not known: the device pass)
+    with pytest.raises(AssertionError, match=f"slab {BOUNDARY} is .* of period 1"):
+        _check_along(ref, out, tail, tail_ref, bands, {})
+
+
+def test_the_checker_fails_on_one_zeroed_interior_period():
+    ref, out, tail, tail_ref, bands = _synthetic_along()
+    out[4 * E.PERIOD:5 * E.PERIOD] = 0.0  # (period 4: in no window)
+    with pytest.raises(AssertionError, match=f"slab {4 * E.PERIOD} is"):
+        _check_along(ref, out, tail, tail_ref, bands, {"pretend wrap": BOUNDARY})
+
+
+def test_the_checker_fails_on_an_unwritten_tail():
+    ref, out, tail, tail_ref, bands = _synthetic_along()
+    tail[-1] = float("nan")
+    with pytest.raises(AssertionError, match="the tail behind the last whole period"):
+        _check_along(ref, out, tail, tail_ref, bands, {"pretend wrap": BOUNDARY})
+    ref, out, tail, tail_ref, bands = _synthetic_along()
+    tail[2] = 0.0  # (written, wrong)
+    with pytest.raises(AssertionError, match="synthetic tail"):
+        _check_along(ref, out, tail, tail_ref, bands, {"pretend wrap": BOUNDARY})
+
+
+def test_the_checker_fails_on_one_flipped_bit_of_an_interior_period():
+    ref, out, tail, tail_ref, bands = _synthetic_along()
+    out[7 * E.PERIOD + 11].view(torch.int32)[3] ^= 1  # (period 7: in no window; one ulp: within the bound)
+    assert _check_along(ref, out, tail, tail_ref, bands, {"pretend wrap": BOUNDARY}) is False
+    with pytest.raises(AssertionError, match="an interior period differs in its bits"):
+        _check_along(ref, out, tail, tail_ref, bands, {"pretend wrap": BOUNDARY}, exact=True)
+    ref, out, tail, tail_ref, bands = _synthetic_along()
+    out[3].view(torch.int32)[3] ^= 1  # (an edge is held to float64 only)
+    assert _check_along(ref, out, tail, tail_ref, bands, {"pretend wrap": BOUNDARY}, exact=True) is True
+
+
+def test_the_checker_takes_whole_periods_under_a_norm_wise_bound():
+    """The form of istft and fir_filter: one absolute bound per period of the reference, the window check on a whole period."""
+    ref, out, tail, tail_ref, bands = _synthetic_along()
+    bnd = [A.bound(A.F32, POINTS) * float(np.sqrt((ref[q * E.PERIOD:(q + 1) * E.PERIOD] ** 2).sum())) for q in range(4)]
+
+    def accurate(got, r, rp, what):
+        assert got.shape == r.shape == (E.PERIOD, POINTS) and np.sqrt(((got - r) ** 2).sum()) <= bnd[rp], what
+
+    def run(exact=True):
+        along = E.Along(1, {0: 0, SLABS // E.PERIOD - 1: 3}, None, whole=True)
+        return E.check(out, ref, bnd, {"pretend wrap": BOUNDARY}, accurate, exact=exact, bands=bands, what="synthetic", along=along)
+
+    assert run() is True
+    out[4 * E.PERIOD + 7] = 0.0
+    with pytest.raises(AssertionError, match="period 4 is"):
+        run(exact=False)
+    out[4 * E.PERIOD + 7] = out[E.PERIOD + 7]
+    out[BOUNDARY] = out[BOUNDARY - WRAP]
+    with pytest.raises(AssertionError, match="pretend wrap"):
+        run()
+
+
 def test_boundaries_and_batches():
     """The first slab at or beyond each limit, only where the case reaches it; the rung B batch leaves one whole period beyond 2^31 elements on both sides."""
     b = E.batch_beyond(256 * 256, 256 * 256)
@@ -150,6 +250,63 @@ def test_averaged_forms_through_the_harness():
     E.run_mean("fasts-mean", 64, 64, 2, 2 * E.PERIOD, {"XRFTHIP_MEAN_ALL": "1"}, L.K_FASTS, "cpu")
     E.run_welch_rows("welch-rows", 64, 32, 3, 2 * E.PERIOD, "cpu")
     E.run_welch_cols("welch-columns", 64, 32, 3, 3, 2 * E.PERIOD, "cpu")
+
+
+# ---- the segment kernels (spectrogram, istft, fir_filter): every new runner once, at four to six periods along the series and 2 x PERIOD series
+ALONG = {
+    "spectrogram-64-37-complex": (lambda: E.keep_along(64, 37, L.OUT_COMPLEX), 5),
+    "spectrogram-64-32-power": (lambda: E.keep_along(64, 32, L.OUT_POWER), 6),
+    "spectrogram-256-128-power": (lambda: E.keep_along(256, 128, L.OUT_POWER), 4),
+    "istft-64-16-hann": (lambda: E.synth_along(64, 16, "hann"), 5),
+    "istft-64-37-boxcar": (lambda: E.synth_along(64, 37, None), 6),
+    "istft-256-128-hann": (lambda: E.synth_along(256, 128, "hann"), 4),
+    "fir-64-8-same": (lambda: E.filter_along(64, 8, "same"), 5),
+    "fir-64-8-full": (lambda: E.filter_along(64, 8, "full"), 5),
+    "fir-256-65-valid": (lambda: E.filter_along(256, 65, "valid"), 4),
+}
+
+
+@pytest.mark.parametrize("cid", list(ALONG))
+def test_one_long_series_through_the_harness(cid):
+    """The period along the series: the MI355X runs these runners at 2^26 segments (rung B), here four to six periods."""
+    make, q = ALONG[cid]
+    _plan, bounds, same = E.run_along(cid, make(), q, "cpu")
+    assert bounds == {} and same
+
+
+def test_segment_kernels_across_the_batch_through_the_harness():
+    """Rung A's four cases at 96 series (columns)."""
+    for cid, c in (("spectrogram-rows", E.keep_batch(64, 37, 130, L.OUT_COMPLEX)), ("istft", E.synth_batch(64, 37, 130, "hann")),
+                   ("fir_filter", E.filter_batch(64, 8, 8000, "same"))):
+        assert E.run_batch(cid, c, 2 * E.PERIOD, "cpu")[2]
+    assert E.run_keep_cols("spectrogram-columns", 64, 37, 9, 3, 2 * E.PERIOD, "cpu")[2]
+    assert E.run_keep_cols("spectrogram-columns-one-block", 64, 32, 20, 1, 2 * E.PERIOD, "cpu")[2]
+
+
+def test_segment_kernels_through_the_pitch_through_the_harness():
+    """Rung C's four runners at pitches a CPU holds (the MI355X: 2^30 + 5 between the series, a sample stride of 2^20)."""
+    E.run_keep_rows_pitched("spectrogram-rows-pitch", "cpu", pitch=128 + 5)
+    E.run_keep_cols_strided("spectrogram-columns-stride", "cpu", s=64, c=(64, 32, 5, 2, 40), beyond=0)
+    E.run_synth_pitched("istft-pitch", "cpu", pitch=3 * 33 + 5)
+    E.run_filter_pitched("fir-pitch", "cpu", pitch=700 + 5)
+
+
+def test_the_one_series_shapes_of_rung_b():
+    """The lengths rung B runs at: one whole period beyond 2^31 elements, the boundaries they reach, and that a wrap lands on another member (boundaries() asserts)."""
+    m = E.batch_beyond(32, 64)
+    assert m % E.PERIOD == 0 and (m - E.PERIOD) * 32 >= 1 << 31 > (m - 2 * E.PERIOD) * 32
+    bd = E.boundaries(m, 32, 4, 64, 4)
+    assert set(bd) == {f"{s} {n}" for s in ("input", "output") for n in ("2^31 elements", "2^32 bytes", "2^33 bytes")}
+    assert bd["input 2^31 elements"] == bd["input 2^33 bytes"] == 1 << 26 and bd["output 2^31 elements"] == 1 << 25
+    m = E.batch_beyond(33, None)
+    assert (m - E.PERIOD) * 33 >= 1 << 31 and (m - 1) * 16 + 64 < (1 << 31) - 1  # (the span stays under the span guard)
+    bd = E.boundaries(m, 33, 8, 16, 4, limits=E.MORE_LIMITS)
+    assert {"input 2^31 elements", "input 2^33 bytes", "input 2^34 bytes"} <= set(bd) and not [k for k in bd if k.startswith("output 2^3")]
+    assert bd["input 2^34 bytes"] == bd["input 2^31 elements"] == -(-(1 << 31) // 33)
+    n = E.batch_beyond(57, 57)
+    assert (n - E.PERIOD) * 57 >= 1 << 31
+    assert set(E.boundaries(n, 57, 4, 57, 4)) == {f"{s} {x}" for s in ("input", "output") for x in ("2^31 elements", "2^32 bytes", "2^33 bytes")}
+    assert set(E.SEGMENT_EXACT) == {"spectrogram", "istft", "fir_filter"} and all(E.SEGMENT_EXACT.values()) and not set(E.SEGMENT_EXACT) & set(E.EXACT)
 
 
 def test_strided_boxes_through_the_harness():

@@ -4,7 +4,12 @@
 * rung B: dense batches whose last period lies beyond element offset 2^31 (float32: byte offset 2^33) in input and output, 11 to 83 GiB per case;
 * rung C: the same offsets through the descriptor's strides -- 2^30 + 16 elements between the slabs, the largest pitch a plan accepts, a Welch series pitch of
   2^30 + 5 samples, a Welch sample stride of 2^20 --, in buffers that are allocated and never filled;
-* rung D: the host guards at the limit and one step past it (plan creation only), as on the CPU.
+* rung D: the host guards at the limit and one step past it (plan creation only), as on the CPU;
+* the spectrogram, istft and fir_filter kernels on each rung: 70 080 series or columns with several workgroups each (A); ONE series of 2^26 segments per kernel, whose
+  sample offsets pass 2^31 inside the series, dense batches of short series, and a column-layout output beyond 2^31 elements inside one block (B, 17 to 26 GiB); a
+  series pitch of 2^30 + 5 and a sample stride of 2^20 (C); their guards (D).  Along a series the first and last periods are edges held to float64, every interior
+  period has the bits of the first interior one.  Not covered: API-level calls at these sizes (a span past 2^31 - 1: the composed route), 2^32 complex elements of
+  istft input, L = 4096 variants of the one-series cases.
 
 Every case of rungs A and B asserts its family, whole periods (the first, the last, every one that holds the first slab beyond a boundary) slab by slab against the
 float64 reference at rounding level, every slab on the device against its member of the first period, and the guard bands around output, radial sums and workspace.
@@ -136,6 +141,109 @@ def test_rung_c_welch_rows_with_a_huge_series_pitch():
 
 def test_rung_c_welch_columns_with_a_huge_sample_stride():
     _run(E.run_welch_cols_strided, "welch-columns-stride", "cuda")
+
+
+# ---------------------------------------------------------------------------------- the segment kernels: spectrogram (fastk.h), istft (fasto.h), fir_filter (fastf.h)
+# Every case asserts K_FASTW and its own describe line (spectrogram.assert_keep_plan, istft.assert_synth_plan, fir_filter.assert_filter_plan), a workspace of 0
+# bytes, and bit identity (extents.SEGMENT_EXACT): the third value the runners return.
+def _segments(f, *args, **kw):
+    _plan, bounds, same = _run(f, *args, **kw)
+    assert same is True
+    return bounds
+
+
+# ---- rung A: 70 080 series (columns), several workgroups per series, the last one short
+SEGMENT_RUNG_A = {
+    "spectrogram-rows": lambda: E.keep_batch(64, 37, 130, L.OUT_COMPLEX),  # 2 rounds per series, the second nearly empty
+    "istft": lambda: E.synth_batch(64, 37, 130, "hann"),                   # 2 workgroups per series
+    "fir_filter": lambda: E.filter_batch(64, 8, 8000, "same"),             # V = 57, unaligned; 141 segments: 2 workgroups per series
+}
+
+
+@pytest.mark.parametrize("cid", list(SEGMENT_RUNG_A))
+def test_rung_a_segment_counts(cid):
+    _segments(E.run_batch, cid, SEGMENT_RUNG_A[cid](), E.COUNT, "cuda")  # (the complex spectrogram's output also passes 2^32 bytes: a window of its own)
+
+
+def test_rung_a_spectrogram_columns():
+    """3 blocks of 70 080 columns, seg_stride = inner, POWER; block b scaled by 2^b and taken out again."""
+    _segments(E.run_keep_cols, "spectrogram-columns", 64, 37, 9, 3, E.COUNT, "cuda")
+
+
+# ---- rung B: each term at its smallest shape.  One series: the offsets grow INSIDE it
+def _reached(bounds, *names):
+    for name in names:
+        assert name in bounds, (name, bounds)
+
+
+def test_rung_b_spectrogram_one_series():
+    """(64, 32, M, 1), POWER, full output: segment s starts at s H >= 2^31 samples and writes at s 64 >= 2^31 elements (2^33 bytes) -- seg_tile.h:77, fastk.h:60."""
+    m = E.batch_beyond(32, 64)
+    bounds = _segments(E.run_along, "spectrogram-one-series", E.keep_along(64, 32, L.OUT_POWER), m // E.PERIOD, "cuda")
+    _beyond(bounds)
+    _reached(bounds, "input 2^33 bytes", "output 2^33 bytes")
+
+
+def test_rung_b_spectrogram_many_series():
+    """(64, 32, 32, P): blk * pitch and blk * M * nxo."""
+    bounds = _segments(E.run_batch, "spectrogram-many-series", E.keep_batch(64, 32, 32, L.OUT_POWER), E.batch_beyond(1056, 32 * 64), "cuda")
+    _beyond(bounds)
+    _reached(bounds, "input 2^33 bytes", "output 2^33 bytes")
+
+
+def test_rung_b_spectrogram_columns_output():
+    """(64, 32, 480), one block of 70 080 columns: (obase + r) inner + c0 + col passes 2^31 elements (fastk.h:75) in every column's last segments."""
+    bounds = _segments(E.run_keep_cols, "spectrogram-columns-output", 64, 32, 480, 1, E.COUNT, "cuda")
+    _beyond(bounds, ("output",))
+    _reached(bounds, "output 2^33 bytes")
+
+
+def test_rung_b_istft_one_series():
+    """(64, 16, M, 1): 33 M beyond 2^31 complex elements (2^34 bytes) through s0 (n + 1) with s0 an int (fasto.h:45-48); R = 4, F = 125; the span of about 2^30
+    samples stays under the span guard."""
+    m = E.batch_beyond(33, None)
+    bounds = _segments(E.run_along, "istft-one-series", E.synth_along(64, 16, "hann"), m // E.PERIOD, "cuda")
+    _beyond(bounds, ("input",))
+    _reached(bounds, "input 2^33 bytes", "input 2^34 bytes")
+
+
+def test_rung_b_istft_many_series():
+    """(64, 32, 32, P): series * pitch, series * span (fasto.h:48, :77)."""
+    bounds = _segments(E.run_batch, "istft-many-series", E.synth_batch(64, 32, 32, "hann"), E.batch_beyond(32 * 33, 1056), "cuda")
+    _beyond(bounds)
+    _reached(bounds, "input 2^34 bytes", "output 2^33 bytes")
+
+
+def test_rung_b_fir_filter_one_series():
+    """(64, 8, N, 1), "same": first, idx < N and o0 (fastf.h:52-58, :104-107) beyond sample 2^31."""
+    q = E.batch_beyond(57, 57) // E.PERIOD
+    bounds = _segments(E.run_along, "fir-one-series", E.filter_along(64, 8, "same"), q, "cuda")
+    _beyond(bounds)
+    _reached(bounds, "input 2^33 bytes", "output 2^33 bytes")
+
+
+def test_rung_b_fir_filter_many_series():
+    """(64, 8, 8000, P): series * pitch, series * n_out."""
+    bounds = _segments(E.run_batch, "fir-many-series", E.filter_batch(64, 8, 8000, "same"), E.batch_beyond(8000, 8000), "cuda")
+    _beyond(bounds)
+    _reached(bounds, "input 2^33 bytes", "output 2^33 bytes")
+
+
+# ---- rung C: through the pitch
+def test_rung_c_spectrogram_rows_with_a_huge_series_pitch():
+    _run(E.run_keep_rows_pitched, "spectrogram-rows-pitch", "cuda")
+
+
+def test_rung_c_spectrogram_columns_with_a_huge_sample_stride():
+    _run(E.run_keep_cols_strided, "spectrogram-columns-stride", "cuda")
+
+
+def test_rung_c_istft_with_a_huge_series_pitch():
+    _run(E.run_synth_pitched, "istft-pitch", "cuda")
+
+
+def test_rung_c_fir_filter_with_a_huge_series_pitch():
+    _run(E.run_filter_pitched, "fir-pitch", "cuda")
 
 
 # ---------------------------------------------------------------------------------- rung D: the guards
