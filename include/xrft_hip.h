@@ -370,6 +370,27 @@ typedef struct xrfthip_desc {
     int64_t seg_lead;    /* the four words were appended together: no struct_size between them */
     int64_t seg_in_len;
     int64_t seg_out_len;
+    /* Multitaper spectra in ONE pass (Thomson's estimate: the series of N samples multiplied by K orthogonal tapers, zero-extended to L points, transformed K times, the
+     * K spectra added): out[p][k] = scale * sum_j |sum_{n<N} t_j[n] y_p[n] exp(-2 pi i k n / L)|^2 (XRFTHIP_OUT_CROSS: sum_j X0_j conj(X1_j), times the phase table),
+     * y_p the series after the detrend over its N samples, t_j the rows of the table xrfthip_plan_set_tapers carries.  Neither the K tapered copies nor the K spectra
+     * reach memory: 4 bytes per sample read, one spectrum per series written.
+     *   seg_tapers = K >= 1      Valid with ndim = 1, ny = 1, nx = L; dtype XRFTHIP_F32; out_mode XRFTHIP_OUT_POWER | XRFTHIP_OUT_CROSS; mean_batch <= 1, batch = P the
+     *                            series; seg_hop = 0 and every other seg_* word 0; inner <= 1; detrend NONE | CONSTANT | LINEAR; the flags a Welch plan takes
+     *                            (XRFTHIP_SHIFT_X, XRFTHIP_HALF_X, XRFTHIP_REALDIM_X2; XRFTHIP_ISHIFT_X is ignored); no window (xrfthip_plan_set_window:
+     *                            XRFTHIP_BAD_ARG -- the tapers are the windows).
+     *   seg_taper_len = N        1 <= N <= L samples per series.  d_in0 (d_in1) is [P] series of N float32, series p at d_in0 + p * in_stride_batch: in_stride_batch is
+     *                            HERE the series pitch in samples, 0 = dense = N, any other value >= N.  d_out is [P][nx_out], real or complex64 (CROSS), dense.
+     *                            0 = off: seg_taper_len must be 0 too and everything about the descriptor is as without the fields.
+     * Alignment: d_in0, d_in1 and d_out 4-byte (CROSS d_out: 8-byte) aligned.  No byte outside the N samples of a series is read.  One workgroup owns whole outputs: no
+     * workspace (xrfthip_workspace_bytes is 0), no second kernel, no atomics; an output's bits depend on its own series, the table, L and `scale` only -- not on P or
+     * on the workgroups -- and a non-finite sample makes exactly its own series' output non-finite.
+     * XRFTHIP_BAD_ARG: K < 1; N < 1 or N > L; seg_taper_len set while seg_tapers = 0; every violation of the rules above.  XRFTHIP_UNSUPPORTED_LENGTH ("the caller
+     * composes"): L not a power of two in 64 .. 4096; K > 32; XRFTHIP_FLIP_X / XRFTHIP_FLIP0_X; more than 2^31 - 1 workgroups; XRFTHIP_FASTW=0 or
+     * XRFTHIP_FASTW_TAPERS=0 in the environment when the plan is created (docs/TUNING.md).
+     * Still XRFTHIP_K_FASTW: a form of the same family (xrfthip_plan_describe prints a [fastw tapers] line).  Descriptors with the struct_size of the eleven earlier
+     * versions are accepted (0, 0); an older library answers XRFTHIP_BAD_ARG to the larger struct_size.  Offsets are computed in 64 bits. */
+    int64_t seg_tapers;
+    int64_t seg_taper_len; /* appended together with seg_tapers: no struct_size between the two */
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;
@@ -388,6 +409,10 @@ int xrfthip_plan_set_window(xrfthip_plan* plan, int axis, const double* h_window
  * the INPUT and is indexed by source position; a C2R_X plan then takes nx/2 + 1 entries on axis 1.  NULL clears.
  * An XRFTHIP_HERM_FIELD plan: axis 0, 1, 2 = t, herm_ny, herm_nx (see xrfthip_desc.herm_ny); axis 2 is XRFTHIP_BAD_ARG on every other plan. */
 int xrfthip_plan_set_phase(xrfthip_plan* plan, int axis, const double* h_phase, int64_t n);
+/* The taper table of a multitaper plan (xrfthip_desc.seg_tapers = K, seg_taper_len = N): h_tapers is [K][N] float32, row j the taper d_j already multiplied by
+ * sqrt(w_j) (w_j its weight in the sum: the kernel knows no weights), copied to the device beside the plan's other tables.  NULL clears.  Any other plan:
+ * XRFTHIP_BAD_ARG.  xrfthip_exec of a multitaper plan without a table: XRFTHIP_BAD_ARG. */
+int xrfthip_plan_set_tapers(xrfthip_plan* plan, const float* h_tapers);
 /* h_binmap: [ny][nx_out] int32 bin codes indexed by UNSHIFTED frequency indices (nx_out = nx, or nx/2+1 with
  * HALF_X); negative = not binned.  The host computes it with the reference's float64 pd.cut expression.
  * An ISO plan of the inner / mid layouts: [ny][nx] in the plan's own axis order (the first axis in memory = y), and the map must be RADIAL -- every sample binned; along a

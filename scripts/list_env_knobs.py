@@ -15,6 +15,7 @@ NOTES = {
     "XRFTHIP_FASTW_KEEP": "0: the segments-kept form of the Welch family (`fastk.h`) off: a plan with `xrfthip_desc.seg_keep` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) composes `spectrogram` / `stft` -- segments unfolded and copied, the plain 1-D plan, the dims moved: the route before the form, kept for measurements (profiles/r21_spectrogram.txt)",
     "XRFTHIP_FASTW_SYNTH": "0: the synthesis form of the Welch family (`fasto.h`) off: a plan with `xrfthip_desc.seg_synth` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) composes `istft` -- `ifft` of every segment, the window, R strided adds, the division: the route without the form, kept for measurements (profiles/r26_istft.txt)",
     "XRFTHIP_FASTW_FILTER": "0: the filter form of the Welch family (`fastf.h`) off: a plan with `xrfthip_desc.seg_filter` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) composes `fir_filter` -- a zero-extended copy, the segments unfolded, the real 1-D plan, the table product, the C2R plan, the kept samples sliced out: the route without the form, kept for measurements (profiles/r27_fir_filter.txt)",
+    "XRFTHIP_FASTW_TAPERS": "0: the multitaper form of the Welch family (`fastt.h`) off: a plan with `xrfthip_desc.seg_tapers` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) composes `multitaper_*` -- the library's detrend, a taper dim by broadcasting the table, zero-extension, `power_spectrum` / `cross_spectrum`, the weighted sum: the route without the form, kept for measurements (profiles/r29_multitaper.txt)",
     "XRFTHIP_FASTC": "0: complex rows of 2048 ... 16384 points leave `fastc_kernel`",
     "XRFTHIP_CROWS": "0: complex rows of 256 ... 4096 points leave the row pass of `fasty_c2c.h`",
     "XRFTHIP_FASTYC": "0: complex power-of-two slabs leave the two-pass pipeline of `fasty_c2c.h`",

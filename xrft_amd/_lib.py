@@ -36,7 +36,7 @@ EXPORTS = [
     "xrfthip_detrend", "xrfthip_detrend3", "xrfthip_spectrum_tail", "xrfthip_spectrum_tail_axis", "xrfthip_gather_axis", "xrfthip_isotropize",
     "xrfthip_isotropize_workspace_bytes", "xrfthip_table_mul", "xrfthip_reduce_axis", "xrfthip_detrend_inner_workspace_bytes", "xrfthip_detrend_inner", "xrfthip_angle",
     "xrfthip_plan_uses_bluestein", "xrfthip_convert", "xrfthip_plan_kernel_info", "xrfthip_selftest_floor",
-    "xrfthip_plan_pass1_bytes", "xrfthip_plan_pass1_signature", "xrfthip_exec_ex", "xrfthip_coherence",
+    "xrfthip_plan_pass1_bytes", "xrfthip_plan_pass1_signature", "xrfthip_exec_ex", "xrfthip_coherence", "xrfthip_plan_set_tapers",
 ]
 PASS1_PRIVATE, PASS1_PRODUCE, PASS1_CONSUME = 0, 1, 2  # xrfthip_exec_args.field[].pass1_mode
 
@@ -100,12 +100,20 @@ class DescSynth(C.Structure):
 
 
 class DescFilt(C.Structure):
-    """xrfthip_desc as the library has it now: ``DescSynth`` and the four words appended together after it."""
+    """``DescSynth`` and the four words appended together after it; still accepted under its own struct_size."""
     _fields_ = DescSynth._fields_ + [
         ("seg_filter", C.c_int64),  # 1 (with seg_hop = V >= nx / 2, F32, flags 0): a series filtered by overlap-save, K = nx - V + 1 taps -- [series][seg_in_len] in, [series][seg_out_len] real out; 0: off
         ("seg_lead", C.c_int64),  # the first output sample within the full convolution, 0 .. K - 1
         ("seg_in_len", C.c_int64),  # samples per series
         ("seg_out_len", C.c_int64),  # samples per filtered series; mean_batch = ceil(seg_out_len / V)
+    ]
+
+
+class DescTaper(C.Structure):
+    """xrfthip_desc as the library has it now: ``DescFilt`` and the two words appended together after it."""
+    _fields_ = DescFilt._fields_ + [
+        ("seg_tapers", C.c_int64),  # K >= 1 (with seg_hop = 0, F32, POWER | CROSS): multitaper spectra -- [series][seg_taper_len] in, the sum over K tapers of each series' nx-point spectra out; 0: off
+        ("seg_taper_len", C.c_int64),  # N <= nx samples per series (in_stride_batch: the series pitch)
     ]
 
 
@@ -126,10 +134,11 @@ def _bind(dll):
     dll.xrfthip_strerror.restype = C.c_char_p
     dll.xrfthip_strerror.argtypes = [C.c_int]
     dll.xrfthip_last_hip_error.restype = C.c_int
-    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg, a DescCols, a DescKeep, a DescSynth or a DescFilt, by reference)
+    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg, a DescCols, a DescKeep, a DescSynth, a DescFilt or a DescTaper, by reference)
     dll.xrfthip_plan_destroy.argtypes = [vp]
     dll.xrfthip_plan_set_window.argtypes = [vp, C.c_int, vp, i64]
     dll.xrfthip_plan_set_phase.argtypes = [vp, C.c_int, vp, i64]
+    dll.xrfthip_plan_set_tapers.argtypes = [vp, vp]
     dll.xrfthip_plan_set_binmap.argtypes = [vp, vp, i64, i64, i32]
     dll.xrfthip_plan_set_profiling.argtypes = [vp, C.c_int]
     dll.xrfthip_plan_profile_read.argtypes = [vp, C.c_char_p, sz]

@@ -1,5 +1,5 @@
 """The segment surface of the call API: Welch spectra (welch_power_spectrum, welch_cross_spectrum, welch_coherence) and spectrograms (spectrogram, stft) -- the spectra
-of the overlapping segments of a series, averaged or kept -- the synthesis that rebuilds the series from the kept ones (istft), and FIR filtering along a dim by overlap-save (fir_filter).  Fused where a segment plan takes the call (xrfthip_desc.seg_hop: csrc/fastw.h, fastk.h), else composed from
+of the overlapping segments of a series, averaged or kept -- the synthesis that rebuilds the series from the kept ones (istft), FIR filtering along a dim by overlap-save (fir_filter), and multitaper spectra of a whole record (multitaper_*).  Fused where a segment plan takes the call (xrfthip_desc.seg_hop: csrc/fastw.h, fastk.h), else composed from
 the calls of api.py on the unfolded segments.  api.py re-exports the public names.
 
 This module sits ON TOP of api.py and is imported by it, behind the definitions it uses (`_api.` below: resolved at call time; the two tuning constants
@@ -696,3 +696,279 @@ def fir_filter(da, dim, taps, mode="same", nfft=None, spacing_tol=1e-3):
         elif dim not in c.dims or n_out == n:
             coords[name] = c
     return to_like(DataArray(out.movedim(-1, ax), da.dims, coords, da.name, da.attrs), src)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Multitaper spectra (Thomson): the whole record of N samples under K orthogonal Slepian (DPSS) tapers, zero-extended to L points, transformed K times, the K spectra
+# added with weights -- the estimator for short records that cannot be cut into segments.  Fused where a plan takes the call (xrfthip_desc.seg_tapers, csrc/fastt.h:
+# neither the K tapered copies nor the K spectra reach memory), else composed: detrend, a taper dim by broadcasting the table, zero-extension, power_spectrum /
+# cross_spectrum, the weighted sum.
+# ------------------------------------------------------------------------------------------------------
+_DPSS = {}  # (N, NW, K, route) -> (tapers [K][N] float64, unit L2 norm, scipy's signs; concentration ratios [K]), read-only
+
+
+def _dpss_compute(n, nw, k, use_scipy=None):
+    """scipy.signal.windows.dpss(n, nw, k, return_ratios=True) without scipy: the K eigenvectors of the largest eigenvalues of the symmetric tridiagonal matrix that
+    commutes with the concentration operator (Percival & Walden, 1993, ch. 8), in float64; symmetric tapers with a positive mean, antisymmetric ones beginning with a
+    positive lobe; the ratios as scipy computes them, from the tapers' autocorrelation and the sinc kernel.  ``use_scipy``: None = scipy.linalg.eigh_tridiagonal
+    where scipy imports, else numpy.linalg.eigh of the dense matrix (seconds at N = 4096: memoised by _dpss)."""
+    w = float(nw) / n
+    idx = np.arange(n, dtype=np.float64)
+    diag = ((n - 1 - 2 * idx) / 2.0) ** 2 * np.cos(2 * np.pi * w)
+    off = idx[1:] * (n - idx[1:]) / 2.0
+    eigh_tridiagonal = None
+    if use_scipy is None or use_scipy:
+        try:
+            from scipy.linalg import eigh_tridiagonal
+        except Exception:
+            if use_scipy:
+                raise
+    if eigh_tridiagonal is not None:
+        _, vec = eigh_tridiagonal(diag, off, select="i", select_range=(n - k, n - 1))
+    else:
+        _, vec = np.linalg.eigh(np.diag(diag) + np.diag(off, 1) + np.diag(off, -1))
+        vec = vec[:, n - k:]
+    d = np.ascontiguousarray(vec[:, ::-1].T)
+    d /= np.sqrt((d * d).sum(axis=1, keepdims=True))
+    for j in range(0, k, 2):
+        if d[j].sum() < 0:
+            d[j] *= -1
+    thresh = max(1e-7, 1.0 / n)
+    for j in range(1, k, 2):
+        if d[j][d[j] * d[j] > thresh][0] < 0:
+            d[j] *= -1
+    m = 1
+    while m < 2 * n - 1:
+        m *= 2
+    f = np.fft.rfft(d, m)
+    rxx = np.fft.irfft(f * np.conj(f), m)[:, :n]
+    r = 4 * w * np.sinc(2 * w * idx)
+    r[0] = 2 * w
+    return _ro(d), _ro(rxx @ r)
+
+
+def _dpss(n, nw, k, use_scipy=None):
+    key = (int(n), float(nw), int(k), use_scipy)
+    with _plan_lock:
+        hit = _DPSS.get(key)
+    if hit is None:
+        hit = _dpss_compute(n, nw, k, use_scipy)
+        with _plan_lock:
+            if len(_DPSS) > 64:
+                _DPSS.clear()
+            _DPSS[key] = hit
+    return hit
+
+
+_TAPER_TABLES = {}  # (digest of the tapers, digest of the weights, K, N) -> sqrt(w_j) d_j[n] float32, read-only: the plan key digests it once
+
+
+def _taper_table(d, w):
+    key = (_digest(d), _digest(w), d.shape)
+    with _plan_lock:
+        t = _TAPER_TABLES.get(key)
+    if t is None:
+        t = _ro((np.sqrt(w).reshape(-1, 1) * d).astype(np.float32))
+        with _plan_lock:
+            if len(_TAPER_TABLES) > 64:
+                _TAPER_TABLES.clear()
+            _TAPER_TABLES[key] = t
+    return t
+
+
+def _multitaper_args(da, dim, nw, k, nfft, weights, tapers):
+    """(N, L, K, the tapers [K][N] float64 with unit L2 norm, the weights [K] float64, sum 1) after the checks."""
+    if not isinstance(dim, str):
+        raise ValueError(f"dim must be the name of ONE dimension (the axis the tapers run along), not {dim!r}")
+    n = da.shape[da.get_axis_num(dim)]
+    if n < 1:
+        raise ValueError(f"{dim!r} holds no samples")
+    if weights not in ("unity", "eigen"):
+        raise ValueError(f"weights must be 'unity' or 'eigen', not {weights!r}")
+    if tapers is not None:
+        if np.iscomplexobj(tapers):
+            raise ValueError("tapers must be real")
+        d = np.array(tapers, dtype=np.float64, ndmin=2)
+        if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] != n:
+            raise ValueError(f"tapers must be a real array (K, {n}): K >= 1 tapers as long as {dim!r}")
+        if weights == "eigen":
+            raise ValueError("weights='eigen' needs the library's own DPSS tapers: given tapers carry no concentration ratios")
+        norm = np.sqrt((d * d).sum(axis=1, keepdims=True))
+        if not np.all(np.isfinite(d)) or np.any(norm == 0):
+            raise ValueError("every taper must be finite and not identically zero")
+        d, k, lam = d / norm, d.shape[0], None
+        if k > n:
+            raise ValueError(f"K = {k} tapers is not in 1 .. {n}, the length of {dim!r}")
+    else:
+        nw = float(nw)
+        if not nw > 0 or not 2 * nw <= n:
+            raise ValueError(f"NW = {nw} must satisfy 0 < 2 NW <= {n}, the length of {dim!r}")
+        k = int(2 * nw) - 1 if k is None else int(k)
+        if k < 1 or k > n:
+            raise ValueError(f"K = {k} tapers is not in 1 .. {n}, the length of {dim!r}")
+        d, lam = _dpss(n, nw, k)
+    if nfft is None:
+        l = 1
+        while l < n:
+            l *= 2
+    else:
+        l = int(nfft)
+        if l < n:
+            raise ValueError(f"nfft = {l} is shorter than {dim!r} ({n} samples): the series is zero-extended, never cut")
+    w = np.full(k, 1.0 / k) if weights == "unity" else lam / lam.sum()
+    return n, l, k, d, w
+
+
+def _multitaper_head(da, dim, n, l, spacing_tol):
+    """The labels of the series zero-extended to L samples, ``dim`` last, over no data (a 0-stride view): what the analysis of power_spectrum and _label_output read.
+    The coordinate of ``dim`` is extended at its spacing (as ``pad`` extends it)."""
+    if dim not in da.coords:
+        raise ValueError(f"{dim!r} carries no coordinate: the spacing of the spectrum comes from it")
+    cv = da.coords[dim]
+    v = np.asarray(cv.values)
+    if l > n:
+        if n < 2:
+            raise ValueError(f"the coordinate of {dim!r} has one value: its spacing, by which the zero-extension extends it, is unknown")
+        _get_coordinate_spacing(v, spacing_tol, dim)  # (evenly spaced, or ValueError)
+        v = _pad_coordinate(v, (0, l - n), (v[-1] - v[0]) / (n - 1))
+    other = [d for d in da.dims if d != dim]
+    t = _to_device(da.data)
+    coords = {name: c for name, c in da.coords.items() if name != dim and dim not in c.dims}
+    coords[dim] = Coordinate((dim,), v, cv.attrs, dim)
+    return DataArray(t.new_empty(()).expand([da.sizes[d] for d in other] + [l]), other + [dim], coords, da.name, da.attrs), other
+
+
+def _multitaper_fused(c, c2, ts, ax, n, l, k, table, det, mode, scale, flags):
+    """The (series, nx_out) values of ONE plan with seg_tapers, or None where the call composes: data that are not float32, an empty array, L not a power of two in
+    64 .. 4096, K > 32, a flag the plan declines (a descending coordinate's flip; XRFTHIP_UNSUPPORTED_LENGTH, remembered), XRFTHIP_FASTW_TAPERS=0.  A trailing ``dim``
+    with one pitch between the series is read where it lies; any other is arranged first (one transposed copy)."""
+    if any(t.dtype != torch.float32 for t in ts) or math.prod(ts[0].shape) == 0 or os.environ.get("XRFTHIP_FASTW_TAPERS", "1") == "0":  # (the knob of the library, honoured before a cached plan could answer)
+        return None
+    if l < 64 or l > 4096 or l & (l - 1) or k > 32:  # (what the library would answer XRFTHIP_UNSUPPORTED_LENGTH to, known here)
+        return None
+    views = []
+    for t in ts:
+        v = t if ax == t.dim() - 1 else t.movedim(ax, -1)
+        lead = _collapse(v.shape[:-1], v.stride()[:-1])
+        if (v.stride(-1) == 1 or n == 1) and lead is not None and (lead[0] == 1 or lead[1] >= n):
+            views.append((torch.as_strided(v, (lead[0], n), (lead[1] if lead[0] > 1 else n, 1), v.storage_offset()), lead[1] if lead[0] > 1 else 0))
+        else:
+            views.append((v.contiguous().reshape(-1, n), 0))
+    if len(views) == 2 and views[0][1] != views[1][1]:  # (two pitches: both arranged)
+        views = [(r.contiguous(), 0) for r, _ in views]
+    fl, _, ph = _flags_tables(c, c.da, None if c2 is None else c2.lag_x, None if c2 is None else c2.reversed)
+    kw = dict(ndim=1, ny=1, nx=l, dtype=torch.float32, out_mode=mode, detrend=det, flags=fl | flags, scale=float(scale), phase_x=ph["x"] if mode == _lib.OUT_CROSS else None,
+              seg_tapers=k, seg_taper_len=n, tapers=table, batch=views[0][0].shape[0], in_stride_batch=int(views[0][1]))
+    plan = _segment_plan(kw, {})
+    if plan is None:
+        return None
+    return plan.execute(*[r for r, _ in views])[0]
+
+
+def _multitaper_composed(das, heads, dim, l, d, w, detrend, real_dim, shift, spacing_tol, true_phase):
+    """The definition of the result, values only, ``dim`` last: the library's detrend over the N samples, a leading taper dim by broadcasting the table, zero-extension
+    to L, ``power_spectrum`` / ``cross_spectrum`` along ``dim`` (density scaling, no detrend, no window), the weighted sum over the tapers.  The density scaling of an
+    L-sample series is dt / L: times L, the tapers having unit norm over their N samples (mean(d^2) = 1 / L of the zero-extended taper)."""
+    k, n = d.shape
+    tname = "taper"
+    while tname in das[0].dims:
+        tname += "_"
+    stacks = []
+    for da, head in zip(das, heads):
+        y = from_any(_api.detrend(da, dim, detrend)) if detrend is not None else da
+        v = _to_device(y.data).movedim(da.get_axis_num(dim), -1)
+        if v.dtype in (torch.float16, torch.bfloat16):
+            v = engine.convert(v.contiguous(), torch.float32)
+        if v.dtype not in (torch.float32, torch.float64):
+            v = v.to(torch.float64)
+        tab = torch.from_numpy(np.array(d)).to(v.dtype).to(v.device).reshape((k,) + (1,) * (v.dim() - 1) + (n,))
+        ext = torch.zeros((k,) + tuple(v.shape[:-1]) + (l,), dtype=v.dtype, device=v.device)
+        ext[..., :n] = v.unsqueeze(0) * tab
+        stacks.append(DataArray(ext, (tname,) + tuple(head.dims), {dim: head.coords[dim]}))
+    kw = dict(dim=[dim], real_dim=real_dim, scaling="density", detrend=None, window=None, shift=shift, spacing_tol=spacing_tol)
+    full = _api.power_spectrum(stacks[0], **kw) if len(stacks) == 1 else _api.cross_spectrum(stacks[0], stacks[1], true_phase=true_phase, **kw)
+    f = _to_device(from_any(full).data)
+    rdt = f.real.dtype if f.is_complex() else f.dtype
+    wt = torch.from_numpy(np.asarray(w, dtype=np.float64) * l).to(rdt).to(f.device).reshape((k,) + (1,) * (f.dim() - 1))
+    return (f * wt).sum(dim=0)
+
+
+def _multitaper(da, da2, dim, nw, k, nfft, weights, tapers, real_dim, detrend, shift, spacing_tol, true_phase, least=1):
+    da = from_any(da)
+    da2 = None if da2 is None else from_any(da2)
+    if da2 is not None and (tuple(da2.dims) != tuple(da.dims) or da2.shape != da.shape):
+        raise ValueError("The two datasets have different dimensions")
+    n, l, k, d, w = _multitaper_args(da, dim, nw, k, nfft, weights, tapers)
+    if k < least:
+        raise ValueError(f"K = {k} taper(s): at least {least} are needed (of one spectrum the coherence is 1 everywhere)")
+    if real_dim is not None and real_dim != dim:
+        raise ValueError(f"real_dim must be {dim!r}, the one transform dimension, or None")
+    if detrend not in (None, "constant", "linear"):
+        raise NotImplementedError("%s is not a valid detrending option. Valid options are: 'constant','linear', or None." % detrend)
+    das = [da] if da2 is None else [da, da2]
+    heads = [_multitaper_head(x, dim, n, l, spacing_tol) for x in das]
+    other = heads[0][1]
+    heads = [h for h, _ in heads]
+    # the labels, the scaling and the tables are those of the spectrum of ONE zero-extended series (no detrend there: it is taken over the N samples, below)
+    c, c2, mode, scale, flags = _api._spectrum(heads[0], None if da2 is None else heads[1], [dim], real_dim, "density", False, true_phase,
+                                               dict(detrend=None, window=None, shift=shift, spacing_tol=spacing_tol))
+    det = {None: _lib.DETREND_NONE, "constant": _lib.DETREND_CONSTANT, "linear": _lib.DETREND_LINEAR}[detrend]
+    if det == _lib.DETREND_LINEAR and math.prod(da.shape):
+        for x in das:
+            _refuse_nonfinite_span(x, dim, n)
+    ax = da.get_axis_num(dim)
+    ts = []
+    for x in das:
+        t = _to_device(x.data)
+        ts.append(engine.convert(t.contiguous(), torch.float32) if t.dtype in (torch.float16, torch.bfloat16) else t)
+    out = _multitaper_fused(c, c2, ts, ax, n, l, k, _taper_table(d, w), det, mode, scale * l, flags)
+    if out is None:
+        out = _multitaper_composed(das, heads, dim, l, d, w, detrend, real_dim, shift, spacing_tol, true_phase)
+    res = _label_output(c, heads[0], out, other, _direct_lag_attrs(c) if c2 is not None and c.true_phase else None)  # (as _cross_result)
+    res.attrs["tapers"] = k
+    return res
+
+
+def multitaper_power_spectrum(da, dim, NW=4.0, K=None, nfft=None, weights="unity", tapers=None, real_dim=None, detrend=None, shift=True, spacing_tol=1e-3):
+    """Thomson's multitaper estimate of the power spectrum along ``dim``: the whole record of N samples is multiplied by K orthogonal Slepian (DPSS) tapers of
+    time-bandwidth product ``NW`` (``K`` defaults to ``int(2 NW) - 1``; 1 <= K <= N), zero-extended to ``nfft`` = L samples (default: the smallest power of two
+    >= N; a given ``nfft`` < N raises), transformed K times, and the K spectra are added with the weights w_j -- ``weights="unity"``: 1 / K; ``"eigen"``: the
+    tapers' concentration ratios over their sum.  With y the series after ``detrend`` (None, "constant", "linear": over its N samples), d_j the tapers (unit L2
+    norm) and dt the spacing of ``dim``:
+        S[k] = dt sum_j w_j |sum_{n<N} d_j[n] y[n] exp(-2 pi i k n / L)|^2,   k over L frequencies of spacing 1 / (L dt)
+    -- a density (sum_k S[k] / (L dt) = sum_j w_j sum_n (d_j y)^2[n]); there is no ``scaling`` argument.  ``real_dim=dim`` gives the half output k <= L / 2 with the
+    factor 2 on 0 < k < L / 2.  ``tapers``: a real array (K, N) used as given instead of the DPSS (rows normalised to unit L2 norm; it replaces ``NW`` / ``K``, and
+    ``weights="eigen"`` then raises).  The DPSS are computed in the library, in float64, from the symmetric tridiagonal eigenproblem
+    (scipy.linalg.eigh_tridiagonal where scipy imports, else numpy.linalg.eigh), with scipy.signal.windows.dpss's signs and ratios, and remembered per (N, NW, K).
+    Dims: the other dims in their order, then ``freq_<dim>``; coordinates, name and attrs are those ``power_spectrum`` gives for the same series zero-extended to L
+    samples, plus ``attrs["tapers"] = K``.
+    float32 data with L a power of two in 64 .. 4096 and K <= 32 are transformed by ONE pass (xrfthip_desc.seg_tapers): the series is read where it lies, neither
+    the K tapered copies nor the K spectra reach memory.  A trailing ``dim`` with one pitch between the series is read in place; any other is arranged first (one
+    transposed copy); float16 / bfloat16 are widened first.  Every other call -- float64, other L, K > 32, XRFTHIP_FASTW_TAPERS=0 -- composes: ``detrend``, a taper dim by
+    broadcasting the table, zero-extension, ``power_spectrum``, the weighted sum.  A linear detrend refuses non-finite samples (ValueError)."""
+    src = da
+    return to_like(_multitaper(da, None, dim, NW, K, nfft, weights, tapers, real_dim, detrend, shift, spacing_tol, False), src)
+
+
+def multitaper_cross_spectrum(da1, da2, dim, NW=4.0, K=None, nfft=None, weights="unity", tapers=None, real_dim=None, detrend=None, shift=True, spacing_tol=1e-3,
+                              true_phase=True):
+    """The multitaper cross spectrum ``dt sum_j w_j X1_j conj(X2_j)`` of two series under the same tapers (see ``multitaper_power_spectrum``), times the net
+    true-phase factor of the two coordinates' origins exactly as ``cross_spectrum`` / ``welch_cross_spectrum`` apply it (``true_phase=False``: none).  Complex.  A
+    descending coordinate under ``true_phase`` (the reference flips such a field) composes."""
+    src = da1
+    return to_like(_multitaper(da1, da2, dim, NW, K, nfft, weights, tapers, real_dim, detrend, shift, spacing_tol, true_phase), src)
+
+
+def multitaper_coherence(da1, da2, dim, NW=4.0, K=None, nfft=None, weights="unity", tapers=None, real_dim=None, detrend=None, shift=True, spacing_tol=1e-3,
+                         true_phase=True):
+    """Magnitude-squared coherence ``|S12|^2 / (S11 S22)`` of the three multitaper spectra, composed as ``welch_coherence`` is: ``multitaper_cross_spectrum`` and
+    ``multitaper_power_spectrum`` of each series, the division the library's (xrfthip_coherence; no clamp).  Fewer than two tapers: ValueError (of one spectrum the
+    coherence is 1 everywhere)."""
+    src = da1
+    da1, da2 = from_any(da1), from_any(da2)
+    a = (dim, NW, K, nfft, weights, tapers, real_dim, detrend, shift, spacing_tol)
+    cs = _multitaper(da1, da2, *a, true_phase, least=2)
+    p1, p2 = (_multitaper(x, None, *a, False) for x in (da1, da2))
+    res = _api._coherence_result(cs, p1, p2, da1, da2)
+    res.attrs["tapers"] = cs.attrs["tapers"]
+    return to_like(res, src)

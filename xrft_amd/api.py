@@ -36,7 +36,7 @@ from .labeled import Coordinate, DataArray, from_any, to_like
 
 __all__ = ["clear_plan_cache", "fft", "ifft", "dft", "idft", "detrend", "power_spectrum", "cross_spectrum", "cross_phase", "isotropize",
            "isotropic_power_spectrum", "isotropic_cross_spectrum", "fit_loglog", "mean_power_spectrum", "mean_cross_spectrum", "welch_power_spectrum", "welch_cross_spectrum",
-           "welch_coherence", "spectrogram", "stft", "istft", "fir_filter"]
+           "welch_coherence", "spectrogram", "stft", "istft", "fir_filter", "multitaper_power_spectrum", "multitaper_cross_spectrum", "multitaper_coherence"]
 
 
 def clear_plan_cache():
@@ -847,7 +847,7 @@ def coherence(da1, da2, mean_dim, dim=None, real_dim=None, scaling="density", wi
 _WELCH_COLS_WS_CAP = 256 << 20
 _WELCH_COLS_ALIGN = 32  # blocks are whole groups of columns (fastw.h, kWCols): every column is summed as in the unblocked call
 
-from ._segments import _welch_segments, fir_filter, istft, spectrogram, stft, welch_coherence, welch_cross_spectrum, welch_power_spectrum  # noqa: E402,F401
+from ._segments import _welch_segments, fir_filter, istft, multitaper_coherence, multitaper_cross_spectrum, multitaper_power_spectrum, spectrogram, stft, welch_coherence, welch_cross_spectrum, welch_power_spectrum  # noqa: E402,F401
 
 
 def _cross_result(c, c2, mode, scale, flags):

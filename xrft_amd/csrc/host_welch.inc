@@ -8,6 +8,8 @@
 //           layout only, no workspace.  It is a form of FastK and not an enum value of its own: the segment spectra's family, both directions
 //           ... and both directions in one tile, the FIR filter by overlap-save (xrfthip_desc.seg_filter, fastf.h; the *_fastf entries below): a series' segments
 //           transformed, multiplied by the response, transformed back, the samples that do not wrap around written once; rows layout only, no workspace
+//   FastW   ... and its multitaper form (xrfthip_desc.seg_tapers, fastt.h; the *_fastt entries below): ONE series of N samples per output under K tapers, two tapers of the same
+//           samples packed per sequence, a workgroup owns whole outputs -- no workspace, no finish kernel; rows layout only, seg_hop = 0
 // FastW and FastK in the rows layout (one series per workgroup) or the column layout (xrfthip_desc.seg_stride: C adjacent columns of a (time, ..) block per workgroup).
 
 // xrfthip_plan_create's checks of seg_hop / seg_stride / seg_keep (XRFTHIP_BAD_ARG; what try_fastw declines is "the caller composes"), on its own copy of the descriptor: seg_stride = 1 is the rows layout and becomes it;
@@ -15,6 +17,20 @@
 // nothing of the strided-view rules (16-byte strides and pointers) applies to such a plan.  mean_batch counts the segments of a series (1 included when they are kept)
 int seg_desc_check(xrfthip_desc& s, long long* pitch) {
     *pitch = 0;
+    // seg_tapers / seg_taper_len: the multitaper form (fastt.h) -- ONE series of N samples per output, no segments: seg_hop and every other seg_* word 0
+    if (s.seg_tapers < 0 || (s.seg_tapers == 0 && s.seg_taper_len != 0)) return XRFTHIP_BAD_ARG;
+    if (s.seg_tapers > 0) {
+        if (s.seg_hop || s.seg_reserved || s.seg_stride || s.seg_reserved2 || s.seg_keep || s.seg_reserved3 || s.seg_synth || s.seg_reserved4 || s.seg_filter || s.seg_lead ||
+            s.seg_in_len || s.seg_out_len) return XRFTHIP_BAD_ARG;
+        const uint32_t known = XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2 | XRFTHIP_ISHIFT_X | XRFTHIP_FLIP_X | XRFTHIP_FLIP0_X;  // (the flips: try_fastt declines them)
+        if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.nx > (1LL << 30) || s.dtype != XRFTHIP_F32 || (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != XRFTHIP_OUT_CROSS) ||
+            s.mean_batch > 1 || s.batch < 0 || s.inner > 1 || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y || (s.flags & ~known)) return XRFTHIP_BAD_ARG;
+        if (s.seg_taper_len < 1 || s.seg_taper_len > s.nx || (s.in_stride_batch != 0 && s.in_stride_batch < s.seg_taper_len)) return XRFTHIP_BAD_ARG;
+        *pitch = s.in_stride_batch ? s.in_stride_batch : s.seg_taper_len;
+        s.in_stride_batch = 0;
+        s.mean_batch = 0;
+        return XRFTHIP_OK;
+    }
     if ((s.seg_filter != 0 && s.seg_filter != 1) || (!s.seg_filter && (s.seg_lead != 0 || s.seg_in_len != 0 || s.seg_out_len != 0))) return XRFTHIP_BAD_ARG;
     const bool filt = s.seg_filter == 1;
     if (filt && (s.seg_hop <= 0 || s.seg_keep != 0 || s.seg_synth != 0 || s.seg_stride != 0)) return XRFTHIP_BAD_ARG;
@@ -133,10 +149,41 @@ static int try_fastf(xrfthip_plan* P) {
     return plan_twiddle(P, P->w_twr, d.nx, d.nx / 2 + 1);  // (W_L^k, k <= L / 2, the unpacking and the packing)
 }
 
+// The multitaper form of FastW (seg_tapers = K, seg_taper_len = N; fastt.h): KP = ceil(K / 2) sequences of L points per series, G = 4096 / L in the tile; a workgroup takes
+// NS = max(1, G / KP) consecutive series, or one series in ceil(KP / G) rounds.  tps: the threads per series of the detrend's sums, the largest power of two with
+// NS tps <= 256 -- a function of (L, K) only
+struct TaperGeom { int KP, G, NS, seqs, rounds, tps; long long wgs; };
+static TaperGeom taper_geom(const xrfthip_desc& d) {
+    TaperGeom g;
+    g.KP = (int)((d.seg_tapers + 1) / 2);
+    g.G = (int)(kWPoints / d.nx);
+    g.NS = std::max(1, g.G / g.KP);
+    g.seqs = g.KP <= g.G ? g.NS * g.KP : g.G;
+    g.rounds = g.KP <= g.G ? 1 : (g.KP + g.G - 1) / g.G;
+    g.tps = 1;
+    while (2 * g.tps * g.NS <= kWThreads) g.tps *= 2;
+    g.wgs = (d.batch + g.NS - 1) / g.NS;
+    return g;
+}
+static int try_fastt(xrfthip_plan* P) {
+    const xrfthip_desc& d = P->d;
+    const bool len_ok = d.nx >= 64 && d.nx <= 4096 && (d.nx & (d.nx - 1)) == 0;
+    if (!len_ok || d.seg_tapers > 2 * kMeanChain || (d.flags & (XRFTHIP_FLIP_X | XRFTHIP_FLIP0_X)) || env_ll("XRFTHIP_FASTW", 1) == 0 || env_ll("XRFTHIP_FASTW_TAPERS", 1) == 0)
+        return XRFTHIP_UNSUPPORTED_LENGTH;  // (K <= 32: at most kMeanChain rounds, one float32 chain)
+    if (taper_geom(d).wgs > 0x7fffffffLL) return XRFTHIP_UNSUPPORTED_LENGTH;  // (one launch; declined, never truncated)
+    P->family = P->chosen = Family::FastW;
+    FftTables& t = P->tables[(int)d.nx];
+    const int rc = build_tables<float>(t, (int)d.nx);
+    if (rc) return rc;
+    for (int r : t.radix) if (r != 2 && r != 4 && r != 8 && r != 16) return XRFTHIP_UNSUPPORTED_LENGTH;
+    return XRFTHIP_OK;
+}
+
 // FastW / FastK: float32 series, segments of 64 .. 4096 samples, a power of two (the column layout: up to 512 -- the tile holds 8 adjacent columns at least; beyond,
 // the caller arranges the series as rows)
 int try_fastw(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
+    if (taper_plan(P)) return try_fastt(P);
     if (!welch_plan(P)) return kDeclined;
     if (synth_plan(P)) return try_fasto(P);
     if (filter_plan(P)) return try_fastf(P);
@@ -168,6 +215,19 @@ int try_fastw(xrfthip_plan* P) {
 // the longest run has.  FastK: no workspace (every output element is written once by the thread that computed it), as many segments per round as a series has
 static void layout_fastw(xrfthip_plan* P) {
     layout_one_pass(P);
+    if (taper_plan(P)) {  // the multitaper form: no workspace; the tile holds the pairs of tapers of NS series (or G pairs of one), [red][coef: 2 NS doubles per field] behind it
+        const TaperGeom g = taper_geom(P->d);
+        const long long n = P->d.nx;
+        long long ss = n + (n >> 4) + 1;
+        if ((ss & 1) == 0) ++ss;  // (an odd stride, as seg_geom)
+        P->w = SegGeom();
+        P->w.seqs = g.seqs;
+        P->w.stride = (int)ss;
+        P->w.rounds = g.rounds;
+        const size_t tile = (((size_t)g.seqs * (size_t)ss + 1) & ~(size_t)1) * sizeof(cf);
+        P->w.lds = tile * (P->d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1) + (size_t)(2 * kWThreads + 4 * g.NS) * sizeof(double);
+        return;
+    }
     P->ws_bytes = mean_layout(P, 0, 1, P->d.batch * seg_ngroups(P));  // (the launch: groups x runs workgroups per block)
     P->w = seg_geom(P, (P->mean_run + 1) / 2);
 }
@@ -285,8 +345,48 @@ static int run_fastf(const xrfthip_plan* P, const ExecArgs& a) {
     return XRFTHIP_OK;
 }
 
+// ... the multitaper form: one launch, nothing else
+static int run_fastt(const xrfthip_plan* P, const ExecArgs& a) {
+    const xrfthip_desc& d = P->d;
+    hipStream_t st = a.stream;
+    const TaperGeom g = taper_geom(d);
+    const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
+    if (!P->w_taps.p || g.wgs > 0x7fffffffLL) return XRFTHIP_BAD_ARG;  // (no table: xrfthip_plan_set_tapers; the launch: try_fastt declined it)
+    FastT p{};
+    const FftTables& t = P->tables.at((int)d.nx);
+    p.t.tw = (const cf*)t.tw.p; p.t.rev = (const unsigned*)t.rev.p;
+    p.t.win = nullptr;
+    p.t.pitch = P->w_pitch; p.t.hop = 0; p.t.sstride = 1;
+    p.t.L = (int)d.nx; p.t.M = 1;
+    p.t.seq_stride = P->w.stride; p.t.pad_shift = 4;
+    p.t.nr = (int)t.radix.size();
+    for (int i = 0; i < p.t.nr; ++i) p.t.radix[i] = t.radix[i];
+    p.t.detrend = d.detrend;
+    p.t.scale = (float)d.scale;
+    p.t.inner = 1; p.t.lgC = 0; p.t.ngroups = 1;
+    p.in0 = (const float*)a.in0; p.in1 = (const float*)a.in1;
+    p.tap = (const float*)P->w_taps.p;
+    p.out = a.out;
+    p.ph = reinterpret_cast<const cf*>(P->fph[1].p);
+    p.ph_on = (two && P->fph_on && p.ph) ? 1 : 0;
+    p.P = d.batch;
+    p.K = (int)d.seg_tapers; p.KP = g.KP; p.N = (int)d.seg_taper_len;
+    p.NS = g.NS; p.seqs = g.seqs; p.rounds = g.rounds; p.tps = g.tps;
+    p.nx_out = (int)P->nx_out;
+    p.shift = (d.flags & XRFTHIP_SHIFT_X) ? (int)(d.nx / 2) : 0;
+    p.realdim2 = (d.flags & XRFTHIP_REALDIM_X2) ? 1 : 0;
+    const dim3 grid((unsigned)g.wgs), blk((unsigned)kWThreads);
+    xrfthip_plan::ProfRec* rec = prof_begin(P, "fastt_tapers", st);
+    if (two) { auto k = &fastt_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
+    else { auto k = &fastt_kernel<false>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
+    prof_end(rec, st);
+    HIP_TRY(hipGetLastError());
+    return XRFTHIP_OK;
+}
+
 // FastW: the segments' launch, then one finish workgroup per output
 static int run_fastw(const xrfthip_plan* P, const ExecArgs& a) {
+    if (taper_plan(P)) return run_fastt(P, a);
     const xrfthip_desc& d = P->d;
     hipStream_t st = a.stream;
     const bool two = d.out_mode == XRFTHIP_OUT_CROSS;
@@ -367,7 +467,21 @@ static void describe_fastf(const xrfthip_plan* plan, std::string& s, const char*
             (long long)d.nx, (long long)d.seg_hop, kWThreads, (long long)(d.batch / d.mean_batch), filter_wgs(d), (long long)(2 * kWPoints / d.nx), (long long)d.nx / 2,
             seg_radices(plan).c_str(), plan->phase[1].p ? "L / 2 + 1 complex64 entries" : "none set: ones, a delay", seg_radices(plan).c_str(), plan->w.lds, kFResources);
 }
+static void describe_fastt(const xrfthip_plan* plan, std::string& s) {
+    const xrfthip_desc& d = plan->d;
+    const TaperGeom g = taper_geom(d);
+    std::string rad;
+    for (int r : plan->tables.at((int)d.nx).radix) appendf(rad, "%s%d", rad.empty() ? "" : "x", r);
+    appendf(s, "  [fastw tapers] multitaper spectra, one pass: %lld series of N = %lld samples (series pitch %lld) under K = %lld tapers (%s), zero-extended to L = %lld; "
+               "one %d-thread workgroup per %d series: %lld workgroups, %d pairs of tapers per series packed (t_2q x + i t_2q+1 x) as %d sequences of an LDS tile in %d "
+               "round(s), detrend over the N samples once per series (%d threads each, float64), radix %s in place, |Z|^2 (Z conj Z') summed in %d float32 registers per "
+               "thread, then float64 per series and frequency, symmetrised, fftshift / half output in the same kernel; no workspace, no second kernel, no atomics; ",
+            (long long)d.batch, (long long)d.seg_taper_len, plan->w_pitch, (long long)d.seg_tapers, plan->w_taps.p ? "table set" : "NO TABLE: xrfthip_plan_set_tapers",
+            (long long)d.nx, kWThreads, g.NS, g.wgs, g.KP, g.seqs, g.rounds, g.tps, rad.c_str(), kWAcc * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1));
+    appendf(s, "lds=%zuB; %s; 4 algorithmic bytes per sample read and one spectrum per series written\n", plan->w.lds, kTResources);
+}
 static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*) {
+    if (taper_plan(plan)) return describe_fastt(plan, s);
     const xrfthip_desc& d = plan->d;
     const SegGeom& g = plan->w;
     appendf(s, "  [fastw] Welch spectra, one pass: %lld series of %lld segments of %lld samples, hop %lld (series pitch %lld), each segment read where it lies with 4-byte loads; "
@@ -378,7 +492,7 @@ static void describe_fastw(const xrfthip_plan* plan, std::string& s, const char*
             seg_radices(plan).c_str(), kWAcc * (d.out_mode == XRFTHIP_OUT_CROSS ? 2 : 1), g.lds);
     describe_cols(plan, s, "pairs of segments", "pair", (std::string("the float64 sums per column; fastw_kernel<cols>: ") + kWColsResources).c_str());
 }
-static void info_fastw(const xrfthip_plan* plan, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTW; *n = 2 * plan->w.seqs; }  // (per_workgroup: the segments of a round)
+static void info_fastw(const xrfthip_plan* plan, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTW; *n = taper_plan(plan) ? taper_geom(plan->d).NS : 2 * plan->w.seqs; }  // (per_workgroup: the segments of a round)
 static void info_fastk(const xrfthip_plan* plan, int32_t* k, int32_t* n) { *k = XRFTHIP_K_FASTW; *n = plan->w.seqs; }
 // (the entries in the order of struct FamilyOps; reads_strided is false -- the series pitch is w_pitch, d.in_stride_batch is 0 -- and the last entry, no_generic_passes, true)
 static int finalize_fastk(xrfthip_plan* P) { return synth_plan(P) || filter_plan(P) ? XRFTHIP_OK : fast_phase_tables(P); }  // (the synthesis takes no phase table; the filter's is its response, read as it was set)
@@ -392,6 +506,7 @@ void set_attrs_welch() {
     const int m = (int)kLdsMax;
 #define SETF(K) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, m)
     SETF((fastw_kernel<false>)); SETF((fastw_kernel<true>)); SETF((fastw_kernel<false, true>)); SETF((fastw_kernel<true, true>));
+    SETF((fastt_kernel<false>)); SETF((fastt_kernel<true>));
     SETF((fastk_kernel<true, false>)); SETF((fastk_kernel<false, false>)); SETF((fastk_kernel<true, true>)); SETF((fastk_kernel<false, true>));
 #undef SETF
 }

@@ -67,6 +67,7 @@
 #include "fastk.h"
 #include "fasto.h"
 #include "fastf.h"
+#include "fastt.h"
 #ifdef XRFT_SPLIT_TUS  /* the library built from several translation units: the fasty / fastm kernels are instantiated in inst_g*.cpp */
 namespace xrft {
 #define XRFT_KW extern template __global__
@@ -344,7 +345,7 @@ enum class Family {
     FastR,           // one pass over a long real float32 row in registers (fastr.h)
     FastRComplex,    // ... complex rows of 2048 .. 16384 points (fastc_kernel)
     FastRRows,       // complex rows of 256 .. 4096 points: the row pass of fasty_c2c.h on the input's own rows
-    FastW,           // xrfthip_desc.seg_hop, Welch spectra: the mean spectrum of the overlapping segments of a series, rows or column layout (fastw.h)
+    FastW,           // xrfthip_desc.seg_hop, Welch spectra: the mean spectrum of the overlapping segments of a series, rows or column layout (fastw.h); with xrfthip_desc.seg_tapers the multitaper form, the sum over K tapers of ONE series' spectra (fastt.h)
     FastK,           // ... with xrfthip_desc.seg_keep, spectrograms: every segment's spectrum kept (fastk.h); with seg_synth the way back, the series rebuilt from them (fasto.h); with seg_filter both in one tile, a series filtered by overlap-save (fastf.h)
     FastYC,          // the two passes of fasty_c2c.h over complex float32 slabs
     FastYCFourStep,  // ... over ONE long complex sequence per batch entry, the four-step form of pass 2
@@ -497,6 +498,7 @@ struct xrfthip_plan {
     long long w_pitch = 0;
     SegGeom w;
     DevBuf w_twr;
+    DevBuf w_taps;                 // the multitaper form (xrfthip_desc.seg_tapers): the table [K][N] float32, xrfthip_plan_set_tapers
     ~xrfthip_plan() { for (auto* b : extra) delete b; prof_clear(); delete sub_x; delete sub_y; }
 };
 
@@ -617,6 +619,7 @@ inline bool welch_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0; }  // (
 inline bool keep_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_keep == 1; }  // (... every segment's spectrum kept, none averaged: Family::FastK, fastk.h)
 inline bool synth_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_synth == 1; }  // (... the series rebuilt from its segments' half spectra: the synthesis form of Family::FastK, fasto.h)
 inline bool filter_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_filter == 1; }  // (... a series filtered by overlap-save: the filter form of Family::FastK, fastf.h)
+inline bool taper_plan(const xrfthip_plan* P) { return P->d.seg_tapers > 0; }  // (... the sum over K tapers of one series' spectra: the multitaper form of Family::FastW, fastt.h; seg_hop = 0)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's
 // input take them: pass 1 of the two-pass families, the load of the one-pass families.  The intermediate and the output are dense.

@@ -893,11 +893,11 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // (... and of the versions before `mid` and before the input strides: mid = 1, strides 0)
     // (... and of the version before herm_ny / herm_nx: 0, 0)
     // (... and before each later group of fields, which then read 0: mean_batch; seg_hop / seg_reserved; seg_stride / seg_reserved2; seg_keep / seg_reserved3; seg_synth / seg_reserved4; seg_filter / seg_lead /
-    // seg_in_len / seg_out_len -- each group came together, no size between)
+    // seg_in_len / seg_out_len; seg_tapers / seg_taper_len -- each group came together, no size between)
     static const uint32_t kDescSizes[] = {
         (uint32_t)sizeof(xrfthip_desc), (uint32_t)offsetof(xrfthip_desc, inner), (uint32_t)offsetof(xrfthip_desc, mid), (uint32_t)offsetof(xrfthip_desc, in_stride_y),
         (uint32_t)offsetof(xrfthip_desc, herm_ny), (uint32_t)offsetof(xrfthip_desc, mean_batch), (uint32_t)offsetof(xrfthip_desc, seg_hop), (uint32_t)offsetof(xrfthip_desc, seg_stride),
-        (uint32_t)offsetof(xrfthip_desc, seg_keep), (uint32_t)offsetof(xrfthip_desc, seg_synth), (uint32_t)offsetof(xrfthip_desc, seg_filter)};
+        (uint32_t)offsetof(xrfthip_desc, seg_keep), (uint32_t)offsetof(xrfthip_desc, seg_synth), (uint32_t)offsetof(xrfthip_desc, seg_filter), (uint32_t)offsetof(xrfthip_desc, seg_tapers)};
     if (!plan || !desc || std::find(std::begin(kDescSizes), std::end(kDescSizes), desc->struct_size) == std::end(kDescSizes)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);
@@ -1023,7 +1023,7 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
             if ((rc = try_family(P)) != kDeclined) break;
     if (rc == kDeclined) rc = XRFTHIP_OK;
     if (!rc && herm && P->family != Family::FastH) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family reads a half spectrum as columns: the caller composes the stages)
-    if (!rc && d.seg_hop && P->family != Family::FastW && P->family != Family::FastK) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family cuts segments out of a series: the caller composes)
+    if (!rc && (d.seg_hop || d.seg_tapers) && P->family != Family::FastW && P->family != Family::FastK) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (no other family cuts segments out of a series: the caller composes)
     const bool one_axis = P->family == Family::FastGY || P->family == Family::FastMY;
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_PHASE_IN) && !one_axis) rc = XRFTHIP_BAD_ARG;  // (the generic column tiles have no input phase)
     if (!rc && (d.flags & XRFTHIP_AXIS_Y) && (d.flags & XRFTHIP_HALF_X) && !one_axis) rc = XRFTHIP_UNSUPPORTED_LENGTH;  // (... and no half output: the caller transposes)
@@ -1048,6 +1048,7 @@ int xrfthip_plan_set_window(xrfthip_plan* plan, int axis, const double* h_window
     if (!plan || axis < 0 || axis > 1) return XRFTHIP_BAD_ARG;
     if (herm_plan(plan) && axis == 1) return XRFTHIP_BAD_ARG;  // (the two-axis stage that wrote the half spectrum windowed y and x)
     if (filter_plan(plan) && h_window) return XRFTHIP_BAD_ARG;  // (overlap-save takes no window: a windowed segment is not a linear filter's)
+    if (plan && taper_plan(plan) && h_window) return XRFTHIP_BAD_ARG;  // (the tapers are the windows: xrfthip_plan_set_tapers)
     if (h_window && n != (axis == 0 ? plan->d.ny : plan->d.nx)) return XRFTHIP_BAD_ARG;
     if (plan->sub_x) return xrfthip_plan_set_window(axis == 0 ? plan->sub_y : plan->sub_x, (axis == 1 && plan->sub_x_1d) ? 1 : 0, h_window, n);  // (each one-axis plan transforms its "y"; a 1-D x stage its x)
     if (axis == 0) plan->host_win_y.assign(h_window ? h_window : nullptr, h_window ? h_window + n : nullptr);
@@ -1080,6 +1081,13 @@ int xrfthip_plan_set_phase(xrfthip_plan* plan, int axis, const double* h_phase, 
     int rc = upload_real_table(plan, plan->phase[axis], h_phase, n, 1);
     if (!rc) rc = finalize_plan(plan);  // (a non-trivial phase can take an isotropic cross spectrum off the specialised path: new layout)
     return rc;
+}
+
+// the taper table of a multitaper plan: [K][N] float32, weighted by the caller, kept beside the plan's other tables (fastt.h reads w_taps)
+int xrfthip_plan_set_tapers(xrfthip_plan* plan, const float* h_tapers) {
+    if (!plan || !taper_plan(plan)) return XRFTHIP_BAD_ARG;
+    if (!h_tapers) { plan->w_taps.clear(); return XRFTHIP_OK; }
+    return plan->w_taps.upload(h_tapers, (size_t)plan->d.seg_tapers * (size_t)plan->d.seg_taper_len * sizeof(float));
 }
 
 int xrfthip_plan_set_binmap(xrfthip_plan* plan, const int32_t* h_binmap, int64_t ny, int64_t nx_out, int32_t nbins) {
@@ -1250,6 +1258,7 @@ int xrfthip_exec_ex(const xrfthip_plan* plan, const xrfthip_exec_args* args) {
     if (!d_out && !(d.flags & XRFTHIP_NO_SPECTRUM_OUT)) return XRFTHIP_BAD_ARG;
     if (iso && (!d_iso || !P->binmap.p)) return d_iso ? XRFTHIP_MISSING_TABLE : XRFTHIP_BAD_ARG;
     const bool inner = inner_layout(P);  // (always a workspace)
+    if (taper_plan(P) && !P->w_taps.p) return XRFTHIP_BAD_ARG;  // (a multitaper plan without its table: xrfthip_plan_set_tapers)
     if (!inner && !family_ops(P->family).no_generic_passes && P->passes.empty()) return XRFTHIP_MISSING_TABLE;  // (the generic passes stand behind every other family)
     // pass-1 blocks: the fields of a plan that hands them over (fasty_pass1_bytes), whole, aligned, apart from each other and from the workspace
     ExecArgs a{d_in0, d_in1, nullptr, (double*)d_iso, (char*)d_workspace, (hipStream_t)args->stream};

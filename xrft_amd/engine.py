@@ -41,7 +41,7 @@ class SpectralPlan:
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
                  slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0, seg_stride=0, seg_keep=0, seg_synth=0,
-                 seg_filter=0, seg_lead=0, seg_in_len=0, seg_out_len=0):
+                 seg_filter=0, seg_lead=0, seg_in_len=0, seg_out_len=0, seg_tapers=0, seg_taper_len=0, tapers=None):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
@@ -87,11 +87,19 @@ class SpectralPlan:
         self.seg_filter, self.seg_lead, self.seg_in_len, self.seg_out_len = int(seg_filter), int(seg_lead), int(seg_in_len), int(seg_out_len)
         if self.seg_filter:
             self.batch_out = self.batch // max(self.mean_batch, 1)
-        d = _lib.DescFilt(C.sizeof(_lib.DescFilt), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
+        # multitaper spectra (xrfthip_desc.seg_tapers; float32, POWER | CROSS, seg_hop 0): nx = L the transform length, the input (series, seg_taper_len) -- in_stride_batch
+        # the pitch between series in samples -- and the result (series, nx_out); ``tapers`` is the (seg_tapers, seg_taper_len) table, already weighted by sqrt(w_j)
+        self.seg_tapers, self.seg_taper_len = int(seg_tapers), int(seg_taper_len)
+        d = _lib.DescTaper(C.sizeof(_lib.DescTaper), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
                       int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
                       self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0, self.seg_stride, 0, self.seg_keep, 0, self.seg_synth, 0,
-                      self.seg_filter, self.seg_lead, self.seg_in_len, self.seg_out_len)
+                      self.seg_filter, self.seg_lead, self.seg_in_len, self.seg_out_len, self.seg_tapers, self.seg_taper_len)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
+        if tapers is not None:
+            tp = np.ascontiguousarray(tapers, dtype=np.float32)
+            if tp.shape != (self.seg_tapers, self.seg_taper_len):
+                raise ValueError(f"taper table shape {tp.shape} != {(self.seg_tapers, self.seg_taper_len)}")
+            _lib.check(self._dll.xrfthip_plan_set_tapers(self._h, tp.ctypes.data_as(C.c_void_p)))
         for axis, w in ((0, window_y), (1, window_x)):
             if w is not None:
                 w = np.ascontiguousarray(w, dtype=np.float64)
@@ -175,6 +183,9 @@ class SpectralPlan:
         if self.seg_hop and self.seg_filter:  # (series, samples): exactly seg_in_len samples a series, adjacent, the series the plan's pitch apart
             return (t.dim() == 2 and tuple(t.shape) == (self.batch_out, self.seg_in_len) and (t.stride(1) == 1 or self.seg_in_len == 1)
                     and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or self.seg_in_len)))
+        if self.seg_tapers:  # (series, samples): exactly seg_taper_len samples a series, adjacent, the series the plan's pitch apart; 4-byte alignment is the dtype's
+            return (t.dim() == 2 and tuple(t.shape) == (self.batch, self.seg_taper_len) and (t.stride(1) == 1 or self.seg_taper_len == 1)
+                    and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or self.seg_taper_len)))
         if self.seg_hop and self.seg_stride > 1:  # (blocks, samples, columns): exactly the view the plan addresses -- columns adjacent, samples seg_stride apart, blocks the plan's pitch apart
             span = (self.mean_batch - 1) * self.seg_hop + self.nx
             return (t.dim() == 3 and t.shape[0] == self.batch_out and t.shape[1] >= span and t.shape[2] == self.inner
@@ -200,10 +211,10 @@ class SpectralPlan:
         take part in the reuse of the column pass (``reuse_column_pass``)."""
         dev = in0.device
         nx_in = self.nx // 2 + 1 if (self.flags & _lib.C2R_X) else self.nx
-        if in0.dtype != self.dtype or not self._layout_ok(in0) or (not self.seg_hop and in0.numel() != self.batch * self.ny * nx_in * self.inner * self.mid):
+        if in0.dtype != self.dtype or not self._layout_ok(in0) or (not self.seg_hop and not self.seg_tapers and in0.numel() != self.batch * self.ny * nx_in * self.inner * self.mid):
             raise ValueError("in0 does not match the plan (dtype / contiguity / size)")
         if self.out_mode in (_lib.OUT_CROSS, _lib.OUT_PHASE, _lib.OUT_COHERENCE):
-            if in1 is None or in1.dtype != self.dtype or not self._layout_ok(in1) or (not self.seg_hop and in1.numel() != in0.numel()):
+            if in1 is None or in1.dtype != self.dtype or not self._layout_ok(in1) or (not self.seg_hop and not self.seg_tapers and in1.numel() != in0.numel()):
                 raise ValueError("in1 does not match the plan")
         want_out = not (self.flags & _lib.NO_SPECTRUM_OUT)
         if want_out and out is None:
@@ -216,6 +227,8 @@ class SpectralPlan:
                 shape = (self.batch_out, (self.mean_batch - 1) * self.seg_hop + self.nx)
             if self.seg_hop and self.seg_filter:  # (the filtered series)
                 shape = (self.batch_out, self.seg_out_len)
+            if self.seg_tapers:  # (one spectrum per series)
+                shape = (self.batch, self.nx_out)
             if self.mid > 1:
                 shape = (self.batch, self.ny_out, self.mid, self.nx_out, self.inner)
             if self.herm_ny:
