@@ -345,7 +345,7 @@ typedef struct xrfthip_desc {
      * by the response, transformed back, and the V = L - K + 1 samples that do not wrap around kept.  No window, no overlap-add, no division, no gather; nothing but
      * the series (4 bytes per sample read) and the filtered series (4 bytes per sample written) goes through memory.
      *   seg_filter = 1   Valid with seg_hop = V, L / 2 <= V <= L (K = L - V + 1 taps); ndim = 1, ny = 1, nx = L; dtype XRFTHIP_F32, out_mode XRFTHIP_OUT_COMPLEX,
-     *                    flags = 0, detrend NONE, no window; seg_keep = seg_synth = seg_stride = 0, inner <= 1.
+     *                    flags = 0, detrend NONE, no window; seg_keep = seg_synth = seg_stride = 0, inner <= 1 (the column layout, seg_filter_cols below, apart).
      *   seg_in_len = N >= 1       samples per series.  d_in0 is [P] series of N float32, series p at d_in0 + p * in_stride_batch: in_stride_batch is HERE the series
      *                             pitch in samples, 0 = dense = N, any other value >= N.
      *   seg_out_len = n_out >= 1  samples per filtered series.  d_out is [P][n_out] float32, dense, NOT complex whatever out_mode says:
@@ -391,6 +391,27 @@ typedef struct xrfthip_desc {
      * versions are accepted (0, 0); an older library answers XRFTHIP_BAD_ARG to the larger struct_size.  Offsets are computed in 64 bits. */
     int64_t seg_tapers;
     int64_t seg_taper_len; /* appended together with seg_tapers: no struct_size between the two */
+    /* The COLUMN layout of the FIR filter (seg_filter = 1): the series lie along a leading axis of a (time, ..) array and are filtered where they lie; the result is
+     * written in the array's own order.  No transposed copy comes in or goes out: 4 bytes per sample read and 4 written, as in the rows layout.
+     *   seg_filter_cols = 1   Valid with seg_filter = 1 and everything it asks for, but: seg_stride = S >= inner >= 1 (S >= 1: S = 1 with inner = 1 is one column of
+     *                         its own and is NOT turned into the rows layout).  d_in0 is [blocks][N][inner] float32 columns: sample t of column c of block b at
+     *                         d_in0 + b * in_stride_batch + t * S + c.  in_stride_batch is HERE the block pitch in elements, 0 = dense = N * S, any other value
+     *                         >= (N - 1) * S + inner.  d_out is [blocks][n_out][inner] float32, dense -- the final order.  batch = blocks * M, M = mean_batch =
+     *                         ceil(n_out / V); seg_lead, seg_in_len = N and seg_out_len = n_out as in the rows layout.  S, inner, N and n_out at most 2^31 - 1.
+     *                         0 = off: everything about the descriptor is as without the field.
+     * A workgroup takes C = min(32, 8192 / L) adjacent columns of one block and 8192 / (L C) consecutive segments of each; the loads and the stores run column
+     * fastest (consecutive lanes, consecutive addresses of one time row).  Nothing outside the columns [0, inner) and the time rows [0, N) of a block is read.  A
+     * sample's bits depend on its own segment's L inputs, on H and on `scale` only: they are those of the rows layout on the transposed copy, whatever inner, S,
+     * the block and the neighbouring columns are.  A non-finite sample stays in its own column and in the segments that hold it.
+     * XRFTHIP_BAD_ARG: seg_filter_cols not 0 | 1; seg_reserved5 non-zero; seg_filter_cols without seg_filter; seg_stride = 0 or < inner; S, inner, N or n_out beyond
+     * 2^31 - 1; a pitch below (N - 1) * S + inner.  XRFTHIP_UNSUPPORTED_LENGTH ("the caller arranges": one transposed copy, the rows layout): L > 512; a launch
+     * beyond 2^31 - 1 workgroups; a narrow grid, at most half of the groups' columns live (2 inner <= ceil(inner / C) C; it measured slower than the arranged route,
+     * profiles/r30_fir_filter_cols.txt; taken with XRFTHIP_MEAN_ALL=1); XRFTHIP_FASTW=0, XRFTHIP_FASTW_FILTER=0, XRFTHIP_FASTW_COLS=0 or XRFTHIP_FASTW_FILTER_COLS=0 in the environment when the plan is
+     * created (docs/TUNING.md).
+     * Still XRFTHIP_K_FASTW and the [fastw overlap-save] line, with a [fastw columns] line behind it.  Descriptors with the struct_size of the twelve earlier
+     * versions are accepted (0, 0); an older library answers XRFTHIP_BAD_ARG to the larger struct_size.  Offsets are computed in 64 bits. */
+    int64_t seg_filter_cols;
+    int64_t seg_reserved5; /* 0 (anything else: XRFTHIP_BAD_ARG).  Appended together with seg_filter_cols: no struct_size between the two */
 } xrfthip_desc;
 
 typedef struct xrfthip_plan xrfthip_plan;

@@ -15,7 +15,8 @@ NOTES = {
     "XRFTHIP_FASTW_KEEP": "0: the segments-kept form of the Welch family (`fastk.h`) off: a plan with `xrfthip_desc.seg_keep` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) composes `spectrogram` / `stft` -- segments unfolded and copied, the plain 1-D plan, the dims moved: the route before the form, kept for measurements (profiles/r21_spectrogram.txt)",
     "XRFTHIP_FASTW_SYNTH": "0: the synthesis form of the Welch family (`fasto.h`) off: a plan with `xrfthip_desc.seg_synth` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) composes `istft` -- `ifft` of every segment, the window, R strided adds, the division: the route without the form, kept for measurements (profiles/r26_istft.txt)",
     "XRFTHIP_FASTW_FILTER": "0: the filter form of the Welch family (`fastf.h`) off: a plan with `xrfthip_desc.seg_filter` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) composes `fir_filter` -- a zero-extended copy, the segments unfolded, the real 1-D plan, the table product, the C2R plan, the kept samples sliced out: the route without the form, kept for measurements (profiles/r27_fir_filter.txt)",
-    "XRFTHIP_FASTW_TAPERS": "0: the multitaper form of the Welch family (`fastt.h`) off: a plan with `xrfthip_desc.seg_tapers` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) composes `multitaper_*` -- the library's detrend, a taper dim by broadcasting the table, zero-extension, `power_spectrum` / `cross_spectrum`, the weighted sum: the route without the form, kept for measurements (profiles/r29_multitaper.txt)",
+    "XRFTHIP_FASTW_FILTER_COLS": "0: the column layout of the filter form (`fastf.h`, `fastf_kernel<.., true>`) off: a plan with `xrfthip_desc.seg_filter_cols` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) arranges a leading dim of `fir_filter` first -- one transposed copy, the rows layout, the result moved back as a view: the route before the layout, kept for measurements (profiles/r30_fir_filter_cols.txt)",
+    "XRFTHIP_FASTW_TAPERS":"0: the multitaper form of the Welch family (`fastt.h`) off: a plan with `xrfthip_desc.seg_tapers` answers XRFTHIP_UNSUPPORTED_LENGTH, and the API (which reads the variable itself, per call) composes `multitaper_*` -- the library's detrend, a taper dim by broadcasting the table, zero-extension, `power_spectrum` / `cross_spectrum`, the weighted sum: the route without the form, kept for measurements (profiles/r29_multitaper.txt)",
     "XRFTHIP_FASTC": "0: complex rows of 2048 ... 16384 points leave `fastc_kernel`",
     "XRFTHIP_CROWS": "0: complex rows of 256 ... 4096 points leave the row pass of `fasty_c2c.h`",
     "XRFTHIP_FASTYC": "0: complex power-of-two slabs leave the two-pass pipeline of `fasty_c2c.h`",
@@ -26,7 +27,7 @@ NOTES = {
     "XRFTHIP_GROUP": "slabs per pass-1 / pass-2 launch pair of the two-pass pipelines (default: the whole batch up to the workspace cap)",
     "XRFTHIP_DBG": "1: plan-selection trace on stderr",
     "XRFTHIP_MEAN_RUNS": "runs per output of a mean plan (`xrfthip_desc.mean_batch`): each run is a workgroup (per unit of rows) with a float64 partial of its own; 0 = the rule of `mean_layout` (fill the card, at most ny / 4; a Welch plan: at most M / 2)",
-    "XRFTHIP_MEAN_ALL": "1: a plan with `xrfthip_desc.mean_batch` takes the mean form of every class the kernels of `fasty_mean.h` / `fasts_mean.h` serve (default 0: only the classes that measured faster than the composition, profiles/r15_batch_mean.txt); likewise a plan with `xrfthip_desc.seg_keep` takes L = 4096 without overlap (profiles/r21_spectrogram.txt)",
+    "XRFTHIP_MEAN_ALL": "1: a plan with `xrfthip_desc.mean_batch` takes the mean form of every class the kernels of `fasty_mean.h` / `fasts_mean.h` serve (default 0: only the classes that measured faster than the composition, profiles/r15_batch_mean.txt); likewise a plan with `xrfthip_desc.seg_keep` takes L = 4096 without overlap (profiles/r21_spectrogram.txt) and one with `xrfthip_desc.seg_filter_cols` a narrow grid (profiles/r30_fir_filter_cols.txt)",
 }
 
 

@@ -110,10 +110,18 @@ class DescFilt(C.Structure):
 
 
 class DescTaper(C.Structure):
-    """xrfthip_desc as the library has it now: ``DescFilt`` and the two words appended together after it."""
+    """``DescFilt`` and the two words appended together after it; still accepted under its own struct_size."""
     _fields_ = DescFilt._fields_ + [
         ("seg_tapers", C.c_int64),  # K >= 1 (with seg_hop = 0, F32, POWER | CROSS): multitaper spectra -- [series][seg_taper_len] in, the sum over K tapers of each series' nx-point spectra out; 0: off
         ("seg_taper_len", C.c_int64),  # N <= nx samples per series (in_stride_batch: the series pitch)
+    ]
+
+
+class DescFiltCols(C.Structure):
+    """xrfthip_desc as the library has it now: ``DescTaper`` and the two words appended together after it."""
+    _fields_ = DescTaper._fields_ + [
+        ("seg_filter_cols", C.c_int64),  # 1 (with seg_filter and seg_stride = S >= inner): the filter's column layout -- [blocks][seg_in_len][inner] columns in, samples S apart (in_stride_batch: the block pitch), [blocks][seg_out_len][inner] out; 0: off
+        ("seg_reserved5", C.c_int64),  # 0
     ]
 
 
@@ -134,7 +142,7 @@ def _bind(dll):
     dll.xrfthip_strerror.restype = C.c_char_p
     dll.xrfthip_strerror.argtypes = [C.c_int]
     dll.xrfthip_last_hip_error.restype = C.c_int
-    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg, a DescCols, a DescKeep, a DescSynth, a DescFilt or a DescTaper, by reference)
+    dll.xrfthip_plan_create.argtypes = [C.POINTER(vp), vp]  # (a Desc, a DescSeg, a DescCols, a DescKeep, a DescSynth, a DescFilt, a DescTaper or a DescFiltCols, by reference)
     dll.xrfthip_plan_destroy.argtypes = [vp]
     dll.xrfthip_plan_set_window.argtypes = [vp, C.c_int, vp, i64]
     dll.xrfthip_plan_set_phase.argtypes = [vp, C.c_int, vp, i64]

@@ -584,16 +584,40 @@ def _fir_args(da, dim, taps, mode, nfft):
     return ax, h, k, l, a, n_out
 
 
+def _fir_columns(t, ax, k, l, a, n_out, resp, hop, m):
+    """The values of ONE plan with seg_filter and seg_filter_cols, contiguous in the dims' own order, or None where the caller arranges: a trailing ``dim``, L beyond
+    512, a view the column layout cannot describe (_welch_columns: XRFTHIP_FASTW_COLS=0 included), a refusal of the plan (remembered: a narrow grid -- at most half of the
+    column groups live -- is declined by default, profiles/r30_fir_filter_cols.txt), XRFTHIP_FASTW_FILTER_COLS=0."""
+    if ax == t.dim() - 1 or l < 64 or l > 512 or l & (l - 1) or os.environ.get("XRFTHIP_FASTW_FILTER_COLS", "1") == "0":  # (the knob of the library, honoured before a cached plan could answer)
+        return None
+    n = t.shape[ax]
+    v = _welch_columns(t, ax, n)
+    if v is None:
+        return None
+    view, pitch, ss = v
+    kw = dict(ndim=1, ny=1, nx=l, dtype=torch.float32, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0, scale=1.0 / l, phase_x=resp, mean_batch=m,
+              seg_hop=hop, seg_filter=1, seg_lead=a, seg_in_len=n, seg_out_len=n_out, batch=view.shape[0] * m, in_stride_batch=int(pitch), inner=view.shape[2],
+              seg_stride=int(ss), seg_filter_cols=1)
+    plan = _segment_plan(kw, {})
+    if plan is None:
+        return None
+    return plan.execute(view)[0].reshape(tuple(t.shape[:ax]) + (n_out,) + tuple(t.shape[ax + 1:]))
+
+
 def _fir_fused(t, ax, k, l, a, n_out, resp):
-    """The values of ONE plan with seg_filter, the series last, or None where the call composes: data that are not float32, an empty array, L not a power of two in
-    64 .. 4096, K - 1 > L / 2, a class the plan declines (XRFTHIP_UNSUPPORTED_LENGTH, remembered), XRFTHIP_FASTW_FILTER=0.  A trailing ``dim`` is read where it lies,
-    with one pitch between the series; any other is arranged first (one transposed copy)."""
+    """The values of ONE plan with seg_filter, in the dims' own order, or None where the call composes: data that are not float32, an empty array, L not a power of
+    two in 64 .. 4096, K - 1 > L / 2, a class the plan declines (XRFTHIP_UNSUPPORTED_LENGTH, remembered), XRFTHIP_FASTW_FILTER=0.  A trailing ``dim`` is read where it
+    lies, with one pitch between the series.  Any other is read where it lies too where the column layout takes it (_fir_columns: L <= 512, the dims behind ``dim``
+    one unit-stride run, those in front one pitch) and the result is contiguous; else it is arranged first (one transposed copy) and the result moved back as a view."""
     if t.dtype != torch.float32 or math.prod(t.shape) == 0 or n_out < 1 or os.environ.get("XRFTHIP_FASTW_FILTER", "1") == "0":  # (the knob of the library, honoured before a cached plan could answer)
         return None
     if 2 * (k - 1) > l:  # (the library's XRFTHIP_BAD_ARG: less than half of a transform would be kept; L itself it judges: 64 .. 4096, a power of two)
         return None
     hop = l - k + 1
     m = -(-n_out // hop)
+    out = _fir_columns(t, ax, k, l, a, n_out, resp, hop, m)
+    if out is not None:
+        return out
     v = t if ax == t.dim() - 1 else t.movedim(ax, -1)
     n = v.shape[-1]
     lead = _collapse(v.shape[:-1], v.stride()[:-1])
@@ -607,11 +631,11 @@ def _fir_fused(t, ax, k, l, a, n_out, resp):
     plan = _segment_plan(kw, {})
     if plan is None:
         return None
-    return plan.execute(rows)[0].reshape(tuple(v.shape[:-1]) + (n_out,))
+    return plan.execute(rows)[0].reshape(tuple(v.shape[:-1]) + (n_out,)).movedim(-1, ax)
 
 
 def _fir_composed(t, ax, k, l, a, n_out, resp):
-    """The definition of the result, values only, the series last: overlap-save at the same L out of the library's own pieces -- a zero-extended copy of the series,
+    """The definition of the result, values only, in the dims' own order (a view, the series last in memory): overlap-save at the same L out of the library's own pieces -- a zero-extended copy of the series,
     the segments unfolded at hop V = L - K + 1, the real 1-D forward plan, engine.table_mul by the response, the C2R inverse plan, the kept samples sliced out."""
     v = t.movedim(ax, -1)
     n = v.shape[-1]
@@ -625,14 +649,14 @@ def _fir_composed(t, ax, k, l, a, n_out, resp):
     seg = xe.unfold(-1, l, hop).contiguous().reshape(-1, l)
     b, nb = seg.shape[0], l // 2 + 1
     if b == 0:
-        return torch.empty(tuple(v.shape[:-1]) + (n_out,), dtype=t.dtype, device=t.device)
+        return torch.empty(tuple(v.shape[:-1]) + (n_out,), dtype=t.dtype, device=t.device).movedim(-1, ax)
     spec = _get_plan(ndim=1, batch=b, ny=1, nx=l, dtype=t.dtype, out_mode=_lib.OUT_COMPLEX, flags=_lib.HALF_X).execute(seg)[0].reshape(b, nb)
     del seg, xe
     prod = engine.table_mul(spec, _fir_device_response(resp, cdt, t.device), nb)
     del spec
     y = _get_plan(ndim=1, batch=b, ny=1, nx=l, dtype=cdt, out_mode=_lib.OUT_COMPLEX, flags=_lib.INVERSE | _lib.C2R_X, scale=1.0 / l).execute(prod)[0]
     y = y.reshape(tuple(v.shape[:-1]) + (m, l))[..., k - 1:]
-    return y.reshape(tuple(v.shape[:-1]) + (m * hop,))[..., :n_out]
+    return y.reshape(tuple(v.shape[:-1]) + (m * hop,))[..., :n_out].movedim(-1, ax)
 
 
 def _fir_coordinate(da, dim, mode, k, n, spacing_tol):
@@ -665,8 +689,12 @@ def fir_filter(da, dim, taps, mode="same", nfft=None, spacing_tol=1e-3):
     The work is overlap-save with segments of ``nfft`` = L samples, of which V = L - K + 1 are kept: by default the smallest power of two >= max(512, 4 (K - 1)),
     capped at 4096 (shorter, down to 64, where one shorter segment holds the whole series; profiles/r27_fir_filter.txt); a given ``nfft`` must be at least K (an odd one is raised by one; the result does not depend on it but for rounding).  float32 data with L a power
     of two in 64 .. 4096 and K - 1 <= L / 2 are filtered by ONE pass (xrfthip_desc.seg_filter): the series is read once and the result written once, no spectrum
-    reaches memory.  A trailing ``dim`` is read where it lies (a batch pitch included); any other is arranged first (one transposed copy) and the result moved back
-    as a view.  Every other call -- float64, other L, longer taps, XRFTHIP_FASTW_FILTER=0 -- composes the same overlap-save from the library's own real 1-D plans and
+    reaches memory.  A trailing ``dim`` is read where it lies (a batch pitch included).  Any other ``dim`` -- ``time`` of a (time, y, x) or (member, time, lat, lon)
+    array -- is read where it lies too, by the column layout of the same pass (xrfthip_desc.seg_filter_cols), and the result is contiguous in the dims' own order: no
+    transposed copy comes in or goes out.  That holds for L <= 512 (the default for K <= 129; longer taps with ``nfft`` <= 512) where the dims behind ``dim`` are one
+    unit-stride run and those in front one pitch, and more than half of the groups of 32 (L = 512: 16) adjacent columns are live (a narrower grid measured slower,
+    profiles/r30_fir_filter_cols.txt; XRFTHIP_MEAN_ALL=1 takes it); otherwise, or with XRFTHIP_FASTW_FILTER_COLS=0, the array is arranged first (one transposed copy) and the result moved
+    back as a view.  Every other call -- float64, other L, longer taps, XRFTHIP_FASTW_FILTER=0 -- composes the same overlap-save from the library's own real 1-D plans and
     a table product.  float16 / bfloat16 data are widened to float32 first and the result is float32; complex data run as two real calls, the real and the imaginary
     part."""
     src = da
@@ -683,7 +711,7 @@ def fir_filter(da, dim, taps, mode="same", nfft=None, spacing_tol=1e-3):
 
     def one(x):
         if math.prod(x.shape) == 0:  # (nothing to filter: the zeros of an empty sum)
-            return x.new_zeros(tuple(s for i, s in enumerate(x.shape) if i != ax) + (n_out,))
+            return x.new_zeros(tuple(n_out if i == ax else s for i, s in enumerate(x.shape)))
         out = _fir_fused(x, ax, k, l, a, n_out, resp)
         return _fir_composed(x, ax, k, l, a, n_out, resp) if out is None else out
 
@@ -695,7 +723,7 @@ def fir_filter(da, dim, taps, mode="same", nfft=None, spacing_tol=1e-3):
                 coords[name] = coord
         elif dim not in c.dims or n_out == n:
             coords[name] = c
-    return to_like(DataArray(out.movedim(-1, ax), da.dims, coords, da.name, da.attrs), src)
+    return to_like(DataArray(out, da.dims, coords, da.name, da.attrs), src)
 
 
 # ------------------------------------------------------------------------------------------------------

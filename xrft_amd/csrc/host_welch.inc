@@ -7,7 +7,8 @@
 //           inverse transform, window, overlap-add and the division by the summed squared windows in one pass, every output sample gathered by one thread; rows
 //           layout only, no workspace.  It is a form of FastK and not an enum value of its own: the segment spectra's family, both directions
 //           ... and both directions in one tile, the FIR filter by overlap-save (xrfthip_desc.seg_filter, fastf.h; the *_fastf entries below): a series' segments
-//           transformed, multiplied by the response, transformed back, the samples that do not wrap around written once; rows layout only, no workspace
+//           transformed, multiplied by the response, transformed back, the samples that do not wrap around written once; no workspace; rows layout, or (xrfthip_desc.
+//           seg_filter_cols with seg_stride) the column layout, its result in the array's own order
 //   FastW   ... and its multitaper form (xrfthip_desc.seg_tapers, fastt.h; the *_fastt entries below): ONE series of N samples per output under K tapers, two tapers of the same
 //           samples packed per sequence, a workgroup owns whole outputs -- no workspace, no finish kernel; rows layout only, seg_hop = 0
 // FastW and FastK in the rows layout (one series per workgroup) or the column layout (xrfthip_desc.seg_stride: C adjacent columns of a (time, ..) block per workgroup).
@@ -21,7 +22,7 @@ int seg_desc_check(xrfthip_desc& s, long long* pitch) {
     if (s.seg_tapers < 0 || (s.seg_tapers == 0 && s.seg_taper_len != 0)) return XRFTHIP_BAD_ARG;
     if (s.seg_tapers > 0) {
         if (s.seg_hop || s.seg_reserved || s.seg_stride || s.seg_reserved2 || s.seg_keep || s.seg_reserved3 || s.seg_synth || s.seg_reserved4 || s.seg_filter || s.seg_lead ||
-            s.seg_in_len || s.seg_out_len) return XRFTHIP_BAD_ARG;
+            s.seg_in_len || s.seg_out_len || s.seg_filter_cols || s.seg_reserved5) return XRFTHIP_BAD_ARG;
         const uint32_t known = XRFTHIP_SHIFT_X | XRFTHIP_HALF_X | XRFTHIP_REALDIM_X2 | XRFTHIP_ISHIFT_X | XRFTHIP_FLIP_X | XRFTHIP_FLIP0_X;  // (the flips: try_fastt declines them)
         if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.nx > (1LL << 30) || s.dtype != XRFTHIP_F32 || (s.out_mode != XRFTHIP_OUT_POWER && s.out_mode != XRFTHIP_OUT_CROSS) ||
             s.mean_batch > 1 || s.batch < 0 || s.inner > 1 || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y || (s.flags & ~known)) return XRFTHIP_BAD_ARG;
@@ -33,14 +34,17 @@ int seg_desc_check(xrfthip_desc& s, long long* pitch) {
     }
     if ((s.seg_filter != 0 && s.seg_filter != 1) || (!s.seg_filter && (s.seg_lead != 0 || s.seg_in_len != 0 || s.seg_out_len != 0))) return XRFTHIP_BAD_ARG;
     const bool filt = s.seg_filter == 1;
-    if (filt && (s.seg_hop <= 0 || s.seg_keep != 0 || s.seg_synth != 0 || s.seg_stride != 0)) return XRFTHIP_BAD_ARG;
+    // seg_filter_cols: the filter's column layout -- seg_stride = S >= inner, kept as it came (S = 1 with inner = 1 is one column, not the rows layout)
+    if ((s.seg_filter_cols != 0 && s.seg_filter_cols != 1) || s.seg_reserved5 != 0 || (s.seg_filter_cols && !filt)) return XRFTHIP_BAD_ARG;
+    const bool fcols = s.seg_filter_cols == 1;
+    if (filt && (s.seg_hop <= 0 || s.seg_keep != 0 || s.seg_synth != 0 || (fcols ? s.seg_stride < 1 : s.seg_stride != 0))) return XRFTHIP_BAD_ARG;
     if ((s.seg_synth != 0 && s.seg_synth != 1) || s.seg_reserved4 != 0 || (s.seg_synth && (s.seg_hop <= 0 || s.seg_keep != 0))) return XRFTHIP_BAD_ARG;
     const bool synth = s.seg_synth == 1;
     if ((s.seg_keep != 0 && s.seg_keep != 1) || s.seg_reserved3 != 0 || (s.seg_keep && s.seg_hop <= 0)) return XRFTHIP_BAD_ARG;
     const bool keep = s.seg_keep == 1;
     if (s.seg_hop < 0 || s.seg_reserved != 0 || s.seg_stride < 0 || s.seg_reserved2 != 0) return XRFTHIP_BAD_ARG;
     if (s.seg_stride > 0 && (s.seg_hop == 0 || s.seg_stride < s.inner)) return XRFTHIP_BAD_ARG;
-    if (s.seg_stride == 1) s.seg_stride = 0;
+    if (s.seg_stride == 1 && !fcols) s.seg_stride = 0;
     if (s.seg_hop == 0) return XRFTHIP_OK;
     if (s.ndim != 1 || s.ny != 1 || s.nx < 1 || s.seg_hop > s.nx || (s.flags & (XRFTHIP_AXIS_Y | XRFTHIP_ISO)) || (s.inner > 1 && !s.seg_stride) || s.mid > 1 || s.herm_ny || s.herm_nx || s.in_stride_y) return XRFTHIP_BAD_ARG;
     if (s.mean_batch < (keep || synth || filt ? 1 : 2) || s.batch < 0 || s.batch % s.mean_batch != 0) return XRFTHIP_BAD_ARG;
@@ -50,6 +54,15 @@ int seg_desc_check(xrfthip_desc& s, long long* pitch) {
         if (s.dtype != XRFTHIP_F32 || s.out_mode != XRFTHIP_OUT_COMPLEX || s.detrend != XRFTHIP_DETREND_NONE || s.flags != 0 || 2 * s.seg_hop < s.nx) return XRFTHIP_BAD_ARG;
         if (s.seg_in_len < 1 || s.seg_in_len > cap || s.seg_out_len < 1 || s.seg_out_len > cap || s.seg_lead < 0 || s.seg_lead > K - 1) return XRFTHIP_BAD_ARG;
         if (s.seg_lead + s.seg_out_len > s.seg_in_len + K - 1 || s.mean_batch != (s.seg_out_len + s.seg_hop - 1) / s.seg_hop) return XRFTHIP_BAD_ARG;
+        if (fcols) {  // [blocks][N][inner] columns, samples S apart: the pitch counts elements between blocks (the offsets stay far inside 64 bits, as in the other column forms)
+            const long long lim = (1LL << 31) - 1;
+            if (s.seg_stride > lim || s.inner > lim || s.seg_in_len > lim || s.seg_out_len > lim) return XRFTHIP_BAD_ARG;
+            const long long dense = (s.seg_in_len - 1) * s.seg_stride + s.inner;  // the elements one block reaches
+            if (s.in_stride_batch != 0 && s.in_stride_batch < dense) return XRFTHIP_BAD_ARG;
+            *pitch = s.in_stride_batch ? s.in_stride_batch : s.seg_in_len * s.seg_stride;
+            s.in_stride_batch = 0;
+            return XRFTHIP_OK;
+        }
         if (s.in_stride_batch != 0 && s.in_stride_batch < s.seg_in_len) return XRFTHIP_BAD_ARG;
         *pitch = s.in_stride_batch ? s.in_stride_batch : s.seg_in_len;
         s.in_stride_batch = 0;
@@ -131,15 +144,30 @@ static int try_fasto(xrfthip_plan* P) {
 }
 
 // The filter form of FastK (seg_filter): the tile holds NS = 8192 / L segments, ceil(M / NS) workgroups serve a series (fastf.h); no segment is transformed twice
+// The column layout (seg_filter_cols): a unit is C = min(kWCols, NS) adjacent columns of a block and the tile holds spr = NS / C consecutive segments of each
+// (4, 2, 1, 1 at L = 64, 128, 256, 512): ceil(M / spr) workgroups serve a unit
 static long long filter_wgs(const xrfthip_desc& d) {
     const long long NS = 2 * kWPoints / d.nx;
-    return (d.mean_batch + NS - 1) / NS;
+    const long long spr = d.seg_filter_cols == 1 ? NS / std::min<long long>(kWCols, NS) : NS;  // segments of one series (column) per tile
+    return (d.mean_batch + spr - 1) / spr;
 }
 static int try_fastf(xrfthip_plan* P) {
     const xrfthip_desc& d = P->d;
-    const bool len_ok = d.nx >= 64 && d.nx <= 4096 && (d.nx & (d.nx - 1)) == 0;
+    const bool cols = filter_cols(P);
+    const bool len_ok = d.nx >= 64 && d.nx <= (cols ? kWColsMaxL : 4096) && (d.nx & (d.nx - 1)) == 0;
     if (!len_ok || env_ll("XRFTHIP_FASTW", 1) == 0 || env_ll("XRFTHIP_FASTW_FILTER", 1) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
-    const long long series = d.batch / d.mean_batch;
+    if (cols && (env_ll("XRFTHIP_FASTW_COLS", 1) == 0 || env_ll("XRFTHIP_FASTW_FILTER_COLS", 1) == 0)) return XRFTHIP_UNSUPPORTED_LENGTH;  // (the caller arranges: one transposed copy, the rows layout)
+    long long series = d.batch / d.mean_batch;  // series, or (the column layout) groups of columns over all blocks
+    if (cols) {
+        const long long groups = seg_ngroups(P);
+        if (series > 0 && groups > 0x7fffffffLL / series) return XRFTHIP_UNSUPPORTED_LENGTH;
+        series *= groups;
+        // ... and by default only the classes that measured faster than the route they replace (profiles/r30_fir_filter_cols.txt): wide grids, 0.38 .. 0.47 of its
+        // time.  A narrow grid lost -- (8192, 4096, 8) along dim 1 at L = 512, 8 of a group's 16 columns live, 3.4 against 2.8 ms: the dead columns of a group are
+        // loaded as zeros, transformed and dropped, so the tile does half its work for nothing -- and a grid with less of its groups live wastes more.  Declined:
+        // at most half of the groups' columns live (2 inner <= groups C).  XRFTHIP_MEAN_ALL=1: every class this kernel takes
+        if (2 * d.inner <= groups * seg_cols(P) && env_ll("XRFTHIP_MEAN_ALL", 0) == 0) return XRFTHIP_UNSUPPORTED_LENGTH;
+    }
     if (series > 0 && filter_wgs(d) > 0x7fffffffLL / series) return XRFTHIP_UNSUPPORTED_LENGTH;  // (one launch; declined, never truncated)
     P->family = P->chosen = Family::FastK;
     FftTables& t = P->tables[seg_n(P)];
@@ -241,7 +269,7 @@ static void layout_fasto(xrfthip_plan* P) {
 // ... the filter: the same
 static void layout_fastf(xrfthip_plan* P) {
     layout_one_pass(P);
-    P->w = seg_geom(P, std::min<long long>(P->d.mean_batch, 2 * kWPoints / P->d.nx));
+    P->w = seg_geom(P, std::min<long long>(P->d.mean_batch, 2 * kWPoints / P->d.nx / seg_cols(P)));  // (the column layout: C sequences per segment of the tile)
     P->w.lds = (((size_t)P->w.seqs * (size_t)P->w.stride + 1) & ~(size_t)1) * sizeof(cf);
     P->w.rounds = filter_wgs(P->d);
 }
@@ -334,11 +362,16 @@ static int run_fastf(const xrfthip_plan* P, const ExecArgs& a) {
     p.NS = (int)(2 * kWPoints / d.nx); p.wgs = (int)filter_wgs(d);
     p.K = (int)(d.nx - d.seg_hop + 1);
     p.N = d.seg_in_len; p.n_out = d.seg_out_len; p.lead = d.seg_lead;
-    const long long nwg = d.batch / d.mean_batch * filter_wgs(d);
+    const bool cols = filter_cols(P);
+    const long long nwg = d.batch / d.mean_batch * (cols ? P->w.ngroups : 1) * filter_wgs(d);
     if (nwg > 0x7fffffffLL) return XRFTHIP_BAD_ARG;  // (try_fastf declined it)
     const dim3 grid((unsigned)nwg), blk((unsigned)kWThreads);
-    xrfthip_plan::ProfRec* rec = prof_begin(P, "fastf_overlap_save", st);
-    if (p.resp) { auto k = &fastf_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
+    xrfthip_plan::ProfRec* rec = prof_begin(P, cols ? "fastf_overlap_save_cols" : "fastf_overlap_save", st);
+    if (cols) {
+        if (p.resp) { auto k = &fastf_kernel<true, true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
+        else { auto k = &fastf_kernel<false, true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
+    }
+    else if (p.resp) { auto k = &fastf_kernel<true>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
     else { auto k = &fastf_kernel<false>; XRFT_LAUNCH(k, grid, blk, P->w.lds, st, p); }
     prof_end(rec, st);
     HIP_TRY(hipGetLastError());
@@ -457,15 +490,18 @@ static void describe_fasto(const xrfthip_plan* plan, std::string& s, const char*
 }
 static void describe_fastf(const xrfthip_plan* plan, std::string& s, const char*) {
     const xrfthip_desc& d = plan->d;
+    const bool cols = filter_cols(plan);
     appendf(s, "  [fastw overlap-save] FIR filter, one pass: %lld series of N = %lld samples (series pitch %lld) to %lld samples each from sample %lld of the full convolution, "
                "K = %lld taps, segments of L = %lld samples of which V = %lld are kept; one %d-thread workgroup per (series, run): %lld x %lld workgroups, %lld segments "
                "per tile, each read where it lies with guarded 4-byte loads (zeros outside the series) and packed with itself as a %lld-point sequence; radix %s in "
                "place, per pair (k, n - k) unpacked, multiplied by the response (%s), packed and conjugated in registers and stored in natural order, radix %s again; "
                "lanes store consecutive samples, each written once; no workspace, no second tile, no atomics; lds=%zuB; %s; 4 algorithmic bytes per sample read and 4 per "
                "sample written\n",
-            (long long)(d.batch / d.mean_batch), (long long)d.seg_in_len, plan->w_pitch, (long long)d.seg_out_len, (long long)d.seg_lead, (long long)(d.nx - d.seg_hop + 1),
-            (long long)d.nx, (long long)d.seg_hop, kWThreads, (long long)(d.batch / d.mean_batch), filter_wgs(d), (long long)(2 * kWPoints / d.nx), (long long)d.nx / 2,
+            (long long)(d.batch / d.mean_batch * (cols ? d.inner : 1)), (long long)d.seg_in_len, plan->w_pitch, (long long)d.seg_out_len, (long long)d.seg_lead, (long long)(d.nx - d.seg_hop + 1),
+            (long long)d.nx, (long long)d.seg_hop, kWThreads, (long long)(d.batch / d.mean_batch * (cols ? plan->w.ngroups : 1)), filter_wgs(d), (long long)(2 * kWPoints / d.nx), (long long)d.nx / 2,
             seg_radices(plan).c_str(), plan->phase[1].p ? "L / 2 + 1 complex64 entries" : "none set: ones, a delay", seg_radices(plan).c_str(), plan->w.lds, kFResources);
+    // (the column layout: the series above are the columns of all blocks, the pitch the block pitch, a "series" of the workgroup count a group of columns)
+    if (cols) describe_cols(plan, s, "segments", "segment", (std::string("the result is [block][sample][column], the array's own order: loads and stores coalesced across columns, no transposed copy; ") + kFColsResources).c_str());
 }
 static void describe_fastt(const xrfthip_plan* plan, std::string& s) {
     const xrfthip_desc& d = plan->d;

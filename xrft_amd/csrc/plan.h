@@ -614,11 +614,12 @@ inline bool mean_plan(const xrfthip_plan* P) { return P->d.mean_batch > 1 && !P-
 inline bool mean_family(const xrfthip_plan* P) { return P->family == Family::FastY || (P->family == Family::FastS && !P->coherence) || P->family == Family::FastW; }  // (FastS has no two-field form)
 size_t mean_layout(xrfthip_plan* P, size_t off, long long units, long long slabs);  // (xrft_hip.cpp: mean_P and the partials behind `off`; returns the new end)
 int run_mean_finish(const xrfthip_plan* P, const double* part, void* out, hipStream_t st);  // (... and the finishing kernel, after the last group)
-inline bool welch_cols(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_stride > 0; }  // (... along a leading axis: d.inner adjacent series, samples d.seg_stride apart; S = 1 was normalised to 0, the rows layout)
+inline bool welch_cols(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_stride > 0; }  // (... along a leading axis: d.inner adjacent series, samples d.seg_stride apart; S = 1 was normalised to 0, the rows layout -- but for the filter's column layout, filter_cols())
 inline bool welch_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0; }  // (the descriptor asks for the segments of a series: served by FastW / FastK or not at all)
 inline bool keep_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_keep == 1; }  // (... every segment's spectrum kept, none averaged: Family::FastK, fastk.h)
 inline bool synth_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_synth == 1; }  // (... the series rebuilt from its segments' half spectra: the synthesis form of Family::FastK, fasto.h)
 inline bool filter_plan(const xrfthip_plan* P) { return P->d.seg_hop > 0 && P->d.seg_filter == 1; }  // (... a series filtered by overlap-save: the filter form of Family::FastK, fastf.h)
+inline bool filter_cols(const xrfthip_plan* P) { return filter_plan(P) && P->d.seg_filter_cols == 1; }  // (... its column layout: welch_cols() holds too -- seg_stride >= 1 is kept as it came, S = 1 included)
 inline bool taper_plan(const xrfthip_plan* P) { return P->d.seg_tapers > 0; }  // (... the sum over K tapers of one series' spectra: the multitaper form of Family::FastW, fastt.h; seg_hop = 0)
 inline bool herm_plan(const xrfthip_plan* P) { return P->d.herm_ny > 0; }  // (the DESCRIPTOR asks for the last pass of a three-axis spectrum: argument checks; the family that serves it is Family::FastH)
 // Input strides (xrfthip_desc.in_stride_y / in_stride_batch, normalised by xrfthip_plan_create: both 0 on a dense plan).  Only the kernels that read the caller's

@@ -893,11 +893,12 @@ int xrfthip_plan_create(xrfthip_plan** plan, const xrfthip_desc* desc) {
     // (... and of the versions before `mid` and before the input strides: mid = 1, strides 0)
     // (... and of the version before herm_ny / herm_nx: 0, 0)
     // (... and before each later group of fields, which then read 0: mean_batch; seg_hop / seg_reserved; seg_stride / seg_reserved2; seg_keep / seg_reserved3; seg_synth / seg_reserved4; seg_filter / seg_lead /
-    // seg_in_len / seg_out_len; seg_tapers / seg_taper_len -- each group came together, no size between)
+    // seg_in_len / seg_out_len; seg_tapers / seg_taper_len; seg_filter_cols / seg_reserved5 -- each group came together, no size between)
     static const uint32_t kDescSizes[] = {
         (uint32_t)sizeof(xrfthip_desc), (uint32_t)offsetof(xrfthip_desc, inner), (uint32_t)offsetof(xrfthip_desc, mid), (uint32_t)offsetof(xrfthip_desc, in_stride_y),
         (uint32_t)offsetof(xrfthip_desc, herm_ny), (uint32_t)offsetof(xrfthip_desc, mean_batch), (uint32_t)offsetof(xrfthip_desc, seg_hop), (uint32_t)offsetof(xrfthip_desc, seg_stride),
-        (uint32_t)offsetof(xrfthip_desc, seg_keep), (uint32_t)offsetof(xrfthip_desc, seg_synth), (uint32_t)offsetof(xrfthip_desc, seg_filter), (uint32_t)offsetof(xrfthip_desc, seg_tapers)};
+        (uint32_t)offsetof(xrfthip_desc, seg_keep), (uint32_t)offsetof(xrfthip_desc, seg_synth), (uint32_t)offsetof(xrfthip_desc, seg_filter), (uint32_t)offsetof(xrfthip_desc, seg_tapers),
+        (uint32_t)offsetof(xrfthip_desc, seg_filter_cols)};
     if (!plan || !desc || std::find(std::begin(kDescSizes), std::end(kDescSizes), desc->struct_size) == std::end(kDescSizes)) return XRFTHIP_BAD_ARG;
     xrfthip_desc dcopy{};
     memcpy(&dcopy, desc, desc->struct_size);

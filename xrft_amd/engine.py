@@ -41,7 +41,7 @@ class SpectralPlan:
     def __init__(self, ndim, batch, ny, nx, dtype, out_mode=_lib.OUT_COMPLEX, detrend=_lib.DETREND_NONE, flags=0,
                  scale=1.0, window_y=None, window_x=None, phase_y=None, phase_x=None, binmap=None, nbins=0,
                  slabs_per_group=0, inner=1, mid=1, in_stride_y=0, in_stride_batch=0, herm_ny=0, herm_nx=0, phase_hx=None, mean_batch=0, seg_hop=0, seg_stride=0, seg_keep=0, seg_synth=0,
-                 seg_filter=0, seg_lead=0, seg_in_len=0, seg_out_len=0, seg_tapers=0, seg_taper_len=0, tapers=None):
+                 seg_filter=0, seg_lead=0, seg_in_len=0, seg_out_len=0, seg_tapers=0, seg_taper_len=0, tapers=None, seg_filter_cols=0):
         self._dll = _lib.load()
         self._h = C.c_void_p(0)
         self._serial = next(_PLAN_SERIAL)  # who produced a pass-1 block (an id() can come back after the plan has gone)
@@ -87,13 +87,16 @@ class SpectralPlan:
         self.seg_filter, self.seg_lead, self.seg_in_len, self.seg_out_len = int(seg_filter), int(seg_lead), int(seg_in_len), int(seg_out_len)
         if self.seg_filter:
             self.batch_out = self.batch // max(self.mean_batch, 1)
+        # ... along a leading axis (xrfthip_desc.seg_filter_cols, with seg_stride = S >= inner): the input is the (blocks, seg_in_len, inner) view the plan addresses --
+        # columns adjacent, samples S apart, blocks in_stride_batch apart -- and the result (blocks, seg_out_len, inner), the array's own order
+        self.seg_filter_cols = int(seg_filter_cols)
         # multitaper spectra (xrfthip_desc.seg_tapers; float32, POWER | CROSS, seg_hop 0): nx = L the transform length, the input (series, seg_taper_len) -- in_stride_batch
         # the pitch between series in samples -- and the result (series, nx_out); ``tapers`` is the (seg_tapers, seg_taper_len) table, already weighted by sqrt(w_j)
         self.seg_tapers, self.seg_taper_len = int(seg_tapers), int(seg_taper_len)
-        d = _lib.DescTaper(C.sizeof(_lib.DescTaper), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
+        d = _lib.DescFiltCols(C.sizeof(_lib.DescFiltCols), self.ndim, self.batch, self.ny, self.nx, _HALF[dtype] if dtype in _HALF else _DTYPES[dtype], self.out_mode,
                       int(detrend), self.flags, float(scale), int(slabs_per_group), 0, self.inner, self.mid, self.in_stride_y, self.in_stride_batch,
                       self.herm_ny, self.herm_nx, self.mean_batch, self.seg_hop, 0, self.seg_stride, 0, self.seg_keep, 0, self.seg_synth, 0,
-                      self.seg_filter, self.seg_lead, self.seg_in_len, self.seg_out_len, self.seg_tapers, self.seg_taper_len)
+                      self.seg_filter, self.seg_lead, self.seg_in_len, self.seg_out_len, self.seg_tapers, self.seg_taper_len, self.seg_filter_cols, 0)
         _lib.check(self._dll.xrfthip_plan_create(C.byref(self._h), C.byref(d)))
         if tapers is not None:
             tp = np.ascontiguousarray(tapers, dtype=np.float32)
@@ -180,6 +183,10 @@ class SpectralPlan:
             nb = self.nx // 2 + 1
             return (t.dim() == 3 and tuple(t.shape) == (self.batch_out, self.mean_batch, nb) and (t.stride(2) == 1 or nb == 1) and (t.stride(1) == nb or self.mean_batch == 1)
                     and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or self.mean_batch * nb)))
+        if self.seg_hop and self.seg_filter and self.seg_filter_cols:  # (blocks, samples, columns): exactly the view the plan addresses, seg_in_len samples a column
+            return (t.dim() == 3 and tuple(t.shape) == (self.batch_out, self.seg_in_len, self.inner) and (self.inner <= 1 or t.stride(2) == 1)
+                    and (self.seg_in_len <= 1 or t.stride(1) == self.seg_stride)
+                    and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or self.seg_in_len * self.seg_stride)))
         if self.seg_hop and self.seg_filter:  # (series, samples): exactly seg_in_len samples a series, adjacent, the series the plan's pitch apart
             return (t.dim() == 2 and tuple(t.shape) == (self.batch_out, self.seg_in_len) and (t.stride(1) == 1 or self.seg_in_len == 1)
                     and (t.shape[0] <= 1 or t.stride(0) == (self.in_stride_batch or self.seg_in_len)))
@@ -225,8 +232,8 @@ class SpectralPlan:
                 shape = (self.batch_out, self.mean_batch, self.nx_out) + ((self.inner,) if self.seg_stride > 1 else ())
             if self.seg_hop and self.seg_synth:  # (the series)
                 shape = (self.batch_out, (self.mean_batch - 1) * self.seg_hop + self.nx)
-            if self.seg_hop and self.seg_filter:  # (the filtered series)
-                shape = (self.batch_out, self.seg_out_len)
+            if self.seg_hop and self.seg_filter:  # (the filtered series; the column layout: where the time axis lay, the columns innermost)
+                shape = (self.batch_out, self.seg_out_len) + ((self.inner,) if self.seg_filter_cols else ())
             if self.seg_tapers:  # (one spectrum per series)
                 shape = (self.batch, self.nx_out)
             if self.mid > 1:
@@ -239,7 +246,7 @@ class SpectralPlan:
             if self.seg_hop and self.seg_synth:
                 need = self.batch_out * ((self.mean_batch - 1) * self.seg_hop + self.nx)
             if self.seg_hop and self.seg_filter:
-                need = self.batch_out * self.seg_out_len
+                need = self.batch_out * self.seg_out_len * (self.inner if self.seg_filter_cols else 1)
             if out.dtype != self.out_dtype() or not out.is_contiguous() or out.numel() != need or out.device != dev:
                 raise ValueError(f"out does not match the plan (dtype {self.out_dtype()}, contiguous, {need} elements on {dev})")
         iso_dtype = torch.complex128 if self.out_mode == _lib.OUT_CROSS else torch.float64
